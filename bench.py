@@ -3,7 +3,7 @@
 (model forward -> CrossEntropy + SILog -> backward to every parameter [+ one RCCL gradient
 all-reduce when N > 1]) on synthetic data, fp32, model in train mode — BASELINE.json's metric.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1 runs one process per GPU over RCCL: either the driver starts the ranks itself (python -m torch.distributed.run
 ... bench.py --gpus N, WORLD_SIZE set) or - plain `python bench.py --gpus N` - this process starts them: before anything
@@ -120,6 +120,25 @@ def time_conv_kernels(module, batch, reps=3):
     return fam
 
 
+DUMP_MAX_ELEMS = 1 << 23  # per array (32 MB of float32): loss + gradient + BatchNorm statistics stay under 64 MB
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as <path>/<name>.npy, flattened, in its float32 / float64 dtype.  An array of more
+    than DUMP_MAX_ELEMS elements is replaced by a fixed sample of that many (seed 0, ascending indices): the same
+    elements in every run of the same configuration, so two builds compare output for output."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().reshape(-1).cpu()
+        if a.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMS].sort().values
+            a = a[idx]
+        np.save(os.path.join(path, f"{name}.npy"), a.numpy())
+    log(f"outputs of the last timed step written to {path}: {', '.join(arrays)}")
+
+
 def cpu_baseline(args):
     """Oracle step (fwd + CE + SILog + bwd, train mode) on the host cores; bounded sample."""
     from oracle.losses import step_losses, synthetic_batch
@@ -171,9 +190,10 @@ def cpu_baseline(args):
             "sample": f"oracle {args.model} {args.height}x{args.width} bs={bs} fwd+CE+SILog+bwd, {n} steps in {dt:.1f}s"}
 
 
-def measure(args, device, rank, world, extras=False):
+def measure(args, device, rank, world, extras=False, dump=None):
     """One configuration: build, warm up, capture, time exactly args.steps steps; returns the result object
-    (rank 0; None elsewhere).  extras: add the roofline (per-launch conv timing) and, at N = 1, the CPU baseline."""
+    (rank 0; None elsewhere).  extras: add the roofline (per-launch conv timing) and, at N = 1, the CPU baseline.
+    dump: directory for what the last timed step computed (rank 0; see dump_outputs)."""
     import torch.distributed as dist
 
     import gc
@@ -233,11 +253,13 @@ def measure(args, device, rank, world, extras=False):
         log("hipGraph captured (vision_mtl_amd.graphed.GraphedStep)")
     graph = gstep.graph if gstep is not None else None
 
+    last = {}
+
     def run_step():
         if graph is not None:
             graph.replay()  # the batch is already resident in the step's static input buffers (metric: inputs in HBM)
         else:
-            step()
+            last["loss"] = step()
         after_step()
 
     for _ in range(args.warmup):
@@ -256,6 +278,11 @@ def measure(args, device, rank, world, extras=False):
         t = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if dump and rank == 0:  # before anything below runs another step
+        loss_last = gstep._loss if gstep is not None else last["loss"]
+        running = [b for n, b in model.named_buffers() if n.endswith(("running_mean", "running_var"))]
+        dump_outputs(dump, {"loss": loss_last.reshape(1).float(), "grad": arena.flat_grad,
+                            "bn_running_stats": torch.cat([b.reshape(-1).float() for b in running])})
     if ops._STAMPS is not None and graph is not None:
         stamps, ops._STAMPS = ops._STAMPS, None
         n = len(stamps) // 3  # GraphedStep's warm-up step, its rehearsal step and the captured step all appended
@@ -434,7 +461,12 @@ def main():
     ap.add_argument("--only-headline", action="store_true", help="skip the `configs` array of the other BASELINE configurations")
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="only the multi-rank plumbing (rendezvous, one all-reduce, rank 0's JSON line): runs on CPU over gloo")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the headline's last timed step (loss, flat parameter gradient, BatchNorm running "
+                         "statistics) as DIR/<name>.npy; the inputs are seeded, identical from run to run")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus, sys.argv[1:]))  # nothing above this line touches the GPU
@@ -462,7 +494,7 @@ def main():
         raise SystemExit("bench.py needs an MI355X: the hot path has no CPU fallback")
     device = torch.device("cuda", local_rank)
     log(f"rank {rank}/{world} on {torch.cuda.get_device_name(device)}; building {args.model}")
-    out = measure(args, device, rank, world, extras=True)
+    out = measure(args, device, rank, world, extras=True, dump=args.dump_outputs)
     default_headline = (args.model, args.batch, args.height, args.width) == ("basic", 32, 128, 256)
     if default_headline and not args.only_headline and not args.no_graph:
         # driver-visible lines for the other BASELINE.json configurations (same measurement, fewer steps).  At N > 1 every

@@ -62,8 +62,21 @@ def test_every_gradient_is_tight_without_mask_flips(dev, kind, shape, C):
     batch = synthetic_batch(B, H, W, C, seed=11, masked=0.1)
     extra = {"levels": 4}
     with identity_activations():
-        loss32, g32 = _oracle_grads(name, sd0, batch, torch.float32, extra)
-        loss64, g64 = _oracle_grads(name, sd0, batch, torch.float64, extra)
+        # The fp32 oracle's own error is the bar of cancellation-heavy tensors (the layer-wise stitch weights).  Its CPU
+        # convolutions sum in an order that follows the thread count, and one order can be far luckier than the rest
+        # (csnet_layer, encoder stitch 1: 9e-6 at 16 threads, 9e-5 at one).  The bar is its worst error over a fixed
+        # set of thread counts: the same on every host, whatever thread count the host defaults to.
+        threads = torch.get_num_threads()
+        try:
+            loss64, g64 = _oracle_grads(name, sd0, batch, torch.float64, extra)
+            runs = []
+            for n in (1, 2, 4, 8, 16):
+                torch.set_num_threads(n)
+                runs.append(_oracle_grads(name, sd0, batch, torch.float32, extra)[1])
+        finally:
+            torch.set_num_threads(threads)
+        err32 = lambda g, k: float((g[k].double() - g64[k].double()).abs().max())
+        g32 = {k: max(runs, key=lambda g: err32(g, k))[k] for k, v in g64.items() if v is not None}
         model = model.to(dev).train()
         module = MTLModule(model, num_classes=C, device=str(dev))
         loss = module.training_step({k: v.to(dev) for k, v in batch.items()}, 0)
