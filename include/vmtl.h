@@ -28,6 +28,13 @@ extern "C" {
 #define VMTL_ACT_HSIGMOID 3
 #define VMTL_ACT_SIGMOID 4
 
+/* operand precision of the implicit-GEMM convolutions (the *_p entry points below; their namesakes without the suffix
+ * are VMTL_PREC_FP32).  VMTL_PREC_BF16: every product term is bf16(a)*bf16(b) (round-to-nearest-even, NaN stays NaN),
+ * accumulated in fp32; tensors in memory, epilogues (bias, activation, statistics, BatchNorm backward) stay fp32.  Tile
+ * choice, K split, statistics layout and weight-gradient slab counts do not depend on it.  Unknown values: -1. */
+#define VMTL_PREC_FP32 0
+#define VMTL_PREC_BF16 1
+
 const char* vmtl_version(void);
 /* HIP's text for the last launch failure (status -2) seen on the calling thread */
 const char* vmtl_last_error_string(void);
@@ -37,7 +44,7 @@ int vmtl_reload_env(void);
 /* tuning aid: *out = 100 MHz device wall clock at the moment `stream` gets there */
 int vmtl_timestamp(long long* out, void* stream);
 
-/* ---- convolution (implicit GEMM on exact-fp32 MFMA) -------------------------------------
+/* ---- convolution (implicit GEMM on exact-fp32 MFMA; bf16 operands on request: VMTL_PREC_*) ----------------
  * replaces nn.Conv2d / nn.ConvTranspose2d at utils/model_utils.py:71,74;
  * models/mtan_model.py:31-46,105-129,214-216,369; models/basic_model.py:30-41 (SegmentationHead);
  * utils/model_utils.py:25-34 (smp.Unet decoder + timm pointwise convs). */
@@ -50,12 +57,18 @@ int vmtl_timestamp(long long* out, void* stream);
 int vmtl_conv2d_fwd(const float* x, const float* wp, const float* bias, float* y, float* stats,
                     int B, int H, int W, int Cs, int Ho, int Wo, int ldy, int Nw, int Cout,
                     int KH, int KW, int stride, int pad, int act, int shuffle, void* stream);
+int vmtl_conv2d_fwd_p(const float* x, const float* wp, const float* bias, float* y, float* stats,
+                      int B, int H, int W, int Cs, int Ho, int Wo, int ldy, int Nw, int Cout,
+                      int KH, int KW, int stride, int pad, int act, int shuffle, int precision, void* stream);
 /* split-K form for contractions without activation / statistics / shuffle (data gradients, and forward convs of
  * tile-starved layers - decoder blocks 0-1 at small batch - whose BatchNorm then takes its statistics from a sweep):
  * ws = vmtl_conv2d_ksplit(...)*B*Ho*Wo*ldy floats; bias (nullable) is added by the slab sum */
 int vmtl_conv2d_ksplit(int B, int Ho, int Wo, int ldy, int Ktot);
 int vmtl_conv2d_fwd_ws(const float* x, const float* wp, const float* bias, float* y, float* ws, int B, int H, int W, int Cs,
                        int Ho, int Wo, int ldy, int Nw, int Cout, int KH, int KW, int stride, int pad, void* stream);
+int vmtl_conv2d_fwd_ws_p(const float* x, const float* wp, const float* bias, float* y, float* ws, int B, int H, int W,
+                         int Cs, int Ho, int Wo, int ldy, int Nw, int Cout, int KH, int KW, int stride, int pad,
+                         int precision, void* stream);
 int vmtl_conv2d_stats_rows(int B, int Ho, int Wo, int ldy);
 int vmtl_conv2d_stats_block(int B, int Ho, int Wo, int ldy); /* output rows per stats row block */
 
@@ -80,6 +93,8 @@ int vmtl_conv1x1_cat_dgrad(const float* dy, const float* wp, float* dx, int N1, 
 /* and its weight gradient in one launch: slabs [splits][Nw][K1 + K2s], splits = vmtl_conv2d_wgrad_splits(M, Nw, K1 + K2s) */
 int vmtl_conv1x1_cat_wgrad(const float* x, int K1, const float* x2, int K2s, const float* dy, float* slabs, int splits,
                            int M, int ldy, int Nw, void* stream);
+int vmtl_conv1x1_cat_wgrad_p(const float* x, int K1, const float* x2, int K2s, const float* dy, float* slabs, int splits,
+                             int M, int ldy, int Nw, int precision, void* stream);
 /* pointwise pre-activation node (the 1x1 counterpart of vmtl_conv3x3_small's prologue / vmtl_conv2d_bnbwd):
  * y = conv1x1(act(coef_a[k]*x + coef_c[k])) - BatchNorm + activation (none / relu / hardswish) of the layer that produced
  * x applied to the operand fragments, a_out (nullable [M][Ks]) = the activated matrix for the weight gradient;
@@ -109,6 +124,10 @@ int vmtl_conv2d_bnbwd(const float* x, const float* wp, float* y, float* stats, c
                       const float* ez_invstd, const float* ez_gamma, const float* ez_beta, int ez_act, int B, int H,
                       int W, int Cs, int Ho, int Wo, int ldy, int Nw, int Cout, int KH, int KW, int stride, int pad,
                       void* stream);
+int vmtl_conv2d_bnbwd_p(const float* x, const float* wp, float* y, float* stats, const float* ez_x, const float* ez_mean,
+                        const float* ez_invstd, const float* ez_gamma, const float* ez_beta, int ez_act, int B, int H,
+                        int W, int Cs, int Ho, int Wo, int ldy, int Nw, int Cout, int KH, int KW, int stride, int pad,
+                        int precision, void* stream);
 
 /* nearest-x2 upsample of xl + concat with skip + 3x3/pad-1 conv (smp DecoderBlock entry, reference
  * utils/model_utils.py:25-34) as four 2x2 phase convolutions on the low-res map: wp_eff from
@@ -116,11 +135,15 @@ int vmtl_conv2d_bnbwd(const float* x, const float* wp, float* y, float* stats, c
  * vmtl_conv2d_fwd(k4,s2,p1) over dY with vmtl_pack_up2_dgrad, vmtl_conv2d_wgrad(k4,s2,p1) + vmtl_unpack_up2. */
 int vmtl_conv2d_up2_fwd(const float* xl, const float* skip, const float* wp_eff, float* y, float* stats,
                         int B, int H2, int W2, int C0s, int C1s, int ldy, int Cout, void* stream);
+int vmtl_conv2d_up2_fwd_p(const float* xl, const float* skip, const float* wp_eff, float* y, float* stats,
+                          int B, int H2, int W2, int C0s, int C1s, int ldy, int Cout, int precision, void* stream);
 int vmtl_conv2d_up2_stats_block(int B, int H2, int W2, int ldy);
 /* split-K form of vmtl_conv2d_up2_fwd (no statistics): ws = vmtl_conv2d_up2_ksplit(...)*B*2H2*2W2*ldy floats */
 int vmtl_conv2d_up2_ksplit(int B, int H2, int W2, int ldy, int Ktot);
 int vmtl_conv2d_up2_fwd_ws(const float* xl, const float* skip, const float* wp_eff, float* y, float* ws, int B, int H2,
                            int W2, int C0s, int C1s, int ldy, int Cout, void* stream);
+int vmtl_conv2d_up2_fwd_ws_p(const float* xl, const float* skip, const float* wp_eff, float* y, float* ws, int B, int H2,
+                             int W2, int C0s, int C1s, int ldy, int Cout, int precision, void* stream);
 int vmtl_pack_up2_fwd(const float* w, float* dst, int Cout, int C0, int C0s, int C1, int C1s, void* stream);
 int vmtl_pack_up2_dgrad(const float* w, float* dst, int Cout, int Cos, int C0, int Cin, void* stream);
 int vmtl_unpack_up2(const float* slabs, float* grad, int Cout, int Cos, int C0, int Cin, int nslabs, void* stream);
@@ -132,6 +155,9 @@ int vmtl_unpack_up2(const float* slabs, float* grad, int Cout, int Cos, int C0, 
 int vmtl_conv2d_wgrad_splits(int M, int Nw, int Ktot);
 int vmtl_conv2d_wgrad(const float* x, const float* dy, float* slabs, int splits, int B, int H, int W, int Cs,
                       int Ho, int Wo, int ldy, int Nw, int KH, int KW, int stride, int pad, void* stream);
+int vmtl_conv2d_wgrad_p(const float* x, const float* dy, float* slabs, int splits, int B, int H, int W, int Cs,
+                        int Ho, int Wo, int ldy, int Nw, int KH, int KW, int stride, int pad, int precision,
+                        void* stream);
 
 /* Weight gradient of a NARROW 3x3 / stride 1 / pad 1 conv on a strip-walking halo kernel (csrc/conv_wgrad_small.hip): x is read
  * from memory once instead of once per tap.  Replaces the same conv2d backward-weight call sites of the reference as

@@ -1,6 +1,9 @@
 """Micro-benchmark (GPU box) of the implicit-GEMM kernels on the `basic` decoder shapes at bs 32,
-called through the C ABI.  VMTL_FORCE_TILE=<id> / VMTL_FORCE_WG_SPLITS=<n> override the host heuristics."""
+called through the C ABI.  VMTL_FORCE_TILE=<id> / VMTL_FORCE_WG_SPLITS=<n> override the host heuristics.
+--precision fp32|bf16|both: operand precision of the covered kernels (VMTL_PREC_*); `both` times the two modes
+alternately on every shape in one process and ends with one JSON line of per-shape times and bf16 speed-ups."""
 import argparse
+import json
 import sys
 
 import torch
@@ -13,7 +16,9 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--only", default="")
 ap.add_argument("--stats", action="store_true", help="forward launches also write the BatchNorm partial rows (as in a training step)")
+ap.add_argument("--precision", choices=["fp32", "bf16", "both"], default="fp32")
 args = ap.parse_args()
+PRECS = ["fp32", "bf16"] if args.precision == "both" else [args.precision]
 dev = torch.device("cuda:0")
 L = lib()
 st = torch.cuda.current_stream().cuda_stream
@@ -42,6 +47,14 @@ LAYERS = [("blk0.c1", 32, 8, 16, 1072, 540, 3), ("blk0.c2", 32, 8, 16, 540, 540,
           ("cs.16-1", 32, 128, 256, 16, 1, 3), ("cs.80-32", 32, 64, 128, 80, 32, 3), ("mtan.c0", 16, 256, 256, 3, 32, 3)]
 
 
+def call(name, prec, *a):
+    """fp32: the legacy entry point; bf16: its _p variant with VMTL_PREC_BF16 in front of the stream argument"""
+    if prec == "fp32":
+        L.call(name, *a)
+    else:
+        L.call(name + "_p", *a[:-1], 1, a[-1])
+
+
 def timeit(fn):
     fn()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -53,8 +66,9 @@ def timeit(fn):
     return e0.elapsed_time(e1) / args.reps
 
 
-tot = {"fwd": 0.0, "dgrad": 0.0, "wgrad": 0.0}
+tots = {p: {"fwd": 0.0, "dgrad": 0.0, "wgrad": 0.0} for p in PRECS}
 flops = 0.0
+table = {}
 for name, B, H, W, Cin, Cout, K in LAYERS:
     if args.only and args.only not in name:
         continue
@@ -71,33 +85,42 @@ for name, B, H, W, Cin, Cout, K in LAYERS:
     if args.stats:
         stats_t = torch.empty(L.raw("vmtl_conv2d_stats_rows")(B, H, W, ldy) + 1, 2, ldy, device=dev)
         stats = stats_t.data_ptr()
-    t_f = timeit(lambda: L.call("vmtl_conv2d_fwd", x.data_ptr(), wp.data_ptr(), None, y.data_ptr(), stats, B, H, W, Cs, H, W,
-                                ldy, Cout, Cout, K, K, 1, K // 2, 0, 0, st))
-    t_d = timeit(lambda: L.call("vmtl_conv2d_fwd", dy.data_ptr(), wd.data_ptr(), None, dx.data_ptr(), None, B, H, W, ldy, H,
-                                W, Cs, Cin, Cin, K, K, 1, K // 2, 0, 0, st))
-    # the data gradient with the producer's BatchNorm + ReLU backward in its epilogue (vmtl_conv2d_bnbwd)
     ezs = torch.empty(L.raw("vmtl_conv2d_stats_rows")(B, H, W, Cs) + 1, 2, Cs, device=dev)
     ezx = torch.randn(B, H, W, Cs, device=dev)
     vec = [torch.rand(Cs, device=dev) + 0.5 for _ in range(4)]
-    t_z = timeit(lambda: L.call("vmtl_conv2d_bnbwd", dy.data_ptr(), wd.data_ptr(), dx.data_ptr(), ezs.data_ptr(), ezx.data_ptr(),
-                                vec[0].data_ptr(), vec[1].data_ptr(), vec[2].data_ptr(), vec[3].data_ptr(), 1, B, H, W, ldy, H,
-                                W, Cs, Cin, Cin, K, K, 1, K // 2, st))
     S = L.raw("vmtl_conv2d_wgrad_splits")(M, Cout, KK * Cs)
     slabs = torch.empty(S, Cout, KK * Cs, device=dev)
-    t_w = timeit(lambda: L.call("vmtl_conv2d_wgrad", x.data_ptr(), dy.data_ptr(), slabs.data_ptr(), S, B, H, W, Cs, H, W, ldy,
-                                Cout, K, K, 1, K // 2, st))
-    t_ws = None
-    if K == 3 and L.raw("vmtl_conv3x3_wgrad_small_supported")(Cs, ldy, W):  # the strip-walking halo kernel on the same layer
-        ns = L.raw("vmtl_conv3x3_wgrad_small_slabs")(B, H, W)
-        slabs_s = torch.empty(ns, Cout, KK * Cs, device=dev)
-        t_ws = timeit(lambda: L.call("vmtl_conv3x3_wgrad_small", x.data_ptr(), dy.data_ptr(), slabs_s.data_ptr(), ns, B, H, W, Cs,
-                                     ldy, Cout, st))
-    tot["fwd"] += t_f
-    tot["dgrad"] += t_d
-    tot["wgrad"] += t_w
     flops += fl
-    print(f"{name:8s} M={M:8d} Cin={Cin:5d} Cout={Cout:4d}  fwd {t_f * 1e3:7.1f} us {fl / t_f / 1e9:6.1f} TF | "
-          f"dgrad {t_d * 1e3:7.1f} us {fl / t_d / 1e9:6.1f} TF (+bnbwd {t_z * 1e3:6.1f}) | wgrad(S={S:3d}) {t_w * 1e3:7.1f} us {fl / t_w / 1e9:6.1f} TF"
-          + (f" | halo wgrad {t_ws * 1e3:7.1f} us {fl / t_ws / 1e9:6.1f} TF" if t_ws else ""))
-print(f"TOTAL fwd {tot['fwd']:.3f} ms ({flops / tot['fwd'] / 1e9:.1f} TF)  dgrad {tot['dgrad']:.3f} ms ({flops / tot['dgrad'] / 1e9:.1f} TF)"
-      f"  wgrad {tot['wgrad']:.3f} ms ({flops / tot['wgrad'] / 1e9:.1f} TF)  sum {sum(tot.values()):.3f} ms")
+    for prec in PRECS:  # alternating modes, shape by shape
+        t_f = timeit(lambda: call("vmtl_conv2d_fwd", prec, x.data_ptr(), wp.data_ptr(), None, y.data_ptr(), stats, B, H, W, Cs, H, W,
+                                    ldy, Cout, Cout, K, K, 1, K // 2, 0, 0, st))
+        t_d = timeit(lambda: call("vmtl_conv2d_fwd", prec, dy.data_ptr(), wd.data_ptr(), None, dx.data_ptr(), None, B, H, W, ldy, H,
+                                    W, Cs, Cin, Cin, K, K, 1, K // 2, 0, 0, st))
+        # the data gradient with the producer's BatchNorm + ReLU backward in its epilogue (vmtl_conv2d_bnbwd)
+        t_z = timeit(lambda: call("vmtl_conv2d_bnbwd", prec, dy.data_ptr(), wd.data_ptr(), dx.data_ptr(), ezs.data_ptr(), ezx.data_ptr(),
+                                    vec[0].data_ptr(), vec[1].data_ptr(), vec[2].data_ptr(), vec[3].data_ptr(), 1, B, H, W, ldy, H,
+                                    W, Cs, Cin, Cin, K, K, 1, K // 2, st))
+        t_w = timeit(lambda: call("vmtl_conv2d_wgrad", prec, x.data_ptr(), dy.data_ptr(), slabs.data_ptr(), S, B, H, W, Cs, H, W, ldy,
+                                    Cout, K, K, 1, K // 2, st))
+        t_ws = None
+        if prec == "fp32" and K == 3 and L.raw("vmtl_conv3x3_wgrad_small_supported")(Cs, ldy, W):  # the strip-walking halo kernel on the same layer
+            ns = L.raw("vmtl_conv3x3_wgrad_small_slabs")(B, H, W)
+            slabs_s = torch.empty(ns, Cout, KK * Cs, device=dev)
+            t_ws = timeit(lambda: L.call("vmtl_conv3x3_wgrad_small", x.data_ptr(), dy.data_ptr(), slabs_s.data_ptr(), ns, B, H, W, Cs,
+                                         ldy, Cout, st))
+        tot = tots[prec]
+        tot["fwd"] += t_f
+        tot["dgrad"] += t_d
+        tot["wgrad"] += t_w
+        table.setdefault(name, {})[prec] = {"fwd_us": round(t_f * 1e3, 1), "dgrad_us": round(t_d * 1e3, 1),
+                                            "bnbwd_us": round(t_z * 1e3, 1), "wgrad_us": round(t_w * 1e3, 1)}
+        print(f"{name:8s} {prec} M={M:8d} Cin={Cin:5d} Cout={Cout:4d}  fwd {t_f * 1e3:7.1f} us {fl / t_f / 1e9:6.1f} TF | "
+              f"dgrad {t_d * 1e3:7.1f} us {fl / t_d / 1e9:6.1f} TF (+bnbwd {t_z * 1e3:6.1f}) | wgrad(S={S:3d}) {t_w * 1e3:7.1f} us {fl / t_w / 1e9:6.1f} TF"
+              + (f" | halo wgrad {t_ws * 1e3:7.1f} us {fl / t_ws / 1e9:6.1f} TF" if t_ws else ""))
+for prec, tot in tots.items():
+    print(f"TOTAL {prec} fwd {tot['fwd']:.3f} ms ({flops / tot['fwd'] / 1e9:.1f} TF)  dgrad {tot['dgrad']:.3f} ms ({flops / tot['dgrad'] / 1e9:.1f} TF)"
+          f"  wgrad {tot['wgrad']:.3f} ms ({flops / tot['wgrad'] / 1e9:.1f} TF)  sum {sum(tot.values()):.3f} ms")
+if len(PRECS) == 2:
+    speedup = {n: {k[:-3]: round(v["fp32"][k] / v["bf16"][k], 2) for k in v["fp32"]} for n, v in table.items()}
+    print(json.dumps({"bench_conv": table, "bf16_speedup": speedup,
+                      "total_ms": {p: round(sum(t.values()), 3) for p, t in tots.items()}}))

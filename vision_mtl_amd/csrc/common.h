@@ -22,6 +22,11 @@
 #define VMTL_ACT_HSIGMOID 3
 #define VMTL_ACT_SIGMOID 4
 
+// operand precision of the implicit-GEMM convolutions (the *_p entry points)
+#define VMTL_PREC_FP32 0
+#define VMTL_PREC_BF16 1
+static inline bool valid_prec(int prec) { return prec == VMTL_PREC_FP32 || prec == VMTL_PREC_BF16; }
+
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));

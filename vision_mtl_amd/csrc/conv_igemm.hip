@@ -1,4 +1,5 @@
-// Implicit-GEMM convolution on exact-fp32 MFMA (v_mfma_f32_16x16x4_f32), NHWC.
+// Implicit-GEMM convolution on exact-fp32 MFMA (v_mfma_f32_16x16x4_f32), NHWC; opt-in bf16 operands (VMTL_PREC_BF16:
+// every product bf16(a)*bf16(b), fp32 accumulation, v_mfma_f32_16x16x32_bf16) through the *_p entry points.
 //
 // Replaces the ATen conv2d / conv_transpose2d dispatches reached from
 //   reference vision_mtl/utils/model_utils.py:71,74 (DoubleConv 3x3),
@@ -90,12 +91,21 @@ __device__ __forceinline__ void glds16(const float* src, float* lds_dst) {
                                    (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
 }
 
-// X3 = 1 (opt-in, VMTL_BF16X3=1; NOT the default path): every fp32 operand is split EXACTLY into three bf16
-// values while it is staged (a = a1 + a2 + a3 by truncation, 8 significand bits each; LDS holds three
+// PL = operand planes in LDS: 0 = fp32 (the default), 1 = bf16 (VMTL_PREC_BF16), 3 = bf16x3.
+// PL = 1: every operand is rounded to bf16 (round-to-nearest-even, a plain cast: v_cvt_pk_bf16_f32) while it is staged,
+// LDS holds one [row][32 bf16] plane per tile and a product is one v_mfma_f32_16x16x32_bf16 per BK chunk.  The VALU tail
+// columns multiply the same rounded values (exact products of two bf16 in fp32), so the whole launch honours the contract.
+// PL = 3 (tuning experiment, VMTL_BF16X3=1, fp32 precision only; NOT the default path): every fp32 operand is split
+// EXACTLY into three bf16 values while it is staged (a = a1 + a2 + a3 by truncation, 8 significand bits each; LDS holds three
 // [row][32 bf16] planes per tile) and a product is formed from six v_mfma_f32_16x16x32_bf16 with fp32
 // accumulation: a1b1 + a1b2 + a2b1 + a1b3 + a2b2 + a3b1, dropped terms < 2^-24 relative.  Measured error is
 // below the fp32-MFMA path's (tools/ubench/gemm_bf16x3_vs_f32.hip); see DESIGN.md section 7 for why it is
 // not switched on.
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ u32x2 round_bf16x4(f32x4 v) {
+  return __builtin_bit_cast(u32x2, __builtin_convertvector(v, bf16x4));
+}
+
 __device__ __forceinline__ void split3(f32x4 v, u32x2& p1, u32x2& p2, u32x2& p3) {
   unsigned x[4], r1[4], r2[4];
 #pragma unroll
@@ -111,7 +121,7 @@ __device__ __forceinline__ void split3(f32x4 v, u32x2& p1, u32x2& p2, u32x2& p3)
   p3 = (u32x2){__builtin_amdgcn_perm(r2[1], r2[0], 0x07060302u), __builtin_amdgcn_perm(r2[3], r2[2], 0x07060302u)};
 }
 
-template <int TM, int TN, int WAVES_M, int WAVES_N, bool UP2 = false, int NT = 0, int NS = 0, int X3 = 0>
+template <int TM, int TN, int WAVES_M, int WAVES_N, bool UP2 = false, int NT = 0, int NS = 0, int PL = 0>
 // The 128x160 tile took 264 registers: ONE wave per SIMD, nothing to overlap its loads with.  Its second launch bound asks
 // for two (<= 256 registers: 216-238, no spills): 13-18 % faster on the 145..160-column layers (tools/bench_conv.py dgrad
 // blk1-3.c1: 465 -> 405, 501 -> 426, 590 -> 484 us).  Only that tile: the same bound on every instantiation made the
@@ -127,7 +137,8 @@ __global__ __launch_bounds__(256, (TM * TN >= 20 && WAVES_N == 2) ? 2 : 1) void 
   static_assert(WAVES_M * WAVES_N == 4, "4 waves per workgroup");
   static_assert(NT == 0 || WAVES_N == 1, "tail columns need all waves to span the full tile width");
   static_assert(NS == 0 || (NS >= 2 && NS <= 4 && BM % 32 == 0), "LDS-DMA staging: 2..4 buffers, whole 32-row passes");
-  static_assert(X3 == 0 || (NS == 0 && NT == 0), "bf16x3 operands: register staging, no VALU tail columns");
+  static_assert(PL == 0 || PL == 1 || PL == 3, "operand planes: fp32, bf16 or bf16x3");
+  static_assert(PL == 0 || (NS == 0 && (NT == 0 || PL == 1)), "bf16 operands: register staging; bf16x3: no tail columns");
 
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* As = smem;                    // [NBUF][BM][LDT]
@@ -289,12 +300,29 @@ __global__ __launch_bounds__(256, (TM * TN >= 20 && WAVES_N == 2) ? 2 : 1) void 
     ci += BK;
     normalize();
   };
-  // X3 LDS image (bytes): A planes [2][3][BM][64], then B planes [2][3][BN][64]; the 16-byte slot s of row r
+  // bf16 LDS image (bytes): A planes [2][PL][BM][64], then B planes [2][PL][BN][64]; the 16-byte slot s of row r
   // sits at s ^ ((r >> 2) & 3) (rows r, r+4, r+8, r+12 of a fragment read would share a bank group otherwise)
   unsigned char* A3 = reinterpret_cast<unsigned char*>(smem);
-  unsigned char* B3 = A3 + 2 * 3 * BM * 64;
+  unsigned char* B3 = A3 + 2 * (PL ? PL : 1) * BM * 64;
   auto store_tile = [&](int buf) {
-    if constexpr (X3) {
+    if constexpr (PL == 1) {
+#pragma unroll
+      for (int i = 0; i < RA; ++i) {
+        const int row = r0 + 32 * i;
+        if (BM % 32 == 0 || row < BM)
+          *reinterpret_cast<u32x2*>(A3 + (buf * BM + row) * 64 + (((k4 >> 1) ^ ((row >> 2) & 3)) << 4) + ((k4 & 1) << 3)) =
+              round_bf16x4(ra[i]);
+      }
+#pragma unroll
+      for (int i = 0; i < RB; ++i) {
+        const int row = r0 + 32 * i;
+        if (BN % 32 == 0 || row < BN)
+          *reinterpret_cast<u32x2*>(B3 + (buf * BN + row) * 64 + (((k4 >> 1) ^ ((row >> 2) & 3)) << 4) + ((k4 & 1) << 3)) =
+              round_bf16x4(rb[i]);
+      }
+      return;
+    }
+    if constexpr (PL == 3) {
 #pragma unroll
       for (int i = 0; i < RA; ++i) {
         const int row = r0 + 32 * i;
@@ -358,7 +386,38 @@ __global__ __launch_bounds__(256, (TM * TN >= 20 && WAVES_N == 2) ? 2 : 1) void 
   const int ntc = NT > 0 ? max(0, min(NT, p.Nw - (n0 + BNM))) : 0;
   // one BK chunk of MFMAs (+ VALU tail columns) on staging buffer `cur`
   auto compute = [&](int cur) {
-    if constexpr (X3) {
+    if constexpr (PL == 1) {
+      // lane (l15, lq) holds k = 8*lq .. 8*lq+7 of its row: the 16-byte slot lq of the plane
+      bf16x8 fa[TM];
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+        const int row = (wm * TM + i) * 16 + l15;
+        fa[i] = *reinterpret_cast<const bf16x8*>(A3 + (cur * BM + row) * 64 + ((lq ^ ((row >> 2) & 3)) << 4));
+      }
+#pragma unroll
+      for (int j = 0; j < TN; ++j) {
+        const int row = (wn * TN + j) * 16 + l15;
+        const bf16x8 fb = *reinterpret_cast<const bf16x8*>(B3 + (cur * BN + row) * 64 + ((lq ^ ((row >> 2) & 3)) << 4));
+#pragma unroll
+        for (int i = 0; i < TM; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb, acc[i][j], 0, 0, 0);
+      }
+      if (NT > 0) {
+        // tail weight rows BNM + t: the same k slot of the rounded plane, products formed on the VALU (exact in fp32)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          if (t >= ntc) break;
+          const int row = BNM + t;
+          const bf16x8 ft = *reinterpret_cast<const bf16x8*>(B3 + (cur * BN + row) * 64 + ((lq ^ ((row >> 2) & 3)) << 4));
+#pragma unroll
+          for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int e = 0; e < 8; e += 2)
+              tacc[i][t] += (f32x2){(float)fa[i][e], (float)fa[i][e + 1]} * (f32x2){(float)ft[e], (float)ft[e + 1]};
+        }
+      }
+      return;
+    }
+    if constexpr (PL == 3) {
       // lane (l15, lq) holds k = 8*lq .. 8*lq+7 of its row: the 16-byte slot lq of each plane
       bf16x8 fa[TM][3];
 #pragma unroll
@@ -868,7 +927,7 @@ extern "C" int vmtl_conv2d_stats_block(int B, int Ho, int Wo, int ldy) {
   return kTiles[conv_pick_tile(B * Ho * Wo, ldy)].bm;
 }
 
-template <int TM, int TN, int WMV, int WNV, bool UP2, int NT, int NS, int X3 = 0>
+template <int TM, int TN, int WMV, int WNV, bool UP2, int NT, int NS, int PL = 0>
 static int launch_conv_ns(ConvP& p, hipStream_t st);
 
 // opt-in bf16x3 operand split for the wide tiles (VMTL_BF16X3=1); see the kernel comment
@@ -885,11 +944,13 @@ static int conv_glds_stages() {
 }
 
 template <int TM, int TN, int WMV, int WNV, bool UP2 = false, int NT = 0>
-static int launch_conv(ConvP& p, hipStream_t st) {
+static int launch_conv(ConvP& p, hipStream_t st, int prec) {
+  // bf16 precision: one plane, register staging; the tuning switches below (VMTL_BF16X3, VMTL_GLDS) are fp32-only
+  if (prec == VMTL_PREC_BF16) return launch_conv_ns<TM, TN, WMV, WNV, UP2, NT, 0, 1>(p, st);
   if constexpr (NT == 0 && WNV * TN >= 5) {
     // long K loops only: the three planes need 1.5x the LDS (one workgroup per CU for the 128-row tiles), which a
     // 4-6 step loop cannot amortise (MTAN's full-resolution 1x1 convs ran 40 % slower with it)
-    if (conv_bf16x3() && cdiv(p.Ktot, BK) >= 24) return launch_conv_ns<TM, TN, WMV, WNV, UP2, NT, 0, 1>(p, st);
+    if (conv_bf16x3() && cdiv(p.Ktot, BK) >= 24) return launch_conv_ns<TM, TN, WMV, WNV, UP2, NT, 0, 3>(p, st);
   }
   if constexpr (!UP2 && (WMV * TM) % 2 == 0) {
     const int ns = conv_glds_stages();
@@ -899,7 +960,7 @@ static int launch_conv(ConvP& p, hipStream_t st) {
   return launch_conv_ns<TM, TN, WMV, WNV, UP2, NT, 0>(p, st);
 }
 
-template <int TM, int TN, int WMV, int WNV, bool UP2, int NT, int NS, int X3>
+template <int TM, int TN, int WMV, int WNV, bool UP2, int NT, int NS, int PL>
 static int launch_conv_ns(ConvP& p, hipStream_t st) {
   constexpr int BM = WMV * TM * 16, BN = WNV * TN * 16 + NT;
   p.tiles_m = cdiv(p.M, BM) * (UP2 ? 4 : 1);
@@ -910,14 +971,14 @@ static int launch_conv_ns(ConvP& p, hipStream_t st) {
     return VMTL_ERR_UNSUPPORTED;
   constexpr int NBUF = NS >= 2 ? NS : 2;
   constexpr int BNR = NS >= 2 ? (BN + 31) / 32 * 32 : BN;
-  const size_t lds = X3 ? (size_t)2 * 3 * (BM + BN) * 64 : (size_t)NBUF * (BM + BNR) * LDT * sizeof(float);
+  const size_t lds = PL ? (size_t)2 * PL * (BM + BN) * 64 : (size_t)NBUF * (BM + BNR) * LDT * sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<TM, TN, WMV, WNV, UP2, NT, NS, X3>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<TM, TN, WMV, WNV, UP2, NT, NS, PL>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_set = true;
   }
-  hipLaunchKernelGGL((conv_igemm_kernel<TM, TN, WMV, WNV, UP2, NT, NS, X3>),
+  hipLaunchKernelGGL((conv_igemm_kernel<TM, TN, WMV, WNV, UP2, NT, NS, PL>),
                      dim3(p.tiles_m * p.tiles_n, p.ksplit > 1 ? p.ksplit : 1), dim3(256), lds, st, p);
   return vmtl_check_launch();
 }
@@ -965,9 +1026,9 @@ static int conv2d_fwd_impl(const float* x, const float* wp, const float* bias, f
                            int B, int H, int W, int Cs, int Ho, int Wo, int ldy, int Nw, int Cout,
                            int KH, int KW, int stride, int pad, int act, int shuffle, const float* ez_x,
                            const float* ez_mean, const float* ez_invstd, const float* ez_gamma, const float* ez_beta,
-                           int ez_act, void* stream) {
+                           int ez_act, int prec, void* stream) {
   VMTL_ENTER();
-  if (!x || !wp || !y) return VMTL_ERR_ARG;
+  if (!valid_prec(prec) || !x || !wp || !y) return VMTL_ERR_ARG;
   if (Cs <= 0 || (Cs & 3) || B <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0) return VMTL_ERR_ARG;
   if (KH <= 0 || KW <= 0 || stride <= 0 || pad < 0 || Nw <= 0 || Cout <= 0 || ldy <= 0) return VMTL_ERR_ARG;
   if (!shuffle && (Cout > ldy || Nw > ldy)) return VMTL_ERR_ARG;
@@ -986,53 +1047,71 @@ static int conv2d_fwd_impl(const float* x, const float* wp, const float* bias, f
       hipMemsetAsync(y, 0, (size_t)B * 4 * Ho * Wo * ldy * sizeof(float), st) != hipSuccess)
     return VMTL_ERR_LAUNCH;
   switch (conv_pick_tile(p.M, shuffle ? Nw : ldy)) {
-    case 0: return launch_conv<2, 2, 4, 1>(p, st);
-    case 1: return launch_conv<2, 3, 4, 1>(p, st);
-    case 2: return launch_conv<2, 4, 4, 1>(p, st);
-    case 3: return launch_conv<2, 5, 4, 1>(p, st);
-    case 4: return launch_conv<4, 3, 2, 2>(p, st);
-    case 5: return launch_conv<4, 4, 2, 2>(p, st);
-    case 6: return launch_conv<2, 9, 4, 1>(p, st);
-    case 7: return launch_conv<4, 5, 2, 2>(p, st);
-    case 8: return launch_conv<1, 2, 4, 1>(p, st);
-    case 9: return launch_conv<1, 4, 4, 1>(p, st);
-    case 10: return launch_conv<2, 4, 2, 2>(p, st);
-    case 11: return launch_conv<1, 9, 4, 1>(p, st);
-    case 12: return launch_conv<2, 2, 4, 1, false, 4>(p, st);
-    case 13: return launch_conv<2, 1, 4, 1, false, 4>(p, st);
-    case 14: return launch_conv<2, 4, 4, 1, false, 4>(p, st);
-    default: return launch_conv<2, 1, 4, 1>(p, st);
+    case 0: return launch_conv<2, 2, 4, 1>(p, st, prec);
+    case 1: return launch_conv<2, 3, 4, 1>(p, st, prec);
+    case 2: return launch_conv<2, 4, 4, 1>(p, st, prec);
+    case 3: return launch_conv<2, 5, 4, 1>(p, st, prec);
+    case 4: return launch_conv<4, 3, 2, 2>(p, st, prec);
+    case 5: return launch_conv<4, 4, 2, 2>(p, st, prec);
+    case 6: return launch_conv<2, 9, 4, 1>(p, st, prec);
+    case 7: return launch_conv<4, 5, 2, 2>(p, st, prec);
+    case 8: return launch_conv<1, 2, 4, 1>(p, st, prec);
+    case 9: return launch_conv<1, 4, 4, 1>(p, st, prec);
+    case 10: return launch_conv<2, 4, 2, 2>(p, st, prec);
+    case 11: return launch_conv<1, 9, 4, 1>(p, st, prec);
+    case 12: return launch_conv<2, 2, 4, 1, false, 4>(p, st, prec);
+    case 13: return launch_conv<2, 1, 4, 1, false, 4>(p, st, prec);
+    case 14: return launch_conv<2, 4, 4, 1, false, 4>(p, st, prec);
+    default: return launch_conv<2, 1, 4, 1>(p, st, prec);
   }
+}
+
+extern "C" int vmtl_conv2d_fwd_p(const float* x, const float* wp, const float* bias, float* y, float* stats,
+                                 int B, int H, int W, int Cs, int Ho, int Wo, int ldy, int Nw, int Cout,
+                                 int KH, int KW, int stride, int pad, int act, int shuffle, int precision, void* stream) {
+  return conv2d_fwd_impl(x, wp, bias, y, stats, B, H, W, Cs, Ho, Wo, ldy, Nw, Cout, KH, KW, stride, pad, act, shuffle,
+                         nullptr, nullptr, nullptr, nullptr, nullptr, 0, precision, stream);
 }
 
 extern "C" int vmtl_conv2d_fwd(const float* x, const float* wp, const float* bias, float* y, float* stats,
                                int B, int H, int W, int Cs, int Ho, int Wo, int ldy, int Nw, int Cout,
                                int KH, int KW, int stride, int pad, int act, int shuffle, void* stream) {
-  return conv2d_fwd_impl(x, wp, bias, y, stats, B, H, W, Cs, Ho, Wo, ldy, Nw, Cout, KH, KW, stride, pad, act, shuffle,
-                         nullptr, nullptr, nullptr, nullptr, nullptr, 0, stream);
+  return vmtl_conv2d_fwd_p(x, wp, bias, y, stats, B, H, W, Cs, Ho, Wo, ldy, Nw, Cout, KH, KW, stride, pad, act, shuffle,
+                           VMTL_PREC_FP32, stream);
 }
 
 // Data gradient with the BatchNorm + activation backward of the producer of the differentiated tensor fused into
 // the epilogue (ConvP::ez_x): y = dz, stats[vmtl_conv2d_stats_rows(...)][2][ldy] = per-row-block (sum dz, sum dz*xhat).
 // The caller finishes with vmtl_bn_bwd_finalize + vmtl_bn_bwd_apply (no reduce pass over x and dy).
+extern "C" int vmtl_conv2d_bnbwd_p(const float* x, const float* wp, float* y, float* stats, const float* ez_x,
+                                   const float* ez_mean, const float* ez_invstd, const float* ez_gamma,
+                                   const float* ez_beta, int ez_act, int B, int H, int W, int Cs, int Ho, int Wo, int ldy,
+                                   int Nw, int Cout, int KH, int KW, int stride, int pad, int precision, void* stream) {
+  if (!valid_prec(precision) || !stats || !ez_x || !ez_mean || !ez_invstd || !ez_gamma || !ez_beta) return VMTL_ERR_ARG;
+  return conv2d_fwd_impl(x, wp, nullptr, y, stats, B, H, W, Cs, Ho, Wo, ldy, Nw, Cout, KH, KW, stride, pad, 0, 0, ez_x,
+                         ez_mean, ez_invstd, ez_gamma, ez_beta, ez_act, precision, stream);
+}
+
 extern "C" int vmtl_conv2d_bnbwd(const float* x, const float* wp, float* y, float* stats, const float* ez_x,
                                  const float* ez_mean, const float* ez_invstd, const float* ez_gamma,
                                  const float* ez_beta, int ez_act, int B, int H, int W, int Cs, int Ho, int Wo, int ldy,
                                  int Nw, int Cout, int KH, int KW, int stride, int pad, void* stream) {
-  if (!stats || !ez_x || !ez_mean || !ez_invstd || !ez_gamma || !ez_beta) return VMTL_ERR_ARG;
-  return conv2d_fwd_impl(x, wp, nullptr, y, stats, B, H, W, Cs, Ho, Wo, ldy, Nw, Cout, KH, KW, stride, pad, 0, 0, ez_x,
-                         ez_mean, ez_invstd, ez_gamma, ez_beta, ez_act, stream);
+  return vmtl_conv2d_bnbwd_p(x, wp, y, stats, ez_x, ez_mean, ez_invstd, ez_gamma, ez_beta, ez_act, B, H, W, Cs, Ho, Wo, ldy,
+                             Nw, Cout, KH, KW, stride, pad, VMTL_PREC_FP32, stream);
 }
 
 // split-K form of vmtl_conv2d_fwd for plain contractions (no bias / act / stats / shuffle): `ws` holds
 // vmtl_conv2d_ksplit(...) * B*Ho*Wo*ldy floats.  With ksplit == 1 it is exactly vmtl_conv2d_fwd.
-extern "C" int vmtl_conv2d_fwd_ws(const float* x, const float* wp, const float* bias, float* y, float* ws, int B, int H,
-                                  int W, int Cs, int Ho, int Wo, int ldy, int Nw, int Cout, int KH, int KW, int stride,
-                                  int pad, void* stream) {
+extern "C" int vmtl_conv2d_fwd_ws_p(const float* x, const float* wp, const float* bias, float* y, float* ws, int B, int H,
+                                    int W, int Cs, int Ho, int Wo, int ldy, int Nw, int Cout, int KH, int KW, int stride,
+                                    int pad, int precision, void* stream) {
   VMTL_ENTER();
+  if (!valid_prec(precision)) return VMTL_ERR_ARG;
+  const int prec = precision;
   const int splits = vmtl_conv2d_ksplit(B, Ho, Wo, ldy, KH * KW * Cs);
   if (splits <= 1 || ws == nullptr)
-    return vmtl_conv2d_fwd(x, wp, bias, y, nullptr, B, H, W, Cs, Ho, Wo, ldy, Nw, Cout, KH, KW, stride, pad, 0, 0, stream);
+    return vmtl_conv2d_fwd_p(x, wp, bias, y, nullptr, B, H, W, Cs, Ho, Wo, ldy, Nw, Cout, KH, KW, stride, pad, 0, 0, prec,
+                             stream);
   if (!x || !wp || !y || Cs <= 0 || (Cs & 3) || Nw > ldy || Cout > ldy) return VMTL_ERR_ARG;
   if ((H + 2 * pad - KH) / stride + 1 != Ho || (W + 2 * pad - KW) / stride + 1 != Wo) return VMTL_ERR_ARG;
   ConvP p;
@@ -1045,22 +1124,22 @@ extern "C" int vmtl_conv2d_fwd_ws(const float* x, const float* wp, const float* 
   hipStream_t st = (hipStream_t)stream;
   int rc;
   switch (conv_pick_tile(p.M, ldy)) {
-    case 0: rc = launch_conv<2, 2, 4, 1>(p, st); break;
-    case 1: rc = launch_conv<2, 3, 4, 1>(p, st); break;
-    case 2: rc = launch_conv<2, 4, 4, 1>(p, st); break;
-    case 3: rc = launch_conv<2, 5, 4, 1>(p, st); break;
-    case 4: rc = launch_conv<4, 3, 2, 2>(p, st); break;
-    case 5: rc = launch_conv<4, 4, 2, 2>(p, st); break;
-    case 6: rc = launch_conv<2, 9, 4, 1>(p, st); break;
-    case 7: rc = launch_conv<4, 5, 2, 2>(p, st); break;
-    case 8: rc = launch_conv<1, 2, 4, 1>(p, st); break;
-    case 9: rc = launch_conv<1, 4, 4, 1>(p, st); break;
-    case 10: rc = launch_conv<2, 4, 2, 2>(p, st); break;
-    case 11: rc = launch_conv<1, 9, 4, 1>(p, st); break;
-    case 12: rc = launch_conv<2, 2, 4, 1, false, 4>(p, st); break;
-    case 13: rc = launch_conv<2, 1, 4, 1, false, 4>(p, st); break;
-    case 14: rc = launch_conv<2, 4, 4, 1, false, 4>(p, st); break;
-    default: rc = launch_conv<2, 1, 4, 1>(p, st); break;
+    case 0: rc = launch_conv<2, 2, 4, 1>(p, st, prec); break;
+    case 1: rc = launch_conv<2, 3, 4, 1>(p, st, prec); break;
+    case 2: rc = launch_conv<2, 4, 4, 1>(p, st, prec); break;
+    case 3: rc = launch_conv<2, 5, 4, 1>(p, st, prec); break;
+    case 4: rc = launch_conv<4, 3, 2, 2>(p, st, prec); break;
+    case 5: rc = launch_conv<4, 4, 2, 2>(p, st, prec); break;
+    case 6: rc = launch_conv<2, 9, 4, 1>(p, st, prec); break;
+    case 7: rc = launch_conv<4, 5, 2, 2>(p, st, prec); break;
+    case 8: rc = launch_conv<1, 2, 4, 1>(p, st, prec); break;
+    case 9: rc = launch_conv<1, 4, 4, 1>(p, st, prec); break;
+    case 10: rc = launch_conv<2, 4, 2, 2>(p, st, prec); break;
+    case 11: rc = launch_conv<1, 9, 4, 1>(p, st, prec); break;
+    case 12: rc = launch_conv<2, 2, 4, 1, false, 4>(p, st, prec); break;
+    case 13: rc = launch_conv<2, 1, 4, 1, false, 4>(p, st, prec); break;
+    case 14: rc = launch_conv<2, 4, 4, 1, false, 4>(p, st, prec); break;
+    default: rc = launch_conv<2, 1, 4, 1>(p, st, prec); break;
   }
   if (rc) return rc;
   const long long n4 = (long long)p.M * ldy / 4;
@@ -1068,6 +1147,13 @@ extern "C" int vmtl_conv2d_fwd_ws(const float* x, const float* wp, const float* 
   if (nb > 4096) nb = 4096;
   hipLaunchKernelGGL(sum_slabs_kernel, dim3((int)nb), dim3(256), 0, st, ws, y, splits, n4, bias, ldy, Cout);
   return vmtl_check_launch();
+}
+
+extern "C" int vmtl_conv2d_fwd_ws(const float* x, const float* wp, const float* bias, float* y, float* ws, int B, int H,
+                                  int W, int Cs, int Ho, int Wo, int ldy, int Nw, int Cout, int KH, int KW, int stride,
+                                  int pad, void* stream) {
+  return vmtl_conv2d_fwd_ws_p(x, wp, bias, y, ws, B, H, W, Cs, Ho, Wo, ldy, Nw, Cout, KH, KW, stride, pad, VMTL_PREC_FP32,
+                              stream);
 }
 
 // ---- nearest-x2 upsample + concat + 3x3 conv as four 2x2 phase convolutions ------------------------
@@ -1101,12 +1187,14 @@ extern "C" int vmtl_conv2d_up2_ksplit(int B, int H2, int W2, int ldy, int Ktot) 
   return ksplit_for((long long)cdiv(Mq, kTiles[id].bm) * 4 * cdiv(ldy, kTiles[id].bn), cdiv(Ktot, BK), ldy);
 }
 
-static int up2_launch(ConvP& p, int id, hipStream_t st);
+static int up2_launch(ConvP& p, int id, hipStream_t st, int prec);
 
 // stats (optional): [4 * ceil(B*H2*W2 / block)][2][ldy]; only valid when block divides B*H2*W2
-extern "C" int vmtl_conv2d_up2_fwd(const float* xl, const float* skip, const float* wp_eff, float* y, float* stats,
-                                   int B, int H2, int W2, int C0s, int C1s, int ldy, int Cout, void* stream) {
+extern "C" int vmtl_conv2d_up2_fwd_p(const float* xl, const float* skip, const float* wp_eff, float* y, float* stats,
+                                     int B, int H2, int W2, int C0s, int C1s, int ldy, int Cout, int precision,
+                                     void* stream) {
   VMTL_ENTER();
+  if (!valid_prec(precision)) return VMTL_ERR_ARG;
   if (!xl || !wp_eff || !y || B <= 0 || H2 <= 0 || W2 <= 0 || C0s <= 0 || (C0s & 3) || (C1s & 3) || C1s < 0)
     return VMTL_ERR_ARG;
   if ((skip == nullptr) != (C1s == 0) || Cout <= 0 || Cout > ldy) return VMTL_ERR_ARG;
@@ -1119,17 +1207,24 @@ extern "C" int vmtl_conv2d_up2_fwd(const float* xl, const float* skip, const flo
   p.ez_x = nullptr; p.ez_mean = p.ez_invstd = p.ez_gamma = p.ez_beta = nullptr; p.ez_act = 0;
   const int id = up2_pick_tile(p.M, ldy);
   if (stats && (p.M % kTiles[id].bm)) return VMTL_ERR_ARG;
-  return up2_launch(p, id, (hipStream_t)stream);
+  return up2_launch(p, id, (hipStream_t)stream, precision);
+}
+
+extern "C" int vmtl_conv2d_up2_fwd(const float* xl, const float* skip, const float* wp_eff, float* y, float* stats,
+                                   int B, int H2, int W2, int C0s, int C1s, int ldy, int Cout, void* stream) {
+  return vmtl_conv2d_up2_fwd_p(xl, skip, wp_eff, y, stats, B, H2, W2, C0s, C1s, ldy, Cout, VMTL_PREC_FP32, stream);
 }
 
 // split-K form (no statistics): ws = vmtl_conv2d_up2_ksplit(...) * B*2H2*2W2*ldy floats; the slices' partial outputs
 // (full-resolution layout each) are summed in slice order
-extern "C" int vmtl_conv2d_up2_fwd_ws(const float* xl, const float* skip, const float* wp_eff, float* y, float* ws, int B,
-                                      int H2, int W2, int C0s, int C1s, int ldy, int Cout, void* stream) {
+extern "C" int vmtl_conv2d_up2_fwd_ws_p(const float* xl, const float* skip, const float* wp_eff, float* y, float* ws,
+                                        int B, int H2, int W2, int C0s, int C1s, int ldy, int Cout, int precision,
+                                        void* stream) {
   VMTL_ENTER();
+  if (!valid_prec(precision)) return VMTL_ERR_ARG;
   const int splits = vmtl_conv2d_up2_ksplit(B, H2, W2, ldy, 4 * C0s + 9 * C1s);
   if (splits <= 1 || ws == nullptr)
-    return vmtl_conv2d_up2_fwd(xl, skip, wp_eff, y, nullptr, B, H2, W2, C0s, C1s, ldy, Cout, stream);
+    return vmtl_conv2d_up2_fwd_p(xl, skip, wp_eff, y, nullptr, B, H2, W2, C0s, C1s, ldy, Cout, precision, stream);
   if (!xl || !wp_eff || !y || B <= 0 || H2 <= 0 || W2 <= 0 || C0s <= 0 || (C0s & 3) || (C1s & 3) || C1s < 0)
     return VMTL_ERR_ARG;
   if ((skip == nullptr) != (C1s == 0) || Cout <= 0 || Cout > ldy || (ldy & 3)) return VMTL_ERR_ARG;
@@ -1141,7 +1236,7 @@ extern "C" int vmtl_conv2d_up2_fwd_ws(const float* xl, const float* skip, const 
   p.act = 0; p.shuffle = 0; p.ksplit = splits; p.ksteps_per_split = cdiv(cdiv(p.Ktot, BK), splits);
   p.ez_x = nullptr; p.ez_mean = p.ez_invstd = p.ez_gamma = p.ez_beta = nullptr; p.ez_act = 0;
   hipStream_t st = (hipStream_t)stream;
-  const int rc = up2_launch(p, up2_pick_tile(p.M, ldy), st);
+  const int rc = up2_launch(p, up2_pick_tile(p.M, ldy), st, precision);
   if (rc) return rc;
   const long long n4 = (long long)4 * p.M * ldy / 4;
   long long nb = cdivll(n4, 256);
@@ -1150,23 +1245,28 @@ extern "C" int vmtl_conv2d_up2_fwd_ws(const float* xl, const float* skip, const 
   return vmtl_check_launch();
 }
 
-static int up2_launch(ConvP& p, int id, hipStream_t st) {
+extern "C" int vmtl_conv2d_up2_fwd_ws(const float* xl, const float* skip, const float* wp_eff, float* y, float* ws, int B,
+                                      int H2, int W2, int C0s, int C1s, int ldy, int Cout, void* stream) {
+  return vmtl_conv2d_up2_fwd_ws_p(xl, skip, wp_eff, y, ws, B, H2, W2, C0s, C1s, ldy, Cout, VMTL_PREC_FP32, stream);
+}
+
+static int up2_launch(ConvP& p, int id, hipStream_t st, int prec) {
   switch (id) {
-    case 0: return launch_conv<2, 2, 4, 1, true>(p, st);
-    case 1: return launch_conv<2, 3, 4, 1, true>(p, st);
-    case 2: return launch_conv<2, 4, 4, 1, true>(p, st);
-    case 3: return launch_conv<2, 5, 4, 1, true>(p, st);
-    case 4: return launch_conv<4, 3, 2, 2, true>(p, st);
-    case 5: return launch_conv<4, 4, 2, 2, true>(p, st);
-    case 6: return launch_conv<2, 9, 4, 1, true>(p, st);
-    case 7: return launch_conv<4, 5, 2, 2, true>(p, st);
-    case 8: return launch_conv<1, 2, 4, 1, true>(p, st);
-    case 9: return launch_conv<1, 4, 4, 1, true>(p, st);
-    case 10: return launch_conv<2, 4, 2, 2, true>(p, st);
-    case 11: return launch_conv<1, 9, 4, 1, true>(p, st);
-    case 12: return launch_conv<2, 2, 4, 1, true, 4>(p, st);
-    case 13: return launch_conv<2, 1, 4, 1, true, 4>(p, st);
-    case 14: return launch_conv<2, 4, 4, 1, true, 4>(p, st);
-    default: return launch_conv<2, 1, 4, 1, true>(p, st);
+    case 0: return launch_conv<2, 2, 4, 1, true>(p, st, prec);
+    case 1: return launch_conv<2, 3, 4, 1, true>(p, st, prec);
+    case 2: return launch_conv<2, 4, 4, 1, true>(p, st, prec);
+    case 3: return launch_conv<2, 5, 4, 1, true>(p, st, prec);
+    case 4: return launch_conv<4, 3, 2, 2, true>(p, st, prec);
+    case 5: return launch_conv<4, 4, 2, 2, true>(p, st, prec);
+    case 6: return launch_conv<2, 9, 4, 1, true>(p, st, prec);
+    case 7: return launch_conv<4, 5, 2, 2, true>(p, st, prec);
+    case 8: return launch_conv<1, 2, 4, 1, true>(p, st, prec);
+    case 9: return launch_conv<1, 4, 4, 1, true>(p, st, prec);
+    case 10: return launch_conv<2, 4, 2, 2, true>(p, st, prec);
+    case 11: return launch_conv<1, 9, 4, 1, true>(p, st, prec);
+    case 12: return launch_conv<2, 2, 4, 1, true, 4>(p, st, prec);
+    case 13: return launch_conv<2, 1, 4, 1, true, 4>(p, st, prec);
+    case 14: return launch_conv<2, 4, 4, 1, true, 4>(p, st, prec);
+    default: return launch_conv<2, 1, 4, 1, true>(p, st, prec);
   }
 }

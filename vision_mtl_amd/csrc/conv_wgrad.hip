@@ -12,6 +12,10 @@
 // banks, so the quarters of a group (consecutive pixel rows) must land on disjoint bank ranges: the row stride is padded to
 // == 16 (mod 64) floats (wg_ld below).  Round 2 used stride = width + 4 (== 4 or 20 mod 32): 12 (4) of the 16 banks
 // of the two quarters overlapped - 0.38-0.41 of the LDS cycles were bank conflicts (profiles/r02_*_pmc.json).
+// BF16 (VMTL_PREC_BF16, the *_p entry points): the fragments are rounded to bf16 as they are read (plain casts:
+// v_cvt_pk_bf16_f32) and one v_mfma_f32_16x16x32_bf16 per (i, j) covers the whole 32-pixel chunk.  Element s of a lane's
+// 8-element fragment is pixel 4s+lq - the LDS words the fp32 path reads at step s, so the bank pattern is unchanged (the
+// pixel order inside a chunk is free as long as both operands use the same one).  Tail rows multiply the rounded values.
 // Each pixel slice
 // writes its own slab with plain stores; vmtl_unpack_weights sums the slabs in a fixed
 // order (deterministic, no float atomics) while converting to the torch layout.
@@ -34,6 +38,13 @@ struct WgradP {
 };
 
 #define BP 32
+
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+// (lo, hi) rounded to bf16 (round-to-nearest-even, NaN stays NaN: a plain cast, v_cvt_pk_bf16_f32), packed in one word
+__device__ __forceinline__ unsigned rne_bf16x2(float lo, float hi) {
+  return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){lo, hi}, bf16x2));
+}
 #define WG_BNK 128  // kk columns per workgroup (4 waves x 2 tiles x 16)
 
 // smallest row stride >= w (floats, multiple of 4) that is == 16 (mod 64): the four pixel rows of one fragment read
@@ -58,7 +69,8 @@ static_assert(wg_ld(16) == 16 && wg_ld(20) == 80 && wg_ld(144) == 144 && wg_ld(1
 // scalar chunk base + per-thread constant, its bounds test one add + one compare.  The general loader tracks
 // (b, ho, wo) per gather row in vector registers and rebuilds every offset with two quarter-rate multiplies: ~10
 // non-MFMA instructions per MFMA on the 32-row tile (ISA count), which is what bounded the narrow tiles.
-template <int TM, int NTR = 0, int PM = 1, int PD = (TM <= 2 ? 3 : (TM <= 4 && NTR == 0) ? 2 : 1), bool FAST = false>
+template <int TM, int NTR = 0, int PM = 1, int PD = (TM <= 2 ? 3 : (TM <= 4 && NTR == 0) ? 2 : 1), bool FAST = false,
+          bool BF16 = false>
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradP p) {
   constexpr int TN = 2;
   constexpr int BMM = TM * 16;    // rows covered by MFMA tiles
@@ -252,6 +264,42 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradP p) {
     if (nj == 0) return;
     const float* ys = Ys + cb * BP * LDY + lq * LDY + l15;
     const float* xs = Xs + cb * BP * LDX + lq * LDX + wn * TN * 16 + l15;
+    if constexpr (BF16) {
+      unsigned fa[TM][4], fb[TN][4];  // packed bf16 pairs: word w holds pixels 4(2w)+lq and 4(2w+1)+lq
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+          fa[i][w] = rne_bf16x2(ys[8 * w * LDY + i * 16], ys[(8 * w + 4) * LDY + i * 16]);
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+          fb[j][w] = rne_bf16x2(xs[8 * w * LDX + j * 16], xs[(8 * w + 4) * LDX + j * 16]);
+      }
+#pragma unroll
+      for (int j = 0; j < TN; ++j) {
+        if (j > 0 && j >= nj) break;
+        const bf16x8 b = __builtin_bit_cast(bf16x8, (u32x4){fb[j][0], fb[j][1], fb[j][2], fb[j][3]});
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              __builtin_bit_cast(bf16x8, (u32x4){fa[i][0], fa[i][1], fa[i][2], fa[i][3]}), b, acc[i][j], 0, 0, 0);
+      }
+      if (NTR > 0) {  // dY[pixel 4s+lq][BMM .. BMM+3] rounded, against the rounded X fragment element s
+#pragma unroll
+        for (int s = 0; s < BP / 4; ++s) {
+          const f32x4 ty = *reinterpret_cast<const f32x4*>(Ys + cb * BP * LDY + (4 * s + lq) * LDY + BMM);
+#pragma unroll
+          for (int t = 0; t < NTR; ++t) {
+            if (t >= ntr) break;
+            const float tyr = (float)(__bf16)ty[t];
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+              tacc[t][j] += tyr * __uint_as_float((s & 1) ? (fb[j][s >> 1] & 0xFFFF0000u) : (fb[j][s >> 1] << 16));
+          }
+        }
+      }
+      return;
+    }
 #pragma unroll
     for (int s = 0; s < BP / 4; ++s) {  // 4 pixels per MFMA: lane quarter q supplies pixel 4s+q
       float fa[TM], fb[TN];
@@ -426,7 +474,7 @@ static int wgrad_splits_uncached(int M, int Nw, int Ktot) {
   return (int)best;
 }
 
-template <int TM, int NTR, int PM, bool FAST>
+template <int TM, int NTR, int PM, bool FAST, bool BF16 = false>
 static int launch_wgrad_pm(WgradP& p, int splits, hipStream_t st);
 
 // Stride rule per tile height.  Measured on MI355X (tools/bench_conv.py, VMTL_WG_PAD A/B, round 3): the conflict-free
@@ -452,11 +500,11 @@ static bool wgrad_fast_ok(const WgradP& p) {
 }
 
 template <int TM, int NTR = 0>
-static int launch_wgrad(WgradP& p, int splits, hipStream_t st) {
+static int launch_wgrad(WgradP& p, int splits, hipStream_t st, int prec) {
   constexpr int PMD = wg_pm<TM * 16 + NTR>();
 #ifdef VMTL_TUNING
   static EnvInt e_pad{"VMTL_WG_PAD", -1};  // force one LDS row-stride rule (wg_ld) for every tile height
-  switch (env_int(e_pad)) {
+  switch (prec == VMTL_PREC_FP32 ? env_int(e_pad) : -1) {
     case 0: return launch_wgrad_pm<TM, NTR, 0, false>(p, splits, st);
     case 1: return launch_wgrad_pm<TM, NTR, 1, false>(p, splits, st);
     case 2: return launch_wgrad_pm<TM, NTR, 2, false>(p, splits, st);
@@ -467,18 +515,22 @@ static int launch_wgrad(WgradP& p, int splits, hipStream_t st) {
     // a pointwise conv has no borders: one flat row of M pixels (so any image width takes the scalar-chunk loader)
     p.B = 1; p.H = 1; p.W = p.M; p.Ho = 1; p.Wo = p.M;
   }
+  if (prec == VMTL_PREC_BF16) {
+    if (wgrad_fast_ok(p)) return launch_wgrad_pm<TM, NTR, PMD, true, true>(p, splits, st);
+    return launch_wgrad_pm<TM, NTR, PMD, false, true>(p, splits, st);
+  }
   if (wgrad_fast_ok(p)) return launch_wgrad_pm<TM, NTR, PMD, true>(p, splits, st);
   return launch_wgrad_pm<TM, NTR, PMD, false>(p, splits, st);
 }
 
-template <int TM, int NTR, int PM, bool FAST>
+template <int TM, int NTR, int PM, bool FAST, bool BF16>
 static int launch_wgrad_pm(WgradP& p, int splits, hipStream_t st) {
   constexpr int BMC = TM * 16 + NTR;
   constexpr int PD = (TM <= 2 ? 3 : (TM <= 4 && NTR == 0) ? 2 : 1);
   const size_t lds = (size_t)2 * BP * (wg_ld(BMC, PM) + wg_ld(WG_BNK, PM)) * sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<TM, NTR, PM, PD, FAST>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<TM, NTR, PM, PD, FAST, BF16>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_set = true;
   }
@@ -487,18 +539,18 @@ static int launch_wgrad_pm(WgradP& p, int splits, hipStream_t st) {
   p.tiles_kk = cdiv(p.Ktot, WG_BNK);
   p.tiles_co = cdiv(p.Nw, BMC);
   p.splits = splits;
-  hipLaunchKernelGGL((conv_wgrad_kernel<TM, NTR, PM, PD, FAST>), dim3(p.tiles_kk * p.tiles_co * splits), dim3(256), lds, st,
+  hipLaunchKernelGGL((conv_wgrad_kernel<TM, NTR, PM, PD, FAST, BF16>), dim3(p.tiles_kk * p.tiles_co * splits), dim3(256), lds, st,
                      p);
   return vmtl_check_launch();
 }
 
-static int wgrad_dispatch(WgradP& p, int splits, void* stream);
+static int wgrad_dispatch(WgradP& p, int splits, void* stream, int prec);
 
-extern "C" int vmtl_conv2d_wgrad(const float* x, const float* dy, float* slabs, int splits, int B, int H, int W,
-                                 int Cs, int Ho, int Wo, int ldy, int Nw, int KH, int KW, int stride, int pad,
-                                 void* stream) {
+extern "C" int vmtl_conv2d_wgrad_p(const float* x, const float* dy, float* slabs, int splits, int B, int H, int W,
+                                   int Cs, int Ho, int Wo, int ldy, int Nw, int KH, int KW, int stride, int pad,
+                                   int precision, void* stream) {
   VMTL_ENTER();
-  if (!x || !dy || !slabs) return VMTL_ERR_ARG;
+  if (!valid_prec(precision) || !x || !dy || !slabs) return VMTL_ERR_ARG;
   if (Cs <= 0 || (Cs & 3) || (ldy & 3) || Nw <= 0 || Nw > ldy) return VMTL_ERR_ARG;
   if ((H + 2 * pad - KH) / stride + 1 != Ho || (W + 2 * pad - KW) / stride + 1 != Wo) return VMTL_ERR_ARG;
   if ((long long)B * Ho * Wo > 0x7fffffffLL || (long long)B * H * W > 0x7fffffffLL) return VMTL_ERR_ARG;
@@ -506,14 +558,22 @@ extern "C" int vmtl_conv2d_wgrad(const float* x, const float* dy, float* slabs, 
   p.x = x; p.dy = dy; p.slabs = slabs; p.B = B; p.H = H; p.W = W; p.Cs = Cs; p.Ho = Ho; p.Wo = Wo; p.ldy = ldy;
   p.Nw = Nw; p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.Ktot = KH * KW * Cs; p.M = B * Ho * Wo;
   p.x2 = nullptr; p.K1 = 0;
-  return wgrad_dispatch(p, splits, stream);
+  return wgrad_dispatch(p, splits, stream, precision);
+}
+
+extern "C" int vmtl_conv2d_wgrad(const float* x, const float* dy, float* slabs, int splits, int B, int H, int W,
+                                 int Cs, int Ho, int Wo, int ldy, int Nw, int KH, int KW, int stride, int pad,
+                                 void* stream) {
+  return vmtl_conv2d_wgrad_p(x, dy, slabs, splits, B, H, W, Cs, Ho, Wo, ldy, Nw, KH, KW, stride, pad, VMTL_PREC_FP32,
+                             stream);
 }
 
 // weight gradient of conv1x1(cat[x, x2]) (vmtl_conv1x1_cat_fwd) in one launch: slabs [splits][Nw][K1 + K2s] with
 // splits = vmtl_conv2d_wgrad_splits(M, Nw, K1 + K2s); x [M][K1] (K1 % 4 == 0), x2 [M][K2s]
-extern "C" int vmtl_conv1x1_cat_wgrad(const float* x, int K1, const float* x2, int K2s, const float* dy, float* slabs,
-                                      int splits, int M, int ldy, int Nw, void* stream) {
+extern "C" int vmtl_conv1x1_cat_wgrad_p(const float* x, int K1, const float* x2, int K2s, const float* dy, float* slabs,
+                                        int splits, int M, int ldy, int Nw, int precision, void* stream) {
   VMTL_ENTER();
+  if (!valid_prec(precision)) return VMTL_ERR_ARG;
   if (!x || !x2 || !dy || !slabs || M <= 0 || K1 <= 0 || (K1 & 3) || K2s <= 0 || (K2s & 3) || (ldy & 3) || Nw <= 0 ||
       Nw > ldy)
     return VMTL_ERR_ARG;
@@ -521,24 +581,29 @@ extern "C" int vmtl_conv1x1_cat_wgrad(const float* x, int K1, const float* x2, i
   p.x = x; p.dy = dy; p.slabs = slabs; p.B = 1; p.H = 1; p.W = M; p.Cs = K1 + K2s; p.Ho = 1; p.Wo = M; p.ldy = ldy;
   p.Nw = Nw; p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0; p.Ktot = p.Cs; p.M = M;
   p.x2 = x2; p.K1 = K1;
-  return wgrad_dispatch(p, splits, stream);
+  return wgrad_dispatch(p, splits, stream, precision);
 }
 
-static int wgrad_dispatch(WgradP& p, int splits, void* stream) {
+extern "C" int vmtl_conv1x1_cat_wgrad(const float* x, int K1, const float* x2, int K2s, const float* dy, float* slabs,
+                                      int splits, int M, int ldy, int Nw, void* stream) {
+  return vmtl_conv1x1_cat_wgrad_p(x, K1, x2, K2s, dy, slabs, splits, M, ldy, Nw, VMTL_PREC_FP32, stream);
+}
+
+static int wgrad_dispatch(WgradP& p, int splits, void* stream, int prec) {
   const int Nw = p.Nw;
   if (splits != vmtl_conv2d_wgrad_splits(p.M, Nw, p.Ktot)) return VMTL_ERR_ARG;
   p.chunk = cdiv(cdiv(p.M, splits), BP) * BP;
   hipStream_t st = (hipStream_t)stream;
   switch (wgrad_rows(Nw)) {
-    case 16: return launch_wgrad<1>(p, splits, st);
-    case 32: return launch_wgrad<2>(p, splits, st);
-    case 48: return launch_wgrad<3>(p, splits, st);
-    case 64: return launch_wgrad<4>(p, splits, st);
-    case 80: return launch_wgrad<5>(p, splits, st);
-    case 20: return launch_wgrad<1, 4>(p, splits, st);
-    case 36: return launch_wgrad<2, 4>(p, splits, st);
-    case 68: return launch_wgrad<4, 4>(p, splits, st);
-    case 128: return launch_wgrad<8>(p, splits, st);
-    default: return launch_wgrad<9>(p, splits, st);
+    case 16: return launch_wgrad<1>(p, splits, st, prec);
+    case 32: return launch_wgrad<2>(p, splits, st, prec);
+    case 48: return launch_wgrad<3>(p, splits, st, prec);
+    case 64: return launch_wgrad<4>(p, splits, st, prec);
+    case 80: return launch_wgrad<5>(p, splits, st, prec);
+    case 20: return launch_wgrad<1, 4>(p, splits, st, prec);
+    case 36: return launch_wgrad<2, 4>(p, splits, st, prec);
+    case 68: return launch_wgrad<4, 4>(p, splits, st, prec);
+    case 128: return launch_wgrad<8>(p, splits, st, prec);
+    default: return launch_wgrad<9>(p, splits, st, prec);
   }
 }

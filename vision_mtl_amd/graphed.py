@@ -32,6 +32,7 @@ from __future__ import annotations
 import torch
 
 from . import dp, ops
+from .precision import conv_precision, get_conv_precision
 
 
 class _Replayed(torch.autograd.Function):
@@ -55,7 +56,9 @@ class GraphedStep:
     data.upload_batch inside the graph).  arena: an existing dp.FlatArena of module.model (default: module.dp_arena,
     else a new one - built here, so construct the GraphedStep on every rank).  warmup: eager steps before capture
     (allocator pools, code objects, packed-operand table).  NOTE: the warm-up steps and the capture rehearsal run real
-    training steps on `example_batch` (BatchNorm running statistics move, no optimizer step is taken)."""
+    training steps on `example_batch` (BatchNorm running statistics move, no optimizer step is taken).  The step is captured
+    under the convolution precision in force at construction (recorded as `conv_precision`), and every replay keeps it
+    whatever vision_mtl_amd.set_conv_precision says later."""
 
     def __init__(self, module, example_batch: dict, arena: "dp.FlatArena | None" = None, warmup: int = 2,
                  stage: str = "train"):
@@ -70,6 +73,7 @@ class GraphedStep:
         self._fill(example_batch)
         self._sample_layout = (self.static["img"].dim() == 4 and self.static["img"].shape[-1] == 3
                                and self.static["img"].shape[1] != 3)
+        self.conv_precision = get_conv_precision()
         attached, module.dp_arena = module.dp_arena, None  # the collective stays outside the graph (see __call__)
         try:
             so = module.step_outputs[stage]
@@ -87,7 +91,7 @@ class GraphedStep:
             for k, v in so.items():
                 del v[mark[k]:]
             self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
+            with conv_precision(self.conv_precision), torch.cuda.graph(self.graph):
                 loss = self._step()
                 loss.backward()
                 # everything the step appended to step_outputs (loss + the four metrics), as ONE static vector

@@ -18,6 +18,7 @@ import weakref
 import torch
 
 from ._lib import lib
+from .precision import conv_prec_code
 
 ACT_NONE, ACT_RELU, ACT_HSWISH, ACT_HSIGMOID, ACT_SIGMOID = 0, 1, 2, 3, 4
 ACT_CODES = {None: 0, "none": 0, "relu": 1, "hardswish": 2, "hardsigmoid": 3, "sigmoid": 4}
@@ -51,6 +52,16 @@ def _k(name, _flop=None, _xflop=None, **kw):
         # really executes when an algebraic rewrite makes them differ (up2_conv)
         _RECORD.append((name, dict(kw), float(_flop), float(_flop if _xflop is None else _xflop)))
     lib().callk(name, stream=_stream(), **kw)
+
+
+def _kp(name, prec, _flop=None, _xflop=None, **kw):
+    """A launch of an entry point that has a precision variant (include/vmtl.h VMTL_PREC_*).  fp32 (0) calls the legacy
+    entry point with its legacy keywords - bench.py sorts the launches it records into families BY NAME - and only
+    bf16 calls the `_p` variant.  `prec` is what the autograd node recorded in its forward (precision.conv_prec_code)."""
+    if prec:
+        _k(name + "_p", _flop, _xflop, precision=prec, **kw)
+    else:
+        _k(name, _flop, _xflop, **kw)
 
 
 # (the launch-dropping ablation switches of round 2 - VMTL_DBG_SKIP_SIDE / VMTL_DBG_SKIP / VMTL_DBG_EXTRA - produce WRONG
@@ -431,8 +442,9 @@ def unpack(packed, shape, R1, R0, T, C, Cs, sr1, sr0, st, sc, flip=0, out=None, 
     return grad
 
 
-def _wgrad(x, dy, B, H, W, Cs, Ho, Wo, ldy, Nw, KH, KW, stride, pad, flop, xflop=None):
-    """Weight-gradient slabs [splits][Nw][KH*KW*Cs] (summed later by unpack)."""
+def _wgrad(x, dy, B, H, W, Cs, Ho, Wo, ldy, Nw, KH, KW, stride, pad, flop, xflop=None, prec=0):
+    """Weight-gradient slabs [splits][Nw][KH*KW*Cs] (summed later by unpack).  prec applies to the dense kernel only (the
+    narrow halo-tile kernel stays fp32)."""
     if (KH == 3 and KW == 3 and stride == 1 and pad == 1 and B * H * W * max(Cs, ldy) * 4 < 1 << 32
             and lib().raw("vmtl_conv3x3_wgrad_small_supported")(Cs, ldy, W)):
         # narrow full-resolution layers: the strip-walking halo kernel reads x once instead of once per tap
@@ -443,7 +455,7 @@ def _wgrad(x, dy, B, H, W, Cs, Ho, Wo, ldy, Nw, KH, KW, stride, pad, flop, xflop
         return slabs, ns
     splits = lib().raw("vmtl_conv2d_wgrad_splits")(B * Ho * Wo, Nw, KH * KW * Cs)
     slabs = _empty((splits, Nw, KH * KW * Cs), x)
-    _k("vmtl_conv2d_wgrad", _flop=flop, _xflop=xflop, x=x, dy=dy, slabs=slabs, splits=splits, B=B, H=H, W=W, Cs=Cs, Ho=Ho, Wo=Wo,
+    _kp("vmtl_conv2d_wgrad", prec, _flop=flop, _xflop=xflop, x=x, dy=dy, slabs=slabs, splits=splits, B=B, H=H, W=W, Cs=Cs, Ho=Ho, Wo=Wo,
        ldy=ldy, Nw=Nw, KH=KH, KW=KW, stride=stride, pad=pad)
     return slabs, splits
 
@@ -536,7 +548,7 @@ def conv_stats_geometry(B, Ho, Wo, Cs, ldy, KH, KW, stride, pad):
 
 
 def _conv_launch(x, wp, bias, y, stats, B, H, W, Cs, Ho, Wo, ldy, Nw, Cout, KH, KW, stride, pad, shuffle=0, cin=None,
-                 algo_flop=None):
+                 algo_flop=None, prec=0):
     flop = 2.0 * B * Ho * Wo * Nw * KH * KW * (Cs if cin is None else cin)
     if _is_pw(B, Ho, Wo, KH, KW, stride, pad, shuffle):
         _k("vmtl_conv1x1_fwd", _flop=flop if algo_flop is None else algo_flop, _xflop=flop, x=x, wp=wp, bias=bias, y=y,
@@ -553,10 +565,10 @@ def _conv_launch(x, wp, bias, y, stats, B, H, W, Cs, Ho, Wo, ldy, Nw, Cout, KH, 
         ks = lib().raw("vmtl_conv2d_ksplit")(B, Ho, Wo, ldy, KH * KW * Cs)
         if ks > 1:
             ws = _empty((ks, B * Ho * Wo, ldy), x)
-            _k("vmtl_conv2d_fwd_ws", _flop=flop if algo_flop is None else algo_flop, _xflop=flop, x=x, wp=wp, bias=bias, y=y,
+            _kp("vmtl_conv2d_fwd_ws", prec, _flop=flop if algo_flop is None else algo_flop, _xflop=flop, x=x, wp=wp, bias=bias, y=y,
                ws=ws, B=B, H=H, W=W, Cs=Cs, Ho=Ho, Wo=Wo, ldy=ldy, Nw=Nw, Cout=Cout, KH=KH, KW=KW, stride=stride, pad=pad)
             return
-    _k("vmtl_conv2d_fwd", _flop=flop if algo_flop is None else algo_flop, _xflop=flop, x=x, wp=wp, bias=bias, y=y, stats=stats, B=B, H=H, W=W, Cs=Cs, Ho=Ho, Wo=Wo, ldy=ldy,
+    _kp("vmtl_conv2d_fwd", prec, _flop=flop if algo_flop is None else algo_flop, _xflop=flop, x=x, wp=wp, bias=bias, y=y, stats=stats, B=B, H=H, W=W, Cs=Cs, Ho=Ho, Wo=Wo, ldy=ldy,
        Nw=Nw, Cout=Cout, KH=KH, KW=KW, stride=stride, pad=pad, act=0, shuffle=shuffle)
 
 
@@ -605,7 +617,8 @@ class _Conv2d(torch.autograd.Function):
         if want_stats:
             rows, _ = conv_stats_geometry(B, Ho, Wo, Cs, ldy, KH, KW, stride, pad)
             stats = _empty((rows, 2, ldy), x)
-        _conv_launch(x, wp, bias, y, stats, B, H, W, Cs, Ho, Wo, ldy, Cout, Cout, KH, KW, stride, pad, cin=Cin)
+        prec = ctx.prec = conv_prec_code()  # backward runs under the precision of this forward
+        _conv_launch(x, wp, bias, y, stats, B, H, W, Cs, Ho, Wo, ldy, Cout, Cout, KH, KW, stride, pad, cin=Cin, prec=prec)
         ctx.save_for_backward(x, weight, stitch_w)
         ctx.cfg = (stride, pad, bias is not None)
         ctx.zero_bias_grad = bool(zero_bias_grad)
@@ -644,12 +657,13 @@ class _Conv2d(torch.autograd.Function):
                 wd = packs.get(weight, f"dgrad_st{stitch_task}", (1, Cin, KK, Cout, ldy, 0, KK, 1, Cin * KK, 1),
                                scale=(stitch_w, soff, sstride, 2))
             dx = _empty((B, H, W, Cs), x)
-            _conv_launch(dy, wd, None, dx, None, B, Ho, Wo, ldy, H, W, Cs, Cin, Cin, KH, KW, 1, KH - 1 - pad, cin=Cout)
+            _conv_launch(dy, wd, None, dx, None, B, Ho, Wo, ldy, H, W, Cs, Cin, Cin, KH, KW, 1, KH - 1 - pad, cin=Cout,
+                         prec=ctx.prec)
         if ctx.needs_input_grad[1] or (stitch_w is not None and ctx.needs_input_grad[7]):
             use_side = ctx.slots[0] is not None and (stitch_w is None or stitch_slot is not None)
             with side.branch(use_side, B * Ho * Wo, fork, x, dy):
                 slabs, ns = _wgrad(x, dy, B, H, W, Cs, Ho, Wo, ldy, Cout, KH, KW, stride, pad,
-                                   2.0 * B * Ho * Wo * Cout * KK * Cin)
+                                   2.0 * B * Ho * Wo * Cout * KK * Cin, prec=ctx.prec)
                 if stitch_w is None:
                     dw = unpack(slabs, weight.shape, 1, Cout, KK, Cin, Cs, 0, Cin * KK, 1, KK, out=ctx.slots[0], nslabs=ns)
                 else:
@@ -710,6 +724,7 @@ class _BNActPw(torch.autograd.Function):
                wp=wp, bias=bias, y=y, stats=ostats, M=M, Ks=Cs, ldy=ldy, Nw=Cout, Cout=Cout)
         ctx.save_for_backward(x, a, weight, mean, invstd, gamma, beta)
         ctx.cfg = (C, training, act, bias is not None, bool(zero_bias_grad), res is not None)
+        ctx.prec = conv_prec_code()  # the weight gradient's (the pointwise GEMMs themselves stay fp32)
         ctx.slots = (_slot(gamma), _slot(beta), _slot(weight), _slot(bias))
         ctx.bias = bias
         ctx.set_materialize_grads(False)
@@ -760,7 +775,7 @@ class _BNActPw(torch.autograd.Function):
         # ---- parameter gradients (side stream when they go to arena slots)
         dw = _empty(weight.shape, x) if sw is None else sw
         with side.branch(sw is not None, M, fork, dy, a):
-            slabs, ns = _wgrad(a, dy, B, H, W, Cs, H, W, ldy, Cout, 1, 1, 1, 0, 2.0 * M * Cout * Cin)
+            slabs, ns = _wgrad(a, dy, B, H, W, Cs, H, W, ldy, Cout, 1, 1, 1, 0, 2.0 * M * Cout * Cin, prec=ctx.prec)
             unpack(slabs, weight.shape, 1, Cout, 1, Cin, Cs, 0, Cin, 1, 1, out=dw, nslabs=ns)
         db = None
         if has_bias and ctx.needs_input_grad[9]:
@@ -822,6 +837,7 @@ class _Conv1x1Cat(torch.autograd.Function):
            M=M, ldy=ldy, Nw=Cout, Cout=Cout)
         ctx.save_for_backward(xa, xb, weight)
         ctx.cfg = (Cb, bias is not None, bool(zero_bias_grad))
+        ctx.prec = conv_prec_code()  # the weight gradient's (the pointwise GEMMs themselves stay fp32)
         ctx.slots = (_slot(weight), _slot(bias))
         ctx.bias = bias
         ctx.set_materialize_grads(False)
@@ -855,7 +871,7 @@ class _Conv1x1Cat(torch.autograd.Function):
                 Ks = Ca + Cbs
                 ns = lib().raw("vmtl_conv2d_wgrad_splits")(M, Cout, Ks)
                 slabs = _empty((ns, Cout, Ks), xa)
-                _k("vmtl_conv1x1_cat_wgrad", _flop=2.0 * M * Cout * Cin, x=xa, K1=Ca, x2=xb, K2s=Cbs, dy=dy, slabs=slabs,
+                _kp("vmtl_conv1x1_cat_wgrad", ctx.prec, _flop=2.0 * M * Cout * Cin, x=xa, K1=Ca, x2=xb, K2s=Cbs, dy=dy, slabs=slabs,
                    splits=ns, M=M, ldy=ldy, Nw=Cout)
                 unpack(slabs, None, 1, Cout, 1, Cin, Ks, 0, Cin, 1, 1, out=flat, nslabs=ns)
             dw = None if sw is not None else dwt
@@ -908,10 +924,11 @@ class _Up2Conv(torch.autograd.Function):
         y = _empty((B, 2 * H2, 2 * W2, ldy), xl)
         stats = None
         M = B * 4 * H2 * W2
+        prec = ctx.prec = conv_prec_code()
         # algorithmic FLOPs = the reference formulation (9 taps on every channel); executed: 4 taps on xl's
         ks = lib().raw("vmtl_conv2d_up2_ksplit")(B, H2, W2, ldy, Ktot)
         if ks > 1:  # tile-starved (deep decoder blocks at small batch): split K, no statistics epilogue
-            _k("vmtl_conv2d_up2_fwd_ws", _flop=2.0 * M * Cout * 9 * Cin, _xflop=2.0 * M * Cout * (4 * C0 + 9 * C1), xl=xl,
+            _kp("vmtl_conv2d_up2_fwd_ws", prec, _flop=2.0 * M * Cout * 9 * Cin, _xflop=2.0 * M * Cout * (4 * C0 + 9 * C1), xl=xl,
                skip=skip, wp_eff=wp, y=y, ws=_empty((ks, B, 2 * H2, 2 * W2, ldy), xl), B=B, H2=H2, W2=W2, C0s=C0s, C1s=C1s,
                ldy=ldy, Cout=Cout)
         else:
@@ -920,7 +937,7 @@ class _Up2Conv(torch.autograd.Function):
                 Mq = B * H2 * W2
                 if Mq % bm == 0:
                     stats = _empty((4 * (Mq // bm), 2, ldy), xl)
-            _k("vmtl_conv2d_up2_fwd", _flop=2.0 * M * Cout * 9 * Cin, _xflop=2.0 * M * Cout * (4 * C0 + 9 * C1), xl=xl,
+            _kp("vmtl_conv2d_up2_fwd", prec, _flop=2.0 * M * Cout * 9 * Cin, _xflop=2.0 * M * Cout * (4 * C0 + 9 * C1), xl=xl,
                skip=skip, wp_eff=wp, y=y, stats=stats, B=B, H2=H2, W2=W2, C0s=C0s, C1s=C1s, ldy=ldy, Cout=Cout)
         ctx.save_for_backward(xl, skip, weight)
         ctx.cfg = (C0, C1, stats.shape[0] if stats is not None else 0)
@@ -948,23 +965,23 @@ class _Up2Conv(torch.autograd.Function):
                 "vmtl_pack_up2_dgrad", w=w, dst=dst, Cout=Cout, Cos=ldy, C0=C0, Cin=Cin))
             dxl = _empty((B, H2, W2, C0s), xl)
             _conv_launch(dy, wd, None, dxl, None, B, H, W, ldy, H2, W2, C0s, C0, C0, 4, 4, 2, 1, cin=Cout,
-                         algo_flop=2.0 * B * H * W * C0 * 9 * Cout)
+                         algo_flop=2.0 * B * H * W * C0 * 9 * Cout, prec=ctx.prec)
         if skip is not None and ctx.needs_input_grad[1]:  # plain 3x3 data gradient restricted to the skip channels
             C1s = skip.shape[3]
             wds = packs.get(weight, "up2_dskip", (1, C1, 9, Cout, ldy, 0, 9, 1, Cin * 9, 1), offset=C0 * 9)
             dskip = _empty((B, H, W, C1s), xl)
-            _conv_launch(dy, wds, None, dskip, None, B, H, W, ldy, H, W, C1s, C1, C1, 3, 3, 1, 1, cin=Cout)
+            _conv_launch(dy, wds, None, dskip, None, B, H, W, ldy, H, W, C1s, C1, C1, 3, 3, 1, 1, cin=Cout, prec=ctx.prec)
         if ctx.needs_input_grad[2]:
             dw = _empty(weight.shape, xl) if ctx.slot is None else ctx.slot
             with side.branch(ctx.slot is not None, B * H * W, fork, dy, xl, skip):
                 # low-res part: weight gradient of that 4x4/s2/p1 convolution (dY in the role of its input)
                 slabs, ns = _wgrad(dy, xl, B, H, W, ldy, H2, W2, C0s, C0, 4, 4, 2, 1, 2.0 * B * H * W * Cout * 9 * C0,
-                                   xflop=2.0 * B * H2 * W2 * C0 * 16 * Cout)
+                                   xflop=2.0 * B * H2 * W2 * C0 * 16 * Cout, prec=ctx.prec)
                 _k("vmtl_unpack_up2", slabs=slabs, grad=dw, Cout=Cout, Cos=ldy, C0=C0, Cin=Cin, nslabs=ns)
                 if skip is not None:
                     C1s = skip.shape[3]
                     slabs, ns = _wgrad(skip, dy, B, H, W, C1s, H, W, ldy, Cout, 3, 3, 1, 1,
-                                       2.0 * B * H * W * Cout * 9 * C1)
+                                       2.0 * B * H * W * Cout * 9 * C1, prec=ctx.prec)
                     unpack(slabs, None, 1, Cout, 9, C1, C1s, 0, Cin * 9, 1, 9, out=dw.view(-1)[C0 * 9:], nslabs=ns)
                 stamp(f"side up2 M={B * H * W} N={Cout} Cin={Cin}")
             if ctx.slot is not None:
@@ -1013,6 +1030,7 @@ class _BNActConv(torch.autograd.Function):
             _k("vmtl_bn_apply", x=x, mean=mean, invstd=invstd, gamma=gamma, beta=beta, mul=None, res=None, y=a, M=M, C=C,
                Cs=Cs, act=act)
         # ---- the conv on a
+        prec = ctx.prec = conv_prec_code()
         ldy = ceil4(Cout)
         ostats, orpb = None, 0
         if up2:
@@ -1033,7 +1051,7 @@ class _BNActConv(torch.autograd.Function):
             Mo = 4 * M
             ks = lib().raw("vmtl_conv2d_up2_ksplit")(B, H, W, ldy, Ktot)
             if ks > 1:  # tile-starved (deep decoder blocks at small batch): split K, no statistics epilogue
-                _k("vmtl_conv2d_up2_fwd_ws", _flop=2.0 * Mo * Cout * 9 * Cin, _xflop=2.0 * Mo * Cout * (4 * C + 9 * C1),
+                _kp("vmtl_conv2d_up2_fwd_ws", prec, _flop=2.0 * Mo * Cout * 9 * Cin, _xflop=2.0 * Mo * Cout * (4 * C + 9 * C1),
                    xl=a, skip=skip, wp_eff=wp, y=y, ws=_empty((ks, B, 2 * H, 2 * W, ldy), x), B=B, H2=H, W2=W, C0s=Cs,
                    C1s=C1s, ldy=ldy, Cout=Cout)
             else:
@@ -1041,7 +1059,7 @@ class _BNActConv(torch.autograd.Function):
                     bm = lib().raw("vmtl_conv2d_up2_stats_block")(B, H, W, ldy)
                     if M % bm == 0:
                         ostats, orpb = _empty((4 * (M // bm), 2, ldy), x), bm
-                _k("vmtl_conv2d_up2_fwd", _flop=2.0 * Mo * Cout * 9 * Cin, _xflop=2.0 * Mo * Cout * (4 * C + 9 * C1), xl=a,
+                _kp("vmtl_conv2d_up2_fwd", prec, _flop=2.0 * Mo * Cout * 9 * Cin, _xflop=2.0 * Mo * Cout * (4 * C + 9 * C1), xl=a,
                    skip=skip, wp_eff=wp, y=y, stats=ostats, B=B, H2=H, W2=W, C0s=Cs, C1s=C1s, ldy=ldy, Cout=Cout)
         else:
             if Cin != C or skip is not None:
@@ -1051,7 +1069,7 @@ class _BNActConv(torch.autograd.Function):
             if want_stats and conv_ksplit(B, H, W, Cs, ldy, 3, 3, 1, 1) == 1:
                 rows, orpb = conv_stats_geometry(B, H, W, Cs, ldy, 3, 3, 1, 1)
                 ostats = _empty((rows, 2, ldy), x)
-            _conv_launch(a, wp, None, y, ostats, B, H, W, Cs, H, W, ldy, Cout, Cout, 3, 3, 1, 1, cin=Cin)
+            _conv_launch(a, wp, None, y, ostats, B, H, W, Cs, H, W, ldy, Cout, Cout, 3, 3, 1, 1, cin=Cin, prec=prec)
         ctx.save_for_backward(x, a, skip, weight, mean, invstd, gamma, beta)
         ctx.cfg = (C, training, act, up2)
         ctx.slots = (_slot(gamma), _slot(beta), _slot(weight))
@@ -1103,7 +1121,7 @@ class _BNActConv(torch.autograd.Function):
             else:
                 rows = lib().raw("vmtl_conv2d_stats_rows")(B, H, W, Cs)
                 part = _empty((rows, 2, Cs), x)
-                _k("vmtl_conv2d_bnbwd", _flop=flop, _xflop=xflop, x=dy, wp=wd, y=dz, stats=part, ez_x=x, ez_mean=mean,
+                _kp("vmtl_conv2d_bnbwd", ctx.prec, _flop=flop, _xflop=xflop, x=dy, wp=wd, y=dz, stats=part, ez_x=x, ez_mean=mean,
                    ez_invstd=invstd, ez_gamma=gamma, ez_beta=beta, ez_act=act, **geo)
             _k("vmtl_bn_bwd_finalize", partial=part, nblk=rows, M=M, C=C, Cs=Cs, sum_dz=dbeta, sum_dzx=dgamma, mean=None,
                invstd=None, gamma=None, training=1 if training else 0, coef_a=None, coef_b=None, coef_c=None)
@@ -1113,7 +1131,8 @@ class _BNActConv(torch.autograd.Function):
         else:  # split-K data gradient (tile-starved layers): unfused BatchNorm backward
             da = _empty(x.shape, x)
             _conv_launch(dy, wd, None, da, None, geo["B"], geo["H"], geo["W"], geo["Cs"], geo["Ho"], geo["Wo"], geo["ldy"],
-                         geo["Nw"], geo["Cout"], geo["KH"], geo["KW"], geo["stride"], geo["pad"], cin=Cout, algo_flop=flop)
+                         geo["Nw"], geo["Cout"], geo["KH"], geo["KW"], geo["stride"], geo["pad"], cin=Cout, algo_flop=flop,
+                         prec=ctx.prec)
             part = _empty((_reduce_rows(M), 2, Cs), x)
             _k("vmtl_bn_bwd", x=x, dy=da, mean=mean, invstd=invstd, gamma=gamma, beta=beta, mul=None, dmul=None,
                partial=part, sum_dz=dbeta, sum_dzx=dgamma, dx=dx if dx is not None else _empty(x.shape, x), M=M, C=C, Cs=Cs,
@@ -1123,21 +1142,21 @@ class _BNActConv(torch.autograd.Function):
             C1, C1s = Cin - C, skip.shape[3]
             wds = packs.get(weight, "up2_dskip", (1, C1, 9, Cout, ldy, 0, 9, 1, Cin * 9, 1), offset=C * 9)
             dskip = _empty(skip.shape, x)
-            _conv_launch(dy, wds, None, dskip, None, B, Hd, Wd, ldy, Hd, Wd, C1s, C1, C1, 3, 3, 1, 1, cin=Cout)
+            _conv_launch(dy, wds, None, dskip, None, B, Hd, Wd, ldy, Hd, Wd, C1s, C1, C1, 3, 3, 1, 1, cin=Cout, prec=ctx.prec)
         # ---- weight gradient (side stream when it goes to an arena slot)
         dw = _empty(weight.shape, x) if sw is None else sw
         with side.branch(sw is not None, B * Hd * Wd, fork, dy, a, skip):
             if up2:
                 slabs, ns = _wgrad(dy, a, B, Hd, Wd, ldy, H, W, Cs, C, 4, 4, 2, 1, 2.0 * B * Hd * Wd * Cout * 9 * C,
-                                   xflop=2.0 * M * C * 16 * Cout)
+                                   xflop=2.0 * M * C * 16 * Cout, prec=ctx.prec)
                 _k("vmtl_unpack_up2", slabs=slabs, grad=dw, Cout=Cout, Cos=ldy, C0=C, Cin=Cin, nslabs=ns)
                 if skip is not None:
                     C1, C1s = Cin - C, skip.shape[3]
                     slabs, ns = _wgrad(skip, dy, B, Hd, Wd, C1s, Hd, Wd, ldy, Cout, 3, 3, 1, 1,
-                                       2.0 * B * Hd * Wd * Cout * 9 * C1)
+                                       2.0 * B * Hd * Wd * Cout * 9 * C1, prec=ctx.prec)
                     unpack(slabs, None, 1, Cout, 9, C1, C1s, 0, Cin * 9, 1, 9, out=dw.view(-1)[C * 9:], nslabs=ns)
             else:
-                slabs, ns = _wgrad(a, dy, B, H, W, Cs, H, W, ldy, Cout, 3, 3, 1, 1, 2.0 * M * Cout * 9 * Cin)
+                slabs, ns = _wgrad(a, dy, B, H, W, Cs, H, W, ldy, Cout, 3, 3, 1, 1, 2.0 * M * Cout * 9 * Cin, prec=ctx.prec)
                 unpack(slabs, weight.shape, 1, Cout, 9, Cin, Cs, 0, Cin * 9, 1, 9, out=dw, nslabs=ns)
             stamp(f"side bnconv N={Cout} Cin={Cin}")
         nif = lambda g, slot: None if slot is not None else g
@@ -1972,6 +1991,7 @@ class _DecoderTail(torch.autograd.Function):
                bias=bias, yb=ob, Ca=Ca)
         ctx.save_for_backward(x1, a1, x2, a2, mean1, invstd1, mean2, invstd2, g1, b1, g2, b2, w2, wa, wb)
         ctx.cfg = (tr1, tr2)
+        ctx.prec = conv_prec_code()  # the dense weight gradients' (its convolutions run on the fp32 halo-tile kernel)
         ctx.slots = tuple(_slot(t) for t in (g1, b1, w2, g2, b2, wa, ba, wb, bb))
         _remember_mode(ctx)
         return oa, ob
@@ -2016,7 +2036,7 @@ class _DecoderTail(torch.autograd.Function):
         _small(dy, wd, dz2, B, H, W, ldyh, ldy2, C2, C2, 2.0 * M * C2 * 9 * N, stats=part2, ep_mode=2,
                ez=(x2, mean2, invstd2, g2, b2, ACT_RELU))
         with side.branch(all(s is not None for s in (swa, sba, swb, sbb)), M, fork, a2, dy):
-            slabs, ns = _wgrad(a2, dy, B, H, W, ldy2, H, W, ldyh, N, 3, 3, 1, 1, 2.0 * M * N * 9 * C2)
+            slabs, ns = _wgrad(a2, dy, B, H, W, ldy2, H, W, ldyh, N, 3, 3, 1, 1, 2.0 * M * N * 9 * C2, prec=ctx.prec)
             stride = N * 9 * ldy2
             dwa = unpack(slabs, wa.shape, 1, Ca, 9, C2, ldy2, 0, C2 * 9, 1, 9, out=swa, nslabs=ns, slab_stride=stride)
             dwb = unpack(slabs.view(-1)[Ca * 9 * ldy2:], wb.shape, 1, Cb, 9, C2, ldy2, 0, C2 * 9, 1, 9, out=swb, nslabs=ns,
@@ -2052,7 +2072,7 @@ class _DecoderTail(torch.autograd.Function):
             _k("vmtl_bn_bwd_apply", x=x1, dz=dz1, mean=mean1, invstd=invstd1, gamma=g1, sum_dz=dbeta1, sum_dzx=dgamma1,
                dx=dx1, M=M, C=C1, Cs=Cs1, training=1 if tr1 else 0)
         with side.branch(sw2 is not None, M, fork, a1, dx2):
-            slabs, ns = _wgrad(a1, dx2, B, H, W, Cs1, H, W, ldy2, C2, 3, 3, 1, 1, 2.0 * M * C2 * 9 * C1)
+            slabs, ns = _wgrad(a1, dx2, B, H, W, Cs1, H, W, ldy2, C2, 3, 3, 1, 1, 2.0 * M * C2 * 9 * C1, prec=ctx.prec)
             dw2 = unpack(slabs, w2.shape, 1, C2, 9, C1, Cs1, 0, C1 * 9, 1, 9, out=sw2, nslabs=ns)
             stamp("side tail conv2")
         nif = lambda g, slot: None if slot is not None else g
@@ -2108,7 +2128,8 @@ class _DualHead(torch.autograd.Function):
         _copy_vec(ba, bias, Ca)
         _copy_vec(bb, bias[Ca:], Cb)
         y = _empty((B, H, W, ldy), x)
-        _conv_launch(x, wp, bias, y, None, B, H, W, Cs, H, W, ldy, N, N, KH, KW, 1, pad, cin=Cin)
+        prec = ctx.prec = conv_prec_code()
+        _conv_launch(x, wp, bias, y, None, B, H, W, Cs, H, W, ldy, N, N, KH, KW, 1, pad, cin=Cin, prec=prec)
         oa, ob = _empty((B, Ca, H, W), x), _empty((B, Cb, H, W), x)
         yf = y.view(-1)
         _k("vmtl_nhwc_to_nchw", x=yf, y=oa, B=B, C=Ca, HW=H * W, Cs=ldy)
@@ -2143,9 +2164,11 @@ class _DualHead(torch.autograd.Function):
             _k("vmtl_pack_weights_slice", src=wb, dst=wd.view(-1)[Ca:], R0=Cin, T=KK, C=Cb, group=ldy, sr0=KK, st=1,
                sc=Cin * KK, flip=1)
             dx = _empty((B, H, W, Cs), x)
-            _conv_launch(dy, wd, None, dx, None, B, H, W, ldy, H, W, Cs, Cin, Cin, KH, KW, 1, KH - 1 - pad, cin=N)
+            _conv_launch(dy, wd, None, dx, None, B, H, W, ldy, H, W, Cs, Cin, Cin, KH, KW, 1, KH - 1 - pad, cin=N,
+                         prec=ctx.prec)
         with side.branch(all(s is not None for s in ctx.slots), B * H * W, fork, x, dy):
-            slabs, ns = _wgrad(x, dy, B, H, W, Cs, H, W, ldy, N, KH, KW, 1, pad, 2.0 * B * H * W * N * KK * Cin)
+            slabs, ns = _wgrad(x, dy, B, H, W, Cs, H, W, ldy, N, KH, KW, 1, pad, 2.0 * B * H * W * N * KK * Cin,
+                               prec=ctx.prec)
             stride = N * KK * Cs
             dwa = unpack(slabs, wa.shape, 1, Ca, KK, Cin, Cs, 0, Cin * KK, 1, KK, out=ctx.slots[0], nslabs=ns,
                          slab_stride=stride)
