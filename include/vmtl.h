@@ -144,6 +144,15 @@ int vmtl_conv2d_up2_fwd_ws(const float* xl, const float* skip, const float* wp_e
                            int W2, int C0s, int C1s, int ldy, int Cout, void* stream);
 int vmtl_conv2d_up2_fwd_ws_p(const float* xl, const float* skip, const float* wp_eff, float* y, float* ws, int B, int H2,
                              int W2, int C0s, int C1s, int ldy, int Cout, int precision, void* stream);
+/* the same computation for the narrow decoder shapes (vmtl_conv2d_up2_halo_supported: 68 + 0 -> 33 and 136 + 16 -> 67
+ * channels, ldy = round_up(Cout, 4), every tensor under 2 GiB) on a halo-tile kernel, fp32 only, without split-K.  stats (optional):
+ * [vmtl_conv2d_up2_halo_stat_rows(...)][2][ldy] per-tile (mean, M2), vmtl_conv2d_up2_halo_stat_block(...) pixels per
+ * row; stat_rows is 0 (and stats must be null) unless the tiles cover the image exactly.  Unsupported shapes return -3. */
+int vmtl_conv2d_up2_halo(const float* xl, const float* skip, const float* wp_eff, float* y, float* stats,
+                         int B, int H2, int W2, int C0s, int C1s, int ldy, int Cout, void* stream);
+int vmtl_conv2d_up2_halo_supported(int B, int H2, int W2, int C0s, int C1s, int ldy, int Cout);
+int vmtl_conv2d_up2_halo_stat_rows(int B, int H2, int W2, int C0s, int C1s, int ldy, int Cout);
+int vmtl_conv2d_up2_halo_stat_block(int C0s, int C1s, int ldy, int Cout);
 int vmtl_pack_up2_fwd(const float* w, float* dst, int Cout, int C0, int C0s, int C1, int C1s, void* stream);
 int vmtl_pack_up2_dgrad(const float* w, float* dst, int Cout, int Cos, int C0, int Cin, void* stream);
 int vmtl_unpack_up2(const float* slabs, float* grad, int Cout, int Cos, int C0, int Cin, int nslabs, void* stream);

@@ -1,5 +1,6 @@
 """Micro-benchmark (GPU box) of vmtl_conv2d_up2_fwd on the two narrow decoder shapes of `basic` (bs 32, 128x256), one
-tile configuration per process: VMTL_FORCE_TILE=<id> python tools/bench_up2.py"""
+tile configuration per process: VMTL_FORCE_TILE=<id> python tools/bench_up2.py.  Each shape is followed by the halo-tile
+kernel (vmtl_conv2d_up2_halo) on the same operands, with its speed-up and its largest difference from the implicit GEMM."""
 import os
 import sys
 
@@ -34,6 +35,22 @@ for name, B, H2, W2, C0, C1, Cout in [("block5 conv1 67->33", 32, 64, 128, 67, 0
     us = e0.elapsed_time(e1) / 5 * 1e3
     xflop = 2.0 * 4 * M * Cout * (4 * C0 + 9 * C1)
     print(f"tile {os.environ.get('VMTL_FORCE_TILE', 'auto'):>4s}  {name:26s} {us:8.1f} us  executed {xflop / us / 1e6:6.1f} TF", flush=True)
+    # the halo-tile kernel on the same operands (what the training step runs for these shapes in fp32)
+    rows = L.raw("vmtl_conv2d_up2_halo_stat_rows")(B, H2, W2, C0s, C1s, ldy, Cout)
+    hstats = torch.empty(rows, 2, ldy, device=dev) if rows and not os.environ.get("UP2_NO_STATS") else None
+    y_old = y.clone()
+    fn = lambda: L.callk("vmtl_conv2d_up2_halo", xl=xl, skip=skip, wp_eff=wp, y=y, stats=hstats, B=B, H2=H2, W2=W2,
+                         C0s=C0s, C1s=C1s, ldy=ldy, Cout=Cout, stream=st)
+    fn()
+    diff = ((y - y_old).abs().max() / y_old.abs().max()).item()
+    e0.record()
+    for _ in range(5):
+        fn()
+    e1.record()
+    e1.synchronize()
+    hus = e0.elapsed_time(e1) / 5 * 1e3
+    print(f"halo        {name:26s} {hus:8.1f} us  executed {xflop / hus / 1e6:6.1f} TF  ({us / hus:.2f}x, max rel diff {diff:.1e})",
+          flush=True)
 
 # the data gradient of the same two layers w.r.t. the low-res input: a 4x4 stride-2 conv over dY
 for name, B, H2, W2, C0, Cout in [("block5 conv1 dgrad 33->67", 32, 64, 128, 67, 33), ("block4 conv1 dgrad 67->135", 32, 32, 64, 135, 67)]:

@@ -344,10 +344,7 @@ class DecoderBlock(nn.Module):
         The caller fuses conv1's BatchNorm + ReLU into what follows (ops.decoder_tail)."""
         c, bn = self.conv1[0], self.conv1[1]
         y, stats = L.ops.up2_conv(x.t, x.C, None if skip is None else skip.t, c.weight, want_stats=bn.training)
-        rpb = 0
-        if stats is not None:
-            B, H2, W2, _ = x.t.shape
-            rpb = L.ops.lib().raw("vmtl_conv2d_up2_stats_block")(B, H2, W2, y.shape[3])
+        rpb = 0 if stats is None else stats._vmtl_rpb  # up2_conv tags the rows with the pixels each covers
         return L.Act(y, c.out_channels), stats, rpb
 
 

@@ -506,6 +506,31 @@ _PW = os.environ.get("VMTL_PW", "1") != "0"  # pointwise GEMM kernel for 1x1 con
 _PW_MAX_ROWS = int(os.environ.get("VMTL_PW_MAX_ROWS", str(1 << 21)))  # measured on MTAN (M = 2^20): 57.1 -> 55.5 ms/step
 
 
+_UP2_HALO = os.environ.get("VMTL_UP2_HALO", "1") != "0"  # halo-tile kernel for the narrow UP2 convs (csrc/conv_up2_halo.hip)
+
+
+def _up2_halo_route(B, H2, W2, C0s, C1s, ldy, Cout, prec) -> bool:
+    """True when an UP2 conv runs on vmtl_conv2d_up2_halo: fp32, a supported shape, and no split-K on the implicit GEMM
+    (the tile-starved small-batch launches keep their split-K form).  bf16 stays on the implicit GEMM."""
+    return (_UP2_HALO and prec == 0 and bool(lib().raw("vmtl_conv2d_up2_halo_supported")(B, H2, W2, C0s, C1s, ldy, Cout))
+            and lib().raw("vmtl_conv2d_up2_ksplit")(B, H2, W2, ldy, 4 * C0s + 9 * C1s) == 1)
+
+
+def up2_stats_geometry(B, H2, W2, C0s, C1s, ldy, Cout, prec=None):
+    """(statistics rows, pixels per row) of the UP2 conv's BatchNorm partials for this shape (rows = 0: no statistics
+    epilogue, the BatchNorm reduces the output itself).  The two UP2 kernels tile differently, so the row geometry follows
+    the route; prec defaults to the current conv precision."""
+    prec = conv_prec_code() if prec is None else prec
+    if _up2_halo_route(B, H2, W2, C0s, C1s, ldy, Cout, prec):
+        return (lib().raw("vmtl_conv2d_up2_halo_stat_rows")(B, H2, W2, C0s, C1s, ldy, Cout),
+                lib().raw("vmtl_conv2d_up2_halo_stat_block")(C0s, C1s, ldy, Cout))
+    if lib().raw("vmtl_conv2d_up2_ksplit")(B, H2, W2, ldy, 4 * C0s + 9 * C1s) > 1:
+        return 0, 0
+    bm = lib().raw("vmtl_conv2d_up2_stats_block")(B, H2, W2, ldy)
+    Mq = B * H2 * W2
+    return (4 * (Mq // bm), bm) if Mq % bm == 0 else (0, bm)
+
+
 def _is_pw(B, Ho, Wo, KH, KW, stride, pad, shuffle=0):
     return _PW and KH == 1 and KW == 1 and stride == 1 and pad == 0 and not shuffle and B * Ho * Wo <= _PW_MAX_ROWS
 
@@ -927,7 +952,14 @@ class _Up2Conv(torch.autograd.Function):
         prec = ctx.prec = conv_prec_code()
         # algorithmic FLOPs = the reference formulation (9 taps on every channel); executed: 4 taps on xl's
         ks = lib().raw("vmtl_conv2d_up2_ksplit")(B, H2, W2, ldy, Ktot)
-        if ks > 1:  # tile-starved (deep decoder blocks at small batch): split K, no statistics epilogue
+        if _up2_halo_route(B, H2, W2, C0s, C1s, ldy, Cout, prec):
+            if want_stats:
+                rows, _ = up2_stats_geometry(B, H2, W2, C0s, C1s, ldy, Cout, prec)
+                if rows:
+                    stats = _empty((rows, 2, ldy), xl)
+            _k("vmtl_conv2d_up2_halo", _flop=2.0 * M * Cout * 9 * Cin, _xflop=2.0 * M * Cout * (4 * C0 + 9 * C1), xl=xl,
+               skip=skip, wp_eff=wp, y=y, stats=stats, B=B, H2=H2, W2=W2, C0s=C0s, C1s=C1s, ldy=ldy, Cout=Cout)
+        elif ks > 1:  # tile-starved (deep decoder blocks at small batch): split K, no statistics epilogue
             _kp("vmtl_conv2d_up2_fwd_ws", prec, _flop=2.0 * M * Cout * 9 * Cin, _xflop=2.0 * M * Cout * (4 * C0 + 9 * C1), xl=xl,
                skip=skip, wp_eff=wp, y=y, ws=_empty((ks, B, 2 * H2, 2 * W2, ldy), xl), B=B, H2=H2, W2=W2, C0s=C0s, C1s=C1s,
                ldy=ldy, Cout=Cout)
@@ -1050,7 +1082,14 @@ class _BNActConv(torch.autograd.Function):
             y = _empty((B, 2 * H, 2 * W, ldy), x)
             Mo = 4 * M
             ks = lib().raw("vmtl_conv2d_up2_ksplit")(B, H, W, ldy, Ktot)
-            if ks > 1:  # tile-starved (deep decoder blocks at small batch): split K, no statistics epilogue
+            if _up2_halo_route(B, H, W, Cs, C1s, ldy, Cout, prec):
+                if want_stats:
+                    rows, bm = up2_stats_geometry(B, H, W, Cs, C1s, ldy, Cout, prec)
+                    if rows:
+                        ostats, orpb = _empty((rows, 2, ldy), x), bm
+                _k("vmtl_conv2d_up2_halo", _flop=2.0 * Mo * Cout * 9 * Cin, _xflop=2.0 * Mo * Cout * (4 * C + 9 * C1), xl=a,
+                   skip=skip, wp_eff=wp, y=y, stats=ostats, B=B, H2=H, W2=W, C0s=Cs, C1s=C1s, ldy=ldy, Cout=Cout)
+            elif ks > 1:  # tile-starved (deep decoder blocks at small batch): split K, no statistics epilogue
                 _kp("vmtl_conv2d_up2_fwd_ws", prec, _flop=2.0 * Mo * Cout * 9 * Cin, _xflop=2.0 * Mo * Cout * (4 * C + 9 * C1),
                    xl=a, skip=skip, wp_eff=wp, y=y, ws=_empty((ks, B, 2 * H, 2 * W, ldy), x), B=B, H2=H, W2=W, C0s=Cs,
                    C1s=C1s, ldy=ldy, Cout=Cout)
@@ -1175,17 +1214,18 @@ def bn_act_conv(x, stats, rpb, bn, C, act, weight, skip=None, up2=False, want_st
     if ostats is not None:
         B, H, W, _ = x.shape
         ldy = y.shape[3]
-        orpb = (lib().raw("vmtl_conv2d_up2_stats_block")(B, H, W, ldy) if up2
+        orpb = (up2_stats_geometry(B, H, W, x.shape[3], 0 if skip is None else skip.shape[3], ldy, weight.shape[0])[1] if up2
                 else conv_stats_geometry(B, H, W, x.shape[3], ldy, 3, 3, 1, 1)[1])
     return y, ostats, orpb
 
 
 def up2_conv(xl, C0, skip, weight, want_stats=False):
     """(y, stats) = conv3x3(cat[nearest_x2(xl), skip]); C0 = logical channels of xl; stats may be None.  Like conv2d's, the
-    statistics rows carry the pixels each covers (`_vmtl_rpb`: the up2 tile picker's row block, not conv_pick_tile's)."""
+    statistics rows carry the pixels each covers (`_vmtl_rpb`: up2_stats_geometry's row block, not conv_pick_tile's)."""
     y, stats = _Up2Conv.apply(xl, skip, weight, C0, want_stats)
     if stats is not None:
-        stats._vmtl_rpb = lib().raw("vmtl_conv2d_up2_stats_block")(xl.shape[0], xl.shape[1], xl.shape[2], y.shape[3])
+        stats._vmtl_rpb = up2_stats_geometry(xl.shape[0], xl.shape[1], xl.shape[2], xl.shape[3],
+                                             0 if skip is None else skip.shape[3], y.shape[3], weight.shape[0])[1]
     return y, stats
 
 
