@@ -368,6 +368,20 @@ int vmtl_nhwc_to_nchw(const float* x, float* y, int B, int C, int HW, int Cs, vo
 /* input side (lit_module.py:211-219 + the dataset sample contract of data_modules/cityscapes.py:39-83,
  * nyuv2.py:100-141): HWC pixel rows [P][C] -> internal NHWC storage [P][Cs] (zero pad channels), y = x * scale */
 int vmtl_hwc_to_nhwc_pad(const float* x, float* y, long long P, int C, int Cs, float scale, void* stream);
+/* NYUv2 sample transform on the device (csrc/resize.hip): the reference's host chain ToTensor() + Resize((Ho, Wo),
+ * antialias=True) of cfg.py:144-155, applied per sample by data_modules/nyuv2.py:100-141, followed by the value rules of
+ * that loader (img in [0,1], mask class ids, depth = counts / 1e4, then / max_depth for a sample whose resized maximum
+ * exceeds 1).  Inputs are the decoded files as stacked by data.collate_raw: img uint8 [B][Hi][Wi][3], mask uint8
+ * [B][Hi][Wi], depth [B][Hi][Wi] of type depth_dtype (VMTL_DEPTH_*).  Outputs: img_out the model's NHWC input storage
+ * [B][Ho][Wo][4] (pad channel 0), mask_out int64 [B][Ho][Wo], depth_out float [B][Ho][Wo]; part holds
+ * vmtl_nyuv2_resize_parts(...) floats of scratch (per-tile depth maxima).  img, mask, depth and img_out are 16-byte
+ * aligned.  Two launches; -3 for a downscale too steep for the kernel's LDS tiles. */
+#define VMTL_DEPTH_U16 0
+#define VMTL_DEPTH_I32 1
+int vmtl_nyuv2_resize_parts(int B, int Hi, int Wi, int Ho, int Wo, int depth_dtype);
+int vmtl_nyuv2_resize(const void* img, const void* mask, const void* depth, int depth_dtype, float* img_out,
+                      long long* mask_out, float* depth_out, float* part, int B, int Hi, int Wi, int Ho, int Wo,
+                      float max_depth, void* stream);
 
 /* ---- losses ------------------------------------------------------------------------------
  * lit_module.py:31,123 (CrossEntropyLoss); losses.py:14-36 (SILogLoss); lit_module.py:68,112 (MAE). */

@@ -11,6 +11,11 @@ C-1, dtypes, depth normalisation, depth as (H, W, 1)), `collate` stacks into PIN
 the model's input storage.  What the caller sees stays the reference's contract: batch["img"] is a (B, 3, H, W)
 float tensor (a channels-last view over that storage; the models pick the storage up without another copy).
 Dataset file I/O, augmentation and DataLoader workers stay out of scope (host code).
+
+NYUv2's host transform also resizes (cfg.py:144-155: ToTensor + Resize((256, 256), antialias=True)), the expensive part
+of its input side.  `collate_raw` stacks the samples as the files decode (uint8 image and mask, uint16 / int32 depth),
+and `DeviceTransform`, handed to `upload_batch` (or set as `MTLModule.device_transform`), runs that resize and the
+loader's value rules as HIP kernels on the uploaded batch.  PNG decode and file reading stay on the host.
 """
 from __future__ import annotations
 
@@ -82,14 +87,20 @@ def collate(samples: t.Sequence[dict], pin: bool = True) -> dict:
     return out
 
 
-def upload_batch(batch: dict, device) -> dict:
+def upload_batch(batch: dict, device, transform=None) -> dict:
     """Host batch -> device batch in the reference's contract.  An image stacked in sample layout (B,H,W,3) is
     re-laid by one HIP kernel into the model's NHWC storage and returned as a (B,3,H,W) view of it; everything
-    else (an NCHW image included) is an asynchronous copy when pinned (reference lit_module.py:211-219)."""
+    else (an NCHW image included) is an asynchronous copy when pinned (reference lit_module.py:211-219).
+
+    transform: a device transform (DeviceTransform) for a raw batch from collate_raw: every tensor is copied as it is
+    (asynchronously when pinned) and the transform produces the batch on the device."""
     from . import ops
 
     def up(v):
         return v.to(device, non_blocking=v.device.type == "cpu" and v.is_pinned())
+
+    if transform is not None:
+        return transform({k: up(v) for k, v in batch.items()})
 
     out = {}
     for k, v in batch.items():
@@ -98,3 +109,81 @@ def upload_batch(batch: dict, device) -> dict:
         else:
             out[k] = up(v)
     return out
+
+
+_RAW_DTYPES = {"img": (torch.uint8,), "mask": (torch.uint8,), "depth": (torch.uint16, torch.int32)}
+
+
+def collate_raw(samples: t.Sequence[dict], pin: bool = True) -> dict:
+    """Stack raw decoded NYUv2 samples {"img": (H,W,3) uint8, "mask": (H,W) uint8, "depth": (H,W) uint16 or int32}
+    (numpy arrays or tensors: what Pillow returns for the reference's PNGs, nyuv2.py:100-141) WITHOUT any dtype
+    conversion, into {"img": (B,H,W,3), "mask": (B,H,W), "depth": (B,H,W)}; pinned when a GPU is present.  The
+    DataLoader's collate_fn when DeviceTransform does the sample transform on the device."""
+    if len(samples) == 0:
+        raise ValueError("collate_raw: no samples")
+    as_t = lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+    cols = {k: [] for k in _RAW_DTYPES}
+    size = None
+    for i, smp in enumerate(samples):
+        for k, dtypes in _RAW_DTYPES.items():
+            if k not in smp:
+                raise ValueError(f"collate_raw: sample {i} has no {k!r}")
+            v = as_t(smp[k])
+            if v.dtype not in dtypes:
+                raise ValueError(f"collate_raw: sample {i} {k!r} must be {' or '.join(str(d) for d in dtypes)}, "
+                                 f"got {v.dtype}")
+            want = 3 if k == "img" else 2
+            if v.dim() != want or (k == "img" and v.shape[-1] != 3):
+                raise ValueError(f"collate_raw: sample {i} {k!r} must be {'(H, W, 3)' if k == 'img' else '(H, W)'}, "
+                                 f"got {tuple(v.shape)}")
+            if size is None:
+                size = tuple(v.shape[:2])
+            if tuple(v.shape[:2]) != size:
+                raise ValueError(f"collate_raw: sample {i} {k!r} is {tuple(v.shape[:2])}, expected {size}")
+            cols[k].append(v)
+    if len({v.dtype for v in cols["depth"]}) != 1:
+        raise ValueError("collate_raw: the depth maps of one batch must share a dtype")
+    out = {k: torch.stack(v) for k, v in cols.items()}
+    if pin and torch.cuda.is_available():
+        out = {k: v.pin_memory() for k, v in out.items()}
+    return out
+
+
+class DeviceTransform:
+    """The reference's NYUv2 sample transform as HIP kernels on a raw device batch (data.collate_raw, uploaded).
+
+    Reference NYUv2Config.train_transform / test_transform (cfg.py:144-155) are ToTensor() + Resize(size,
+    antialias=True), applied per sample to the image, the class-id mask and the uint16 depth PNG by
+    NYUv2Dataset.prepare_sample (nyuv2.py:100-141).  Called on {"img": (B,H,W,3) uint8, "mask": (B,H,W) uint8,
+    "depth": (B,H,W) uint16 | int32} it returns what prepare_sample(dataset="nyuv2", max_depth=max_depth) gives for
+    each resized sample, batched: img (B,3,Ho,Wo) float32 (the model's input storage), mask (B,Ho,Wo) int64, depth
+    (B,Ho,Wo,1) float32.  The filter is PyTorch's antialiased bilinear resample, value for value.
+
+    Mask: ToTensor scales the class ids by 1/255; after the resample they are multiplied back and ROUNDED (half to
+    even), as prepare_sample does.  The reference truncates there (`.long()`), which turns an id that came back as
+    4.9999995 into 4; this project keeps prepare_sample's rounding.  Depth: resampled as float and rounded back to its
+    integer type (what Resize does to integer images), then / 1e4, then / max_depth for a sample whose resized maximum
+    exceeds 1.  Other keys of the batch pass through unchanged.
+
+    Only dataset="nyuv2": Cityscapes' stored samples are already at the model's size, so its resize is an identity."""
+
+    def __init__(self, size=(256, 256), max_depth: float = 10.0, dataset: str = "nyuv2"):
+        if dataset != "nyuv2":
+            raise ValueError(f"DeviceTransform: only dataset='nyuv2' is supported, got {dataset!r}")
+        if (not isinstance(size, (tuple, list)) or len(size) != 2
+                or not all(isinstance(v, int) and not isinstance(v, bool) and v > 0 for v in size)):
+            raise ValueError(f"DeviceTransform: size must be (height, width) of positive ints, got {size!r}")
+        if not max_depth > 0:
+            raise ValueError(f"DeviceTransform: max_depth must be > 0, got {max_depth!r}")
+        self.size, self.max_depth, self.dataset = (int(size[0]), int(size[1])), float(max_depth), dataset
+
+    def __call__(self, batch: dict) -> dict:
+        from . import ops
+
+        img, mask, depth = ops.nyuv2_resize(batch["img"], batch["mask"], batch["depth"], self.size, self.max_depth)
+        out = dict(batch)
+        out.update(img=img, mask=mask, depth=depth)
+        return out
+
+    def __repr__(self) -> str:
+        return f"DeviceTransform(size={self.size}, max_depth={self.max_depth}, dataset={self.dataset!r})"

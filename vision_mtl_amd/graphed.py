@@ -58,7 +58,8 @@ class GraphedStep:
     (allocator pools, code objects, packed-operand table).  NOTE: the warm-up steps and the capture rehearsal run real
     training steps on `example_batch` (BatchNorm running statistics move, no optimizer step is taken).  The step is captured
     under the convolution precision in force at construction (recorded as `conv_precision`), and every replay keeps it
-    whatever vision_mtl_amd.set_conv_precision says later."""
+    whatever vision_mtl_amd.set_conv_precision says later.  Likewise `module.device_transform` (data.DeviceTransform)
+    at construction: the static buffers then hold raw batches (data.collate_raw) and the transform is captured too."""
 
     def __init__(self, module, example_batch: dict, arena: "dp.FlatArena | None" = None, warmup: int = 2,
                  stage: str = "train"):
@@ -69,10 +70,12 @@ class GraphedStep:
         if arena is None:
             arena = module.dp_arena if module.dp_arena is not None else dp.FlatArena(module.model)
         self.arena = arena
+        # a raw batch (data.collate_raw) whose sample transform runs inside the graph: recorded once, like the precision
+        self.device_transform = getattr(module, "device_transform", None)
         self.static = {k: self._static_like(v) for k, v in example_batch.items()}
         self._fill(example_batch)
-        self._sample_layout = (self.static["img"].dim() == 4 and self.static["img"].shape[-1] == 3
-                               and self.static["img"].shape[1] != 3)
+        self._sample_layout = (self.device_transform is None and self.static["img"].dim() == 4
+                               and self.static["img"].shape[-1] == 3 and self.static["img"].shape[1] != 3)
         self.conv_precision = get_conv_precision()
         attached, module.dp_arena = module.dp_arena, None  # the collective stays outside the graph (see __call__)
         try:
@@ -119,7 +122,9 @@ class GraphedStep:
 
     def _step(self) -> torch.Tensor:
         batch = dict(self.static)
-        if self._sample_layout:
+        if self.device_transform is not None:
+            batch = self.device_transform(batch)
+        elif self._sample_layout:
             batch["img"] = ops.hwc_to_model_input(self.static["img"])
         return self.module.shared_step(batch, self.stage)
 

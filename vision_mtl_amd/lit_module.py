@@ -42,6 +42,9 @@ class MTLModule(nn.Module):
         self.compute_metrics = True  # bench.py turns this off to time exactly fwd + losses + bwd
         self._nan = {}  # device -> the NaN placeholder of the skipped metrics (built once, not filled every step)
         self.dp_arena = None  # a dp.FlatArena: training_step's loss then averages gradients over ranks at end of backward
+        # a data.DeviceTransform: transfer_batch_to_device then takes raw batches (data.collate_raw) and runs the sample
+        # transform on the device (GraphedStep records it at construction)
+        self.device_transform = None
 
     def forward(self, x: torch.Tensor) -> dict:
         return self.model(x)
@@ -139,11 +142,12 @@ class MTLModule(nn.Module):
     def transfer_batch_to_device(self, batch: dict, device, dataloader_idx: int = 0):
         """reference lit_module.py:211-219.  Pinned host tensors (DataLoader(pin_memory=True), data.collate) go up
         asynchronously on the current stream; an image batch kept in dataset sample layout (B,H,W,3) is re-laid on
-        the device by one kernel straight into the model's input storage (data.upload_batch)."""
+        the device by one kernel straight into the model's input storage (data.upload_batch).  With device_transform
+        set, the batch is a raw one (data.collate_raw) and the transform runs on the device after the copy."""
         from .data import upload_batch
 
         if isinstance(batch, dict):
-            up = upload_batch(batch, device)
+            up = upload_batch(batch, device, transform=self.device_transform)
             for key in batch.keys():
                 batch[key] = up[key]
             return batch

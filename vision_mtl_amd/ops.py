@@ -1916,6 +1916,54 @@ def hwc_to_model_input(x_hwc, scale: float = 1.0):
     return view
 
 
+
+def _req_dtype(t: torch.Tensor, name: str, dtypes: tuple) -> torch.Tensor:
+    """_req for the non-float inputs of the input side: a device tensor of one of `dtypes`, contiguous, 16-byte aligned
+    (the kernels read it in 16-byte granules; a misaligned view is copied)."""
+    if not t.is_cuda:
+        raise RuntimeError(
+            f"{name} is on {t.device}: the vmtl hot path only runs as HIP kernels on an MI355X "
+            "(there is deliberately no CPU fallback)"
+        )
+    if t.dtype not in dtypes:
+        raise TypeError(f"{name} must be one of {[str(d) for d in dtypes]}, got {t.dtype}")
+    t = t if t.is_contiguous() else t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+DEPTH_DTYPES = {torch.uint16: 0, torch.int32: 1}  # VMTL_DEPTH_U16 / VMTL_DEPTH_I32
+
+
+def nyuv2_resize(img, mask, depth, size, max_depth: float = 10.0):
+    """The reference's NYUv2 sample transform (cfg.py:144-155: ToTensor + Resize(size, antialias=True)) and loader value
+    rules (nyuv2.py:100-141) on a raw device batch, as two launches (csrc/resize.hip).
+
+    img uint8 (B,Hi,Wi,3), mask uint8 (B,Hi,Wi), depth uint16 or int32 (B,Hi,Wi) -> img (B,3,Ho,Wo) float32 (a
+    channels-last view of the model's NHWC input storage, as hwc_to_model_input returns it), mask (B,Ho,Wo) int64,
+    depth (B,Ho,Wo,1) float32."""
+    img = _req_dtype(img, "img", (torch.uint8,))
+    mask = _req_dtype(mask, "mask", (torch.uint8,))
+    depth = _req_dtype(depth, "depth", tuple(DEPTH_DTYPES))
+    if img.dim() != 4 or img.shape[-1] != 3:
+        raise ValueError(f"nyuv2_resize: img must be (B, H, W, 3), got {tuple(img.shape)}")
+    B, Hi, Wi, _ = img.shape
+    if tuple(mask.shape) != (B, Hi, Wi) or tuple(depth.shape) != (B, Hi, Wi):
+        raise ValueError(f"nyuv2_resize: mask {tuple(mask.shape)} and depth {tuple(depth.shape)} must be {(B, Hi, Wi)}")
+    Ho, Wo = (int(v) for v in size)
+    code = DEPTH_DTYPES[depth.dtype]
+    nparts = lib().raw("vmtl_nyuv2_resize_parts")(B, Hi, Wi, Ho, Wo, code)
+    if nparts < 0:
+        lib()._raise("vmtl_nyuv2_resize_parts", nparts)
+    st = _empty((B, Ho, Wo, 4), img)
+    m = torch.empty((B, Ho, Wo), dtype=torch.int64, device=img.device)
+    d = _empty((B, Ho, Wo, 1), img)
+    part = _empty((nparts,), img)
+    _k("vmtl_nyuv2_resize", img=img, mask=mask, depth=depth, depth_dtype=code, img_out=st, mask_out=m, depth_out=d,
+       part=part, B=B, Hi=Hi, Wi=Wi, Ho=Ho, Wo=Wo, max_depth=float(max_depth))
+    view = st[..., :3].permute(0, 3, 1, 2)
+    view._vmtl_nhwc = st
+    return view, m, d
+
 class _ToNCHW(torch.autograd.Function):
     """internal [B,H,W,Cs] -> (B,C,H,W) contiguous, the reference's output layout."""
 
