@@ -202,6 +202,26 @@ int vmtl_conv3x3_small(const float* x, const float* x2, const float* pa, const f
                        const float* ez_gamma, const float* ez_beta, int ez_act, int B, int H, int W, int Cs, int ldy,
                        int Nw, int Cout, void* stream);
 
+/* The same 3x3 / stride 1 / pad 1 conv for the MID-WIDTH layers on a halo-tile kernel (csrc/conv3x3_halo.hip), fp32 only:
+ * Cs in {64, 68} storage channels in, ldy in {16, 32, 64, 68} storage channels out, Nw rows of the packed [Nw][9*Cs] weight,
+ * ldy = round_up(Nw, 4), x under 2 GiB (vmtl_conv3x3_halo_supported; anything else returns -3).  One workgroup per
+ * 4 x 32 output tile; the weights stream from L2.
+ *   prologue: v = act_in(pa[c]*x + pc[c]) once per input element (pa null: identity); a_out (optional, needs pa)
+ *             receives the transformed input.
+ *   ep_mode 0: y = conv + bias (stats must be null).
+ *   ep_mode 1: y = conv + bias, stats[row][2][ldy] = (mean, M2) of y over the row's pixels.
+ *   ep_mode 2: y = conv * act'(z), z = ez_gamma*xhat + ez_beta, xhat = (ez_x - ez_mean)*ez_invstd;
+ *              stats[row][2][ldy] = (sum y, sum y*xhat) over the row's pixels (no bias).
+ * A statistics row is one tile: vmtl_conv3x3_halo_stat_rows / _stat_block; rows = 0 (and ep_mode 1/2 are refused) unless
+ * H % 4 == 0 and W % 32 == 0. */
+int vmtl_conv3x3_halo_supported(int B, int H, int W, int Cs, int ldy, int Nw);
+int vmtl_conv3x3_halo_stat_rows(int B, int H, int W);
+int vmtl_conv3x3_halo_stat_block(int B, int H, int W);
+int vmtl_conv3x3_halo(const float* x, const float* pa, const float* pc, int act_in, float* a_out, const float* wp,
+                      const float* bias, float* y, float* stats, int ep_mode, const float* ez_x, const float* ez_mean,
+                      const float* ez_invstd, const float* ez_gamma, const float* ez_beta, int ez_act, int B, int H,
+                      int W, int Cs, int ldy, int Nw, int Cout, void* stream);
+
 /* depthwise KxK (K in {3,5}, stride in {1,2}); wp is packed [K*K][Cs]. */
 int vmtl_dwconv_fwd(const float* x, const float* wp, float* y, int B, int H, int W, int Cs, int Ho, int Wo,
                     int K, int stride, int pad, void* stream);

@@ -562,10 +562,39 @@ def _small_route(B, H, W, Cs, ldy, KH, KW, stride, pad, shuffle=0, with_stats=Fa
     return not with_stats or (_SMALL_STATS and H % 4 == 0 and W % 32 == 0)
 
 
+_MID_HALO = os.environ.get("VMTL_MID_HALO", "1") != "0"  # halo-tile kernel for the 64/68-channel 3x3 convs (csrc/conv3x3_halo.hip)
+_MID_HALO_MIN_ROWS = int(os.environ.get("VMTL_MID_HALO_MIN_ROWS", str(1 << 16)))
+
+
+def _mid_halo_route(B, H, W, Cs, ldy, KH, KW, stride, pad, shuffle=0, with_stats=False, prec=None) -> bool:
+    """A 3x3 / stride 1 / pad 1 launch with 64 or 68 input storage channels and 16 / 32 / 64 / 68 output storage channels
+    that runs on vmtl_conv3x3_halo instead of the implicit GEMM: fp32, no split-K, at least _MID_HALO_MIN_ROWS output
+    pixels (tools/bench_halo3.py), and whole 4 x 32 tiles when the launch emits statistics.  bf16 stays on the implicit GEMM."""
+    prec = conv_prec_code() if prec is None else prec
+    if not _MID_HALO or prec != 0 or shuffle or KH != 3 or KW != 3 or stride != 1 or pad != 1 or B * H * W < _MID_HALO_MIN_ROWS:
+        return False
+    if not lib().raw("vmtl_conv3x3_halo_supported")(B, H, W, Cs, ldy, ldy):
+        return False
+    if lib().raw("vmtl_conv2d_ksplit")(B, H, W, ldy, 9 * Cs) > 1:
+        return False
+    return not with_stats or lib().raw("vmtl_conv3x3_halo_stat_rows")(B, H, W) > 0
+
+
+def _mid_halo(x, wp, y, B, H, W, Cs, ldy, Nw, Cout, flop, pa=None, pc=None, act_in=ACT_NONE, a_out=None, bias=None,
+              stats=None, ep_mode=0, ez=None):
+    """One vmtl_conv3x3_halo launch; ez = (x, mean, invstd, gamma, beta, act) for ep_mode 2."""
+    ez = ez or (None, None, None, None, None, ACT_NONE)
+    _k("vmtl_conv3x3_halo", _flop=flop, x=x, pa=pa, pc=pc, act_in=act_in, a_out=a_out, wp=wp, bias=bias, y=y, stats=stats,
+       ep_mode=ep_mode, ez_x=ez[0], ez_mean=ez[1], ez_invstd=ez[2], ez_gamma=ez[3], ez_beta=ez[4], ez_act=ez[5], B=B, H=H,
+       W=W, Cs=Cs, ldy=ldy, Nw=Nw, Cout=Cout)
+
+
 def conv_stats_geometry(B, Ho, Wo, Cs, ldy, KH, KW, stride, pad):
     """(rows, pixels per row) of the BatchNorm partial rows a conv launch of this shape emits from its epilogue."""
     if _small_route(B, Ho, Wo, Cs, ldy, KH, KW, stride, pad, with_stats=True):
         return lib().raw("vmtl_conv3x3_small_stat_rows")(B, Ho, Wo), lib().raw("vmtl_conv3x3_small_stat_block")(B, Ho, Wo)
+    if _mid_halo_route(B, Ho, Wo, Cs, ldy, KH, KW, stride, pad, with_stats=True):
+        return lib().raw("vmtl_conv3x3_halo_stat_rows")(B, Ho, Wo), lib().raw("vmtl_conv3x3_halo_stat_block")(B, Ho, Wo)
     if _is_pw(B, Ho, Wo, KH, KW, stride, pad):
         M = B * Ho * Wo
         return lib().raw("vmtl_conv1x1_stats_rows")(M, ldy, Cs, 0), lib().raw("vmtl_conv1x1_stats_block")(M, ldy, Cs, 0)
@@ -583,6 +612,11 @@ def _conv_launch(x, wp, bias, y, stats, B, H, W, Cs, Ho, Wo, ldy, Nw, Cout, KH, 
         # narrow full-resolution layer: the halo-tile kernel reads the input once (statistics rows: conv_stats_geometry)
         _small(x, wp, y, B, H, W, Cs, ldy, Nw, Cout, flop if algo_flop is None else algo_flop, bias=bias, stats=stats,
                ep_mode=1 if stats is not None else 0)
+        return
+    if _mid_halo_route(B, H, W, Cs, ldy, KH, KW, stride, pad, shuffle, with_stats=stats is not None, prec=prec):
+        # 64/68-channel layer: the halo-tile kernel reads each input pixel once (statistics rows: conv_stats_geometry)
+        _mid_halo(x, wp, y, B, H, W, Cs, ldy, Nw, Cout, flop if algo_flop is None else algo_flop, bias=bias, stats=stats,
+                  ep_mode=1 if stats is not None else 0)
         return
     if stats is None and not shuffle:
         # contraction without a statistics epilogue (data gradients; forward convs of tile-starved layers, see
@@ -1039,10 +1073,18 @@ class _BNActConv(torch.autograd.Function):
         Cout, Cin = weight.shape[0], weight.shape[1]
         if ceil4(C) != Cs or tuple(weight.shape[2:]) != (3, 3):
             raise ValueError("bn_act_conv: 3x3 weight over x's channels expected")
+        prec = ctx.prec = conv_prec_code()
+        ldy = ceil4(Cout)
+        # a 64/68-channel layer on the halo-tile kernel applies BatchNorm + activation as the conv's prologue (once per
+        # input element, written back to a); everything else materialises a first
+        pro = (not up2 and skip is None and Cin == C and act in (ACT_NONE, ACT_RELU)
+               and _mid_halo_route(B, H, W, Cs, ldy, 3, 3, 1, 1, with_stats=want_stats, prec=prec))
         # ---- BatchNorm + activation (materialised: the weight gradient reads it)
-        mean, invstd = _empty((Cs,), x), _empty((Cs,), x)
         a = _empty(x.shape, x)
-        if training:
+        if pro:
+            mean, invstd, ca, cc = _bn_fwd_coef(x, stats, rpb, gamma, beta, rm, rv, nbt, C, training, momentum, eps)
+        elif training:
+            mean, invstd = _empty((Cs,), x), _empty((Cs,), x)
             if stats is not None:
                 partial, nblk = stats, stats.shape[0]
             else:
@@ -1058,12 +1100,11 @@ class _BNActConv(torch.autograd.Function):
                 _k("vmtl_bn_apply", x=x, mean=mean, invstd=invstd, gamma=gamma, beta=beta, mul=None, res=None, y=a, M=M,
                    C=C, Cs=Cs, act=act)
         else:
+            mean, invstd = _empty((Cs,), x), _empty((Cs,), x)
             _k("vmtl_bn_eval_stats", running_mean=rm, running_var=rv, C=C, Cs=Cs, eps=eps, save_mean=mean, save_invstd=invstd)
             _k("vmtl_bn_apply", x=x, mean=mean, invstd=invstd, gamma=gamma, beta=beta, mul=None, res=None, y=a, M=M, C=C,
                Cs=Cs, act=act)
         # ---- the conv on a
-        prec = ctx.prec = conv_prec_code()
-        ldy = ceil4(Cout)
         ostats, orpb = None, 0
         if up2:
             if skip is not None:
@@ -1108,7 +1149,11 @@ class _BNActConv(torch.autograd.Function):
             if want_stats and conv_ksplit(B, H, W, Cs, ldy, 3, 3, 1, 1) == 1:
                 rows, orpb = conv_stats_geometry(B, H, W, Cs, ldy, 3, 3, 1, 1)
                 ostats = _empty((rows, 2, ldy), x)
-            _conv_launch(a, wp, None, y, ostats, B, H, W, Cs, H, W, ldy, Cout, Cout, 3, 3, 1, 1, cin=Cin, prec=prec)
+            if pro:
+                _mid_halo(x, wp, y, B, H, W, Cs, ldy, Cout, Cout, 2.0 * M * Cout * 9 * Cin, pa=ca, pc=cc, act_in=act, a_out=a,
+                          stats=ostats, ep_mode=1 if ostats is not None else 0)
+            else:
+                _conv_launch(a, wp, None, y, ostats, B, H, W, Cs, H, W, ldy, Cout, Cout, 3, 3, 1, 1, cin=Cin, prec=prec)
         ctx.save_for_backward(x, a, skip, weight, mean, invstd, gamma, beta)
         ctx.cfg = (C, training, act, up2)
         ctx.slots = (_slot(gamma), _slot(beta), _slot(weight))
@@ -1157,6 +1202,12 @@ class _BNActConv(torch.autograd.Function):
                 part = _empty((rows, 2, Cs), x)
                 _small(dy, wd, dz, B, H, W, ldy, Cs, Cin, Cin, flop, stats=part, ep_mode=2,
                        ez=(x, mean, invstd, gamma, beta, act))
+            elif not up2 and _mid_halo_route(B, H, W, ldy, Cs, 3, 3, 1, 1, with_stats=True, prec=ctx.prec):
+                # 64/68-channel layer: the same fused data gradient on the halo-tile kernel (ep_mode 2)
+                rows = lib().raw("vmtl_conv3x3_halo_stat_rows")(B, H, W)
+                part = _empty((rows, 2, Cs), x)
+                _mid_halo(dy, wd, dz, B, H, W, ldy, Cs, Cin, Cin, flop, stats=part, ep_mode=2,
+                          ez=(x, mean, invstd, gamma, beta, act))
             else:
                 rows = lib().raw("vmtl_conv2d_stats_rows")(B, H, W, Cs)
                 part = _empty((rows, 2, Cs), x)
