@@ -1,0 +1,168 @@
+"""-m gpu: the tight-gradient instrument of tests/test_tight_grads_gpu.py at production spatial sizes.
+
+Identity activations (tests/util.py::identity_activations), train-mode BatchNorm, the loss within 1e-4 of the fp64 oracle and
+every parameter gradient within assert_grads_tight of it.  At these sizes the routes gated on pixel count (the narrow and
+64/68-channel halo-tile kernels, the UP2 halo kernel, the statistics epilogues and partial-row merges, the weight-gradient
+split counts) are the ones the benchmark runs; the small-shape tests only reach them with the gates forced open.
+
+The fp32 CPU oracle's own error (the bar of cancellation-heavy tensors) is its worst error over 4 and 16 threads: the
+1..16-thread sweep of the small-shape test is unaffordable at these sizes, and a fixed set keeps the bar the same on every
+host.  MTAN's max-pool arg-max is a kink identity activations do not remove: a window whose two largest inputs are closer
+than fp32 rounding may pick a different winner in the HIP run and in fp64.  The test compares the two arg-max maps of every
+encoder pool and counts the windows that really flipped; see the test for what it does with them.
+"""
+import math
+
+import pytest
+import torch
+
+from tests.production import build
+from tests.test_tight_grads_gpu import _oracle_grads
+from tests.util import (assert_close, assert_grads_as_good_as_fp32_cpu, assert_grads_tight, identity_activations,
+                        nontrivial_bn_affine, worst_of_runs)
+
+pytestmark = pytest.mark.gpu
+
+THREADS = (4, 16)
+
+
+def _argmax2x2(z):
+    """(B, C, H, W) -> arg-max (0..3) of every 2x2 window, on the CPU"""
+    B, C, H, W = z.shape
+    w = z.reshape(B, C, H // 2, 2, W // 2, 2).permute(0, 1, 2, 4, 3, 5).reshape(B, C, H // 2, W // 2, 4)
+    return w.argmax(-1).to(torch.uint8).cpu()
+
+
+class _OraclePools:
+    """stands in for torch.nn.functional inside oracle.mtan only: records the arg-max map of every max_pool2d input"""
+
+    def __init__(self, H):
+        import torch.nn.functional as F
+
+        self._F, self.H, self.pools = F, H, []
+
+    def __getattr__(self, name):
+        return getattr(self._F, name)
+
+    def max_pool2d(self, x, *a, **k):
+        self.pools.append((int(round(math.log2(self.H / x.shape[2]))), x.shape[1], _argmax2x2(x.detach())))
+        return self._F.max_pool2d(x, *a, **k)
+
+
+class _HipPools:
+    """wraps ops.maxpool2 / ops.bn_act_pool2 (the model calls them as ops.X): the arg-max map of every pooled input, the
+    BatchNorm of the fused node recomputed from the mean / invstd that node saved for its backward"""
+
+    def __init__(self, H):
+        self.H, self.pools = H, []
+
+    def __enter__(self):
+        from vision_mtl_amd import ops
+
+        self.ops, self.saved = ops, (ops.maxpool2, ops.bn_act_pool2)
+        mp, bnp = self.saved
+
+        def maxpool2(x):
+            C = x.shape[3]
+            self._add(x.detach()[..., :C].permute(0, 3, 1, 2))
+            return mp(x)
+
+        def bn_act_pool2(x, gamma, beta, rm, rv, nbt, C, *a, **k):
+            y = bnp(x, gamma, beta, rm, rv, nbt, C, *a, **k)
+            xs, g, b, mean, invstd = y.grad_fn.saved_tensors
+            z = (xs[..., :C] - mean[:C]) * invstd[:C] * g + b
+            self._add(z.detach().permute(0, 3, 1, 2))
+            return y
+
+        ops.maxpool2, ops.bn_act_pool2 = maxpool2, bn_act_pool2
+        return self
+
+    def _add(self, z):
+        self.pools.append((int(round(math.log2(self.H / z.shape[2]))), z.shape[1], _argmax2x2(z)))
+
+    def __exit__(self, *exc):
+        self.ops.maxpool2, self.ops.bn_act_pool2 = self.saved
+        return False
+
+
+def _flips(hip_pools, oracle_pools):
+    """{encoder level: windows whose arg-max differs between the HIP run and fp64}; the pools are matched in call order
+    within a level, and must agree in number and channel count"""
+    by = lambda pools: {lv: [(c, m) for l, c, m in pools if l == lv] for lv in {l for l, _, _ in pools}}
+    h, o = by(hip_pools), by(oracle_pools)
+    assert sorted(h) == sorted(o), f"pooled levels differ: HIP {sorted(h)}, oracle {sorted(o)}"
+    out = {}
+    for lv in h:
+        assert [c for c, _ in h[lv]] == [c for c, _ in o[lv]], f"level {lv}: pooled channels differ"
+        n = sum(int((mh != mo).sum()) for (_, mh), (_, mo) in zip(h[lv], o[lv]))
+        if n:
+            out[lv] = n
+    return out
+
+
+def production_step(dev, kind, B, H, W, C):
+    """(hip loss, fp64 loss, hip gradients, fp64 gradients, fp32 CPU gradients (worst over THREADS), {encoder level: flipped
+    max-pool windows}, parameters without a gradient)"""
+    import oracle.mtan as om
+    from oracle.losses import synthetic_batch
+    from vision_mtl_amd.lit_module import MTLModule
+
+    name = "csnet" if kind.startswith("csnet") else kind
+    model = build(name, C, channel_wise=False if name == "csnet" else None)
+    nontrivial_bn_affine(model)
+    sd0 = {k: v.clone() for k, v in model.state_dict().items()}
+    batch = synthetic_batch(B, H, W, C, seed=11, masked=0.1)
+    extra = {"levels": 4}
+    opools, hpools = _OraclePools(H), _HipPools(H)
+    with identity_activations():
+        threads = torch.get_num_threads()
+        try:
+            om.F = opools  # the fp64 run records its pools
+            try:
+                loss64, g64 = _oracle_grads(name, sd0, batch, torch.float64, extra)
+            finally:
+                om.F = opools._F
+            runs = []
+            for n in THREADS:
+                torch.set_num_threads(n)
+                runs.append(_oracle_grads(name, sd0, batch, torch.float32, extra)[1])
+        finally:
+            torch.set_num_threads(threads)
+        g32 = worst_of_runs(g64, runs)
+        del runs
+        model = model.to(dev).train()
+        module = MTLModule(model, num_classes=C, device=str(dev))
+        with hpools:
+            loss = module.training_step({k: v.to(dev) for k, v in batch.items()}, 0)
+        loss.backward()
+        torch.cuda.synchronize()
+    flips = _flips(hpools.pools, opools.pools) if name == "mtan" else {}
+    hip = {k: p.grad.cpu() for k, p in model.named_parameters() if p.grad is not None}
+    missing = [k for k, p in model.named_parameters() if p.grad is None and k in g64 and g64[k] is not None
+               and float(g64[k].abs().max()) > 0]
+    return loss.detach().cpu(), loss64, hip, g64, g32, flips, missing
+
+
+@pytest.mark.parametrize("kind,B,H,W,C", [("basic", 8, 128, 256, 19), ("basic", 32, 128, 256, 19), ("basic", 8, 256, 256, 19),
+                                          ("csnet_layer", 8, 128, 256, 19), ("mtan", 4, 256, 256, 14)])
+def test_production_step_is_tight_without_mask_flips(dev, kind, B, H, W, C):
+    """MTAN: a max-pool window whose arg-max really differs between the HIP run and fp64 (a near-tie) routes one gradient
+    element to the other input of the window, which moves the gradients of every parameter in front of that pool (encoder
+    levels <= l) by O(|g| / sqrt(pixels)).  Only those parameters, up to the deepest level with a measured flip, are held to
+    the end-to-end bar of the ReLU networks (assert_grads_as_good_as_fp32_cpu); all others stay on the tight bar."""
+    loss, loss64, hip, g64, g32, ties, missing = production_step(dev, kind, B, H, W, C)
+    assert_close(loss, loss64.float(), tol=1e-4, what=f"{kind} loss (identity activations)")
+    assert not missing, f"no gradient for {missing[:5]}"
+    loose = {}
+    if ties:
+        lmax = max(ties)
+        loose = {k: v for k, v in hip.items() if any(k.startswith(f"enc_layers.{i}.") for i in range(lmax + 1))}
+        hip = {k: v for k, v in hip.items() if k not in loose}
+        assert hip, "every gradient depends on a flipped pool window"
+        g64l = {k: g64[k] for k in loose}
+        g32l = {k: g32[k] for k in loose}
+        assert_grads_as_good_as_fp32_cpu(loose, g64l, g32l)
+    print(f"{kind} {B}x{H}x{W}: flipped max-pool windows per encoder level {ties}: {len(loose)} parameter gradients in "
+          f"front of them on the end-to-end bar, {len(hip)} on the tight bar")
+    eh, ec, k = assert_grads_tight(hip, g64, g32)
+    print(f"{kind} {B}x{H}x{W}: worst gradient error {eh:.2e} of its magnitude at {k} (fp32 CPU oracle there: {ec:.2e})")

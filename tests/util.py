@@ -130,3 +130,18 @@ def assert_grads_tight(named_hip, g64, g32, tol=1e-4, factor=4.0):
         if eh > worst[0]:
             worst = (eh, ec, k)
     return worst
+
+
+def nontrivial_bn_affine(model, seed=5):
+    """BatchNorm affine parameters (1-D, all 0 or all 1 at construction) moved off their initial values, in place."""
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for n, p in model.named_parameters():
+            if p.dim() == 1 and p.numel() > 1 and float(p.detach().abs().max()) in (0.0, 1.0):
+                p.add_(torch.randn(p.shape, generator=g) * 0.1)
+
+
+def worst_of_runs(g64, runs):
+    """per tensor, the run (dict of gradients) whose max-abs error against the fp64 gradient is largest"""
+    err = lambda g, k: float((g[k].double() - g64[k].double()).abs().max())
+    return {k: max(runs, key=lambda g: err(g, k))[k] for k, v in g64.items() if v is not None}
