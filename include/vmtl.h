@@ -288,6 +288,12 @@ int vmtl_bn_stats_coef(const float* x, int M, int C, int Cs, float* partial, int
 int vmtl_bn_eval_stats_coef(const float* running_mean, const float* running_var, int C, int Cs, float eps,
                             float* save_mean, float* save_invstd, const float* gamma, const float* beta,
                             float* coef_a, float* coef_c, void* stream);
+/* batched eval statistics: one launch for n layers.  descs = device array of n records {running_mean*, running_var*,
+ * gamma*, beta*, save_mean*, save_invstd*, coef_a*, coef_c*, i32 C, Cs, f32 eps, i32 pad} (vmtl_bn_eval_desc_bytes()
+ * bytes each); every record writes what vmtl_bn_eval_stats(_coef) writes for it (gamma / beta / coef_a+coef_c may be
+ * null, as there).  max_cs = the largest Cs of the table (a multiple of 4); host-only size query. */
+int vmtl_bn_eval_desc_bytes(void);
+int vmtl_bn_eval_stats_batch(const void* descs, int n, int max_cs, void* stream);
 int vmtl_bn_apply(const float* x, const float* mean, const float* invstd, const float* gamma,
                   const float* beta, const float* mul, const float* res, float* y, long long M, int C,
                   int Cs, int act, void* stream);

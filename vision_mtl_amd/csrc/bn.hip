@@ -157,12 +157,12 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restric
   }
 }
 
-// eval mode: derive mean / invstd from the running buffers
-__global__ void bn_eval_stats_kernel(const float* __restrict__ running_mean, const float* __restrict__ running_var,
-                                     int C, int Cs, float eps, float* save_mean, float* save_invstd,
-                                     const float* gamma, const float* beta, float* coef_a, float* coef_c) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= Cs) return;
+// eval mode: derive mean / invstd from the running buffers.  One channel c < Cs; shared by the per-layer kernel and the
+// batched one below, so the two write the same bits.
+__device__ __forceinline__ void bn_eval_stats_channel(int c, const float* __restrict__ running_mean,
+                                                      const float* __restrict__ running_var, int C, float eps,
+                                                      float* save_mean, float* save_invstd, const float* gamma,
+                                                      const float* beta, float* coef_a, float* coef_c) {
   const float m = c < C ? running_mean[c] : 0.f;
   const float is = c < C ? 1.f / sqrtf(running_var[c] + eps) : 0.f;
   save_mean[c] = m;
@@ -172,6 +172,38 @@ __global__ void bn_eval_stats_kernel(const float* __restrict__ running_mean, con
     coef_a[c] = sc;
     coef_c[c] = c < C ? (beta ? beta[c] : 0.f) - m * sc : 0.f;
   }
+}
+
+__global__ void bn_eval_stats_kernel(const float* __restrict__ running_mean, const float* __restrict__ running_var,
+                                     int C, int Cs, float eps, float* save_mean, float* save_invstd,
+                                     const float* gamma, const float* beta, float* coef_a, float* coef_c) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= Cs) return;
+  bn_eval_stats_channel(c, running_mean, running_var, C, eps, save_mean, save_invstd, gamma, beta, coef_a, coef_c);
+}
+
+// ---- batched form: every eval-mode BatchNorm of a model in ONE launch (a predict step otherwise pays one tiny
+// launch per layer).  Grid (cdiv(max_cs, 128), n): blockIdx.y picks the descriptor, x the channel.
+struct BnEvalDesc {
+  const float* running_mean;
+  const float* running_var;
+  const float* gamma;  // null: 1
+  const float* beta;   // null: 0
+  float* save_mean;
+  float* save_invstd;
+  float* coef_a;  // null (with coef_c): no coefficients
+  float* coef_c;
+  int C, Cs;
+  float eps;
+  int pad_;
+};
+
+__global__ __launch_bounds__(128) void bn_eval_stats_batch_kernel(const BnEvalDesc* __restrict__ descs) {
+  const BnEvalDesc d = descs[blockIdx.y];
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= d.Cs) return;
+  bn_eval_stats_channel(c, d.running_mean, d.running_var, d.C, d.eps, d.save_mean, d.save_invstd, d.gamma, d.beta,
+                        d.coef_a, d.coef_c);
 }
 
 static int bn_stats_impl(const float* x, int M, int C, int Cs, float* partial, int nblk_from_conv,
@@ -232,6 +264,18 @@ extern "C" int vmtl_bn_eval_stats_coef(const float* running_mean, const float* r
     return VMTL_ERR_ARG;
   hipLaunchKernelGGL(bn_eval_stats_kernel, dim3(cdiv(Cs, 128)), dim3(128), 0, (hipStream_t)stream, running_mean,
                      running_var, C, Cs, eps, save_mean, save_invstd, gamma, beta, coef_a, coef_c);
+  return vmtl_check_launch();
+}
+
+extern "C" int vmtl_bn_eval_desc_bytes(void) { return (int)sizeof(BnEvalDesc); }
+
+// descs: device array of n BnEvalDesc records (vmtl_bn_eval_desc_bytes() each, validated by the host that wrote them:
+// 0 < C <= Cs <= max_cs, Cs % 4 == 0, coef_a and coef_c both null or both set); max_cs sizes the grid.
+extern "C" int vmtl_bn_eval_stats_batch(const void* descs, int n, int max_cs, void* stream) {
+  VMTL_ENTER();
+  if (!descs || n <= 0 || n > 65535 || max_cs <= 0 || (max_cs & 3)) return VMTL_ERR_ARG;
+  hipLaunchKernelGGL(bn_eval_stats_batch_kernel, dim3(cdiv(max_cs, 128), n), dim3(128), 0, (hipStream_t)stream,
+                     (const BnEvalDesc*)descs);
   return vmtl_check_launch();
 }
 

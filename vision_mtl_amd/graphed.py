@@ -29,6 +29,8 @@ of the GEMM operands and the per-step metrics are kernels inside the graph.
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 
 from . import dp, ops
@@ -48,7 +50,42 @@ class _Replayed(torch.autograd.Function):
         return None, None
 
 
-class GraphedStep:
+class _StaticBatch:
+    """What a captured step shares: static input buffers the caller's batches are copied into, and the model input
+    made from them inside the graph (dataset sample layout re-laid by one kernel, or the recorded device transform)."""
+
+    def _init_static(self, module, example_batch: dict) -> None:
+        self.device = next(module.model.parameters()).device
+        # a raw batch (data.collate_raw) whose sample transform runs inside the graph: recorded once, like the precision
+        self.device_transform = getattr(module, "device_transform", None)
+        self.static = {k: self._static_like(v) for k, v in example_batch.items()}
+        self._fill(example_batch)
+        self._sample_layout = (self.device_transform is None and self.static["img"].dim() == 4
+                               and self.static["img"].shape[-1] == 3 and self.static["img"].shape[1] != 3)
+        self.conv_precision = get_conv_precision()
+
+    def _static_like(self, v: torch.Tensor) -> torch.Tensor:
+        return torch.empty(v.shape, dtype=torch.float32 if v.is_floating_point() else v.dtype, device=self.device)
+
+    def _fill(self, batch: dict) -> None:
+        name = type(self).__name__
+        for k, dst in self.static.items():
+            src = batch[k]
+            if tuple(src.shape) != tuple(dst.shape):
+                raise ValueError(f"{name}: batch[{k!r}] has shape {tuple(src.shape)}, the captured step expects "
+                                 f"{tuple(dst.shape)} (capture one {name} per batch shape; drop_last=True)")
+            dst.copy_(src, non_blocking=src.device.type == "cpu" and src.is_pinned())
+
+    def _model_batch(self) -> dict:
+        batch = dict(self.static)
+        if self.device_transform is not None:
+            batch = self.device_transform(batch)
+        elif self._sample_layout:
+            batch["img"] = ops.hwc_to_model_input(self.static["img"])
+        return batch
+
+
+class GraphedStep(_StaticBatch):
     """fwd + losses + bwd of `module.training_step` captured once, replayed per batch.
 
     module: an MTLModule already on its device; example_batch: a batch of the shapes / dtypes / layout every later
@@ -66,17 +103,10 @@ class GraphedStep:
         if not torch.cuda.is_available():
             raise RuntimeError("GraphedStep needs an MI355X: the hot path has no CPU fallback")
         self.module, self.stage = module, stage
-        self.device = next(module.model.parameters()).device
         if arena is None:
             arena = module.dp_arena if module.dp_arena is not None else dp.FlatArena(module.model)
         self.arena = arena
-        # a raw batch (data.collate_raw) whose sample transform runs inside the graph: recorded once, like the precision
-        self.device_transform = getattr(module, "device_transform", None)
-        self.static = {k: self._static_like(v) for k, v in example_batch.items()}
-        self._fill(example_batch)
-        self._sample_layout = (self.device_transform is None and self.static["img"].dim() == 4
-                               and self.static["img"].shape[-1] == 3 and self.static["img"].shape[1] != 3)
-        self.conv_precision = get_conv_precision()
+        self._init_static(module, example_batch)  # static buffers; conv precision and module.device_transform recorded
         attached, module.dp_arena = module.dp_arena, None  # the collective stays outside the graph (see __call__)
         try:
             so = module.step_outputs[stage]
@@ -103,30 +133,16 @@ class GraphedStep:
                 self._loss = loss.detach()
             for k, v in so.items():
                 del v[mark[k]:]
+            # the graph reads the packed-operand descriptor tables by address: keep them alive should the cache rebuild
+            self._pack_tables = (ops.packs.table, ops.packs.table_side)
         finally:
             module.dp_arena = attached
         self._anchor = torch.zeros((), device=self.device, requires_grad=True)
         self.replays = 0
 
     # ---- helpers
-    def _static_like(self, v: torch.Tensor) -> torch.Tensor:
-        return torch.empty(v.shape, dtype=torch.float32 if v.is_floating_point() else v.dtype, device=self.device)
-
-    def _fill(self, batch: dict) -> None:
-        for k, dst in self.static.items():
-            src = batch[k]
-            if tuple(src.shape) != tuple(dst.shape):
-                raise ValueError(f"GraphedStep: batch[{k!r}] has shape {tuple(src.shape)}, the captured step expects "
-                                 f"{tuple(dst.shape)} (capture one GraphedStep per batch shape; drop_last=True)")
-            dst.copy_(src, non_blocking=src.device.type == "cpu" and src.is_pinned())
-
     def _step(self) -> torch.Tensor:
-        batch = dict(self.static)
-        if self.device_transform is not None:
-            batch = self.device_transform(batch)
-        elif self._sample_layout:
-            batch["img"] = ops.hwc_to_model_input(self.static["img"])
-        return self.module.shared_step(batch, self.stage)
+        return self.module.shared_step(self._model_batch(), self.stage)
 
     # ---- the step
     def __call__(self, batch: dict) -> torch.Tensor:
@@ -143,6 +159,117 @@ class GraphedStep:
         for i, k in enumerate(self._keys):
             so[k].append(stats[i])
         return _Replayed.apply(stats[self._keys.index("loss")] if "loss" in self._keys else self._loss, self._anchor)
+
+
+class GraphedEval(_StaticBatch):
+    """One forward-only step (no_grad) captured once, replayed per batch: the validation / test / predict loops of
+    the reference (training_lit.py:115-150, 186-216) at hipGraph replay speed::
+
+        geval = GraphedEval(module, example_batch, stage="val")      # module.train(): the reference validates in
+        with torch.no_grad():                                        # train mode (BatchNorm uses batch statistics
+            for batch in val_dataloader:                             # and moves its running buffers)
+                loss = geval(batch)                                  # = module.validation_step(batch)
+
+        module.eval()
+        gpred = GraphedEval(module, example_batch, stage="predict")
+        preds = [gpred(batch) for batch in predict_dataloader]       # = module.predict_step(batch)
+
+    stage "val" / "test": shared_step; the call returns the loss and appends loss + metrics to
+    module.step_outputs[stage] as the eager step does.  stage "predict": predict_step, with or without "mask" / "depth"
+    in the batch; the call returns {"segm", "depth"} as fresh tensors (the reference keeps every batch's predictions)
+    and appends to step_outputs["predict"] when the targets are there.
+
+    When a BatchNorm of the model is in eval mode the step runs inside ops.eval_bn_table: the first node of the graph
+    derives every eval-mode layer's statistics from the running buffers as they are at replay time.  Parameters are
+    read in place (the per-step weight packing is a node of the graph), so a replay after optimizer.step() sees the new
+    weights.  Construction has no side effects: the BatchNorm running buffers are restored in place after the
+    warm-up / rehearsal steps, step_outputs is left as it was and no gradient is written.  Like GraphedStep, the step
+    keeps the convolution precision, module.device_transform and batch shapes in force at construction; a call raises
+    ValueError on another batch shape or when module.training (or a BatchNorm's mode) differs from the capture.
+    bn_table=False keeps the per-layer eval-statistics launches (A/B measurement)."""
+
+    STAGES = ("val", "test", "predict")
+
+    def __init__(self, module, example_batch: dict, stage: str = "val", warmup: int = 2, bn_table: bool = True):
+        if stage not in self.STAGES:
+            raise ValueError(f"GraphedEval: stage must be one of {self.STAGES}, got {stage!r}")
+        if not torch.cuda.is_available():
+            raise RuntimeError("GraphedEval needs an MI355X: the hot path has no CPU fallback")
+        if stage != "predict" and not ("mask" in example_batch and "depth" in example_batch):
+            raise ValueError(f"GraphedEval(stage={stage!r}): the batch needs 'mask' and 'depth'")
+        self.module, self.stage = module, stage
+        self._init_static(module, example_batch)
+        bns = [m for m in module.model.modules() if isinstance(m, torch.nn.BatchNorm2d)]
+        self.training = module.training
+        self._modes = tuple(m.training for m in bns)
+        self._bns = bns
+        self.bn_table = bool(bn_table) and not all(self._modes)
+        self._table = None
+        so = module.step_outputs[stage]
+        mark = {k: len(v) for k, v in so.items()}
+        snap = [(m, [b.clone() for b in self._buffers(m)]) for m in bns]
+        try:
+            with torch.no_grad():
+                for _ in range(max(1, warmup)):
+                    self._step()  # builds the packed-operand and BatchNorm tables outside the capture
+                torch.cuda.synchronize(self.device)
+                s = _rehearsal_stream(self.device)
+                s.wait_stream(torch.cuda.current_stream(self.device))
+                with torch.cuda.stream(s):
+                    self._step()
+                torch.cuda.current_stream(self.device).wait_stream(s)
+                for k, v in so.items():
+                    del v[mark[k]:]
+                self.graph = torch.cuda.CUDAGraph()
+                with conv_precision(self.conv_precision), torch.cuda.graph(self.graph):
+                    out = self._step()
+                    # everything the step appended to step_outputs (loss + the four metrics), as ONE static vector
+                    self._keys = [k for k, v in so.items() if len(v) > mark[k]]
+                    self._stats = (torch.stack([so[k][-1].detach().reshape(()).float() for k in self._keys])
+                                   if self._keys else None)
+                    self._out = out
+            # the graph reads these by address: keep them alive should a cache rebuild its tables
+            self._pack_tables = (ops.packs.table, ops.packs.table_side)
+        finally:
+            for k, v in so.items():
+                del v[mark[k]:]
+            with torch.no_grad():
+                for m, saved in snap:
+                    for b, v in zip(self._buffers(m), saved):
+                        b.copy_(v)
+        self.replays = 0
+
+    @staticmethod
+    def _buffers(m):
+        return [b for b in (m.running_mean, m.running_var, m.num_batches_tracked) if b is not None]
+
+    def _step(self):
+        ctx = ops.eval_bn_table(self.module.model) if self.bn_table else contextlib.nullcontext()
+        with ctx as table:
+            if table is not None:
+                self._table = table
+            batch = self._model_batch()
+            if self.stage == "predict":
+                return self.module.predict_step(batch)
+            return self.module.shared_step(batch, self.stage)
+
+    def __call__(self, batch: dict):
+        if self.module.training != self.training or tuple(m.training for m in self._bns) != self._modes:
+            raise ValueError(f"GraphedEval: captured with module.training={self.training}, called with "
+                             f"module.training={self.module.training} (or a BatchNorm changed mode); capture one "
+                             "GraphedEval per mode")
+        self._fill(batch)
+        self.graph.replay()
+        self.replays += 1
+        stats = None
+        if self._stats is not None:
+            stats = self._stats.clone()  # one tiny copy: the static vector is overwritten by the next replay
+            so = self.module.step_outputs[self.stage]
+            for i, k in enumerate(self._keys):
+                so[k].append(stats[i])
+        if self.stage == "predict":
+            return {"segm": self._out["segm"].clone(), "depth": self._out["depth"].clone()}
+        return stats[self._keys.index("loss")] if "loss" in self._keys else self._out.clone()
 
 
 _STREAMS = {}

@@ -429,6 +429,113 @@ class _PackCache:
 packs = _PackCache()
 
 
+# ----------------------------------------------------------------------------- eval-mode BatchNorm statistics
+class _EvalBNTable:
+    """(mean, invstd, coef_a, coef_c) of every eval-mode BatchNorm of a model from ONE vmtl_bn_eval_stats_batch launch.
+
+    Outside eval_bn_table() each eval-mode BatchNorm derives them from its running buffers with a launch of its own
+    (vmtl_bn_eval_stats / _coef).  Inside, the launch at the head of the step fills persistent buffers (one flat
+    tensor per model) and the call sites look them up by the address of the layer's running_mean: no launch.  The
+    descriptor table is built and uploaded once per model and re-used while the layers' buffers and parameters stay
+    where they are; it is never built inside a graph capture.  Models are held by weak reference: the tables of a
+    dropped model go with it."""
+
+    DESC = "<QQQQQQQQiifi"
+
+    def __init__(self):
+        self.tables = weakref.WeakKeyDictionary()  # model -> table (dict)
+        self.active = None  # running_mean address -> (mean, invstd, coef_a, coef_c, C, eps, gamma addr, beta addr)
+
+    @staticmethod
+    def _layers(model):
+        return [m for m in model.modules() if isinstance(m, torch.nn.BatchNorm2d) and not m.training
+                and m.running_mean is not None]
+
+    @staticmethod
+    def _signature(layers):
+        ptr = lambda t: 0 if t is None else t.data_ptr()
+        return tuple((id(m), m.running_mean.data_ptr(), m.running_var.data_ptr(), ptr(m.weight), ptr(m.bias),
+                      m.num_features, float(m.eps)) for m in layers)
+
+    def table(self, model):
+        """The descriptor table of model's eval-mode BatchNorms as they are now (None: there are none); built here when
+        missing or stale."""
+        import struct
+
+        layers = self._layers(model)
+        if not layers:
+            return None
+        sig = self._signature(layers)
+        t = self.tables.get(model)
+        if t is not None and t["sig"] == sig:
+            return t
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("eval_bn_table: the BatchNorm table of this model must be built before the capture "
+                               "(enter eval_bn_table once eagerly, e.g. in a warm-up step)")
+        dev = layers[0].running_mean.device
+        sizes = [ceil4(m.num_features) for m in layers]
+        buf = torch.zeros(4 * sum(sizes), dtype=torch.float32, device=dev)
+        recs, lookup, off = [], {}, 0
+        for m, Cs in zip(layers, sizes):
+            _req(m.running_mean, "running_mean"), _req(m.running_var, "running_var")
+            mean, invstd, ca, cc = (buf[off + i * Cs: off + (i + 1) * Cs] for i in range(4))
+            off += 4 * Cs
+            g = 0 if m.weight is None else m.weight.data_ptr()
+            b = 0 if m.bias is None else m.bias.data_ptr()
+            recs.append(struct.pack(self.DESC, m.running_mean.data_ptr(), m.running_var.data_ptr(), g, b,
+                                    mean.data_ptr(), invstd.data_ptr(), ca.data_ptr(), cc.data_ptr(), m.num_features,
+                                    Cs, float(m.eps), 0))
+            lookup[m.running_mean.data_ptr()] = (mean, invstd, ca, cc, m.num_features, float(m.eps), g, b)
+        size = lib().raw("vmtl_bn_eval_desc_bytes")()
+        blob = b"".join(r.ljust(size, b"\0") for r in recs)
+        t = {"sig": sig, "descs": torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(dev), "n": len(recs),
+             "max_cs": max(sizes), "buf": buf, "lookup": lookup}
+        self.tables[model] = t
+        return t
+
+    def get(self, rm, C, eps, coef=None):
+        """The precomputed (mean, invstd, coef_a, coef_c) of the layer whose running_mean is `rm`, or None (no table
+        in force, or it does not describe this call).  coef: the (gamma, beta) the caller's coefficients fold in."""
+        if self.active is None:
+            return None
+        e = self.active.get(rm.data_ptr())
+        if e is None or e[4] != C or e[5] != float(eps):
+            return None
+        if coef is not None and tuple(0 if t is None else t.data_ptr() for t in coef) != e[6:8]:
+            return None
+        return e[:4]
+
+
+eval_bn = _EvalBNTable()
+
+
+@contextlib.contextmanager
+def eval_bn_table(model):
+    """Eval-mode BatchNorm statistics of `model` for the enclosed step from ONE launch, issued here on the current
+    stream (the eval-stats call sites then launch nothing).  Yields the table (None when no BatchNorm of the model is
+    in eval mode: the step then runs exactly as without the context).  The running buffers are read at entry: enter
+    it once per step."""
+    t = eval_bn.table(model)
+    prev = eval_bn.active
+    if t is not None:
+        _k("vmtl_bn_eval_stats_batch", descs=t["descs"], n=t["n"], max_cs=t["max_cs"])
+        eval_bn.active = t["lookup"] if prev is None else {**prev, **t["lookup"]}
+    try:
+        yield t
+    finally:
+        eval_bn.active = prev
+
+
+def _bn_eval_stats(rm, rv, C, Cs, eps, like):
+    """(mean, invstd) of an eval-mode BatchNorm: from the table in force, else one launch."""
+    e = eval_bn.get(rm, C, eps)
+    if e is not None:
+        return e[0], e[1]
+    mean, invstd = _empty((Cs,), like), _empty((Cs,), like)
+    _k("vmtl_bn_eval_stats", running_mean=rm, running_var=rv, C=C, Cs=Cs, eps=eps, save_mean=mean, save_invstd=invstd)
+    return mean, invstd
+
+
 def pack(src, R1, R0, T, C, Cs, sr1, sr0, st, sc, flip=0, out=None):
     dst = _empty((R1 * R0, T * Cs), src) if out is None else out
     _k("vmtl_pack_weights", src=src, dst=dst, R1=R1, R0=R0, T=T, C=C, Cs=Cs, sr1=sr1, sr0=sr0, st=st, sc=sc, flip=flip)
@@ -1100,8 +1207,7 @@ class _BNActConv(torch.autograd.Function):
                 _k("vmtl_bn_apply", x=x, mean=mean, invstd=invstd, gamma=gamma, beta=beta, mul=None, res=None, y=a, M=M,
                    C=C, Cs=Cs, act=act)
         else:
-            mean, invstd = _empty((Cs,), x), _empty((Cs,), x)
-            _k("vmtl_bn_eval_stats", running_mean=rm, running_var=rv, C=C, Cs=Cs, eps=eps, save_mean=mean, save_invstd=invstd)
+            mean, invstd = _bn_eval_stats(rm, rv, C, Cs, eps, x)
             _k("vmtl_bn_apply", x=x, mean=mean, invstd=invstd, gamma=gamma, beta=beta, mul=None, res=None, y=a, M=M, C=C,
                Cs=Cs, act=act)
         # ---- the conv on a
@@ -1506,8 +1612,8 @@ class _BNAct(torch.autograd.Function):
         y = _empty(x.shape, x)
         fused = False
         if gamma is not None:
-            mean, invstd = _empty((Cs,), x), _empty((Cs,), x)
             if training:
+                mean, invstd = _empty((Cs,), x), _empty((Cs,), x)
                 if stats is not None:
                     partial, nblk = stats, stats.shape[0]
                     rpb = stats_rpb if stats_rpb else lib().raw("vmtl_conv2d_stats_block")(B, H, W, Cs)
@@ -1526,8 +1632,7 @@ class _BNAct(torch.autograd.Function):
                        momentum=momentum, running_mean=running_mean, running_var=running_var, num_batches_tracked=nbt,
                        save_mean=mean, save_invstd=invstd)
             else:
-                _k("vmtl_bn_eval_stats", running_mean=running_mean, running_var=running_var, C=C, Cs=Cs, eps=eps,
-                   save_mean=mean, save_invstd=invstd)
+                mean, invstd = _bn_eval_stats(running_mean, running_var, C, Cs, eps, x)
         if not fused:
             _k("vmtl_bn_apply", x=x, mean=mean, invstd=invstd, gamma=gamma, beta=beta, mul=mul, res=res, y=y, M=M, C=C,
                Cs=Cs, act=act)
@@ -1580,8 +1685,8 @@ class _BNActPool(torch.autograd.Function):
         x = _req(x, "x")
         B, H, W, Cs = x.shape
         M = B * H * W
-        mean, invstd = _empty((Cs,), x), _empty((Cs,), x)
         if training:
+            mean, invstd = _empty((Cs,), x), _empty((Cs,), x)
             if stats is not None:
                 partial, nblk = stats, stats.shape[0]
                 rpb = stats_rpb if stats_rpb else lib().raw("vmtl_conv2d_stats_block")(B, H, W, Cs)
@@ -1591,8 +1696,7 @@ class _BNActPool(torch.autograd.Function):
                eps=eps, momentum=momentum, running_mean=running_mean, running_var=running_var, num_batches_tracked=nbt,
                save_mean=mean, save_invstd=invstd)
         else:
-            _k("vmtl_bn_eval_stats", running_mean=running_mean, running_var=running_var, C=C, Cs=Cs, eps=eps,
-               save_mean=mean, save_invstd=invstd)
+            mean, invstd = _bn_eval_stats(running_mean, running_var, C, Cs, eps, x)
         y = _empty((B, H // 2, W // 2, Cs), x)
         _k("vmtl_bn_act_pool2_fwd", x=x, mean=mean, invstd=invstd, gamma=gamma, beta=beta, y=y, B=B, H=H, W=W, C=C, Cs=Cs,
            act=act)
@@ -2067,6 +2171,10 @@ def _bn_fwd_coef(x, stats, rpb, gamma, beta, rm, rv, nbt, C, training, momentum,
     BN(x) = coef_a * x + coef_c per channel (zeros on pad channels)."""
     B, H, W, Cs = x.shape
     M = B * H * W
+    if not training:
+        e = eval_bn.get(rm, C, eps, (gamma, beta))
+        if e is not None:
+            return e
     mean, invstd, ca, cc = (_empty((Cs,), x) for _ in range(4))
     if training:
         if stats is not None:
