@@ -328,6 +328,50 @@ int vmtl_bn_act_pool2_bwd(const float* x, const float* dyp, const float* mean, c
                           const float* gamma, const float* beta, float* partial, float* sum_dz, float* sum_dzx,
                           float* dx, int B, int H, int W, int C, int Cs, int act, int training, void* stream);
 
+/* ---- torchvision BasicBlock ResNet encoder (smp ResNetEncoder "resnet18" / "resnet34" behind encoder_name,
+ * reference vision_mtl/utils/model_utils.py:10-31, models/basic_model.py:10-29; csrc/resnet.hip) ---------------------
+ * Data gradient of a stride-2 dense conv (dx [B][H][W][Cs] from dy [B][Ho][Wo][ldy], Ho = (H + 2*pad - K)/2 + 1) by phase
+ * decomposition: the pixels of phase (ih & 1, iw & 1) get a stride-1 correlation of dy with that phase's subset of the
+ * flipped taps - one launch per phase into ws (implicit GEMM, split-K where the stride-1 data gradient of that shape
+ * splits too; single-tap unpadded phases in fp32 on the pointwise GEMM), then one gather interleaves them; pixels no
+ * window covers get an exact 0.  wp: vmtl_pack_dgrad_s2 of the torch (Cout, Cin, K, K) weight (vmtl_pack_dgrad_s2_size floats);
+ * ws: vmtl_conv2d_dgrad_s2_ws floats.  Supported (K, pad): those whose phases share one correlation pad, e.g. (1, 0),
+ * (3, 1), (7, 3) (vmtl_conv2d_dgrad_s2_supported; the size queries return -1 otherwise). */
+int vmtl_conv2d_dgrad_s2_supported(int K, int pad);
+long long vmtl_conv2d_dgrad_s2_ws(int B, int H, int W, int Cs, int Ho, int Wo, int ldy, int K, int pad);
+long long vmtl_pack_dgrad_s2_size(int Cin, int ldy, int K, int pad);
+int vmtl_pack_dgrad_s2(const float* w, float* dst, int Cout, int Cin, int ldy, int K, int pad, void* stream);
+int vmtl_conv2d_dgrad_s2(const float* dy, const float* wp, float* dx, float* ws, int B, int H, int W, int Cs, int Ho,
+                         int Wo, int ldy, int Cin, int K, int pad, void* stream);
+int vmtl_conv2d_dgrad_s2_p(const float* dy, const float* wp, float* dx, float* ws, int B, int H, int W, int Cs, int Ho,
+                           int Wo, int ldy, int Cin, int K, int pad, int precision, void* stream);
+/* BatchNorm + activation + MaxPool2d(3, stride 2, pad 1) of the ResNet stem as one node: a_out (nullable) [B][H][W][Cs] =
+ * act(BN(x)) (the decoder skip), y [B][Ho][Wo][Cs] its pool, Ho = (H-1)/2 + 1 (floor mode, -inf padding, torch CPU
+ * max_pool2d's tie and NaN rule), idx [B][Ho][Wo][Cs] bytes = the arg-max's window position (0..8).  mean == invstd ==
+ * NULL: no BatchNorm (the plain pool of an activated map: act NONE).  bwd: each input pixel gathers dskip (nullable) plus
+ * dyp of the windows whose arg-max it is (no atomics); with BatchNorm then act' (dz, [B][H][W][Cs] scratch), the partial
+ * rows (partial: vmtl_reduce_rows(B*H*W)*2*Cs floats), sum_dz / sum_dzx [C] = dbeta / dgamma and dx; without, dx = the
+ * gathered gradient times act'(x). */
+int vmtl_bn_act_pool3s2_fwd(const float* x, const float* mean, const float* invstd, const float* gamma,
+                            const float* beta, float* a_out, float* y, unsigned char* idx, int B, int H, int W, int C,
+                            int Cs, int act, void* stream);
+int vmtl_bn_act_pool3s2_bwd(const float* x, const float* dskip, const float* dyp, const unsigned char* idx,
+                            const float* mean, const float* invstd, const float* gamma, const float* beta, float* dz,
+                            float* partial, float* sum_dz, float* sum_dzx, float* dx, int B, int H, int W, int C, int Cs,
+                            int act, int training, void* stream);
+/* Residual close of a BasicBlock: y = act(BN_a(z) + r), r = res (identity) or BN_b(zd) (downsample branch: res NULL);
+ * mean / invstd from vmtl_bn_stats (train) or the running buffers (eval).  bwd: g = dy * act'(pre) (the identity
+ * gradient), the partial rows (partial: vmtl_reduce_rows(M)*3*Cs floats), sum_dz_* / sum_dzx_* [C] = dbeta / dgamma of
+ * each BatchNorm, and dz / dzd (nullable) = the gradients of z / zd through their BatchNorm. */
+int vmtl_bn_add_act_fwd(const float* z, const float* mean_a, const float* invstd_a, const float* gamma_a,
+                        const float* beta_a, const float* res, const float* zd, const float* mean_b, const float* invstd_b,
+                        const float* gamma_b, const float* beta_b, float* y, int M, int C, int Cs, int act, void* stream);
+int vmtl_bn_add_act_bwd(const float* z, const float* mean_a, const float* invstd_a, const float* gamma_a,
+                        const float* beta_a, const float* res, const float* zd, const float* mean_b, const float* invstd_b,
+                        const float* gamma_b, const float* beta_b, const float* dy, float* g, float* partial,
+                        float* sum_dz_a, float* sum_dzx_a, float* sum_dz_b, float* sum_dzx_b, float* dz, float* dzd, int M,
+                        int C, int Cs, int act, int training, void* stream);
+
 /* out[c] = sum_m a[m][c] (mode 0) or a*b (mode 1); reduce_all sums over channels too.
  * partial: (vmtl_reduce_rows(M) + 1) * Cs floats of scratch */
 int vmtl_colsum(const float* a, const float* b, int M, int C, int Cs, int mode, int reduce_all,

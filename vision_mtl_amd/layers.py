@@ -134,6 +134,32 @@ def conv_bn_act_maxpool2(x: Act, c: nn.Conv2d, bn: nn.BatchNorm2d, act: int) -> 
     return Act(p, c.out_channels)
 
 
+def conv_bn_act_maxpool3(x: Act, c: nn.Conv2d, bn: nn.BatchNorm2d, act: int):
+    """(act(BN(conv(x))), MaxPool2d(3, 2, 1) of it) - a ResNet stem - with the BatchNorm + activation + pool as ONE node
+    (ops.bn_act_pool3) that writes both maps: the activation is also a decoder skip."""
+    if c.groups != 1:
+        raise ValueError("conv_bn_act_maxpool3 expects a dense conv")
+    train = bn.training
+    out = ops.conv2d(x.t, c.weight, c.bias, _pair(c.stride), _pair(c.padding), want_stats=train,
+                     zero_bias_grad=train and c.bias is not None)
+    y, stats = out if train else (out, None)
+    a, p = ops.bn_act_pool3(y, bn, c.out_channels, act, stats=stats)
+    return Act(a, c.out_channels), Act(p, c.out_channels)
+
+
+def maxpool3(x: Act) -> Act:
+    """MaxPool2d(kernel_size=3, stride=2, padding=1)."""
+    return Act(ops.maxpool3s2(x.t, x.C), x.C)
+
+
+def bn_add_act(z: Act, stats, rpb: int, bn: nn.BatchNorm2d, act: int, res: Act | None = None, ds=None) -> Act:
+    """act(bn(z) + res) (identity shortcut) or act(bn(z) + bn_d(zd)) with ds = (zd raw, its stats rows, rpb, bn_d)."""
+    if ds is None:
+        return Act(ops.bn_add_act(z.t, stats, rpb, bn, z.C, act, res=res.t), z.C)
+    zd, std, rpbd, bn_d = ds
+    return Act(ops.bn_add_act(z.t, stats, rpb, bn, z.C, act, zd=zd, statsd=std, rpbd=rpbd, bn_d=bn_d), z.C)
+
+
 def activation(x: Act, act: int) -> Act:
     return Act(ops.activation(x.t, act, x.C), x.C)
 

@@ -22,6 +22,7 @@ from torch import nn
 from .. import layers as L
 from .. import ops
 from ..utils.model_utils import get_module_by_name
+from .unet_mobilenetv3 import MobileNetV3Encoder
 
 
 def get_joint_layer_names_before_stitch_for_unet(joint_layer_names: t.List[str]) -> t.List[str]:
@@ -70,6 +71,12 @@ class CSNet(nn.Module):
 
     def __init__(self, models: dict, channel_wise_stitching: bool = False):
         super().__init__()
+        for task, m in models.items():  # the stitch sites below are the timm MobileNetV3 encoder's blocks
+            enc = getattr(m[0], "encoder", None) if isinstance(m, nn.Sequential) and len(m) > 0 else None
+            if enc is not None and not isinstance(enc, MobileNetV3Encoder):
+                name = getattr(enc, "name", type(enc).__name__)
+                raise NotImplementedError(f"CSNet over a {name!r} encoder (task {task!r}): the cross-stitch sites are only "
+                                          "defined for the timm-mobilenetv3_large_100 encoder")
         self.encoder_block_regex = r"0.encoder.model.blocks.(\d+)$"
         self.decoder_block_regex = r"0.decoder.blocks.(\d+)$"
         self.num_tasks = len(models)

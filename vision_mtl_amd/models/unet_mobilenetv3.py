@@ -24,6 +24,7 @@ from torch import nn
 
 from .. import layers as L
 from ..ops import ACT_HSIGMOID, ACT_HSWISH, ACT_NONE, ACT_RELU
+from .resnet_encoder import BASIC_LAYERS, BOTTLENECK, ResNetEncoder
 
 _ACT_CODE = {"relu": ACT_RELU, "hard_swish": ACT_HSWISH, None: ACT_NONE}
 
@@ -415,14 +416,31 @@ class SegmentationHead(nn.Sequential):
         return L.conv(x, self[0])
 
 
+def _load_encoder_weights(module: nn.Module, weights_file: str, arch: str) -> None:
+    """Load a local checkpoint of the encoder's architecture into `module` (its own keys only: the extra keys of a
+    classifier checkpoint - timm's conv_head / classifier, torchvision's fc - are dropped, as the smp encoders drop them);
+    missing keys raise."""
+    sd = torch.load(weights_file, map_location="cpu", weights_only=True)  # a state_dict: tensors only, no pickled code
+    sd = sd.get("state_dict", sd) if isinstance(sd, dict) else sd
+    own = module.state_dict()
+    missing = [k for k in own if k not in sd]
+    if missing:
+        raise RuntimeError(f"{weights_file}: not a {arch} state_dict (missing {missing[:3]} ...)")
+    module.load_state_dict({k: sd[k] for k in own})
+
+
 class Backbone(nn.Module):
     """reference vision_mtl/utils/model_utils.py:10-43."""
 
     def __init__(self, encoder_name: str = "timm-mobilenetv3_large_100", encoder_weights: t.Optional[str] = "imagenet",
                  decoder_first_channel: int = 256, num_decoder_layers: int = 5, in_channels: int = 3):
         super().__init__()
-        if encoder_name != "timm-mobilenetv3_large_100":
-            raise NotImplementedError(f"encoder {encoder_name!r}: only timm-mobilenetv3_large_100 is restated")
+        resnet = encoder_name in BASIC_LAYERS
+        if encoder_name != "timm-mobilenetv3_large_100" and not resnet:
+            raise NotImplementedError(
+                f"encoder {encoder_name!r}: only timm-mobilenetv3_large_100, resnet18 and resnet34 are restated"
+                + (" (Bottleneck ResNets are not)" if encoder_name in BOTTLENECK else ""))
+        arch = encoder_name if resnet else "mobilenetv3_large_100"
         weights_file = None
         if encoder_weights is not None:
             # the reference hands "imagenet" to smp, which downloads the timm checkpoint (a network fetch).  Offline the
@@ -432,19 +450,16 @@ class Backbone(nn.Module):
                 raise RuntimeError(
                     f"encoder_weights={encoder_weights!r} is a network download in the reference (smp -> timm).  Offline: "
                     "pass encoder_weights=None (random init; the reference CLI's default --backbone_weights), a path to a "
-                    "local mobilenetv3_large_100 state_dict, or set VMTL_ENCODER_WEIGHTS to such a file")
+                    f"local {arch} state_dict, or set VMTL_ENCODER_WEIGHTS to such a file")
         self.decoder_channels = [decoder_first_channel // (2 ** i) for i in range(num_decoder_layers)]
-        self.encoder = MobileNetV3Encoder(in_channels, depth=num_decoder_layers)
+        if resnet:
+            self.encoder = ResNetEncoder(encoder_name, in_channels, depth=num_decoder_layers)
+        else:
+            self.encoder = MobileNetV3Encoder(in_channels, depth=num_decoder_layers)
         self.decoder = UnetDecoder(self.encoder.out_channels[: num_decoder_layers + 1], self.decoder_channels)
         if weights_file is not None:
-            sd = torch.load(weights_file, map_location="cpu", weights_only=True)  # a state_dict: tensors only, no pickled code
-            sd = sd.get("state_dict", sd) if isinstance(sd, dict) else sd
-            own = self.encoder.model.state_dict()
-            # timm's classifier checkpoint also carries conv_head / classifier: features_only drops them
-            missing = [k for k in own if k not in sd]
-            if missing:
-                raise RuntimeError(f"{weights_file}: not a mobilenetv3_large_100 state_dict (missing {missing[:3]} ...)")
-            self.encoder.model.load_state_dict({k: sd[k] for k in own})
+            # the smp encoder's own parameter container: timm's features_only model / torchvision's ResNet
+            _load_encoder_weights(self.encoder if resnet else self.encoder.model, weights_file, arch)
 
     def run(self, x: L.Act, raw_tail: bool = False):
         return self.decoder.run(self.encoder.run(x), raw_tail=raw_tail)

@@ -816,15 +816,20 @@ class _Conv2d(torch.autograd.Function):
         fork = side.mark()  # parameter gradients branch off here, before the data gradient
         if ctx.needs_input_grad[0]:
             if stride != 1:
-                raise NotImplementedError("data gradient of a strided dense conv is not on the hot path")
-            if stitch_w is None:
+                # phase-decomposed data gradient (csrc/resnet.hip): stride 2, square kernels, the pads a ResNet uses
+                if stitch_w is not None or stride != 2 or KH != KW or not lib().raw("vmtl_conv2d_dgrad_s2_supported")(KH, pad):
+                    raise NotImplementedError(f"data gradient of a stride-{stride} {KH}x{KW} / pad {pad} dense conv"
+                                              + (" with a stitch scale" if stitch_w is not None else ""))
+                dx = _dgrad_s2(dy, weight, B, H, W, Cs, Ho, Wo, ldy, KH, pad, ctx.prec)
+            elif stitch_w is None:
                 wd = packs.get(weight, "dgrad", (1, Cin, KK, Cout, ldy, 0, KK, 1, Cin * KK, 1))
             else:  # rows of the data-gradient operand are the input channels: d(x) = s * d(s * x)
                 wd = packs.get(weight, f"dgrad_st{stitch_task}", (1, Cin, KK, Cout, ldy, 0, KK, 1, Cin * KK, 1),
                                scale=(stitch_w, soff, sstride, 2))
-            dx = _empty((B, H, W, Cs), x)
-            _conv_launch(dy, wd, None, dx, None, B, Ho, Wo, ldy, H, W, Cs, Cin, Cin, KH, KW, 1, KH - 1 - pad, cin=Cout,
-                         prec=ctx.prec)
+            if stride == 1:
+                dx = _empty((B, H, W, Cs), x)
+                _conv_launch(dy, wd, None, dx, None, B, Ho, Wo, ldy, H, W, Cs, Cin, Cin, KH, KW, 1, KH - 1 - pad, cin=Cout,
+                             prec=ctx.prec)
         if ctx.needs_input_grad[1] or (stitch_w is not None and ctx.needs_input_grad[7]):
             use_side = ctx.slots[0] is not None and (stitch_w is None or stitch_slot is not None)
             with side.branch(use_side, B * Ho * Wo, fork, x, dy):
@@ -851,6 +856,20 @@ class _Conv2d(torch.autograd.Function):
         if has_bias and ctx.needs_input_grad[2]:
             db = _bias_grad(ctx.bias, ctx.slots[1], dy, B * Ho * Wo, Cout, ldy, ctx.zero_bias_grad, fork)
         return dx, dw, db, None, None, None, None, dst_w, None
+
+
+def _dgrad_s2(dy, weight, B, H, W, Cs, Ho, Wo, ldy, K, pad, prec):
+    """dx of a stride-2 K x K dense conv by phase decomposition (vmtl_conv2d_dgrad_s2): four stride-1 implicit-GEMM
+    correlations of dy with the phases' tap subsets, interleaved into dx.  Runs under the forward's precision."""
+    Cout, Cin = weight.shape[0], weight.shape[1]
+    n = lib().raw("vmtl_pack_dgrad_s2_size")(Cin, ldy, K, pad)
+    wd = packs.get_custom(weight, "dgrad_s2", (n,), lambda w, dst: _k(
+        "vmtl_pack_dgrad_s2", w=w, dst=dst, Cout=Cout, Cin=Cin, ldy=ldy, K=K, pad=pad))
+    ws = _empty((lib().raw("vmtl_conv2d_dgrad_s2_ws")(B, H, W, Cs, Ho, Wo, ldy, K, pad),), dy)
+    dx = _empty((B, H, W, Cs), dy)
+    _kp("vmtl_conv2d_dgrad_s2", prec, _flop=2.0 * B * Ho * Wo * Cout * K * K * Cin, dy=dy, wp=wd, dx=dx, ws=ws, B=B, H=H,
+        W=W, Cs=Cs, Ho=Ho, Wo=Wo, ldy=ldy, Cin=Cin, K=K, pad=pad)
+    return dx
 
 
 class _BNActPw(torch.autograd.Function):
@@ -1735,6 +1754,178 @@ def bn_act_pool2(x, gamma, beta, running_mean, running_var, nbt, C, training, mo
         return maxpool2(bn_act(x, gamma, beta, running_mean, running_var, nbt, C, training, momentum, eps, act, stats=stats,
                                stats_rpb=stats_rpb))
     return _BNActPool.apply(x, gamma, beta, running_mean, running_var, nbt, stats, C, training, momentum, eps, act, stats_rpb)
+
+
+def _bn_mean_invstd(x, stats, rpb, rm, rv, nbt, C, training, momentum, eps):
+    """(mean, invstd) of a BatchNorm over x: batch statistics from the producing conv's partial rows `stats` (rpb pixels
+    each) or a sweep of x, the running buffers moved as torch moves them (train); the running statistics (eval, from the
+    eval_bn_table when one is in force)."""
+    B, H, W, Cs = x.shape
+    if not training:
+        return _bn_eval_stats(rm, rv, C, Cs, eps, x)
+    M = B * H * W
+    mean, invstd = _empty((Cs,), x), _empty((Cs,), x)
+    if stats is not None:
+        partial, nblk = stats, stats.shape[0]
+        rpb = rpb if rpb else lib().raw("vmtl_conv2d_stats_block")(B, H, W, Cs)
+    else:
+        partial, nblk, rpb = _empty((_reduce_rows(M), 2, Cs), x), 0, 0
+    _k("vmtl_bn_stats", x=x, M=M, C=C, Cs=Cs, partial=partial, nblk_from_conv=nblk, rows_per_blk_from_conv=rpb, eps=eps,
+       momentum=momentum, running_mean=rm, running_var=rv, num_batches_tracked=nbt, save_mean=mean, save_invstd=invstd)
+    return mean, invstd
+
+
+class _BNActPool3(torch.autograd.Function):
+    """(a, p) = (act(BN(x)), maxpool3x3/s2/p1(a)) as one node - the ResNet stem's bn1 + relu + maxpool, whose activation is
+    also the decoder's stride-2 skip.  gamma None: the plain pool of an already activated x (no BatchNorm; a is not
+    returned then).  Backward: one gather per input pixel (skip gradient + the windows whose arg-max it is), then act' and
+    the BatchNorm backward sweeps (vmtl_bn_act_pool3s2_bwd)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, rm, rv, nbt, stats, cfg):
+        C, training, momentum, eps, act, stats_rpb = cfg
+        x = _req(x, "x")
+        B, H, W, Cs = x.shape
+        bn = rm is not None
+        mean = invstd = None
+        if bn:
+            mean, invstd = _bn_mean_invstd(x, stats, stats_rpb, rm, rv, nbt, C, training, momentum, eps)
+        Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        a = _empty(x.shape, x) if bn else None
+        p = _empty((B, Ho, Wo, Cs), x)
+        idx = torch.empty((B, Ho, Wo, Cs), dtype=torch.uint8, device=x.device)
+        _k("vmtl_bn_act_pool3s2_fwd", x=x, mean=mean, invstd=invstd, gamma=gamma, beta=beta, a_out=a, y=p, idx=idx, B=B,
+           H=H, W=W, C=C, Cs=Cs, act=act)
+        ctx.save_for_backward(x, idx, mean, invstd, gamma, beta)
+        ctx.cfg = (C, training, act, bn)
+        ctx.slots = (_slot(gamma), _slot(beta))
+        ctx.set_materialize_grads(False)
+        return (a, p) if bn else p
+
+    @staticmethod
+    def backward(ctx, *grads):
+        x, idx, mean, invstd, gamma, beta = ctx.saved_tensors
+        C, training, act, bn = ctx.cfg
+        da, dp = grads if bn else (None, grads[0])
+        B, H, W, Cs = x.shape
+        if dp is None:
+            dp = torch.zeros(idx.shape, dtype=torch.float32, device=x.device)
+        dp = _req(dp, "dy")
+        da = None if da is None else _req(da, "dskip")
+        dx = _empty(x.shape, x)
+        dgamma = dbeta = None
+        if bn:
+            M = B * H * W
+            dgamma = _empty((C,), x) if ctx.slots[0] is None else ctx.slots[0]  # exactly C entries: may be arena slots
+            dbeta = _empty((C,), x) if ctx.slots[1] is None else ctx.slots[1]
+            _k("vmtl_bn_act_pool3s2_bwd", x=x, dskip=da, dyp=dp, idx=idx, mean=mean, invstd=invstd, gamma=gamma, beta=beta,
+               dz=_empty(x.shape, x), partial=_empty((_reduce_rows(M), 2, Cs), x), sum_dz=dbeta, sum_dzx=dgamma, dx=dx,
+               B=B, H=H, W=W, C=C, Cs=Cs, act=act, training=1 if training else 0)
+            dgamma = dgamma if ctx.slots[0] is None else None
+            dbeta = dbeta if ctx.slots[1] is None else None
+        else:
+            _k("vmtl_bn_act_pool3s2_bwd", x=x, dskip=None, dyp=dp, idx=idx, mean=None, invstd=None, gamma=None, beta=None,
+               dz=None, partial=None, sum_dz=None, sum_dzx=None, dx=dx, B=B, H=H, W=W, C=C, Cs=Cs, act=act, training=0)
+        return dx, dgamma, dbeta, None, None, None, None, None
+
+
+FUSE_STEM_POOL = os.environ.get("VMTL_FUSE_STEM_POOL", "1") != "0"  # ResNet stem: BN + ReLU + MaxPool2d(3, 2, 1) as one node
+
+
+def bn_act_pool3(x, bn, C, act, stats=None, stats_rpb=0):
+    """(act(bn(x)), maxpool3x3/s2/p1 of it): the activated map and its pool from one node (FUSE_STEM_POOL), else a
+    BatchNorm node followed by the plain pool node."""
+    if stats is not None and not stats_rpb:
+        stats_rpb = getattr(stats, "_vmtl_rpb", 0)
+    if bn.momentum is None:
+        raise NotImplementedError("BatchNorm2d(momentum=None) (cumulative moving average) is not implemented")
+    if not FUSE_STEM_POOL:
+        a = bn_act(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, C, bn.training,
+                   float(bn.momentum), bn.eps, act, stats=stats, stats_rpb=stats_rpb)
+        return a, maxpool3s2(a, C)
+    cfg = (C, bn.training, float(bn.momentum), bn.eps, act, stats_rpb)
+    return _BNActPool3.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, stats, cfg)
+
+
+def maxpool3s2(x, C):
+    """MaxPool2d(3, stride 2, padding 1) of an activation (floor mode, torch's tie / NaN rule)."""
+    return _BNActPool3.apply(x, None, None, None, None, None, None, (C, False, 0.0, 0.0, ACT_NONE, 0))
+
+
+class _BNAddAct(torch.autograd.Function):
+    """y = act(BN_a(z) + r) - the close of a torchvision BasicBlock - with r = res (the block input) or BN_b(zd) (the
+    downsample branch's raw 1x1 conv output); both BatchNorms are applied in the same sweep.  z / zd come with their conv
+    epilogue partial rows.  Backward: g = dy * act'(.) once; it is the identity gradient, and both BatchNorm backwards run
+    off it (vmtl_bn_add_act_bwd)."""
+
+    @staticmethod
+    def forward(ctx, z, stats, ga, ba, rma, rva, nbta, res, zd, statsd, gb, bb, rmb, rvb, nbtb, cfg):
+        C, training, mom_a, eps_a, rpb, mom_b, eps_b, rpbd, act = cfg
+        z = _req(z, "z")
+        B, H, W, Cs = z.shape
+        M = B * H * W
+        mean_a, invstd_a = _bn_mean_invstd(z, stats, rpb, rma, rva, nbta, C, training, mom_a, eps_a)
+        mean_b = invstd_b = None
+        if zd is not None:
+            zd = _req(zd, "zd")
+            if zd.shape != z.shape:
+                raise ValueError(f"bn_add_act: downsample branch {tuple(zd.shape)} vs main branch {tuple(z.shape)}")
+            mean_b, invstd_b = _bn_mean_invstd(zd, statsd, rpbd, rmb, rvb, nbtb, C, training, mom_b, eps_b)
+        else:
+            res = _req(res, "res")
+            if res.shape != z.shape:
+                raise ValueError(f"bn_add_act: residual {tuple(res.shape)} vs main branch {tuple(z.shape)}")
+        y = _empty(z.shape, z)
+        _k("vmtl_bn_add_act_fwd", z=z, mean_a=mean_a, invstd_a=invstd_a, gamma_a=ga, beta_a=ba, res=res, zd=zd,
+           mean_b=mean_b, invstd_b=invstd_b, gamma_b=gb, beta_b=bb, y=y, M=M, C=C, Cs=Cs, act=act)
+        ctx.save_for_backward(z, mean_a, invstd_a, ga, ba, res, zd, mean_b, invstd_b, gb, bb)
+        ctx.cfg = (C, training, act)
+        ctx.slots = (_slot(ga), _slot(ba), _slot(gb), _slot(bb))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        z, mean_a, invstd_a, ga, ba, res, zd, mean_b, invstd_b, gb, bb = ctx.saved_tensors
+        C, training, act = ctx.cfg
+        sga, sba, sgb, sbb = ctx.slots
+        dy = _req(dy, "dy")
+        B, H, W, Cs = z.shape
+        M = B * H * W
+        g = _empty(z.shape, z)
+        dga = _empty((C,), z) if sga is None else sga
+        dba = _empty((C,), z) if sba is None else sba
+        dgb = dbb = dzd = None
+        if zd is not None:
+            dgb = _empty((C,), z) if sgb is None else sgb
+            dbb = _empty((C,), z) if sbb is None else sbb
+            dzd = _empty(z.shape, z)
+        dz = _empty(z.shape, z)
+        _k("vmtl_bn_add_act_bwd", z=z, mean_a=mean_a, invstd_a=invstd_a, gamma_a=ga, beta_a=ba, res=res, zd=zd,
+           mean_b=mean_b, invstd_b=invstd_b, gamma_b=gb, beta_b=bb, dy=dy, g=g, partial=_empty((_reduce_rows(M), 3, Cs), z),
+           sum_dz_a=dba, sum_dzx_a=dga, sum_dz_b=dbb, sum_dzx_b=dgb, dz=dz, dzd=dzd, M=M, C=C, Cs=Cs, act=act,
+           training=1 if training else 0)
+        nif = lambda t, slot: None if slot is not None else t
+        return (dz, None, nif(dga, sga), nif(dba, sba), None, None, None, g if res is not None else None, dzd, None,
+                nif(dgb, sgb), nif(dbb, sbb), None, None, None, None)
+
+
+def bn_add_act(z, stats, rpb, bn, C, act, res=None, zd=None, statsd=None, rpbd=0, bn_d=None):
+    """act(bn(z) + res)  or  act(bn(z) + bn_d(zd)): z / zd raw conv outputs with their statistics rows (rpb pixels each)."""
+    for m in (bn, bn_d):
+        if m is not None and m.momentum is None:
+            raise NotImplementedError("BatchNorm2d(momentum=None) (cumulative moving average) is not implemented")
+    if (res is None) == (zd is None):
+        raise ValueError("bn_add_act: give exactly one of res (identity) and zd (downsample branch)")
+    if stats is not None and not rpb:
+        rpb = getattr(stats, "_vmtl_rpb", 0)
+    if statsd is not None and not rpbd:
+        rpbd = getattr(statsd, "_vmtl_rpb", 0)
+    d = bn_d
+    cfg = (C, bn.training, float(bn.momentum), bn.eps, rpb, float(d.momentum) if d else 0.1, d.eps if d else 1e-5, rpbd,
+           act)
+    return _BNAddAct.apply(z, stats, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, res, zd,
+                           statsd, d.weight if d else None, d.bias if d else None, d.running_mean if d else None,
+                           d.running_var if d else None, d.num_batches_tracked if d else None, cfg)
 
 
 def activation(x, act, C, mul=None):

@@ -3,7 +3,8 @@
 "fp32" (the default) multiplies exact fp32 operands (v_mfma_f32_16x16x4_f32).  "bf16" rounds every operand of the covered
 kernels to bf16 (round-to-nearest-even) and accumulates in fp32 on the bf16 matrix cores: activations, weights,
 statistics and gradients stay fp32 in memory, only the product terms change.  Covered: the implicit-GEMM convolution
-(forward, split-K, data gradient, its BatchNorm-backward epilogue, the upsample + concat + 3x3 phase convolutions) and the
+(forward, split-K, data gradient, its BatchNorm-backward epilogue, the upsample + concat + 3x3 phase convolutions, the
+phase-decomposed stride-2 data gradient vmtl_conv2d_dgrad_s2) and the
 dense weight gradient (vmtl_conv2d_wgrad, vmtl_conv1x1_cat_wgrad).  Everything else stays fp32.
 
     vision_mtl_amd.set_conv_precision("bf16")        # process-wide
