@@ -27,6 +27,10 @@ CONFIGS = {
     "csnet_channel_128x256_bs32": ("csnet", 32, 128, 256, 19, True),
     "csnet_layer_128x256_bs32": ("csnet", 32, 128, 256, 19, False),  # the reference CLI's default
     "mtan_256x256_bs16": ("mtan", 16, 256, 256, 14, None),
+    # `basic` with a torchvision ResNet-34 encoder as tools/bench_resnet.py builds it (resnet18's signatures at these shapes
+    # are a subset of resnet34's: same stem, same first block of every stage, fewer identity blocks)
+    "basic_resnet34_128x256_bs32": ("basic_resnet34", 32, 128, 256, 19, None),
+    "basic_resnet34_128x256_bs8": ("basic_resnet34", 8, 128, 256, 19, None),
 }
 
 # model-facing autograd nodes of vision_mtl_amd.ops (the models call them as ops.X(...))
@@ -34,7 +38,7 @@ NODES = ("conv2d", "bn_act_conv", "up2_conv", "bn_act_conv1x1", "conv1x1_cat", "
          "bn_act_pool2", "decoder_tail", "dual_head", "squeeze_excite", "conv_transpose2x2", "stitch", "concat2", "maxpool2",
          "bilinear_up2", "spatial_mean", "channel_scale", "activation", "sigmoid", "fork", "to_nhwc", "to_nchw",
          "hwc_to_model_input", "cross_entropy", "cross_entropy_with_argmax", "silog", "l1_loss", "add_losses",
-         "argmax_channels")
+         "argmax_channels", "bn_act_pool3", "maxpool3s2", "bn_add_act")
 
 
 def describe(v):
@@ -155,9 +159,14 @@ class Recorder:
 
 
 def build(kind, C, channel_wise=None, seed=11):
+    """build_model's model of this kind; "basic_<encoder>": BasicMTLModel with that encoder and its default decoder"""
     from vision_mtl_amd.utils.pipeline_utils import build_model
 
     torch.manual_seed(seed)
+    if kind.startswith("basic_"):
+        from vision_mtl_amd.models.basic_model import BasicMTLModel
+
+        return BasicMTLModel(C, encoder_name=kind[len("basic_"):], encoder_weights=None)
     ns = argparse.Namespace(model_name=kind, backbone_weights=None)
     if channel_wise is not None:
         ns.channel_wise_stitching = channel_wise

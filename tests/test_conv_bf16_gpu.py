@@ -319,7 +319,8 @@ def test_backward_outside_the_context_keeps_bf16(dev):
 # operands each covered entry point rounds in bf16 mode (ConvTranspose 2x2 - shuffle forward, k2/s2 backward - stays fp32)
 _ROUNDED = {"vmtl_conv2d_fwd": ("x", "wp"), "vmtl_conv2d_fwd_ws": ("x", "wp"), "vmtl_conv2d_bnbwd": ("x", "wp"),
             "vmtl_conv2d_up2_fwd": ("xl", "skip", "wp_eff"), "vmtl_conv2d_up2_fwd_ws": ("xl", "skip", "wp_eff"),
-            "vmtl_conv2d_wgrad": ("x", "dy"), "vmtl_conv1x1_cat_wgrad": ("x", "x2", "dy")}
+            "vmtl_conv2d_wgrad": ("x", "dy"), "vmtl_conv1x1_cat_wgrad": ("x", "x2", "dy"),
+            "vmtl_conv2d_dgrad_s2": ("dy", "wp")}
 
 
 class _emulate_bf16_operands:
@@ -507,11 +508,13 @@ def test_training_sanity_bf16(dev):
     assert abs(final["bf16"] - final["fp32"]) <= 0.05 * final["fp32"], final
 
 
-@pytest.mark.parametrize("case", ["up2", "up2_splitk", "up2_deep", "conv_w64", "conv_s2", "conv1x1", "conv_deep", "bnconv",
-                                  "bnconv_up2"])
+@pytest.mark.parametrize("case", ["up2", "up2_splitk", "up2_deep", "conv_w64", "conv_s2", "conv_s2_l3", "conv1x1", "conv_deep",
+                                  "bnconv", "bnconv_up2"])
 def test_bf16_matches_emulated_contract(dev, case):
     """Each covered route through ops in bf16 mode == the fp32 route fed bf16-rounded operand copies (to 1e-5 of each
-    tensor's magnitude): forward values and every input gradient."""
+    tensor's magnitude): forward values and every input gradient.  The stride-2 cases take the phase-decomposed data
+    gradient (vmtl_conv2d_dgrad_s2); conv_s2_l3 is the ResNet layer-3 conv1 at bs 32, 128x256 (3x3/s2, 128 -> 256 over a
+    16x32 input), where bf16 runs every phase on the implicit GEMM and fp32 the (even, even) phase on the pointwise GEMM."""
     from vision_mtl_amd import conv_precision
 
     ops = _ops()
@@ -531,10 +534,12 @@ def test_bf16_matches_emulated_contract(dev, case):
                to_dev_nhwc(torch.randn(B, C1, 2 * H2, 2 * W2, generator=g), dev)]
         w = (torch.randn(Cout, C0 + C1, 3, 3, generator=g) / ((C0 + C1) * 9) ** 0.5).to(dev)
         fn = lambda xs, w: ops.up2_conv(xs[0], C0, xs[1], w, want_stats=False)[0]
-    elif case in ("conv_w64", "conv_s2", "conv1x1", "conv_deep"):
+    elif case in ("conv_w64", "conv_s2", "conv_s2_l3", "conv1x1", "conv_deep"):
         K, s, Cin, Cout, H, W = {"conv_w64": (3, 1, 40, 36, 16, 64), "conv_s2": (3, 2, 16, 24, 32, 64),
-                                 "conv1x1": (1, 1, 40, 48, 16, 64), "conv_deep": (3, 1, 540, 540, 4, 4)}[case]
-        ins = [to_dev_nhwc(torch.randn(2, Cin, H, W, generator=g), dev).requires_grad_(s == 1)]
+                                 "conv_s2_l3": (3, 2, 128, 256, 16, 32), "conv1x1": (1, 1, 40, 48, 16, 64),
+                                 "conv_deep": (3, 1, 540, 540, 4, 4)}[case]
+        B = 32 if case == "conv_s2_l3" else 2
+        ins = [to_dev_nhwc(torch.randn(B, Cin, H, W, generator=g), dev).requires_grad_(True)]
         w = (torch.randn(Cout, Cin, K, K, generator=g) / (Cin * K * K) ** 0.5).to(dev)
         fn = lambda xs, w: ops.conv2d(xs[0], w, None, stride=s, pad=K // 2)
     else:

@@ -47,13 +47,38 @@ def censuses(dev):
 
 
 def _signatures(censuses, op):
-    """unique signatures of one node across the configurations -> production launches (set) of each"""
+    """unique signatures of one node across the configurations -> production launches (set) of each.  conv2d also gets
+    the image-gradient variant of every stride-2 signature whose input has no gradient (the ResNet stem: its data gradient
+    runs when the image requires one), with no production launches of its own"""
     sigs = {}
     for c in censuses.values():
         for sig in c.nodes:
             if sig[0] == op:
                 sigs.setdefault(sig, set()).update(c.node_launches(sig))
+    if op == "conv2d":
+        for sig in list(sigs):
+            v = _dx_variant(sig)
+            if v is not None:
+                sigs.setdefault(v, set())
     return sigs
+
+
+def _s2_dgrad(a):
+    """a stride-2 conv2d whose data gradient the phase decomposition supports (vmtl_conv2d_dgrad_s2)"""
+    from vision_mtl_amd._lib import lib
+
+    pair = lambda v: tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+    ws, st, pd = a["weight"][1], pair(a["stride"]), pair(a["pad"])
+    return (st == (2, 2) and ws[2] == ws[3] and pd[0] == pd[1] and a["stitch"] is None
+            and bool(lib().raw("vmtl_conv2d_dgrad_s2_supported")(ws[2], pd[0])))
+
+
+def _dx_variant(sig):
+    """the signature with x requiring a gradient, for a stride-2 conv2d whose x has none; else None"""
+    a = sig_args(sig)
+    if a["x"][2] or not _s2_dgrad(a):
+        return None
+    return (sig[0], tuple((k, (v[0], v[1], True) + tuple(v[3:])) if k == "x" else (k, v) for k, v in sig[1]))
 
 
 def _nhwc(x, dev):
@@ -787,6 +812,123 @@ def _dev_tail(a, case, T, bns):
     return {"a": (ya, "nchw", None), "b": (yb, "nchw", None)}, []
 
 
+# bn_act_pool3(x, bn, C, act, stats, stats_rpb) -> (act(BN(x)), maxpool3x3/s2/p1 of it): the ResNet stem
+def _pool3_ladder(B, C, H, W, spec, g, big, hole=16):
+    """BatchNorm input of the stem pool: every (b, c) plane is a random permutation of one ladder of H*W values, so no two
+    values of a plane (hence of any overlapping 3x3/s2 window) are closer than one step: 2^-11 around 0.3 (2048 ulps at
+    magnitude 2) on ordinary channels, 2^-14 around 100 (8 ulps at that magnitude) on the large-mean / small-std quarter
+    `big`.  The ladder has a `hole`-step gap, and beta is chosen so that the BatchNorm maps the ReLU kink to the middle of
+    it: every normalised value lies >= hole/2 steps (>= 1.6e-3 after normalisation) from the kink.  Exact ties between ReLU
+    zeros stay (both sides take the first maximum)."""
+    _, training, momentum, eps, gamma, beta, rm, rv = spec
+    N = H * W
+    x = torch.empty(B, C, H, W, dtype=torch.float64)
+    beta = beta.clone()
+    for c in range(C):
+        step, centre = (2.0 ** -14, 100.0) if c in big else (2.0 ** -11, 0.3 + 0.25 * (c % 5))
+        kh = int(N * (0.3 + 0.4 * float(torch.rand(1, generator=g))))  # the ReLU zeros: 30..70 % of the plane
+        k = torch.arange(N, dtype=torch.float64)
+        ladder = centre + step * torch.round(k - N / 2 + hole * (k >= kh))
+        if training:
+            mean, var = float(ladder.mean()), float(ladder.var(unbiased=False))
+        else:
+            mean, var = float(rm[c]), float(rv[c])
+        kink = float(ladder[kh - 1] + ladder[kh]) / 2  # the hole's centre
+        beta[c] = -float(gamma[c]) * (kink - mean) / (var + eps) ** 0.5
+        perm = torch.rand(B, N, generator=g).argsort(1)
+        x[:, c] = ladder[perm].view(B, H, W)
+    return x.float(), spec[:5] + (beta,) + spec[6:]
+
+
+def _make_bn_act_pool3(a, g):
+    case = Case()
+    B, H, W, Cs = a["x"][1]
+    _, C, training, momentum, eps = a["bn"]
+    assert a["act"] == 1, "the stem pool's inputs are laid out around the ReLU kink"
+    big = list(range(C - C // 4, C))
+    x, spec = _pool3_ladder(B, C, H, W, _bn_spec(C, training, momentum, eps, g), g, big)
+    case.bns["bn"] = spec
+    case.acts["x"] = x
+    if a["x"][2]:
+        case.grad.add("x")
+    st, rpb = _stats_rpb(a, "stats", "stats_rpb", B, H, W, Cs)
+    if st is not None:
+        case.stats_in["x"] = (st[1][0], rpb)
+    return case
+
+
+def _ref_bn_act_pool3(a, case, T, bns):
+    h = ACTS[a["act"]](bns["bn"](T["x"]))
+    return {"a": h, "y": F.max_pool2d(h, 3, 2, 1)}
+
+
+def _dev_bn_act_pool3(a, case, T, bns):
+    from vision_mtl_amd import ops
+
+    h, y = ops.bn_act_pool3(T["x"], bns["bn"], a["C"], a["act"], stats=T.get("stats:x"),
+                            stats_rpb=case.stats_in.get("x", (0, 0))[1])
+    return {"a": (h, "nhwc", a["C"]), "y": (y, "nhwc", a["C"])}, []
+
+
+# bn_add_act(z, stats, rpb, bn, C, act, res, zd, statsd, rpbd, bn_d) -> act(BN_a(z) + res)  or  act(BN_a(z) + BN_d(zd)):
+# the close of a ResNet BasicBlock, each BatchNorm fed its own conv's partial rows
+def _bn_affine64(x, spec):
+    """(BN(x) in fp64 with the statistics this spec uses, per-channel scale gamma * invstd)"""
+    C, training, momentum, eps, gamma, beta, rm, rv = spec
+    x = x.double()
+    mean, var = (x.mean((0, 2, 3)), x.var((0, 2, 3), unbiased=False)) if training else (rm.double(), rv.double())
+    sc = (gamma.double() / (var + eps).sqrt()).view(1, -1, 1, 1)
+    return (x - mean.view(1, -1, 1, 1)) * sc + beta.double().view(1, -1, 1, 1), sc
+
+
+def _make_bn_add_act(a, g):
+    case = Case()
+    B, H, W, Cs = a["z"][1]
+    C, act = a["C"], a["act"]
+    _, nf, training, momentum, eps = a["bn"]
+    case.bns["a"] = _bn_spec(nf, training, momentum, eps, g)
+    st, rpb = _stats_rpb(a, "stats", "rpb", B, H, W, Cs)
+    _bn_input(case, a, g, "z", C, case.bns["a"], 0, B, H, W, st, rpb)
+    if a["zd"] is not None:
+        _, nf, training, momentum, eps = a["bn_d"]
+        case.bns["d"] = _bn_spec(nf, training, momentum, eps, g)
+        std, rpbd = _stats_rpb(a, "statsd", "rpbd", B, H, W, Cs)
+        _bn_input(case, a, g, "zd", C, case.bns["d"], 0, B, H, W, std, rpbd)
+        short = "zd"
+    else:
+        case.acts["res"] = torch.randn(B, C, H, W, generator=g)
+        if a["res"][2]:
+            case.grad.add("res")
+        short = "res"
+    # the kink is on the SUM: move the shortcut's input until no BN_a(z) + r lies within 1e-3 of it
+    za = _bn_affine64(case.acts["z"], case.bns["a"])[0]
+    band = 1e-3
+    for k in KINKS[act]:
+        for _ in range(3):
+            r, sc = _bn_affine64(case.acts["zd"], case.bns["d"]) if short == "zd" else (case.acts["res"].double(), 1.0)
+            d = za + r - k
+            bad = d.abs() < band
+            if not bad.any():
+                break
+            t = k + 2 * band * torch.where(d >= 0, 1.0, -1.0).double()
+            case.acts[short] = torch.where(bad, case.acts[short].double() + (t - d - k) / sc, case.acts[short].double()).float()
+    return case
+
+
+def _ref_bn_add_act(a, case, T, bns):
+    r = bns["d"](T["zd"]) if "d" in bns else T["res"]
+    return {"y": ACTS[a["act"]](bns["a"](T["z"]) + r)}
+
+
+def _dev_bn_add_act(a, case, T, bns):
+    from vision_mtl_amd import ops
+
+    y = ops.bn_add_act(T["z"], T.get("stats:z"), case.stats_in.get("z", (0, 0))[1], bns["a"], a["C"], a["act"],
+                       res=T.get("res"), zd=T.get("zd"), statsd=T.get("stats:zd"), rpbd=case.stats_in.get("zd", (0, 0))[1],
+                       bn_d=bns.get("d"))
+    return {"y": (y, "nhwc", a["C"])}, []
+
+
 GENERIC = {
     "bn_act": (_make_bn_act, _ref_bn_act, _dev_bn_act, False),
     "activation": (_make_bn_act, _ref_bn_act, _dev_bn_act, False),
@@ -798,6 +940,8 @@ GENERIC = {
     "conv_transpose2x2": (_make_convt, _ref_convt, _dev_convt, False),
     "squeeze_excite": (_make_se, _ref_se, _dev_se, False),
     "decoder_tail": (_make_tail, _ref_tail, _dev_tail, True),
+    "bn_act_pool3": (_make_bn_act_pool3, _ref_bn_act_pool3, _dev_bn_act_pool3, False),
+    "bn_add_act": (_make_bn_add_act, _ref_bn_add_act, _dev_bn_add_act, False),
 }
 REPLAYED = ("conv2d", "bn_act_conv", "up2_conv") + tuple(GENERIC)
 IDENTITY_REPLAYED = tuple(k for k, v in GENERIC.items() if v[3])
@@ -892,30 +1036,121 @@ def _narrow3x3(a):
             and B * H * W >= 1 << 16)
 
 
-# (configuration, node, predicate on its arguments, entry point its FORWARD launches must include, description)
+# (configuration, node, predicate on its arguments, entry point its launches must include, description[, phase 'fwd' | 'bwd'])
+def _route(cfg, op, pred, entry, what, phase="fwd"):
+    return cfg, op, pred, entry, what, phase
+
+
 ROUTES = [
-    ("csnet_layer_128x256_bs32", "conv2d", lambda a: _narrow3x3(a) and a["want_stats"],
-     "vmtl_conv3x3_small", "narrow full-resolution 3x3 convs with the statistics epilogue"),
-    ("csnet_layer_128x256_bs32", "conv2d", lambda a: _narrow3x3(a) and not a["want_stats"],
-     "vmtl_conv3x3_small", "narrow full-resolution 3x3 heads without the statistics epilogue"),
-    ("basic_128x256_bs32", "decoder_tail", lambda a: True,
-     "vmtl_conv3x3_small", "the decoder tail's narrow full-resolution conv and heads"),
-    ("basic_128x256_bs32", "bn_act_conv", lambda a: not a["up2"] and a["x"][1][3] in (64, 68),
-     "vmtl_conv3x3_halo", "64/68-channel decoder 3x3 convs"),
-    ("mtan_256x256_bs16", "bn_act_conv", lambda a: not a["up2"] and a["x"][1][3] in (64, 68) and a["weight"][1][0] in (64, 68),
-     "vmtl_conv3x3_halo", "64/68-channel 3x3 convs"),
-    ("basic_128x256_bs32", "bn_act_conv", lambda a: a["up2"] and a["weight"][1][0] <= 36,
-     "vmtl_conv2d_up2_halo", "narrow UP2 decoder convs"),
-    ("mtan_256x256_bs16", "conv2d", lambda a: a["weight"][1][2:] == (1, 1) and a["x"][1][0] * a["x"][1][1] * a["x"][1][2] == 1 << 20,
-     "vmtl_conv1x1_fwd", "M = 2^20 1x1 convs on the pointwise kernel"),
+    _route("csnet_layer_128x256_bs32", "conv2d", lambda a: _narrow3x3(a) and a["want_stats"],
+           "vmtl_conv3x3_small", "narrow full-resolution 3x3 convs with the statistics epilogue"),
+    _route("csnet_layer_128x256_bs32", "conv2d", lambda a: _narrow3x3(a) and not a["want_stats"],
+           "vmtl_conv3x3_small", "narrow full-resolution 3x3 heads without the statistics epilogue"),
+    _route("basic_128x256_bs32", "decoder_tail", lambda a: True,
+           "vmtl_conv3x3_small", "the decoder tail's narrow full-resolution conv and heads"),
+    _route("basic_128x256_bs32", "bn_act_conv", lambda a: not a["up2"] and a["x"][1][3] in (64, 68),
+           "vmtl_conv3x3_halo", "64/68-channel decoder 3x3 convs"),
+    _route("mtan_256x256_bs16", "bn_act_conv", lambda a: not a["up2"] and a["x"][1][3] in (64, 68) and a["weight"][1][0] in (64, 68),
+           "vmtl_conv3x3_halo", "64/68-channel 3x3 convs"),
+    _route("basic_128x256_bs32", "bn_act_conv", lambda a: a["up2"] and a["weight"][1][0] <= 36,
+           "vmtl_conv2d_up2_halo", "narrow UP2 decoder convs"),
+    _route("mtan_256x256_bs16", "conv2d", lambda a: a["weight"][1][2:] == (1, 1) and a["x"][1][0] * a["x"][1][1] * a["x"][1][2] == 1 << 20,
+           "vmtl_conv1x1_fwd", "M = 2^20 1x1 convs on the pointwise kernel"),
+    _route("basic_resnet34_128x256_bs32", "bn_add_act", lambda a: True,
+           "vmtl_bn_add_act_fwd", "ResNet residual closes"),
+    _route("basic_resnet34_128x256_bs32", "bn_act_pool3", lambda a: True,
+           "vmtl_bn_act_pool3s2_fwd", "ResNet stem BatchNorm + ReLU + max-pool"),
+    _route("basic_resnet34_128x256_bs32", "conv2d", lambda a: a["x"][2] and _s2_dgrad(a),
+           "vmtl_conv2d_dgrad_s2", "ResNet stride-2 data gradients", "bwd"),
+    _route("basic_resnet34_128x256_bs8", "conv2d", lambda a: a["x"][2] and _s2_dgrad(a),
+           "vmtl_conv2d_dgrad_s2", "ResNet stride-2 data gradients at bs 8", "bwd"),
 ]
 
 
 @pytest.mark.parametrize("route", ROUTES, ids=[r[4] for r in ROUTES])
 def test_production_layers_take_the_intended_route(censuses, route):
-    cfg, op, pred, entry, what = route
+    cfg, op, pred, entry, what, phase = route
     c = censuses[cfg]
     layers = [sig for sig in c.nodes if sig[0] == op and pred(sig_args(sig))]
     assert layers, f"{cfg}: no {op} layer matches '{what}' (the census changed: revisit this list)"
-    wrong = [f"{fmt_sig(sig)} ran {sorted(_fwd_entries(c, sig))} in its forward" for sig in layers if entry not in _fwd_entries(c, sig)]
+    ran = lambda sig: {n for n, _ in c.node_launches(sig, phase=phase)}
+    wrong = [f"{fmt_sig(sig)} ran {sorted(ran(sig))} in its {phase}" for sig in layers if entry not in ran(sig)]
     assert not wrong, f"{cfg}: {what} should run on {entry}:\n" + "\n".join(wrong)
+
+
+@pytest.mark.parametrize("cfg", [k for k in CONFIGS if "resnet" in k])
+def test_resnet_encoder_has_no_2x2_pool(censuses, cfg):
+    """the stem pool is the fused 3x3/s2 node; the 2x2 max-pool of the MobileNet / MTAN paths never runs"""
+    pools = sorted({n for _, n, _, _ in censuses[cfg].launches if n.startswith(("vmtl_maxpool2", "vmtl_bn_act_pool2"))})
+    assert not pools, f"{cfg}: {pools}"
+
+
+# ------------------------------------------------------------------------------------------------ stride-2 phase routes
+def _s2_dim(a, K, pad):
+    """csrc/resnet.hip s2_dim: (taps, correlation pad) of phase a (0 / 1) of one axis"""
+    k0 = (a + pad) & 1
+    T = (K - k0 + 1) // 2 if k0 < K else 0
+    return T, (T - 1) - (a + pad - k0) // 2 if T else 0
+
+
+def _s2_phases(B, H, W, Cs, Ho, Wo, ldy, K, pad):
+    """csrc/resnet.hip s2_geometry restated: ([(taps h, taps w), launch pad, e, Hp, Wp] per phase with pixels, workspace
+    floats).  The launch route of a phase follows vmtl_conv2d_dgrad_s2_p (fp32)."""
+    from vision_mtl_amd._lib import lib
+
+    ksplit = lib().raw("vmtl_conv2d_ksplit")
+    d = [_s2_dim(a, K, pad) for a in (0, 1)]
+    pc = d[0][1] if d[0][0] else d[1][1]
+    phases, ws, split = [], 0, 0
+    for ph in range(4):
+        a, b = ph >> 1, ph & 1
+        T = (d[a][0], d[b][0])
+        Ha, Wa = (H - a + 1) // 2, (W - b + 1) // 2
+        if 0 in T or Ha == 0 or Wa == 0:
+            continue
+        e = max(0, Ha + T[0] - 1 - Ho - 2 * pc, Wa + T[1] - 1 - Wo - 2 * pc)
+        p = pc + e
+        Hp, Wp = Ho + 2 * p - T[0] + 1, Wo + 2 * p - T[1] + 1
+        ws += B * Cs * Hp * Wp
+        ks = ksplit(B, Hp, Wp, Cs, T[0] * T[1] * ldy)
+        if ks > 1:
+            split = max(split, ks * B * Hp * Wp * Cs)
+        if T == (1, 1) and p == 0 and B * Hp * Wp <= 1 << 21:
+            route = "pointwise"
+        else:
+            route = "split-K" if ks > 1 else "implicit GEMM"
+        phases.append((ph, T, p, e, Hp, Wp, ks, route))
+    return phases, ws + split
+
+
+def test_stride2_data_gradient_phase_routes(censuses):
+    """Every replayed stride-2 data gradient, phase by phase: the route vmtl_conv2d_dgrad_s2 takes (the pointwise GEMM for
+    unpadded single-tap phases, split-K implicit GEMM where vmtl_conv2d_ksplit > 1, else the plain implicit GEMM), from
+    the phase geometry restated here and the library's split count.  The restatement's workspace size must equal
+    vmtl_conv2d_dgrad_s2_ws; across the production replays all three routes must occur, each in a replay that passed fp64."""
+    from vision_mtl_amd._lib import lib
+
+    wsf = lib().raw("vmtl_conv2d_dgrad_s2_ws")
+    routes, lines, failed = {}, [], []
+    for sig in _signatures(censuses, "conv2d"):
+        a = sig_args(sig)
+        if not (a["x"][2] and _s2_dgrad(a)):
+            continue
+        B, H, W, Cs = a["x"][1]
+        Cout, _, K, _ = a["weight"][1]
+        pad = a["pad"][0] if isinstance(a["pad"], (tuple, list)) else a["pad"]
+        Ho, Wo = (H + 2 * pad - K) // 2 + 1, (W + 2 * pad - K) // 2 + 1
+        ldy = ceil4(Cout)
+        phases, ws = _s2_phases(B, H, W, Cs, Ho, Wo, ldy, K, pad)
+        assert ws == wsf(B, H, W, Cs, Ho, Wo, ldy, K, pad), f"{fmt_sig(sig)}: phase geometry restatement drifted"
+        chk, launched = _replay(sig)
+        assert any(n == "vmtl_conv2d_dgrad_s2" for n, _ in launched), f"{fmt_sig(sig)}: no vmtl_conv2d_dgrad_s2 launch"
+        if chk.failures:
+            failed.append(fmt_sig(sig))
+        for ph, T, p, e, Hp, Wp, ks, route in phases:
+            routes.setdefault(route, []).append(fmt_sig(sig))
+            lines.append(f"  {fmt_sig(sig)} phase {ph}: taps {T[0]}x{T[1]} pad {p} (e {e}) -> {Hp}x{Wp}, ksplit {ks}: {route}")
+    print("stride-2 data-gradient phases:\n" + "\n".join(lines))
+    assert not failed, f"replays that failed fp64: {failed}"
+    missing = {"pointwise", "split-K", "implicit GEMM"} - set(routes)
+    assert not missing, f"no replayed stride-2 data-gradient phase takes the {sorted(missing)} route"

@@ -85,6 +85,60 @@ class _HipPools:
         return False
 
 
+def _pool3_window_pos(x):
+    """(B, C, H, W) -> window position (0..8, row-major) of the arg-max of every MaxPool2d(3, 2, 1) window, on the CPU,
+    from torch's own return_indices (the first maximum)"""
+    import torch.nn.functional as F
+
+    _, ind = F.max_pool2d(x, 3, 2, 1, return_indices=True)
+    W = x.shape[3]
+    oh = torch.arange(ind.shape[2]).view(1, 1, -1, 1)
+    ow = torch.arange(ind.shape[3]).view(1, 1, 1, -1)
+    return ((ind // W - (2 * oh - 1)) * 3 + (ind % W - (2 * ow - 1))).to(torch.uint8).cpu()
+
+
+class _OracleStemPool:
+    """stands in for torch.nn.functional inside oracle.resnet only: records the window arg-max of the stem pool"""
+
+    def __init__(self):
+        import torch.nn.functional as F
+
+        self._F, self.pools = F, []
+
+    def __getattr__(self, name):
+        return getattr(self._F, name)
+
+    def max_pool2d(self, x, *a, **k):
+        self.pools.append(_pool3_window_pos(x.detach()))
+        return self._F.max_pool2d(x, *a, **k)
+
+
+class _HipStemPool:
+    """wraps ops.bn_act_pool3: the window arg-max (0..8) the fused node saved for its backward (idx)"""
+
+    def __init__(self):
+        self.pools = []
+
+    def __enter__(self):
+        from vision_mtl_amd import ops
+
+        self.ops, self.saved = ops, ops.bn_act_pool3
+        orig = self.saved
+
+        def bn_act_pool3(x, bn, C, *a, **k):
+            h, p = orig(x, bn, C, *a, **k)
+            idx = p.grad_fn.saved_tensors[1]
+            self.pools.append(idx[..., :C].permute(0, 3, 1, 2).cpu())
+            return h, p
+
+        ops.bn_act_pool3 = bn_act_pool3
+        return self
+
+    def __exit__(self, *exc):
+        self.ops.bn_act_pool3 = self.saved
+        return False
+
+
 def _flips(hip_pools, oracle_pools):
     """{encoder level: windows whose arg-max differs between the HIP run and fp64}; the pools are matched in call order
     within a level, and must agree in number and channel count"""
@@ -104,6 +158,7 @@ def production_step(dev, kind, B, H, W, C):
     """(hip loss, fp64 loss, hip gradients, fp64 gradients, fp32 CPU gradients (worst over THREADS), {encoder level: flipped
     max-pool windows}, parameters without a gradient)"""
     import oracle.mtan as om
+    import oracle.resnet as orn
     from oracle.losses import synthetic_batch
     from vision_mtl_amd.lit_module import MTLModule
 
@@ -113,15 +168,17 @@ def production_step(dev, kind, B, H, W, C):
     sd0 = {k: v.clone() for k, v in model.state_dict().items()}
     batch = synthetic_batch(B, H, W, C, seed=11, masked=0.1)
     extra = {"levels": 4}
-    opools, hpools = _OraclePools(H), _HipPools(H)
+    resnet = name.startswith("basic_resnet")
+    opools, hpools = (_OracleStemPool(), _HipStemPool()) if resnet else (_OraclePools(H), _HipPools(H))
+    omod = orn if resnet else om
     with identity_activations():
         threads = torch.get_num_threads()
         try:
-            om.F = opools  # the fp64 run records its pools
+            omod.F = opools  # the fp64 run records its pools
             try:
                 loss64, g64 = _oracle_grads(name, sd0, batch, torch.float64, extra)
             finally:
-                om.F = opools._F
+                omod.F = opools._F
             runs = []
             for n in THREADS:
                 torch.set_num_threads(n)
@@ -136,27 +193,45 @@ def production_step(dev, kind, B, H, W, C):
             loss = module.training_step({k: v.to(dev) for k, v in batch.items()}, 0)
         loss.backward()
         torch.cuda.synchronize()
-    flips = _flips(hpools.pools, opools.pools) if name == "mtan" else {}
+    if name == "mtan":
+        flips = _flips(hpools.pools, opools.pools)
+    elif resnet:  # the stem pool: "level" 0, in front of conv1 / bn1 only
+        assert len(hpools.pools) == len(opools.pools) == 1, (len(hpools.pools), len(opools.pools))
+        assert hpools.pools[0].shape == opools.pools[0].shape, (hpools.pools[0].shape, opools.pools[0].shape)
+        n = int((hpools.pools[0] != opools.pools[0]).sum())
+        flips = {0: n} if n else {}
+    else:
+        flips = {}
     hip = {k: p.grad.cpu() for k, p in model.named_parameters() if p.grad is not None}
     missing = [k for k, p in model.named_parameters() if p.grad is None and k in g64 and g64[k] is not None
                and float(g64[k].abs().max()) > 0]
     return loss.detach().cpu(), loss64, hip, g64, g32, flips, missing
 
 
+def _in_front_of_pools(kind, k, lmax):
+    """a parameter in front of the encoder pools of levels <= lmax (ResNet: the stem pool, behind conv1 / bn1)"""
+    if kind.startswith("basic_resnet"):
+        return k.startswith(("backbone.encoder.conv1.", "backbone.encoder.bn1."))
+    return any(k.startswith(f"enc_layers.{i}.") for i in range(lmax + 1))
+
+
 @pytest.mark.parametrize("kind,B,H,W,C", [("basic", 8, 128, 256, 19), ("basic", 32, 128, 256, 19), ("basic", 8, 256, 256, 19),
-                                          ("csnet_layer", 8, 128, 256, 19), ("mtan", 4, 256, 256, 14)])
+                                          ("csnet_layer", 8, 128, 256, 19), ("mtan", 4, 256, 256, 14),
+                                          ("basic_resnet34", 8, 128, 256, 19), ("basic_resnet34", 32, 128, 256, 19)])
 def test_production_step_is_tight_without_mask_flips(dev, kind, B, H, W, C):
     """MTAN: a max-pool window whose arg-max really differs between the HIP run and fp64 (a near-tie) routes one gradient
     element to the other input of the window, which moves the gradients of every parameter in front of that pool (encoder
     levels <= l) by O(|g| / sqrt(pixels)).  Only those parameters, up to the deepest level with a measured flip, are held to
-    the end-to-end bar of the ReLU networks (assert_grads_as_good_as_fp32_cpu); all others stay on the tight bar."""
+    the end-to-end bar of the ReLU networks (assert_grads_as_good_as_fp32_cpu); all others stay on the tight bar.  The
+    ResNet's stem pool (3x3/s2; the HIP arg-max is the idx its fused node saves) is treated alike: with flips, conv1 and bn1
+    go to the end-to-end bar."""
     loss, loss64, hip, g64, g32, ties, missing = production_step(dev, kind, B, H, W, C)
     assert_close(loss, loss64.float(), tol=1e-4, what=f"{kind} loss (identity activations)")
     assert not missing, f"no gradient for {missing[:5]}"
     loose = {}
     if ties:
         lmax = max(ties)
-        loose = {k: v for k, v in hip.items() if any(k.startswith(f"enc_layers.{i}.") for i in range(lmax + 1))}
+        loose = {k: v for k, v in hip.items() if _in_front_of_pools(kind, k, lmax)}
         hip = {k: v for k, v in hip.items() if k not in loose}
         assert hip, "every gradient depends on a flipped pool window"
         g64l = {k: g64[k] for k in loose}

@@ -3,22 +3,21 @@ train-mode step (outputs, loss, every parameter gradient, BatchNorm buffers), a 
 eval outputs, the image gradient (also for the MobileNet encoder, whose stride-2 stem used to block it), captured
 training / predict steps, and the production-size step's routes.
 
-The oracle restates torchvision's ResNet (conv1 7x7/s2 -> bn1 -> relu -> maxpool 3x3/s2 -> layer1..4 of BasicBlocks)
-functionally over the state_dict, and reuses oracle.unet_mobilenetv3's _Net / unet_decoder with the heads of
-basic_forward.  Activations go through F.relu at call time (tests/util.py::identity_activations patches it)."""
+The oracle (oracle/resnet.py) restates torchvision's ResNet (conv1 7x7/s2 -> bn1 -> relu -> maxpool 3x3/s2 -> layer1..4
+of BasicBlocks) functionally over the state_dict, and reuses oracle.unet_mobilenetv3's _Net / unet_decoder with the heads
+of basic_forward.  Activations go through F.relu at call time (tests/util.py::identity_activations patches it)."""
 import gc
 
 import pytest
 import torch
-import torch.nn.functional as F
 
+from oracle.resnet import resnet_basic_forward
 from tests.util import (assert_close, assert_grads_as_good_as_fp32_cpu, assert_grads_tight, identity_activations,
                         nontrivial_bn_affine, rel_l2)
 
 pytestmark = pytest.mark.gpu
 
 NC = 19
-LAYERS = {"resnet18": (2, 2, 2, 2), "resnet34": (3, 4, 6, 3)}
 
 
 @pytest.fixture(autouse=True)
@@ -26,41 +25,6 @@ def _collect_models():
     yield
     gc.collect()
     torch.cuda.empty_cache()
-
-
-# ----------------------------------------------------------------------------- fp64 oracle
-def _basic_block(n, x, name, stride, downsample):
-    out = F.relu(n.bn(n.conv(x, f"{name}.conv1", stride, 1), f"{name}.bn1"))
-    out = n.bn(n.conv(out, f"{name}.conv2", 1, 1), f"{name}.bn2")
-    idt = n.bn(n.conv(x, f"{name}.downsample.0", stride, 0), f"{name}.downsample.1") if downsample else x
-    return F.relu(out + idt)
-
-
-def resnet_features(n, x, layers, depth=5):
-    feats = [x]
-    y = F.relu(n.bn(n.conv(x, "conv1", 2, 3), "bn1"))
-    feats.append(y)
-    if depth == 1:
-        return feats
-    y = F.max_pool2d(y, 3, 2, 1)
-    cin = 64
-    for i, (planes, nb) in enumerate(list(zip((64, 128, 256, 512), layers))[: depth - 1]):
-        for j in range(nb):
-            stride = 2 if (i > 0 and j == 0) else 1
-            y = _basic_block(n, y, f"layer{i + 1}.{j}", stride, j == 0 and (stride != 1 or cin != planes))
-            cin = planes
-        feats.append(y)
-    return feats
-
-
-def resnet_basic_forward(sd, x, training, name, depth=5):
-    from oracle.unet_mobilenetv3 import _Net, unet_decoder
-
-    feats = resnet_features(_Net(sd, "backbone.encoder.", training), x, LAYERS[name], depth)
-    dec = unet_decoder(_Net(sd, "backbone.decoder.", training), feats, n_blocks=depth)
-    depth = F.conv2d(dec, sd["depth_head.0.weight"], sd["depth_head.0.bias"], padding=1)
-    segm = F.conv2d(dec, sd["segm_head.0.weight"], sd["segm_head.0.bias"], padding=1)
-    return dict(depth=depth, segm=segm)
 
 
 def _forward(name, depth=5):

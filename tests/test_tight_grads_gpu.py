@@ -28,6 +28,10 @@ def _oracle_grads(kind, sd0, batch, dtype, extra):
         from oracle.unet_mobilenetv3 import basic_forward
 
         raw = basic_forward(sd, img, True)
+    elif kind.startswith("basic_resnet"):  # `basic` with a ResNet encoder (tests/production.py::build)
+        from oracle.resnet import resnet_basic_forward
+
+        raw = resnet_basic_forward(sd, img, True, kind[len("basic_"):])
     elif kind == "csnet":
         from oracle.cross_stitch import csnet_forward
 
