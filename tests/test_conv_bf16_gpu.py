@@ -98,7 +98,8 @@ def test_bf16_conv_natural_tail_tile(dev):
 
 def test_bf16_conv_split_k(dev):
     ops = _ops()
-    assert ops.conv_ksplit(2, 12, 12, 132, 72, 3, 3, 1, 1) > 1
+    plan = ops.conv_plan(2, 12, 12, 132, 12, 12, 72, 3, 3, 1, 1, prec=1, epilogue="stats")
+    assert plan.ksplit > 1 and plan.route == "ksplit" and plan.stats_rows == 0
     stats = _conv_case(dev, 2, 130, 12, 12, 70, True, 77)
     assert stats is None  # split-K launch: no statistics epilogue
 

@@ -71,7 +71,8 @@ def test_conv2d_fwd_bwd(dev, case):
     Ho, Wo = yr.shape[2], yr.shape[3]
     M = B * Ho * Wo
     if stats is None:  # a tile-starved shape runs split-K: no statistics epilogue, the BatchNorm sweeps y itself
-        assert ops.conv_ksplit(B, Ho, Wo, xd.shape[-1], y.shape[-1], K, K, stride, pad) > 1
+        plan = ops.conv_plan(B, H, W, xd.shape[-1], Ho, Wo, y.shape[-1], K, K, stride, pad, epilogue="stats")
+        assert plan.ksplit > 1 and plan.route == "ksplit" and plan.stats_rows == 0
     else:
         rpb = stats._vmtl_rpb  # pixels per statistics row (the launch's row block: implicit GEMM or pointwise kernel)
         st = stats.double().cpu()
@@ -304,7 +305,7 @@ def test_plain_narrow_conv_on_the_halo_tile_kernel(dev, case, monkeypatch):
                                   (2, 16, 8, 32, 19, True)])
 def test_narrow_conv_with_statistics_on_the_halo_tile_kernel(dev, case, monkeypatch):
     """Narrow 3x3 launches WITH the BatchNorm statistics epilogue (and a bias, as MTAN's attention convs have) on
-    vmtl_conv3x3_small: values, the (mean, M2) partial rows under the geometry ops.conv_stats_geometry reports, gradients."""
+    vmtl_conv3x3_small: values, the (mean, M2) partial rows under the geometry ops.conv_plan reports, gradients."""
     ops = _ops()
     recorded = []
     orig_k = ops._k
@@ -457,7 +458,8 @@ def test_conv2d_forward_split_k(dev, bias):
     xd = to_dev_nhwc(x, dev).requires_grad_(True)
     wd = w.to(dev).requires_grad_(True)
     bd = b.to(dev).requires_grad_(True) if bias else None
-    assert ops.conv_ksplit(B, H, W, xd.shape[-1], 72, 3, 3, 1, 1) > 1
+    plan = ops.conv_plan(B, H, W, xd.shape[-1], H, W, 72, 3, 3, 1, 1, epilogue="stats")
+    assert plan.ksplit > 1 and plan.route == "ksplit" and plan.stats_rows == 0
     y, stats = ops.conv2d(xd, wd, bd, stride=1, pad=1, want_stats=True)
     assert stats is None
     assert_close(from_dev_nhwc(y, Cout), yr.detach(), what="split-K fwd")

@@ -27,6 +27,7 @@ def test_up2_halo_argument_checks():
 def test_up2_statistics_geometry_follows_the_route():
     from vision_mtl_amd import ops
 
-    assert ops.up2_stats_geometry(32, 64, 128, 68, 0, 36, 33, prec=0) == (4096, 256)
+    assert ops.up2_plan(32, 64, 128, 68, 0, 36, 33, 0, True) == ops.ConvPlan("up2_halo", 1, 4096, 256)
     bm = lib().raw("vmtl_conv2d_up2_stats_block")(32, 64, 128, 36)
-    assert ops.up2_stats_geometry(32, 64, 128, 68, 0, 36, 33, prec=1) == (4 * 32 * 64 * 128 // bm, bm)
+    assert ops.up2_plan(32, 64, 128, 68, 0, 36, 33, 1, True)[2:] == (4 * 32 * 64 * 128 // bm, bm)  # bf16: implicit GEMM
+    assert ops.up2_plan(32, 64, 128, 68, 0, 36, 33, 0, False)[2:] == (0, 0)

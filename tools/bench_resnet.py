@@ -99,8 +99,8 @@ def bench_dgrad(B, H, W, steps, warmup, dev):
         KK = K * K
         wd = ops.packs.get(wt, "dgrad", (1, cin, KK, cout, ldy, 0, KK, 1, cin * KK, 1))
         dx = torch.empty(B, hh, ww, Cs, device=dev)
-        s1 = _events(lambda: ops._conv_launch(dy1, wd, None, dx, None, B, hh, ww, ldy, hh, ww, Cs, cin, cin, K, K, 1,
-                                              K - 1 - pad, cin=cout), steps, warmup)
+        s1 = _events(lambda: ops._conv_launch(dy1, wd, None, dx, B, hh, ww, ldy, hh, ww, Cs, cin, cin, K, K, 1, K - 1 - pad,
+                                              cin=cout), steps, warmup)
         f2, f1 = 2.0 * B * Ho * Wo * cout * KK * cin, 2.0 * B * hh * ww * cout * KK * cin
         out.append(dict(step="dgrad", layer=name, batch=B, in_hw=[hh, ww], K=K, cin=cin, cout=cout,
                         s2_ms=round(s2, 4), s2_tflops=round(f2 / s2 / 1e9, 2), s1_ms=round(s1, 4),

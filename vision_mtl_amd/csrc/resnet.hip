@@ -181,7 +181,7 @@ extern "C" int vmtl_conv2d_dgrad_s2_p(const float* dy, const float* wp, float* d
     if (s.T[0] == 1 && s.T[1] == 1 && s.pad == 0 && precision == VMTL_PREC_FP32 &&
         (long long)B * s.Hp * s.Wp <= (1LL << 21)) {
       // a single-tap phase without padding (1x1 / pad 0; the (even, even) phase of 3x3 / pad 1) is a plain GEMM over the
-      // pixels of dy: the pointwise kernel, as the stride-1 route takes for 1x1 convs (ops._is_pw)
+      // pixels of dy: the pointwise kernel, as the stride-1 route takes for 1x1 convs (ops.conv_plan)
       rc = vmtl_conv1x1_fwd(dy, wp + s.poff, nullptr, ws + s.woff, nullptr, B * s.Hp * s.Wp, ldy, Cs, Cin, Cin, stream);
     } else {
       rc = vmtl_conv2d_fwd_ws_p(dy, wp + s.poff, nullptr, ws + s.woff, ws + g.split_off, B, Ho, Wo, ldy, s.Hp, s.Wp, Cs,

@@ -14,6 +14,7 @@ from __future__ import annotations
 import contextlib
 import os
 import weakref
+from typing import NamedTuple
 
 import torch
 
@@ -611,80 +612,85 @@ def _bias_grad(bias, slot, dy, M, Cout, ldy, zero, fork):
 FUSE_DW = os.environ.get("VMTL_FUSE_DW", "1") != "0"  # encoder: bn1 + act + depthwise conv as one node (vmtl_dwconv_bn_fwd)
 _PW = os.environ.get("VMTL_PW", "1") != "0"  # pointwise GEMM kernel for 1x1 convs (csrc/conv_pw.hip)
 _PW_MAX_ROWS = int(os.environ.get("VMTL_PW_MAX_ROWS", str(1 << 21)))  # measured on MTAN (M = 2^20): 57.1 -> 55.5 ms/step
-
-
+_SMALL_MIN_ROWS = int(os.environ.get("VMTL_SMALL_MIN_ROWS", str(1 << 16)))  # plain narrow 3x3 launches on the halo-tile kernel
+_SMALL_STATS = os.environ.get("VMTL_SMALL_STATS", "1") != "0"  # statistics-epilogue launches of narrow layers there too
+_MID_HALO = os.environ.get("VMTL_MID_HALO", "1") != "0"  # halo-tile kernel for the 64/68-channel 3x3 convs (csrc/conv3x3_halo.hip)
+_MID_HALO_MIN_ROWS = int(os.environ.get("VMTL_MID_HALO_MIN_ROWS", str(1 << 16)))
 _UP2_HALO = os.environ.get("VMTL_UP2_HALO", "1") != "0"  # halo-tile kernel for the narrow UP2 convs (csrc/conv_up2_halo.hip)
 
 
-def _up2_halo_route(B, H2, W2, C0s, C1s, ldy, Cout, prec) -> bool:
-    """True when an UP2 conv runs on vmtl_conv2d_up2_halo: fp32, a supported shape, and no split-K on the implicit GEMM
-    (the tile-starved small-batch launches keep their split-K form).  bf16 stays on the implicit GEMM."""
-    return (_UP2_HALO and prec == 0 and bool(lib().raw("vmtl_conv2d_up2_halo_supported")(B, H2, W2, C0s, C1s, ldy, Cout))
-            and lib().raw("vmtl_conv2d_up2_ksplit")(B, H2, W2, ldy, 4 * C0s + 9 * C1s) == 1)
+class ConvPlan(NamedTuple):
+    """How one dense or UP2 conv launch runs: decided once (conv_plan / up2_plan), then only dispatched on.
+    route: "pw" pointwise GEMM (csrc/conv_pw.hip), "small" narrow halo tile (vmtl_conv3x3_small), "mid_halo" 64/68-channel
+    halo tile (vmtl_conv3x3_halo), "up2_halo" (vmtl_conv2d_up2_halo), "ksplit" implicit GEMM in K slices, "igemm" implicit
+    GEMM.  ksplit: the K slices the implicit GEMM takes for this shape (1 = none; pointwise and shuffle launches count as 1).
+    stats_rows: partial rows the epilogue writes (0 = no epilogue), rpb: the pixels each row covers (0 without rows)."""
+    route: str
+    ksplit: int
+    stats_rows: int
+    rpb: int
 
 
-def up2_stats_geometry(B, H2, W2, C0s, C1s, ldy, Cout, prec=None):
-    """(statistics rows, pixels per row) of the UP2 conv's BatchNorm partials for this shape (rows = 0: no statistics
-    epilogue, the BatchNorm reduces the output itself).  The two UP2 kernels tile differently, so the row geometry follows
-    the route; prec defaults to the current conv precision."""
-    prec = conv_prec_code() if prec is None else prec
-    if _up2_halo_route(B, H2, W2, C0s, C1s, ldy, Cout, prec):
-        return (lib().raw("vmtl_conv2d_up2_halo_stat_rows")(B, H2, W2, C0s, C1s, ldy, Cout),
-                lib().raw("vmtl_conv2d_up2_halo_stat_block")(C0s, C1s, ldy, Cout))
-    if lib().raw("vmtl_conv2d_up2_ksplit")(B, H2, W2, ldy, 4 * C0s + 9 * C1s) > 1:
-        return 0, 0
-    bm = lib().raw("vmtl_conv2d_up2_stats_block")(B, H2, W2, ldy)
-    Mq = B * H2 * W2
-    return (4 * (Mq // bm), bm) if Mq % bm == 0 else (0, bm)
+def conv_plan(B, H, W, Cs, Ho, Wo, ldy, KH, KW, stride, pad, shuffle=0, prec=0, epilogue=None) -> ConvPlan:
+    """The plan of a dense conv launch [B, H, W, Cs] -> [B, Ho, Wo, ldy] under precision `prec`.  epilogue: None, "stats"
+    (BatchNorm partial rows of y) or "bnbwd" (the fused activation + BatchNorm backward of a data gradient, ep_mode 2).
+    A launch that splits K drops its epilogue (the BatchNorm sweeps the small output itself / runs its own backward reduce);
+    only then is the route chosen, in this order: pointwise, narrow halo tile (not gated on precision: tools/bench_small.py),
+    64/68-channel halo tile (fp32 only: tools/bench_halo3.py), split K, implicit GEMM.  A halo tile with an epilogue needs
+    whole 4 x 32 tiles.  The switches are read here on every call (tests patch them), so a plan is never cached."""
+    raw = lib().raw
+    M = B * Ho * Wo
+    pw = _PW and KH == 1 and KW == 1 and stride == 1 and pad == 0 and not shuffle and M <= _PW_MAX_ROWS
+    ks = 1 if shuffle or pw else raw("vmtl_conv2d_ksplit")(B, Ho, Wo, ldy, KH * KW * Cs)
+    if ks > 1 or (epilogue == "bnbwd" and os.environ.get("VMTL_BNBWD_FUSE", "1") == "0"):
+        epilogue = None
+    tap3 = KH == 3 and KW == 3 and stride == 1 and pad == 1 and not shuffle
+    if pw:
+        route = "pw"
+    elif (tap3 and ldy <= 36 and M >= _SMALL_MIN_ROWS and M * 36 <= 0x7FFFFFFF  # 32-bit element offsets
+          and conv3x3_small_supported(Cs, ldy) and (not epilogue or (_SMALL_STATS and Ho % 4 == 0 and Wo % 32 == 0))):
+        route = "small"
+    elif (_MID_HALO and prec == 0 and tap3 and M >= _MID_HALO_MIN_ROWS and ks == 1
+          and raw("vmtl_conv3x3_halo_supported")(B, Ho, Wo, Cs, ldy, ldy)
+          and (not epilogue or raw("vmtl_conv3x3_halo_stat_rows")(B, Ho, Wo) > 0)):
+        route = "mid_halo"
+    else:
+        route = "ksplit" if ks > 1 else "igemm"
+    if not epilogue:
+        return ConvPlan(route, ks, 0, 0)
+    if route == "small":
+        rows, rpb = raw("vmtl_conv3x3_small_stat_rows")(B, Ho, Wo), raw("vmtl_conv3x3_small_stat_block")(B, Ho, Wo)
+    elif route == "mid_halo":
+        rows, rpb = raw("vmtl_conv3x3_halo_stat_rows")(B, Ho, Wo), raw("vmtl_conv3x3_halo_stat_block")(B, Ho, Wo)
+    elif route == "pw":
+        rows, rpb = raw("vmtl_conv1x1_stats_rows")(M, ldy, Cs, 0), raw("vmtl_conv1x1_stats_block")(M, ldy, Cs, 0)
+    else:
+        rows, rpb = raw("vmtl_conv2d_stats_rows")(B, Ho, Wo, ldy), raw("vmtl_conv2d_stats_block")(B, Ho, Wo, ldy)
+    return ConvPlan(route, ks, rows, rpb)
 
 
-def _is_pw(B, Ho, Wo, KH, KW, stride, pad, shuffle=0):
-    return _PW and KH == 1 and KW == 1 and stride == 1 and pad == 0 and not shuffle and B * Ho * Wo <= _PW_MAX_ROWS
-
-
-_SMALL_MIN_ROWS = int(os.environ.get("VMTL_SMALL_MIN_ROWS", str(1 << 16)))  # plain narrow 3x3 launches on the halo-tile kernel
-
-
-def conv_ksplit(B, Ho, Wo, Cs, ldy, KH, KW, stride, pad, shuffle=0) -> int:
-    """K slices a dense conv launch of this shape runs as (1 = none).  A split launch has no statistics epilogue: the
-    BatchNorm that follows takes its statistics from its own sweep of the (small) output instead."""
-    if shuffle or _is_pw(B, Ho, Wo, KH, KW, stride, pad, shuffle):
-        return 1
-    return lib().raw("vmtl_conv2d_ksplit")(B, Ho, Wo, ldy, KH * KW * Cs)
-
-
-_SMALL_STATS = os.environ.get("VMTL_SMALL_STATS", "1") != "0"  # statistics-epilogue launches of narrow layers there too
-
-
-def _small_route(B, H, W, Cs, ldy, KH, KW, stride, pad, shuffle=0, with_stats=False) -> bool:
-    """A narrow full-resolution 3x3 / stride 1 / pad 1 launch that runs on the halo-tile kernel (vmtl_conv3x3_small) instead
-    of the implicit GEMM: 11-20 % faster on 16/32-channel layers at 1 M pixels (tools/bench_small.py), with or without the
-    statistics epilogue (whose tiles must be whole: H % 4 == 0, W % 32 == 0)."""
-    if shuffle or KH != 3 or KW != 3 or stride != 1 or pad != 1 or ldy > 36 or B * H * W < _SMALL_MIN_ROWS:
-        return False
-    if B * H * W * 36 > 0x7FFFFFFF:  # that kernel's 32-bit element offsets
-        return False
-    if not conv3x3_small_supported(Cs, ldy):  # weight rows <= ldy
-        return False
-    return not with_stats or (_SMALL_STATS and H % 4 == 0 and W % 32 == 0)
-
-
-_MID_HALO = os.environ.get("VMTL_MID_HALO", "1") != "0"  # halo-tile kernel for the 64/68-channel 3x3 convs (csrc/conv3x3_halo.hip)
-_MID_HALO_MIN_ROWS = int(os.environ.get("VMTL_MID_HALO_MIN_ROWS", str(1 << 16)))
-
-
-def _mid_halo_route(B, H, W, Cs, ldy, KH, KW, stride, pad, shuffle=0, with_stats=False, prec=None) -> bool:
-    """A 3x3 / stride 1 / pad 1 launch with 64 or 68 input storage channels and 16 / 32 / 64 / 68 output storage channels
-    that runs on vmtl_conv3x3_halo instead of the implicit GEMM: fp32, no split-K, at least _MID_HALO_MIN_ROWS output
-    pixels (tools/bench_halo3.py), and whole 4 x 32 tiles when the launch emits statistics.  bf16 stays on the implicit GEMM."""
-    prec = conv_prec_code() if prec is None else prec
-    if not _MID_HALO or prec != 0 or shuffle or KH != 3 or KW != 3 or stride != 1 or pad != 1 or B * H * W < _MID_HALO_MIN_ROWS:
-        return False
-    if not lib().raw("vmtl_conv3x3_halo_supported")(B, H, W, Cs, ldy, ldy):
-        return False
-    if lib().raw("vmtl_conv2d_ksplit")(B, H, W, ldy, 9 * Cs) > 1:
-        return False
-    return not with_stats or lib().raw("vmtl_conv3x3_halo_stat_rows")(B, H, W) > 0
+def up2_plan(B, H2, W2, C0s, C1s, ldy, Cout, prec, want_stats) -> ConvPlan:
+    """The plan of an UP2 conv (low-res source [B, H2, W2, C0s], skip of C1s storage channels): the halo-tile kernel when
+    fp32, supported and not split (the tile-starved small-batch launches keep their split-K form; bf16 stays on the
+    implicit GEMM), else split K, else the implicit GEMM.  The two kernels tile differently, so the
+    statistics rows follow the route; the implicit GEMM has them only when its row block divides B * H2 * W2."""
+    raw = lib().raw
+    ks = raw("vmtl_conv2d_up2_ksplit")(B, H2, W2, ldy, 4 * C0s + 9 * C1s)
+    rows = rpb = 0
+    if _UP2_HALO and prec == 0 and ks == 1 and raw("vmtl_conv2d_up2_halo_supported")(B, H2, W2, C0s, C1s, ldy, Cout):
+        route = "up2_halo"
+        if want_stats:
+            rows = raw("vmtl_conv2d_up2_halo_stat_rows")(B, H2, W2, C0s, C1s, ldy, Cout)
+            rpb = raw("vmtl_conv2d_up2_halo_stat_block")(C0s, C1s, ldy, Cout) if rows else 0
+    elif ks > 1:
+        route = "ksplit"
+    else:
+        route = "igemm"
+        if want_stats:
+            bm, Mq = raw("vmtl_conv2d_up2_stats_block")(B, H2, W2, ldy), B * H2 * W2
+            if Mq % bm == 0:
+                rows, rpb = 4 * (Mq // bm), bm
+    return ConvPlan(route, ks, rows, rpb)
 
 
 def _mid_halo(x, wp, y, B, H, W, Cs, ldy, Nw, Cout, flop, pa=None, pc=None, act_in=ACT_NONE, a_out=None, bias=None,
@@ -696,46 +702,78 @@ def _mid_halo(x, wp, y, B, H, W, Cs, ldy, Nw, Cout, flop, pa=None, pc=None, act_
        W=W, Cs=Cs, ldy=ldy, Nw=Nw, Cout=Cout)
 
 
-def conv_stats_geometry(B, Ho, Wo, Cs, ldy, KH, KW, stride, pad):
-    """(rows, pixels per row) of the BatchNorm partial rows a conv launch of this shape emits from its epilogue."""
-    if _small_route(B, Ho, Wo, Cs, ldy, KH, KW, stride, pad, with_stats=True):
-        return lib().raw("vmtl_conv3x3_small_stat_rows")(B, Ho, Wo), lib().raw("vmtl_conv3x3_small_stat_block")(B, Ho, Wo)
-    if _mid_halo_route(B, Ho, Wo, Cs, ldy, KH, KW, stride, pad, with_stats=True):
-        return lib().raw("vmtl_conv3x3_halo_stat_rows")(B, Ho, Wo), lib().raw("vmtl_conv3x3_halo_stat_block")(B, Ho, Wo)
-    if _is_pw(B, Ho, Wo, KH, KW, stride, pad):
-        M = B * Ho * Wo
-        return lib().raw("vmtl_conv1x1_stats_rows")(M, ldy, Cs, 0), lib().raw("vmtl_conv1x1_stats_block")(M, ldy, Cs, 0)
-    return lib().raw("vmtl_conv2d_stats_rows")(B, Ho, Wo, ldy), lib().raw("vmtl_conv2d_stats_block")(B, Ho, Wo, ldy)
+def _conv_launch(x, wp, bias, y, B, H, W, Cs, Ho, Wo, ldy, Nw, Cout, KH, KW, stride, pad, shuffle=0, cin=None,
+                 algo_flop=None, prec=0, plan=None, stats=None):
+    """One dense conv launch, dispatched on its plan; a launch without an epilogue may leave the planning to this function.
+    stats: the [plan.stats_rows][2][ldy] rows of a plan with the statistics epilogue."""
+    if plan is None:
+        plan = conv_plan(B, H, W, Cs, Ho, Wo, ldy, KH, KW, stride, pad, shuffle, prec)
+    xflop = 2.0 * B * Ho * Wo * Nw * KH * KW * (Cs if cin is None else cin)
+    flop = xflop if algo_flop is None else algo_flop
+    ep_mode = 1 if stats is not None else 0
+    if plan.route == "pw":
+        _k("vmtl_conv1x1_fwd", _flop=flop, _xflop=xflop, x=x, wp=wp, bias=bias, y=y, stats=stats, M=B * Ho * Wo, Ks=Cs,
+           ldy=ldy, Nw=Nw, Cout=Cout)
+    elif plan.route == "small":  # narrow full-resolution layer: the halo-tile kernel reads the input once
+        _small(x, wp, y, B, H, W, Cs, ldy, Nw, Cout, flop, bias=bias, stats=stats, ep_mode=ep_mode)
+    elif plan.route == "mid_halo":  # 64/68-channel layer: the halo-tile kernel reads each input pixel once
+        _mid_halo(x, wp, y, B, H, W, Cs, ldy, Nw, Cout, flop, bias=bias, stats=stats, ep_mode=ep_mode)
+    elif plan.route == "ksplit":  # tile-starved contraction: split K when the tile grid alone cannot fill the chip
+        _kp("vmtl_conv2d_fwd_ws", prec, _flop=flop, _xflop=xflop, x=x, wp=wp, bias=bias, y=y,
+            ws=_empty((plan.ksplit, B * Ho * Wo, ldy), x), B=B, H=H, W=W, Cs=Cs, Ho=Ho, Wo=Wo, ldy=ldy, Nw=Nw, Cout=Cout,
+            KH=KH, KW=KW, stride=stride, pad=pad)
+    else:
+        _kp("vmtl_conv2d_fwd", prec, _flop=flop, _xflop=xflop, x=x, wp=wp, bias=bias, y=y, stats=stats, B=B, H=H, W=W,
+            Cs=Cs, Ho=Ho, Wo=Wo, ldy=ldy, Nw=Nw, Cout=Cout, KH=KH, KW=KW, stride=stride, pad=pad, act=0, shuffle=shuffle)
 
 
-def _conv_launch(x, wp, bias, y, stats, B, H, W, Cs, Ho, Wo, ldy, Nw, Cout, KH, KW, stride, pad, shuffle=0, cin=None,
-                 algo_flop=None, prec=0):
-    flop = 2.0 * B * Ho * Wo * Nw * KH * KW * (Cs if cin is None else cin)
-    if _is_pw(B, Ho, Wo, KH, KW, stride, pad, shuffle):
-        _k("vmtl_conv1x1_fwd", _flop=flop if algo_flop is None else algo_flop, _xflop=flop, x=x, wp=wp, bias=bias, y=y,
-           stats=stats, M=B * Ho * Wo, Ks=Cs, ldy=ldy, Nw=Nw, Cout=Cout)
-        return
-    if _small_route(B, H, W, Cs, ldy, KH, KW, stride, pad, shuffle, with_stats=stats is not None):
-        # narrow full-resolution layer: the halo-tile kernel reads the input once (statistics rows: conv_stats_geometry)
-        _small(x, wp, y, B, H, W, Cs, ldy, Nw, Cout, flop if algo_flop is None else algo_flop, bias=bias, stats=stats,
-               ep_mode=1 if stats is not None else 0)
-        return
-    if _mid_halo_route(B, H, W, Cs, ldy, KH, KW, stride, pad, shuffle, with_stats=stats is not None, prec=prec):
-        # 64/68-channel layer: the halo-tile kernel reads each input pixel once (statistics rows: conv_stats_geometry)
-        _mid_halo(x, wp, y, B, H, W, Cs, ldy, Nw, Cout, flop if algo_flop is None else algo_flop, bias=bias, stats=stats,
-                  ep_mode=1 if stats is not None else 0)
-        return
-    if stats is None and not shuffle:
-        # contraction without a statistics epilogue (data gradients; forward convs of tile-starved layers, see
-        # conv_ksplit): split K when the tile grid alone cannot fill the chip
-        ks = lib().raw("vmtl_conv2d_ksplit")(B, Ho, Wo, ldy, KH * KW * Cs)
-        if ks > 1:
-            ws = _empty((ks, B * Ho * Wo, ldy), x)
-            _kp("vmtl_conv2d_fwd_ws", prec, _flop=flop if algo_flop is None else algo_flop, _xflop=flop, x=x, wp=wp, bias=bias, y=y,
-               ws=ws, B=B, H=H, W=W, Cs=Cs, Ho=Ho, Wo=Wo, ldy=ldy, Nw=Nw, Cout=Cout, KH=KH, KW=KW, stride=stride, pad=pad)
-            return
-    _kp("vmtl_conv2d_fwd", prec, _flop=flop if algo_flop is None else algo_flop, _xflop=flop, x=x, wp=wp, bias=bias, y=y, stats=stats, B=B, H=H, W=W, Cs=Cs, Ho=Ho, Wo=Wo, ldy=ldy,
-       Nw=Nw, Cout=Cout, KH=KH, KW=KW, stride=stride, pad=pad, act=0, shuffle=shuffle)
+def _up2_fwd(plan, xl, skip, weight, C0, prec):
+    """(y, stats) of an UP2 conv on its plan: conv3x3(cat[nearest_x2(xl), skip]) as four 2x2 phase convolutions on xl.
+    FLOPs: the reference formulation (9 taps on every channel); executed: 4 taps on xl's."""
+    B, H2, W2, C0s = xl.shape
+    Cout, Cin = weight.shape[0], weight.shape[1]
+    C1, C1s = Cin - C0, 0 if skip is None else skip.shape[3]
+    ldy = ceil4(Cout)
+    wp = packs.get_custom(weight, "up2_fwd", (4, Cout, 4 * C0s + 9 * C1s), lambda w, dst: _k(
+        "vmtl_pack_up2_fwd", w=w, dst=dst, Cout=Cout, C0=C0, C0s=C0s, C1=C1, C1s=C1s))
+    y = _empty((B, 2 * H2, 2 * W2, ldy), xl)
+    stats = _empty((plan.stats_rows, 2, ldy), xl) if plan.stats_rows else None
+    M = B * 4 * H2 * W2
+    kw = dict(_flop=2.0 * M * Cout * 9 * Cin, _xflop=2.0 * M * Cout * (4 * C0 + 9 * C1), xl=xl, skip=skip, wp_eff=wp, y=y,
+              B=B, H2=H2, W2=W2, C0s=C0s, C1s=C1s, ldy=ldy, Cout=Cout)
+    if plan.route == "up2_halo":
+        _k("vmtl_conv2d_up2_halo", stats=stats, **kw)
+    elif plan.route == "ksplit":  # tile-starved (deep decoder blocks at small batch): split K, no statistics epilogue
+        _kp("vmtl_conv2d_up2_fwd_ws", prec, ws=_empty((plan.ksplit, B, 2 * H2, 2 * W2, ldy), xl), **kw)
+    else:
+        _kp("vmtl_conv2d_up2_fwd", prec, stats=stats, **kw)
+    return y, stats
+
+
+def _up2_dskip(dy, weight, skip, C0, prec):
+    """Data gradient of an UP2 conv's skip source: the plain 3x3 data gradient restricted to the skip channels."""
+    B, H, W, ldy = dy.shape
+    Cout, Cin = weight.shape[0], weight.shape[1]
+    C1, C1s = Cin - C0, skip.shape[3]
+    wds = packs.get(weight, "up2_dskip", (1, C1, 9, Cout, ldy, 0, 9, 1, Cin * 9, 1), offset=C0 * 9)
+    dskip = _empty((B, H, W, C1s), dy)
+    _conv_launch(dy, wds, None, dskip, B, H, W, ldy, H, W, C1s, C1, C1, 3, 3, 1, 1, cin=Cout, prec=prec)
+    return dskip
+
+
+def _up2_wgrad(dy, xl, skip, weight, C0, dw, prec):
+    """Weight gradient of an UP2 conv into dw: the low-res part as the weight gradient of the 4x4/s2/p1 convolution of
+    the data gradient (dY in the role of its input), the skip part as a plain 3x3 one."""
+    B, H, W, ldy = dy.shape
+    _, H2, W2, C0s = xl.shape
+    Cout, Cin = weight.shape[0], weight.shape[1]
+    slabs, ns = _wgrad(dy, xl, B, H, W, ldy, H2, W2, C0s, C0, 4, 4, 2, 1, 2.0 * B * H * W * Cout * 9 * C0,
+                       xflop=2.0 * B * H2 * W2 * C0 * 16 * Cout, prec=prec)
+    _k("vmtl_unpack_up2", slabs=slabs, grad=dw, Cout=Cout, Cos=ldy, C0=C0, Cin=Cin, nslabs=ns)
+    if skip is not None:
+        C1, C1s = Cin - C0, skip.shape[3]
+        slabs, ns = _wgrad(skip, dy, B, H, W, C1s, H, W, ldy, Cout, 3, 3, 1, 1, 2.0 * B * H * W * Cout * 9 * C1, prec=prec)
+        unpack(slabs, None, 1, Cout, 9, C1, C1s, 0, Cin * 9, 1, 9, out=dw.view(-1)[C0 * 9:], nslabs=ns)
 
 
 # ----------------------------------------------------------------------------- conv2d
@@ -758,7 +796,7 @@ class _Conv2d(torch.autograd.Function):
     gradient is taken from the conv's own weight-gradient slabs: no pass over the activations for the stitch at all."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, stride, pad, want_stats, zero_bias_grad=False, stitch_w=None, stitch_task=0):
+    def forward(ctx, x, weight, bias, stride, pad, plan, zero_bias_grad=False, stitch_w=None, stitch_task=0):
         x = _req(x, "x")
         weight = _req(weight, "weight")
         B, H, W, Cs = x.shape
@@ -777,14 +815,10 @@ class _Conv2d(torch.autograd.Function):
             wp = packs.get(weight, f"fwd_st{stitch_task}", (1, Cout, KK, Cin, Cs, 0, Cin * KK, 1, KK, 0),
                            scale=(stitch_w, soff, sstride, 1))
         y = _empty((B, Ho, Wo, ldy), x)
-        stats = None
-        if want_stats and conv_ksplit(B, Ho, Wo, Cs, ldy, KH, KW, stride, pad) > 1:
-            want_stats = False  # tile-starved layer: split K, the BatchNorm sweeps the (small) output itself
-        if want_stats:
-            rows, _ = conv_stats_geometry(B, Ho, Wo, Cs, ldy, KH, KW, stride, pad)
-            stats = _empty((rows, 2, ldy), x)
+        stats = _empty((plan.stats_rows, 2, ldy), x) if plan.stats_rows else None
         prec = ctx.prec = conv_prec_code()  # backward runs under the precision of this forward
-        _conv_launch(x, wp, bias, y, stats, B, H, W, Cs, Ho, Wo, ldy, Cout, Cout, KH, KW, stride, pad, cin=Cin, prec=prec)
+        _conv_launch(x, wp, bias, y, B, H, W, Cs, Ho, Wo, ldy, Cout, Cout, KH, KW, stride, pad, cin=Cin, prec=prec, plan=plan,
+                     stats=stats)
         ctx.save_for_backward(x, weight, stitch_w)
         ctx.cfg = (stride, pad, bias is not None)
         ctx.zero_bias_grad = bool(zero_bias_grad)
@@ -792,10 +826,9 @@ class _Conv2d(torch.autograd.Function):
         ctx.stitch = (stitch_task, _slot(stitch_w))
         ctx.bias = bias
         ctx.set_materialize_grads(False)  # no zero-filled "gradient" tensor for the stats output
-        if want_stats:
+        if stats is not None:
             ctx.mark_non_differentiable(stats)
-            return y, stats
-        return y, None
+        return y, stats
 
     @staticmethod
     def backward(ctx, dy, _dstats):
@@ -828,7 +861,7 @@ class _Conv2d(torch.autograd.Function):
                                scale=(stitch_w, soff, sstride, 2))
             if stride == 1:
                 dx = _empty((B, H, W, Cs), x)
-                _conv_launch(dy, wd, None, dx, None, B, Ho, Wo, ldy, H, W, Cs, Cin, Cin, KH, KW, 1, KH - 1 - pad, cin=Cout,
+                _conv_launch(dy, wd, None, dx, B, Ho, Wo, ldy, H, W, Cs, Cin, Cin, KH, KW, 1, KH - 1 - pad, cin=Cout,
                              prec=ctx.prec)
         if ctx.needs_input_grad[1] or (stitch_w is not None and ctx.needs_input_grad[7]):
             use_side = ctx.slots[0] is not None and (stitch_w is None or stitch_slot is not None)
@@ -1086,10 +1119,10 @@ class _Up2Conv(torch.autograd.Function):
     weight keeps the torch layout (Cout, C0 + C1, 3, 3), input channels ordered [xl | skip]."""
 
     @staticmethod
-    def forward(ctx, xl, skip, weight, C0, want_stats):
+    def forward(ctx, xl, skip, weight, C0, plan):
         xl, weight = _req(xl, "xl"), _req(weight, "weight")
         B, H2, W2, C0s = xl.shape
-        Cout, Cin = weight.shape[0], weight.shape[1]
+        Cin = weight.shape[1]
         if tuple(weight.shape[2:]) != (3, 3):
             raise ValueError("up2_conv: 3x3 kernels only")
         if skip is not None:
@@ -1102,37 +1135,10 @@ class _Up2Conv(torch.autograd.Function):
         C1 = Cin - C0
         if ceil4(C0) != C0s or ceil4(C1) != C1s or (C1 > 0) != (skip is not None):
             raise ValueError(f"up2_conv: weight has {Cin} input channels, sources hold {C0s}+{C1s} storage channels")
-        ldy = ceil4(Cout)
-        Ktot = 4 * C0s + 9 * C1s
-        wp = packs.get_custom(weight, "up2_fwd", (4, Cout, Ktot), lambda w, dst: _k(
-            "vmtl_pack_up2_fwd", w=w, dst=dst, Cout=Cout, C0=C0, C0s=C0s, C1=C1, C1s=C1s))
-        y = _empty((B, 2 * H2, 2 * W2, ldy), xl)
-        stats = None
-        M = B * 4 * H2 * W2
         prec = ctx.prec = conv_prec_code()
-        # algorithmic FLOPs = the reference formulation (9 taps on every channel); executed: 4 taps on xl's
-        ks = lib().raw("vmtl_conv2d_up2_ksplit")(B, H2, W2, ldy, Ktot)
-        if _up2_halo_route(B, H2, W2, C0s, C1s, ldy, Cout, prec):
-            if want_stats:
-                rows, _ = up2_stats_geometry(B, H2, W2, C0s, C1s, ldy, Cout, prec)
-                if rows:
-                    stats = _empty((rows, 2, ldy), xl)
-            _k("vmtl_conv2d_up2_halo", _flop=2.0 * M * Cout * 9 * Cin, _xflop=2.0 * M * Cout * (4 * C0 + 9 * C1), xl=xl,
-               skip=skip, wp_eff=wp, y=y, stats=stats, B=B, H2=H2, W2=W2, C0s=C0s, C1s=C1s, ldy=ldy, Cout=Cout)
-        elif ks > 1:  # tile-starved (deep decoder blocks at small batch): split K, no statistics epilogue
-            _kp("vmtl_conv2d_up2_fwd_ws", prec, _flop=2.0 * M * Cout * 9 * Cin, _xflop=2.0 * M * Cout * (4 * C0 + 9 * C1), xl=xl,
-               skip=skip, wp_eff=wp, y=y, ws=_empty((ks, B, 2 * H2, 2 * W2, ldy), xl), B=B, H2=H2, W2=W2, C0s=C0s, C1s=C1s,
-               ldy=ldy, Cout=Cout)
-        else:
-            if want_stats:
-                bm = lib().raw("vmtl_conv2d_up2_stats_block")(B, H2, W2, ldy)
-                Mq = B * H2 * W2
-                if Mq % bm == 0:
-                    stats = _empty((4 * (Mq // bm), 2, ldy), xl)
-            _kp("vmtl_conv2d_up2_fwd", prec, _flop=2.0 * M * Cout * 9 * Cin, _xflop=2.0 * M * Cout * (4 * C0 + 9 * C1), xl=xl,
-               skip=skip, wp_eff=wp, y=y, stats=stats, B=B, H2=H2, W2=W2, C0s=C0s, C1s=C1s, ldy=ldy, Cout=Cout)
+        y, stats = _up2_fwd(plan, xl, skip, weight, C0, prec)
         ctx.save_for_backward(xl, skip, weight)
-        ctx.cfg = (C0, C1, stats.shape[0] if stats is not None else 0)
+        ctx.C0 = C0
         ctx.slot = _slot(weight)
         ctx.set_materialize_grads(False)
         if stats is not None:
@@ -1142,7 +1148,7 @@ class _Up2Conv(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, _dstats):
         xl, skip, weight = ctx.saved_tensors
-        C0, C1, _ = ctx.cfg
+        C0 = ctx.C0
         if dy is None:
             return None, None, None, None
         dy = _req(dy, "dy")
@@ -1156,25 +1162,14 @@ class _Up2Conv(torch.autograd.Function):
             wd = packs.get_custom(weight, "up2_dgrad", (C0, 16 * ldy), lambda w, dst: _k(
                 "vmtl_pack_up2_dgrad", w=w, dst=dst, Cout=Cout, Cos=ldy, C0=C0, Cin=Cin))
             dxl = _empty((B, H2, W2, C0s), xl)
-            _conv_launch(dy, wd, None, dxl, None, B, H, W, ldy, H2, W2, C0s, C0, C0, 4, 4, 2, 1, cin=Cout,
+            _conv_launch(dy, wd, None, dxl, B, H, W, ldy, H2, W2, C0s, C0, C0, 4, 4, 2, 1, cin=Cout,
                          algo_flop=2.0 * B * H * W * C0 * 9 * Cout, prec=ctx.prec)
-        if skip is not None and ctx.needs_input_grad[1]:  # plain 3x3 data gradient restricted to the skip channels
-            C1s = skip.shape[3]
-            wds = packs.get(weight, "up2_dskip", (1, C1, 9, Cout, ldy, 0, 9, 1, Cin * 9, 1), offset=C0 * 9)
-            dskip = _empty((B, H, W, C1s), xl)
-            _conv_launch(dy, wds, None, dskip, None, B, H, W, ldy, H, W, C1s, C1, C1, 3, 3, 1, 1, cin=Cout, prec=ctx.prec)
+        if skip is not None and ctx.needs_input_grad[1]:
+            dskip = _up2_dskip(dy, weight, skip, C0, ctx.prec)
         if ctx.needs_input_grad[2]:
             dw = _empty(weight.shape, xl) if ctx.slot is None else ctx.slot
             with side.branch(ctx.slot is not None, B * H * W, fork, dy, xl, skip):
-                # low-res part: weight gradient of that 4x4/s2/p1 convolution (dY in the role of its input)
-                slabs, ns = _wgrad(dy, xl, B, H, W, ldy, H2, W2, C0s, C0, 4, 4, 2, 1, 2.0 * B * H * W * Cout * 9 * C0,
-                                   xflop=2.0 * B * H2 * W2 * C0 * 16 * Cout, prec=ctx.prec)
-                _k("vmtl_unpack_up2", slabs=slabs, grad=dw, Cout=Cout, Cos=ldy, C0=C0, Cin=Cin, nslabs=ns)
-                if skip is not None:
-                    C1s = skip.shape[3]
-                    slabs, ns = _wgrad(skip, dy, B, H, W, C1s, H, W, ldy, Cout, 3, 3, 1, 1,
-                                       2.0 * B * H * W * Cout * 9 * C1, prec=ctx.prec)
-                    unpack(slabs, None, 1, Cout, 9, C1, C1s, 0, Cin * 9, 1, 9, out=dw.view(-1)[C0 * 9:], nslabs=ns)
+                _up2_wgrad(dy, xl, skip, weight, C0, dw, ctx.prec)
                 stamp(f"side up2 M={B * H * W} N={Cout} Cin={Cin}")
             if ctx.slot is not None:
                 dw = None
@@ -1192,7 +1187,7 @@ class _BNActConv(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, stats, rpb, gamma, beta, rm, rv, nbt, weight, skip, cfg):
-        C, training, momentum, eps, act, up2, want_stats = cfg
+        C, training, momentum, eps, act, up2, plan = cfg
         x, weight = _req(x, "x"), _req(weight, "weight")
         B, H, W, Cs = x.shape
         M = B * H * W
@@ -1203,8 +1198,7 @@ class _BNActConv(torch.autograd.Function):
         ldy = ceil4(Cout)
         # a 64/68-channel layer on the halo-tile kernel applies BatchNorm + activation as the conv's prologue (once per
         # input element, written back to a); everything else materialises a first
-        pro = (not up2 and skip is None and Cin == C and act in (ACT_NONE, ACT_RELU)
-               and _mid_halo_route(B, H, W, Cs, ldy, 3, 3, 1, 1, with_stats=want_stats, prec=prec))
+        pro = not up2 and skip is None and Cin == C and act in (ACT_NONE, ACT_RELU) and plan.route == "mid_halo"
         # ---- BatchNorm + activation (materialised: the weight gradient reads it)
         a = _empty(x.shape, x)
         if pro:
@@ -1230,7 +1224,6 @@ class _BNActConv(torch.autograd.Function):
             _k("vmtl_bn_apply", x=x, mean=mean, invstd=invstd, gamma=gamma, beta=beta, mul=None, res=None, y=a, M=M, C=C,
                Cs=Cs, act=act)
         # ---- the conv on a
-        ostats, orpb = None, 0
         if up2:
             if skip is not None:
                 skip = _req(skip, "skip")
@@ -1242,47 +1235,22 @@ class _BNActConv(torch.autograd.Function):
             C1 = Cin - C
             if ceil4(C1) != C1s or (C1 > 0) != (skip is not None):
                 raise ValueError("bn_act_conv(up2): weight channels do not match x + skip")
-            Ktot = 4 * Cs + 9 * C1s
-            wp = packs.get_custom(weight, "up2_fwd", (4, Cout, Ktot), lambda w, dst: _k(
-                "vmtl_pack_up2_fwd", w=w, dst=dst, Cout=Cout, C0=C, C0s=Cs, C1=C1, C1s=C1s))
-            y = _empty((B, 2 * H, 2 * W, ldy), x)
-            Mo = 4 * M
-            ks = lib().raw("vmtl_conv2d_up2_ksplit")(B, H, W, ldy, Ktot)
-            if _up2_halo_route(B, H, W, Cs, C1s, ldy, Cout, prec):
-                if want_stats:
-                    rows, bm = up2_stats_geometry(B, H, W, Cs, C1s, ldy, Cout, prec)
-                    if rows:
-                        ostats, orpb = _empty((rows, 2, ldy), x), bm
-                _k("vmtl_conv2d_up2_halo", _flop=2.0 * Mo * Cout * 9 * Cin, _xflop=2.0 * Mo * Cout * (4 * C + 9 * C1), xl=a,
-                   skip=skip, wp_eff=wp, y=y, stats=ostats, B=B, H2=H, W2=W, C0s=Cs, C1s=C1s, ldy=ldy, Cout=Cout)
-            elif ks > 1:  # tile-starved (deep decoder blocks at small batch): split K, no statistics epilogue
-                _kp("vmtl_conv2d_up2_fwd_ws", prec, _flop=2.0 * Mo * Cout * 9 * Cin, _xflop=2.0 * Mo * Cout * (4 * C + 9 * C1),
-                   xl=a, skip=skip, wp_eff=wp, y=y, ws=_empty((ks, B, 2 * H, 2 * W, ldy), x), B=B, H2=H, W2=W, C0s=Cs,
-                   C1s=C1s, ldy=ldy, Cout=Cout)
-            else:
-                if want_stats:
-                    bm = lib().raw("vmtl_conv2d_up2_stats_block")(B, H, W, ldy)
-                    if M % bm == 0:
-                        ostats, orpb = _empty((4 * (M // bm), 2, ldy), x), bm
-                _kp("vmtl_conv2d_up2_fwd", prec, _flop=2.0 * Mo * Cout * 9 * Cin, _xflop=2.0 * Mo * Cout * (4 * C + 9 * C1), xl=a,
-                   skip=skip, wp_eff=wp, y=y, stats=ostats, B=B, H2=H, W2=W, C0s=Cs, C1s=C1s, ldy=ldy, Cout=Cout)
+            y, ostats = _up2_fwd(plan, a, skip, weight, C, prec)
         else:
             if Cin != C or skip is not None:
                 raise ValueError("bn_act_conv: weight expects x's channels (skip only with up2)")
             wp = packs.get(weight, "fwd", (1, Cout, 9, Cin, Cs, 0, Cin * 9, 1, 9, 0))
             y = _empty((B, H, W, ldy), x)
-            if want_stats and conv_ksplit(B, H, W, Cs, ldy, 3, 3, 1, 1) == 1:
-                rows, orpb = conv_stats_geometry(B, H, W, Cs, ldy, 3, 3, 1, 1)
-                ostats = _empty((rows, 2, ldy), x)
+            ostats = _empty((plan.stats_rows, 2, ldy), x) if plan.stats_rows else None
             if pro:
                 _mid_halo(x, wp, y, B, H, W, Cs, ldy, Cout, Cout, 2.0 * M * Cout * 9 * Cin, pa=ca, pc=cc, act_in=act, a_out=a,
                           stats=ostats, ep_mode=1 if ostats is not None else 0)
             else:
-                _conv_launch(a, wp, None, y, ostats, B, H, W, Cs, H, W, ldy, Cout, Cout, 3, 3, 1, 1, cin=Cin, prec=prec)
+                _conv_launch(a, wp, None, y, B, H, W, Cs, H, W, ldy, Cout, Cout, 3, 3, 1, 1, cin=Cin, prec=prec, plan=plan,
+                             stats=ostats)
         ctx.save_for_backward(x, a, skip, weight, mean, invstd, gamma, beta)
         ctx.cfg = (C, training, act, up2)
         ctx.slots = (_slot(gamma), _slot(beta), _slot(weight))
-        ctx.orpb = orpb
         ctx.set_materialize_grads(False)
         if ostats is not None:
             ctx.mark_non_differentiable(ostats)
@@ -1307,69 +1275,48 @@ class _BNActConv(torch.autograd.Function):
             Hd, Wd = 2 * H, 2 * W  # dy's extent
             wd = packs.get_custom(weight, "up2_dgrad", (C, 16 * ldy), lambda w, dst: _k(
                 "vmtl_pack_up2_dgrad", w=w, dst=dst, Cout=Cout, Cos=ldy, C0=C, Cin=Cin))
-            geo = dict(B=B, H=Hd, W=Wd, Cs=ldy, Ho=H, Wo=W, ldy=Cs, Nw=C, Cout=C, KH=4, KW=4, stride=2, pad=1)
+            geo = dict(B=B, H=Hd, W=Wd, Cs=ldy, Ho=H, Wo=W, ldy=Cs, KH=4, KW=4, stride=2, pad=1)
             flop, xflop = 2.0 * B * Hd * Wd * C * 9 * Cout, 2.0 * M * C * 16 * Cout
         else:
             Hd, Wd = H, W
             wd = packs.get(weight, "dgrad", (1, Cin, 9, Cout, ldy, 0, 9, 1, Cin * 9, 1))
-            geo = dict(B=B, H=H, W=W, Cs=ldy, Ho=H, Wo=W, ldy=Cs, Nw=Cin, Cout=Cin, KH=3, KW=3, stride=1, pad=1)
+            geo = dict(B=B, H=H, W=W, Cs=ldy, Ho=H, Wo=W, ldy=Cs, KH=3, KW=3, stride=1, pad=1)
             flop = xflop = 2.0 * M * Cin * 9 * Cout
         dgamma = _empty((C,), x) if sg is None else sg
         dbeta = _empty((C,), x) if sb is None else sb
         dx = _empty(x.shape, x) if ctx.needs_input_grad[0] else None
-        fuse = lib().raw("vmtl_conv2d_ksplit")(B, H, W, Cs, geo["KH"] * geo["KW"] * ldy) <= 1 \
-            and os.environ.get("VMTL_BNBWD_FUSE", "1") != "0"
-        if fuse:
+        plan = conv_plan(**geo, prec=ctx.prec, epilogue="bnbwd")
+        if plan.stats_rows:  # fused: the halo-tile kernels (ep_mode 2) or the implicit GEMM's BatchNorm-backward epilogue
             dz = _empty(x.shape, x)
-            if not up2 and _small_route(B, H, W, ldy, Cs, 3, 3, 1, 1, with_stats=True):
-                # narrow layer: the same fused data gradient on the halo-tile kernel (ep_mode 2)
-                rows = lib().raw("vmtl_conv3x3_small_stat_rows")(B, H, W)
-                part = _empty((rows, 2, Cs), x)
-                _small(dy, wd, dz, B, H, W, ldy, Cs, Cin, Cin, flop, stats=part, ep_mode=2,
-                       ez=(x, mean, invstd, gamma, beta, act))
-            elif not up2 and _mid_halo_route(B, H, W, ldy, Cs, 3, 3, 1, 1, with_stats=True, prec=ctx.prec):
-                # 64/68-channel layer: the same fused data gradient on the halo-tile kernel (ep_mode 2)
-                rows = lib().raw("vmtl_conv3x3_halo_stat_rows")(B, H, W)
-                part = _empty((rows, 2, Cs), x)
-                _mid_halo(dy, wd, dz, B, H, W, ldy, Cs, Cin, Cin, flop, stats=part, ep_mode=2,
-                          ez=(x, mean, invstd, gamma, beta, act))
+            part = _empty((plan.stats_rows, 2, Cs), x)
+            ez = (x, mean, invstd, gamma, beta, act)
+            if plan.route == "small":
+                _small(dy, wd, dz, B, H, W, ldy, Cs, C, C, flop, stats=part, ep_mode=2, ez=ez)
+            elif plan.route == "mid_halo":
+                _mid_halo(dy, wd, dz, B, H, W, ldy, Cs, C, C, flop, stats=part, ep_mode=2, ez=ez)
             else:
-                rows = lib().raw("vmtl_conv2d_stats_rows")(B, H, W, Cs)
-                part = _empty((rows, 2, Cs), x)
                 _kp("vmtl_conv2d_bnbwd", ctx.prec, _flop=flop, _xflop=xflop, x=dy, wp=wd, y=dz, stats=part, ez_x=x, ez_mean=mean,
-                   ez_invstd=invstd, ez_gamma=gamma, ez_beta=beta, ez_act=act, **geo)
-            _k("vmtl_bn_bwd_finalize", partial=part, nblk=rows, M=M, C=C, Cs=Cs, sum_dz=dbeta, sum_dzx=dgamma, mean=None,
-               invstd=None, gamma=None, training=1 if training else 0, coef_a=None, coef_b=None, coef_c=None)
+                    ez_invstd=invstd, ez_gamma=gamma, ez_beta=beta, ez_act=act, Nw=C, Cout=C, **geo)
+            _k("vmtl_bn_bwd_finalize", partial=part, nblk=plan.stats_rows, M=M, C=C, Cs=Cs, sum_dz=dbeta, sum_dzx=dgamma,
+               mean=None, invstd=None, gamma=None, training=1 if training else 0, coef_a=None, coef_b=None, coef_c=None)
             if dx is not None:
                 _k("vmtl_bn_bwd_apply", x=x, dz=dz, mean=mean, invstd=invstd, gamma=gamma, sum_dz=dbeta, sum_dzx=dgamma,
                    dx=dx, M=M, C=C, Cs=Cs, training=1 if training else 0)
-        else:  # split-K data gradient (tile-starved layers): unfused BatchNorm backward
+        else:  # split-K data gradient (tile-starved layers) or VMTL_BNBWD_FUSE=0: unfused BatchNorm backward
             da = _empty(x.shape, x)
-            _conv_launch(dy, wd, None, da, None, geo["B"], geo["H"], geo["W"], geo["Cs"], geo["Ho"], geo["Wo"], geo["ldy"],
-                         geo["Nw"], geo["Cout"], geo["KH"], geo["KW"], geo["stride"], geo["pad"], cin=Cout, algo_flop=flop,
-                         prec=ctx.prec)
+            _conv_launch(dy, wd, None, da, Nw=C, Cout=C, cin=Cout, algo_flop=flop, prec=ctx.prec, plan=plan, **geo)
             part = _empty((_reduce_rows(M), 2, Cs), x)
             _k("vmtl_bn_bwd", x=x, dy=da, mean=mean, invstd=invstd, gamma=gamma, beta=beta, mul=None, dmul=None,
                partial=part, sum_dz=dbeta, sum_dzx=dgamma, dx=dx if dx is not None else _empty(x.shape, x), M=M, C=C, Cs=Cs,
                act=act, training=1 if training else 0)
         dskip = None
         if up2 and skip is not None and ctx.needs_input_grad[9]:
-            C1, C1s = Cin - C, skip.shape[3]
-            wds = packs.get(weight, "up2_dskip", (1, C1, 9, Cout, ldy, 0, 9, 1, Cin * 9, 1), offset=C * 9)
-            dskip = _empty(skip.shape, x)
-            _conv_launch(dy, wds, None, dskip, None, B, Hd, Wd, ldy, Hd, Wd, C1s, C1, C1, 3, 3, 1, 1, cin=Cout, prec=ctx.prec)
+            dskip = _up2_dskip(dy, weight, skip, C, ctx.prec)
         # ---- weight gradient (side stream when it goes to an arena slot)
         dw = _empty(weight.shape, x) if sw is None else sw
         with side.branch(sw is not None, B * Hd * Wd, fork, dy, a, skip):
             if up2:
-                slabs, ns = _wgrad(dy, a, B, Hd, Wd, ldy, H, W, Cs, C, 4, 4, 2, 1, 2.0 * B * Hd * Wd * Cout * 9 * C,
-                                   xflop=2.0 * M * C * 16 * Cout, prec=ctx.prec)
-                _k("vmtl_unpack_up2", slabs=slabs, grad=dw, Cout=Cout, Cos=ldy, C0=C, Cin=Cin, nslabs=ns)
-                if skip is not None:
-                    C1, C1s = Cin - C, skip.shape[3]
-                    slabs, ns = _wgrad(skip, dy, B, Hd, Wd, C1s, Hd, Wd, ldy, Cout, 3, 3, 1, 1,
-                                       2.0 * B * Hd * Wd * Cout * 9 * C1, prec=ctx.prec)
-                    unpack(slabs, None, 1, Cout, 9, C1, C1s, 0, Cin * 9, 1, 9, out=dw.view(-1)[C * 9:], nslabs=ns)
+                _up2_wgrad(dy, a, skip, weight, C, dw, ctx.prec)
             else:
                 slabs, ns = _wgrad(a, dy, B, H, W, Cs, H, W, ldy, Cout, 3, 3, 1, 1, 2.0 * M * Cout * 9 * Cin, prec=ctx.prec)
                 unpack(slabs, weight.shape, 1, Cout, 9, Cin, Cs, 0, Cin * 9, 1, 9, out=dw, nslabs=ns)
@@ -1383,36 +1330,42 @@ def bn_act_conv(x, stats, rpb, bn, C, act, weight, skip=None, up2=False, want_st
     bn is the nn.BatchNorm2d parameter container of x's layer, C its logical channel count."""
     if bn.momentum is None:
         raise NotImplementedError("BatchNorm2d(momentum=None) (cumulative moving average) is not implemented")
-    cfg = (C, bn.training, float(bn.momentum), bn.eps, act, bool(up2), bool(want_stats))
+    B, H, W, Cs = x.shape
+    Cout, prec = weight.shape[0], conv_prec_code()
+    if up2:
+        plan = up2_plan(B, H, W, Cs, 0 if skip is None else skip.shape[3], ceil4(Cout), Cout, prec, want_stats)
+    else:
+        plan = conv_plan(B, H, W, Cs, H, W, ceil4(Cout), 3, 3, 1, 1, prec=prec, epilogue="stats" if want_stats else None)
+    cfg = (C, bn.training, float(bn.momentum), bn.eps, act, bool(up2), plan)
     y, ostats = _BNActConv.apply(x, stats, rpb, bn.weight, bn.bias, bn.running_mean, bn.running_var,
                                  bn.num_batches_tracked, weight, skip, cfg)
-    orpb = 0
-    if ostats is not None:
-        B, H, W, _ = x.shape
-        ldy = y.shape[3]
-        orpb = (up2_stats_geometry(B, H, W, x.shape[3], 0 if skip is None else skip.shape[3], ldy, weight.shape[0])[1] if up2
-                else conv_stats_geometry(B, H, W, x.shape[3], ldy, 3, 3, 1, 1)[1])
-    return y, ostats, orpb
+    return y, ostats, plan.rpb
 
 
 def up2_conv(xl, C0, skip, weight, want_stats=False):
     """(y, stats) = conv3x3(cat[nearest_x2(xl), skip]); C0 = logical channels of xl; stats may be None.  Like conv2d's, the
-    statistics rows carry the pixels each covers (`_vmtl_rpb`: up2_stats_geometry's row block, not conv_pick_tile's)."""
-    y, stats = _Up2Conv.apply(xl, skip, weight, C0, want_stats)
+    statistics rows carry the pixels each covers (`_vmtl_rpb`: the UP2 plan's row block, not conv_pick_tile's)."""
+    B, H2, W2, C0s = xl.shape
+    Cout = weight.shape[0]
+    plan = up2_plan(B, H2, W2, C0s, 0 if skip is None else skip.shape[3], ceil4(Cout), Cout, conv_prec_code(), want_stats)
+    y, stats = _Up2Conv.apply(xl, skip, weight, C0, plan)
     if stats is not None:
-        stats._vmtl_rpb = up2_stats_geometry(xl.shape[0], xl.shape[1], xl.shape[2], xl.shape[3],
-                                             0 if skip is None else skip.shape[3], y.shape[3], weight.shape[0])[1]
+        stats._vmtl_rpb = plan.rpb
     return y, stats
 
 
 def conv2d(x, weight, bias=None, stride=1, pad=0, want_stats=False, zero_bias_grad=False, stitch=None):
     """zero_bias_grad: the caller normalises y with a TRAIN-mode BatchNorm next, which makes dL/dbias exactly zero.
     stitch = (CrossStitchLayer weights, task index): y = conv(w[task, task, (c)] * x), the scale folded into the operand."""
-    y, stats = _Conv2d.apply(x, weight, bias, stride, pad, want_stats, zero_bias_grad,
+    B, H, W, Cs = x.shape
+    Cout, _, KH, KW = weight.shape
+    Ho, Wo = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
+    plan = conv_plan(B, H, W, Cs, Ho, Wo, ceil4(Cout), KH, KW, stride, pad, prec=conv_prec_code(),
+                     epilogue="stats" if want_stats else None)
+    y, stats = _Conv2d.apply(x, weight, bias, stride, pad, plan, zero_bias_grad,
                              None if stitch is None else stitch[0], 0 if stitch is None else int(stitch[1]))
     if stats is not None:  # pixels per statistics row, for whoever finalizes them (bn_act)
-        stats._vmtl_rpb = conv_stats_geometry(y.shape[0], y.shape[1], y.shape[2], x.shape[3], y.shape[3], weight.shape[2],
-                                              weight.shape[3], stride, pad)[1]
+        stats._vmtl_rpb = plan.rpb
     return (y, stats) if want_stats else y
 
 
@@ -1431,7 +1384,7 @@ class _ConvT2x2(torch.autograd.Function):
         ldy = ceil4(Cout)
         wp = packs.get(weight, "ct_fwd", (4, Cout, 1, Cin, Cs, 1, 4, 0, Cout * 4, 0))
         y = _empty((B, 2 * H, 2 * W, ldy), x)
-        _conv_launch(x, wp, bias, y, None, B, H, W, Cs, H, W, ldy, 4 * Cout, Cout, 1, 1, 1, 0, shuffle=1, cin=Cin)
+        _conv_launch(x, wp, bias, y, B, H, W, Cs, H, W, ldy, 4 * Cout, Cout, 1, 1, 1, 0, shuffle=1, cin=Cin)
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
         ctx.slots = (_slot(weight), _slot(bias))
@@ -1449,7 +1402,7 @@ class _ConvT2x2(torch.autograd.Function):
         if ctx.needs_input_grad[0]:  # a 2x2 / stride-2 conv over dy
             wd = packs.get(weight, "ct_bwd", (1, Cin, 4, Cout, ldy, 0, Cout * 4, 1, 4, 0))
             dx = _empty((B, H, W, Cs), x)
-            _conv_launch(dy, wd, None, dx, None, B, 2 * H, 2 * W, ldy, H, W, Cs, Cin, Cin, 2, 2, 2, 0, cin=Cout)
+            _conv_launch(dy, wd, None, dx, B, 2 * H, 2 * W, ldy, H, W, Cs, Cin, Cin, 2, 2, 2, 0, cin=Cout)
         if ctx.needs_input_grad[1]:  # weight gradient of that same conv, with x in the role of its output gradient
             with side.branch(ctx.slots[0] is not None, B * H * W, fork, x, dy):
                 slabs, ns = _wgrad(dy, x, B, 2 * H, 2 * W, ldy, H, W, Cs, Cin, 2, 2, 2, 0,
@@ -2567,7 +2520,7 @@ class _DualHead(torch.autograd.Function):
         _copy_vec(bb, bias[Ca:], Cb)
         y = _empty((B, H, W, ldy), x)
         prec = ctx.prec = conv_prec_code()
-        _conv_launch(x, wp, bias, y, None, B, H, W, Cs, H, W, ldy, N, N, KH, KW, 1, pad, cin=Cin, prec=prec)
+        _conv_launch(x, wp, bias, y, B, H, W, Cs, H, W, ldy, N, N, KH, KW, 1, pad, cin=Cin, prec=prec)
         oa, ob = _empty((B, Ca, H, W), x), _empty((B, Cb, H, W), x)
         yf = y.view(-1)
         _k("vmtl_nhwc_to_nchw", x=yf, y=oa, B=B, C=Ca, HW=H * W, Cs=ldy)
@@ -2602,7 +2555,7 @@ class _DualHead(torch.autograd.Function):
             _k("vmtl_pack_weights_slice", src=wb, dst=wd.view(-1)[Ca:], R0=Cin, T=KK, C=Cb, group=ldy, sr0=KK, st=1,
                sc=Cin * KK, flip=1)
             dx = _empty((B, H, W, Cs), x)
-            _conv_launch(dy, wd, None, dx, None, B, H, W, ldy, H, W, Cs, Cin, Cin, KH, KW, 1, KH - 1 - pad, cin=N,
+            _conv_launch(dy, wd, None, dx, B, H, W, ldy, H, W, Cs, Cin, Cin, KH, KW, 1, KH - 1 - pad, cin=N,
                          prec=ctx.prec)
         with side.branch(all(s is not None for s in ctx.slots), B * H * W, fork, x, dy):
             slabs, ns = _wgrad(x, dy, B, H, W, Cs, H, W, ldy, N, KH, KW, 1, pad, 2.0 * B * H * W * N * KK * Cin,
