@@ -1,5 +1,5 @@
-"""Test-only helper (not a conftest, no GPU needed to import): a census of what one eager training step of a production
-configuration calls.
+"""Test-only helper (not a conftest, no GPU needed to import): a census of what one eager step of a production
+configuration calls: the training step, or (stage "val" / "predict") the forward-only steps GraphedEval captures.
 
 census(name) builds the model with build_model exactly as the other tests do, runs forward + training_step + backward on
 oracle.losses.synthetic_batch, and records
@@ -195,29 +195,51 @@ class Census:
         return "\n".join(lines)
 
 
-def census(kind, B, H, W, C=19, channel_wise=None, dev="cuda:0", name=None):
-    """One eager training step of this configuration under a Recorder -> Census."""
+STAGES = ("train", "val", "predict")
+
+
+def census(kind, B, H, W, C=19, channel_wise=None, dev="cuda:0", name=None, stage="train"):
+    """One eager step of this configuration under a Recorder -> Census.  stage "train": training_step + backward;
+    "val": validation_step in train mode under no_grad (the reference validates that way: batch statistics, the running
+    buffers move); "predict": predict_step in eval mode under no_grad, targets in the batch (losses and metrics run)."""
     from oracle.losses import synthetic_batch
     from vision_mtl_amd.lit_module import MTLModule
 
-    model = build(kind, C, channel_wise).to(dev).train()
+    if stage not in STAGES:
+        raise ValueError(f"census: stage must be one of {STAGES}, got {stage!r}")
+    model = build(kind, C, channel_wise).to(dev).train(stage != "predict")
     module = MTLModule(model, num_classes=C, device=str(dev))
+    module.train(stage != "predict")
     batch = {k: v.to(dev) for k, v in synthetic_batch(B, H, W, C, seed=11).items()}
     with Recorder() as rec:
-        loss = module.training_step(batch, 0)
-        loss.backward()
+        if stage == "train":
+            loss = module.training_step(batch, 0)
+            loss.backward()
+        else:
+            with torch.no_grad():
+                if stage == "val":
+                    loss = module.validation_step(batch, 0)
+                else:
+                    module.predict_step(batch)
+                    loss = module.step_outputs["predict"]["loss"][-1]
         torch.cuda.synchronize()
     assert torch.isfinite(loss).item()
     del module, model, batch, loss
     torch.cuda.empty_cache()
-    return Census(name or f"{kind} {B}x{H}x{W}", rec.nodes, rec.launches)
+    return Census(name or f"{kind} {B}x{H}x{W}" + ("" if stage == "train" else f" [{stage}]"), rec.nodes, rec.launches)
 
 
 @functools.lru_cache(maxsize=None)
-def production_census(name):
-    """The census of one CONFIGS entry, once per session."""
+def _production_census(name, stage):
     kind, B, H, W, C, cw = CONFIGS[name]
-    return census(kind, B, H, W, C=C, channel_wise=cw, name=name)
+    return census(kind, B, H, W, C=C, channel_wise=cw, name=name if stage == "train" else f"{name} [{stage}]", stage=stage)
+
+
+def production_census(name, stage="train"):
+    """The census of one CONFIGS entry and stage, once per session."""
+    if stage not in STAGES:
+        raise ValueError(f"production_census: stage must be one of {STAGES}, got {stage!r}")
+    return _production_census(name, stage)
 
 
 @contextlib.contextmanager

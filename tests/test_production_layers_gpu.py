@@ -151,6 +151,25 @@ class Checker:
                              + (f", fp32 CPU restatement {e32:.2e})" if e32 is not None else ")"))
 
 
+def _check_buffers(chk, label, m, spec_training, rm0, rv0, ref_rm, ref_rv, rm_key, rv_key, stage):
+    """the running buffers of one replayed BatchNorm after the call.  Training replays (stage None) and the "val" stage
+    (train mode under no_grad): against the fp64 restatement at BAR_STATS, num_batches_tracked moved once in train mode.
+    The "predict" stage: bitwise what was uploaded, num_batches_tracked still 0."""
+    if stage is not None and spec_training != (stage == "val"):
+        chk.failures.append(f"{chk.label}: BatchNorm {label} is in {'train' if spec_training else 'eval'} mode in a {stage} step")
+    if stage == "predict":
+        if not (torch.equal(m.running_mean.cpu(), rm0) and torch.equal(m.running_var.cpu(), rv0)):
+            chk.failures.append(f"{chk.label}: the running buffers of {label} moved in a predict step")
+        if int(m.num_batches_tracked) != 0:
+            chk.failures.append(f"{chk.label}: num_batches_tracked of {label} moved in a predict step")
+        return
+    sfx = f"[{label}]" if label else ""
+    chk(f"running_mean{sfx}", m.running_mean.cpu(), ref_rm, BAR_STATS, rm_key)
+    chk(f"running_var{sfx}", m.running_var.cpu(), ref_rv, BAR_STATS, rv_key)
+    if int(m.num_batches_tracked) != (1 if spec_training else 0):
+        chk.failures.append(f"{chk.label}: num_batches_tracked of {label or 'the BatchNorm'}")
+
+
 def _check_stats(chk, what, stats, rpb, y64, C, sets, ref_key):
     B, _, H, W = y64.shape
     mean, var = _merge(stats, rpb, B * H * W, C)
@@ -191,14 +210,16 @@ def _conv2d_ref(a, x, w, bias, st, dy, dtype):
         s = sr[task, task]
         xin = xr * (s.view(1, -1, 1, 1) if s.dim() else s)
     y = F.conv2d(xin, wr, br, a["stride"], a["pad"])
-    y.backward(dy.to(dtype))
+    if dy is not None:  # None: a forward-only replay
+        y.backward(dy.to(dtype))
     yd = y.detach()
     return {("y",): yd, ("mean",): yd.mean((0, 2, 3)), ("var",): yd.var((0, 2, 3), unbiased=False),
             ("dx",): None if xr.grad is None else xr.grad, ("dw",): wr.grad, ("db",): None if br is None else br.grad,
             ("dst",): None if sr is None else sr.grad}
 
 
-def _replay_conv2d(sig, dev):
+def _replay_conv2d(sig, dev, stage=None):
+    """stage None: forward + backward of a training signature; "val" / "predict": forward only under no_grad"""
     from vision_mtl_amd import ops
 
     g = torch.Generator().manual_seed(zlib.crc32(repr(sig).encode()))
@@ -208,12 +229,14 @@ def _replay_conv2d(sig, dev):
     wd = w.to(dev).requires_grad_(True)
     bd = None if bias is None else bias.to(dev).requires_grad_(True)
     sd = None if st is None else st.to(dev).requires_grad_(True)
-    with recording() as rec:
+    with recording() as rec, torch.set_grad_enabled(stage is None):
         out = ops.conv2d(xd, wd, bd, a["stride"], a["pad"], want_stats=a["want_stats"], zero_bias_grad=a["zero_bias_grad"],
                          stitch=None if sd is None else (sd, a["stitch"][1]))
         y, stats = out if a["want_stats"] else (out, None)
-        dy = torch.randn(y.shape[0], Cout, y.shape[1], y.shape[2], generator=g)
-        y.backward(_nhwc(dy, dev))
+        dy = None
+        if stage is None:
+            dy = torch.randn(y.shape[0], Cout, y.shape[1], y.shape[2], generator=g)
+            y.backward(_nhwc(dy, dev))
         torch.cuda.synchronize()
     ref = _conv2d_ref(a, x, w, bias, st, dy, torch.float64)
     chk = Checker(fmt_sig(sig), lambda: _conv2d_ref(a, x, w, bias, st, dy, torch.float32))
@@ -221,6 +244,10 @@ def _replay_conv2d(sig, dev):
     if stats is not None:
         norm = [c for c in range(Cout) if c not in big]
         _check_stats(chk, "stats", stats, stats._vmtl_rpb, ref[("y",)], Cout, [("ordinary", norm), ("large-mean", big)], ())
+    if stage is not None:
+        if stage == "predict" and stats is not None:
+            chk.failures.append(f"{chk.label}: a predict step's conv returned statistics rows")
+        return chk, rec
     if a["x"][2]:
         chk("dx", _nchw(xd.grad, x.shape[1]), ref[("dx",)], BAR_GRAD, ("dx",))
     chk("dw", wd.grad.cpu(), ref[("dw",)], BAR_GRAD, ("dw",))
@@ -286,7 +313,8 @@ def _bnconv_ref(a, op, x, skip, bn, w, dy, dtype):
     if sk is not None:
         h = torch.cat([h, sk], 1)
     y = F.conv2d(h, wr, None, 1, 1)
-    y.backward(dy.to(dtype))
+    if dy is not None:  # None: a forward-only replay
+        y.backward(dy.to(dtype))
     outs[("y",)] = yd = y.detach()
     outs[("mean",)], outs[("var",)] = yd.mean((0, 2, 3)), yd.var((0, 2, 3), unbiased=False)
     outs[("dx",)] = xr.grad
@@ -298,7 +326,8 @@ def _bnconv_ref(a, op, x, skip, bn, w, dy, dtype):
     return outs
 
 
-def _replay_bnconv(sig, dev, op):
+def _replay_bnconv(sig, dev, op, stage=None):
+    """stage None: forward + backward of a training signature; "val" / "predict": forward only under no_grad"""
     from vision_mtl_amd import ops
 
     g = torch.Generator().manual_seed(zlib.crc32(repr(sig).encode()))
@@ -328,7 +357,7 @@ def _replay_bnconv(sig, dev, op):
     wd = w.to(dev).requires_grad_(True)
     skd = None if skip is None else _nhwc(skip, dev).requires_grad_(a["skip"][2])
     Hy, Wy = (2 * H, 2 * W) if (op == "up2_conv" or a.get("up2")) else (H, W)
-    dy = torch.randn(B, Cout, Hy, Wy, generator=g)
+    dy = torch.randn(B, Cout, Hy, Wy, generator=g) if stage is None else None
     bnd = None
     if op == "bn_act_conv":
         bnd = torch.nn.BatchNorm2d(C, eps=eps, momentum=momentum).to(dev).train(training)
@@ -340,20 +369,27 @@ def _replay_bnconv(sig, dev, op):
         st_in, rpb_in = None, a["rpb"]
         if a["stats"] is not None:
             st_in = _stats_rows(x, a["stats"][1][0], rpb_in).to(dev)
-    with recording() as rec:
+    with recording() as rec, torch.set_grad_enabled(stage is None):
         if op == "bn_act_conv":
             y, stats, orpb = ops.bn_act_conv(xd, st_in, rpb_in, bnd, C, a["act"], wd, skip=skd, up2=a["up2"],
                                              want_stats=a["want_stats"])
         else:
             y, stats = ops.up2_conv(xd, C, skd, wd, want_stats=a["want_stats"])
             orpb = None if stats is None else stats._vmtl_rpb
-        y.backward(_nhwc(dy, dev))
+        if stage is None:
+            y.backward(_nhwc(dy, dev))
         torch.cuda.synchronize()
     ref = _bnconv_ref(a, op, x, skip, bn, w, dy, torch.float64)
     chk = Checker(fmt_sig(sig), lambda: _bnconv_ref(a, op, x, skip, bn, w, dy, torch.float32))
     chk("y", _nchw(y, Cout), ref[("y",)], BAR_OUT, ("y",))
     if stats is not None:
         _check_stats(chk, "stats", stats, orpb, ref[("y",)], Cout, [("all", list(range(Cout)))], ())
+    if stage is not None:
+        if stage == "predict" and stats is not None:
+            chk.failures.append(f"{chk.label}: a predict step's conv returned statistics rows")
+        if op == "bn_act_conv":
+            _check_buffers(chk, "", bnd, training, rm, rv, ref[("rm",)], ref[("rv",)], ("rm",), ("rv",), stage)
+        return chk, rec
     if a[xkey][2]:
         dx = _nchw(xd.grad, C)
         chk("dx", dx, ref[("dx",)], BAR_GRAD, ("dx",))
@@ -425,10 +461,11 @@ class Case:
         self.acts, self.ws, self.bns, self.grad, self.zero, self.stats_in = {}, {}, {}, set(), set(), {}
 
 
-def _run_generic(sig, dev, make, ref_fn, dev_fn, identity=False, used=None):
+def _run_generic(sig, dev, make, ref_fn, dev_fn, identity=False, used=None, stage=None):
     """make(a, g) -> Case; ref_fn(a, case, T, bns) -> {output: NCHW tensor}; dev_fn(a, case, T, bns) -> ({output: (tensor,
     'nhwc' | 'nchw', C)}, [(output, stats, rpb)]).  Forward, backward with seeded dy per output, then every output, gradient,
-    running buffer against fp64.  used: the outputs that receive a gradient (default: all).  The statistics rows a node
+    running buffer against fp64.  used: the outputs that receive a gradient (default: all).  stage "val" / "predict": a
+    forward-only replay under no_grad (no dy, no gradient; the buffers as _check_buffers holds them).  The statistics rows a node
     emits are merged and held against the moments of the output the node wrote (fp64 over the HIP output; bar max(1e-5,
     4 x the error of fp32 torch moments of it)): the forward error of the output has its own check."""
     import contextlib
@@ -444,13 +481,14 @@ def _run_generic(sig, dev, make, ref_fn, dev_fn, identity=False, used=None):
     def reference(dtype):
         T = {k: v.to(dtype).requires_grad_(k in case.grad) for k, v in list(case.acts.items()) + list(case.ws.items())}
         bns = {k: _RefBN(v, dtype) for k, v in case.bns.items()}
-        with ctx():
+        with ctx(), torch.set_grad_enabled(stage is None):
             outs = ref_fn(a, case, T, bns)
         outs = {k: y for k, y in outs.items() if used is None or k in used}
-        for k, y in outs.items():
-            if k not in dys:
-                dys[k] = torch.randn(y.shape, generator=g)
-        torch.autograd.backward([outs[k] for k in outs], [dys[k].to(dtype) for k in outs])
+        if stage is None:
+            for k, y in outs.items():
+                if k not in dys:
+                    dys[k] = torch.randn(y.shape, generator=g)
+            torch.autograd.backward([outs[k] for k in outs], [dys[k].to(dtype) for k in outs])
         res = {("y", k): y.detach() for k, y in outs.items()}
         for k, y in outs.items():
             res[("mean", k)], res[("var", k)] = y.detach().mean((0, 2, 3)), y.detach().var((0, 2, 3), unbiased=False)
@@ -467,13 +505,14 @@ def _run_generic(sig, dev, make, ref_fn, dev_fn, identity=False, used=None):
     bnd = {k: _dev_bn(v, dev) for k, v in case.bns.items()}
     for k, (rows, rpb) in case.stats_in.items():
         Td["stats:" + k] = _stats_rows(case.acts[k], rows, rpb).to(dev)
-    with recording() as rec:
+    with recording() as rec, torch.set_grad_enabled(stage is None):
         with ctx():
             outs, stats = dev_fn(a, case, Td, bnd)
             outs = {k: v for k, v in outs.items() if used is None or k in used}
-            ys = [t for t, _, _ in outs.values()]
-            gs = [(_nhwc(dys[k], dev) if lay == "nhwc" else dys[k].to(dev)) for k, (_, lay, _) in outs.items()]
-            torch.autograd.backward(ys, gs)
+            if stage is None:
+                ys = [t for t, _, _ in outs.values()]
+                gs = [(_nhwc(dys[k], dev) if lay == "nhwc" else dys[k].to(dev)) for k, (_, lay, _) in outs.items()]
+                torch.autograd.backward(ys, gs)
         torch.cuda.synchronize()
     chk = Checker(fmt_sig(sig), lambda: reference(torch.float32))
     for k, (t, lay, C) in outs.items():
@@ -490,6 +529,13 @@ def _run_generic(sig, dev, make, ref_fn, dev_fn, identity=False, used=None):
             chk.worst[f"stats {what}"] = max(chk.worst.get(f"stats {what}", 0.0), err)
             if err > max(BAR_STATS, 4 * e32):
                 chk.failures.append(f"{chk.label} stats {what}[{k}]: {err:.2e} of the maximum (fp32 torch moments {e32:.2e})")
+    if stage is not None:
+        if stage == "predict" and stats:
+            chk.failures.append(f"{chk.label}: a predict step's node returned statistics rows")
+        for k, m in bnd.items():
+            spec = case.bns[k]
+            _check_buffers(chk, k, m, spec[1], spec[6], spec[7], ref[("rm", k)], ref[("rv", k)], ("rm", k), ("rv", k), stage)
+        return chk, rec
     for k in case.zero:
         if float(Td[k].grad.abs().max()) != 0.0:
             chk.failures.append(f"{chk.label}: {k} feeds a train-mode BatchNorm, its gradient must be exactly zero")
@@ -948,24 +994,28 @@ IDENTITY_REPLAYED = tuple(k for k, v in GENERIC.items() if v[3])
 
 
 @functools.lru_cache(maxsize=None)
-def _replay(sig):
+def _replay(sig, stage=None):
+    """stage None: the training replay (forward + backward).  "val" / "predict": the forward-only replay of a signature
+    of that stage's census, under no_grad and with the activations as they are (a forward value is continuous in its
+    inputs: no node needs identity activations)."""
     dev = torch.device("cuda:0")
     if sig[0] == "conv2d":
-        chk, rec = _replay_conv2d(sig, dev)
+        chk, rec = _replay_conv2d(sig, dev, stage)
     elif sig[0] in GENERIC:
         make, ref_fn, dev_fn, identity = GENERIC[sig[0]]
-        chk, rec = _run_generic(sig, dev, make, ref_fn, dev_fn, identity)
-        if sig_args(sig).get("return_act"):  # the activation handed back may also receive no gradient at all
+        identity = identity and stage is None
+        chk, rec = _run_generic(sig, dev, make, ref_fn, dev_fn, identity, stage=stage)
+        if stage is None and sig_args(sig).get("return_act"):  # the activation handed back may also receive no gradient at all
             chk2, rec2 = _run_generic(sig, dev, make, ref_fn, dev_fn, identity, used=("y",))
             chk.failures += chk2.failures
             chk.relaxed += chk2.relaxed
             rec.launches += rec2.launches
             chk2.ref32_fn = chk2._ref32 = None
     else:
-        chk, rec = _replay_bnconv(sig, dev, sig[0])
+        chk, rec = _replay_bnconv(sig, dev, sig[0], stage)
     chk.ref32_fn = chk._ref32 = None  # the cache keeps the verdict, not the tensors
     torch.cuda.empty_cache()
-    norm = _no_act if sig[0] in IDENTITY_REPLAYED else (lambda k: k)
+    norm = _no_act if sig[0] in IDENTITY_REPLAYED and stage is None else (lambda k: k)
     return chk, set((n, norm(k)) for _, n, k, _ in rec.launches)
 
 

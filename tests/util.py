@@ -132,16 +132,34 @@ def assert_grads_tight(named_hip, g64, g32, tol=1e-4, factor=4.0):
     return worst
 
 
-def nontrivial_bn_affine(model, seed=5):
+def nontrivial_bn_affine(model, seed=5, scale=0.1):
     """BatchNorm affine parameters (1-D, all 0 or all 1 at construction) moved off their initial values, in place."""
     g = torch.Generator().manual_seed(seed)
     with torch.no_grad():
         for n, p in model.named_parameters():
             if p.dim() == 1 and p.numel() > 1 and float(p.detach().abs().max()) in (0.0, 1.0):
-                p.add_(torch.randn(p.shape, generator=g) * 0.1)
+                p.add_(torch.randn(p.shape, generator=g) * scale)
 
 
 def worst_of_runs(g64, runs):
     """per tensor, the run (dict of gradients) whose max-abs error against the fp64 gradient is largest"""
     err = lambda g, k: float((g[k].double() - g64[k].double()).abs().max())
     return {k: max(runs, key=lambda g: err(g, k))[k] for k, v in g64.items() if v is not None}
+
+
+def _metrics_cpu(pred, target, C, beta=1.0):
+    """torchmetrics 0.7.3 definitions (package not installable offline: restated from its documentation).
+    Accuracy(average="micro"), JaccardIndex(num_classes=C) = mean over classes of tp/(tp+fp+fn) with absent_score 0,
+    FBetaScore(average="weighted", mdmc_average="global") = support-weighted mean of the per-class F-beta."""
+    pred, target = pred.reshape(-1), target.reshape(-1)
+    cm = torch.zeros(C, C, dtype=torch.int64)
+    cm.index_put_((target, pred), torch.ones_like(target), accumulate=True)
+    tp = cm.diag().double()
+    fn, fp = cm.sum(1).double() - tp, cm.sum(0).double() - tp
+    acc = tp.sum() / cm.sum()
+    union = tp + fp + fn
+    jac = torch.where(union > 0, tp / union.clamp_min(1), torch.zeros_like(tp)).mean()
+    den = (1 + beta ** 2) * tp + beta ** 2 * fn + fp
+    f = torch.where(den > 0, (1 + beta ** 2) * tp / den.clamp_min(1), torch.zeros_like(tp))
+    support = cm.sum(1).double()
+    return cm, float(acc), float(jac), float((f * support).sum() / support.sum())
