@@ -416,6 +416,22 @@ int vmtl_hw_reduce_parts(int B, int HW, int Cs);
 int vmtl_hw_reduce(const float* x, const float* y, float* part, int B, int HW, int Cs, void* stream);
 int vmtl_channel_scale_add(const float* x, const float* s, const float* t, float t_scale, float* y, int B, int HW,
                            int Cs, void* stream);
+/* The same gate in one launch per direction (timm SqueezeExcite.forward, utils/model_utils.py:25-34, on the encoder of
+ * models/basic_model.py:17-28): one workgroup per image reduces the map and walks both weight matrices in the torch
+ * (R, C, 1, 1) / (C, R, 1, 1) layout.  Cs = ceil4(C), Rs = ceil4(R); every [B][Cs] / [B][Rs] output has zero pad columns.
+ * vmtl_se_gate_supported: the launches ops.squeeze_excite takes for the shape: bit 0 - vmtl_se_gate_bwd and vmtl_se_wgrad,
+ *   bit 1 - vmtl_se_gate_fwd (small weights only: csrc/fc.hip).  VMTL_SE_FUSED=0: none, 2: all wherever supported.
+ * vmtl_se_gate_fwd: pooled = mean_hw x, z1 = W_r pooled + b_r, h = act1(z1), z2 = W_e h + b_e, g = act2(z2).
+ * vmtl_se_gate_bwd: dg = sum_hw dy * x, dh = (dg * act2'(z2)) W_e, dmean (may be NULL) = (dh * act1'(z1)) W_r.
+ * vmtl_se_wgrad: dW_e, db_e from (dg * act2'(z2), h) and dW_r, db_r from (dh * act1'(z1), pooled), torch layout. */
+int vmtl_se_gate_supported(int B, int C, int R);
+int vmtl_se_gate_fwd(const float* x, const float* wr, const float* br, const float* we, const float* be, float* pooled,
+                     float* z1, float* h, float* z2, float* g, int B, int HW, int C, int R, int act1, int act2,
+                     void* stream);
+int vmtl_se_gate_bwd(const float* dy, const float* x, const float* z1, const float* z2, const float* wr, const float* we,
+                     float* dg, float* dh, float* dmean, int B, int HW, int C, int R, int act1, int act2, void* stream);
+int vmtl_se_wgrad(const float* pooled, const float* h, const float* dg, const float* dh, const float* z1, const float* z2,
+                  float* dwr, float* dbr, float* dwe, float* dbe, int B, int C, int R, int act1, int act2, void* stream);
 /* models/cross_stitch_model.py:32-37 (diagonal of the 2x2 stitch matrix) */
 int vmtl_stitch(const float* x, const float* w, float* y, long long M, int C, int Cs, int wstride, void* stream);
 /* its backward in one sweep: dx (nullable) = w * dy, dw[c] = sum_m x*dy (reduce_all: one scalar);

@@ -146,10 +146,11 @@ struct FcWgP {
   int x_parts, dy_parts, M, K, N, lda, ldn, act;
 };
 
-__global__ __launch_bounds__(256) void fc_wgrad_kernel(FcWgP p) {
+// one workgroup's 8 weight rows (bx: its index along N); shared by fc_wgrad_kernel and se_wgrad_kernel
+__device__ __forceinline__ void fc_wgrad_block(const FcWgP& p, int bx) {
   __shared__ float dz[64][8];
   const int tid = threadIdx.x;
-  const int n0 = blockIdx.x * 8;
+  const int n0 = bx * 8;
   for (int idx = tid; idx < p.M * 8; idx += 256) {
     const int m = idx >> 3, i = idx & 7, n = n0 + i;
     float v = 0.f;
@@ -196,6 +197,8 @@ __global__ __launch_bounds__(256) void fc_wgrad_kernel(FcWgP p) {
     p.db[n0 + tid] = s;
   }
 }
+
+__global__ __launch_bounds__(256) void fc_wgrad_kernel(FcWgP p) { fc_wgrad_block(p, blockIdx.x); }
 
 extern "C" int vmtl_fc_wgrad(const float* x, int x_parts, long long x_part_stride, float x_scale, const float* dyo,
                              int dy_parts, long long dy_part_stride, const float* zo, float* dw, float* db, int M,
@@ -307,5 +310,305 @@ extern "C" int vmtl_channel_scale_add(const float* x, const float* s, const floa
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(channel_scale_add_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, s, t, t_scale,
                      y, HW, Cs, total4);
+  return vmtl_check_launch();
+}
+
+// ------------------------------------------------------------------ squeeze-excite gate: one launch per direction
+// The gate of one image is two GEMVs behind a spatial reduction - a dependent chain that three launches (hw_reduce,
+// fc, fc) spent mostly on launch latency and cold first loads.  Here ONE workgroup owns an image: it reduces the map,
+// keeps the [C] / [R] vectors in LDS and walks both weight matrices in the torch layout, forward as row dot products
+// (K contiguous), backward as weighted column sums (the other index order of the same matrices: no packed transposes).
+// Every sum has a fixed order: no atomics, bit-identical from run to run.
+#define SE_THREADS 1024
+#define SE_MAX_VEC 8192  // floats of LDS for the [Cs] + [Rs] vectors
+
+template <int V>
+__device__ __forceinline__ void se_ld(const float* p, float* o) {
+  if constexpr (V == 4) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(p);
+    o[0] = v[0], o[1] = v[1], o[2] = v[2], o[3] = v[3];
+  } else {
+    o[0] = p[0];
+  }
+}
+template <int V>
+__device__ __forceinline__ void se_st(float* p, const float* o) {
+  if constexpr (V == 4) {
+    *reinterpret_cast<f32x4*>(p) = (f32x4){o[0], o[1], o[2], o[3]};
+  } else {
+    p[0] = o[0];
+  }
+}
+
+// out[c] = sum_{r < rows} a[r][c] * f,  c < cols, a row-major with leading dimension ld (a multiple of V, like cols);
+// MODE 0: f = 1, MODE 1: f = b[r][c], MODE 2: f = wv[r] (an LDS vector).  Threads keep a fixed group of V columns; the
+// SE_THREADS / groups row lanes walk the rows in parallel and are summed through LDS in two fixed-order stages.
+// Ends with a barrier: `out` (LDS) is visible to the whole workgroup on return.
+template <int V, int MODE>
+__device__ __forceinline__ void se_colsum(const float* __restrict__ a, const float* __restrict__ b, const float* wv, int rows,
+                                          int cols, int ld, float* red, float* red2, float* out) {
+  const int tid = threadIdx.x;
+  const int ncg = cols / V;
+  for (int q0 = 0; q0 < ncg; q0 += SE_THREADS) {
+    const int cg = min(ncg - q0, SE_THREADS);
+    const int RP = SE_THREADS / cg;
+    const int ql = tid % cg, rg = tid / cg;
+    float acc[4][V];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int e = 0; e < V; ++e) acc[u][e] = 0.f;
+    if (rg < RP) {
+      const size_t col = (size_t)(q0 + ql) * V;
+      int r = rg;
+      for (; r + 3 * RP < rows; r += 4 * RP) {  // 4 independent rows in flight
+        float v[4][V];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) se_ld<V>(a + (size_t)(r + u * RP) * ld + col, v[u]);
+        if constexpr (MODE == 1) {
+          float w[4][V];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) se_ld<V>(b + (size_t)(r + u * RP) * ld + col, w[u]);
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int e = 0; e < V; ++e) v[u][e] *= w[u][e];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const float f = MODE == 2 ? wv[r + u * RP] : 1.f;
+#pragma unroll
+          for (int e = 0; e < V; ++e) acc[u][e] += MODE == 2 ? v[u][e] * f : v[u][e];
+        }
+      }
+      for (; r < rows; r += RP) {
+        float v[V];
+        se_ld<V>(a + (size_t)r * ld + col, v);
+        if constexpr (MODE == 1) {
+          float w[V];
+          se_ld<V>(b + (size_t)r * ld + col, w);
+#pragma unroll
+          for (int e = 0; e < V; ++e) v[e] *= w[e];
+        }
+        const float f = MODE == 2 ? wv[r] : 1.f;
+#pragma unroll
+        for (int e = 0; e < V; ++e) acc[0][e] += MODE == 2 ? v[e] * f : v[e];
+      }
+#pragma unroll
+      for (int e = 0; e < V; ++e) acc[0][e] += acc[1][e] + (acc[2][e] + acc[3][e]);
+    }
+    se_st<V>(red + (size_t)tid * V, acc[0]);
+    __syncthreads();
+    const int G = min(RP, 8);
+    if (rg < G) {  // stage 1: G lanes per column group, each over every G-th row lane
+      float t[V];
+      se_ld<V>(red + (size_t)(rg * cg + ql) * V, t);
+      for (int g = rg + G; g < RP; g += G) {
+        float v[V];
+        se_ld<V>(red + (size_t)(g * cg + ql) * V, v);
+#pragma unroll
+        for (int e = 0; e < V; ++e) t[e] += v[e];
+      }
+      se_st<V>(red2 + (size_t)(rg * cg + ql) * V, t);
+    }
+    __syncthreads();
+    if (rg == 0) {
+      float t[V];
+      se_ld<V>(red2 + (size_t)ql * V, t);
+      for (int g = 1; g < G; ++g) {
+        float v[V];
+        se_ld<V>(red2 + (size_t)(g * cg + ql) * V, v);
+#pragma unroll
+        for (int e = 0; e < V; ++e) t[e] += v[e];
+      }
+      se_st<V>(out + (size_t)(q0 + ql) * V, t);
+    }
+    __syncthreads();
+  }
+}
+
+// fin(n, sum_k w[n][k] * v[k]) for n < rows; w is [rows][K] with K contiguous (a multiple of V), v an LDS vector.
+// 1 .. 16 lanes share a row (four loads in flight each) and are summed by a fixed butterfly.
+template <int V, class F>
+__device__ __forceinline__ void se_rowdot(const float* __restrict__ w, int rows, int K, const float* v, F fin) {
+  const int tid = threadIdx.x;
+  const int KG = K / V;
+  int LPR = 1;
+  while (LPR < KG && LPR < 16) LPR <<= 1;
+  const int l = tid & (LPR - 1), rl = tid / LPR, RIF = SE_THREADS / LPR;
+  for (int n0 = 0; n0 < rows; n0 += RIF) {
+    const int n = n0 + rl;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    if (n < rows) {
+      const float* wp = w + (size_t)n * K;
+      for (int k = l; k < KG; k += 4 * LPR) {
+        float wv[4][V];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) se_ld<V>(wp + (size_t)min(k + u * LPR, KG - 1) * V, wv[u]);  // clamped: in bounds
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int kk = k + u * LPR;
+          if (kk < KG) {
+#pragma unroll
+            for (int e = 0; e < V; ++e) acc[u] += wv[u][e] * v[kk * V + e];
+          }
+        }
+      }
+    }
+    float s = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+    for (int o = LPR >> 1; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (l == 0 && n < rows) fin(n, s);
+  }
+}
+
+struct SeFwdP {
+  const float *x, *wr, *br, *we, *be;
+  float *pooled, *z1, *h, *z2, *g;
+  int HW, C, R, Cs, Rs, act1, act2, vec_r, vec_e;  // vec_*: 16-byte loads along that weight's rows are legal
+};
+
+__global__ __launch_bounds__(SE_THREADS) void se_gate_fwd_kernel(SeFwdP p) {
+  extern __shared__ float se_vec[];  // [Cs] + [Rs]
+  __shared__ f32x4 red4[SE_THREADS], red24[SE_THREADS];
+  float* red = reinterpret_cast<float*>(red4);
+  float* red2 = reinterpret_cast<float*>(red24);
+  float* vc = se_vec;
+  float* vr = se_vec + p.Cs;
+  const int tid = threadIdx.x, b = blockIdx.x;
+  se_colsum<4, 0>(p.x + (size_t)b * p.HW * p.Cs, nullptr, nullptr, p.HW, p.Cs, p.Cs, red, red2, vc);
+  const float inv = 1.f / (float)p.HW;
+  for (int c = tid; c < p.Cs; c += SE_THREADS) {  // pad channels of x are zero: so is their mean
+    const float m = vc[c] * inv;
+    vc[c] = m;
+    p.pooled[(size_t)b * p.Cs + c] = m;
+  }
+  for (int r = p.R + tid; r < p.Rs; r += SE_THREADS) {
+    vr[r] = 0.f;
+    p.z1[(size_t)b * p.Rs + r] = 0.f;
+    p.h[(size_t)b * p.Rs + r] = 0.f;
+  }
+  for (int c = p.C + tid; c < p.Cs; c += SE_THREADS) {
+    p.z2[(size_t)b * p.Cs + c] = 0.f;
+    p.g[(size_t)b * p.Cs + c] = 0.f;
+  }
+  __syncthreads();
+  auto fin1 = [&](int n, float s) {
+    const float z = s + p.br[n];
+    const float hv = act_fwd(z, p.act1);
+    p.z1[(size_t)b * p.Rs + n] = z;
+    p.h[(size_t)b * p.Rs + n] = hv;
+    vr[n] = hv;
+  };
+  if (p.vec_r) se_rowdot<4>(p.wr, p.R, p.C, vc, fin1);
+  else se_rowdot<1>(p.wr, p.R, p.C, vc, fin1);
+  __syncthreads();
+  auto fin2 = [&](int n, float s) {
+    const float z = s + p.be[n];
+    p.z2[(size_t)b * p.Cs + n] = z;
+    p.g[(size_t)b * p.Cs + n] = act_fwd(z, p.act2);
+  };
+  if (p.vec_e) se_rowdot<4>(p.we, p.C, p.R, vr, fin2);
+  else se_rowdot<1>(p.we, p.C, p.R, vr, fin2);
+}
+
+struct SeBwdP {
+  const float *dy, *x, *z1, *z2, *wr, *we;
+  float *dg, *dh, *dmean;  // dmean nullable: the input needs no gradient
+  int HW, C, R, Cs, Rs, act1, act2, vec_r, vec_e;
+};
+
+__global__ __launch_bounds__(SE_THREADS) void se_gate_bwd_kernel(SeBwdP p) {
+  extern __shared__ float se_vec[];
+  __shared__ f32x4 red4[SE_THREADS], red24[SE_THREADS];
+  float* red = reinterpret_cast<float*>(red4);
+  float* red2 = reinterpret_cast<float*>(red24);
+  float* vc = se_vec;
+  float* vr = se_vec + p.Cs;
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const size_t img = (size_t)b * p.HW * p.Cs;
+  se_colsum<4, 1>(p.dy + img, p.x + img, nullptr, p.HW, p.Cs, p.Cs, red, red2, vc);  // dg = sum_hw dy * x
+  for (int c = tid; c < p.Cs; c += SE_THREADS) {
+    const float d = vc[c];
+    p.dg[(size_t)b * p.Cs + c] = d;
+    vc[c] = c < p.C ? d * act_grad(p.z2[(size_t)b * p.Cs + c], p.act2) : 0.f;
+  }
+  __syncthreads();
+  // dh[r] = sum_c dz2[c] * W_e[c][r]
+  if (p.vec_e) se_colsum<4, 2>(p.we, nullptr, vc, p.C, p.R, p.R, red, red2, vr);
+  else se_colsum<1, 2>(p.we, nullptr, vc, p.C, p.R, p.R, red, red2, vr);
+  for (int r = tid; r < p.Rs; r += SE_THREADS) {
+    const float d = r < p.R ? vr[r] : 0.f;
+    p.dh[(size_t)b * p.Rs + r] = d;
+    vr[r] = r < p.R ? d * act_grad(p.z1[(size_t)b * p.Rs + r], p.act1) : 0.f;
+  }
+  if (p.dmean == nullptr) return;
+  __syncthreads();
+  // dmean[c] = sum_r dz1[r] * W_r[r][c]
+  if (p.vec_r) se_colsum<4, 2>(p.wr, nullptr, vr, p.R, p.C, p.C, red, red2, vc);
+  else se_colsum<1, 2>(p.wr, nullptr, vr, p.R, p.C, p.C, red, red2, vc);
+  for (int c = tid; c < p.Cs; c += SE_THREADS) p.dmean[(size_t)b * p.Cs + c] = c < p.C ? vc[c] : 0.f;
+}
+
+// both weight gradients of one gate: workgroups [0, nbe) take 8 rows of dW_e each, the rest 8 rows of dW_r
+__global__ __launch_bounds__(256) void se_wgrad_kernel(FcWgP pe, FcWgP pr, int nbe) {
+  if ((int)blockIdx.x < nbe) fc_wgrad_block(pe, blockIdx.x);
+  else fc_wgrad_block(pr, blockIdx.x - nbe);
+}
+
+static inline int ceil4i(int c) { return (c + 3) & ~3; }
+static inline bool se_vec_ok(const float* w, int ld) { return (ld & 3) == 0 && ((uintptr_t)w & 15) == 0; }
+static inline bool se_shape_ok(int B, int HW, int C, int R) {
+  return B > 0 && B <= 64 && HW > 0 && C > 0 && R > 0 && ceil4i(C) + ceil4i(R) <= SE_MAX_VEC;
+}
+
+// Which launches ops.squeeze_excite takes for a shape: bit 0 - vmtl_se_gate_bwd + vmtl_se_wgrad, bit 1 - vmtl_se_gate_fwd.
+// One workgroup per image reads both weight matrices itself (B reads of each in all, ~16 dependent rounds of loads
+// per 240 KB on one CU), where the batch-sized GEMM reads them once over N / 16 workgroups.  Measured in the step at
+// bs 32 (profiles/r06_se_gate): the backward launch wins on every production shape (its reduction reads two maps and
+// the GEMM it replaces sums up to 32 partial slices per workgroup), the forward launch wins at C x R = 72 x 24 and
+// 120 x 32 (8-9 us against 17-19) and loses from 480 x 120 up (28 against 26 us, 58 against 26 at 960 x 240).  Its
+// time grows with C x R, the sequence's hardly: the interpolated break-even is near 5e4 weights, the limit sits a
+// factor of three below it.  VMTL_SE_FUSED: 0 - the four-launch sequence, 2 - both fused launches wherever supported.
+#define SE_FWD_MAX_WEIGHTS 16384
+extern "C" int vmtl_se_gate_supported(int B, int C, int R) {
+  static EnvInt e{"VMTL_SE_FUSED", 1};
+  const int mode = env_int(e);
+  if (mode == 0 || !se_shape_ok(B, 1, C, R)) return 0;
+  return 1 | ((mode >= 2 || (long long)C * R <= SE_FWD_MAX_WEIGHTS) ? 2 : 0);
+}
+
+extern "C" int vmtl_se_gate_fwd(const float* x, const float* wr, const float* br, const float* we, const float* be,
+                                float* pooled, float* z1, float* h, float* z2, float* g, int B, int HW, int C, int R,
+                                int act1, int act2, void* stream) {
+  VMTL_ENTER();
+  if (!x || !wr || !br || !we || !be || !pooled || !z1 || !h || !z2 || !g || !se_shape_ok(B, HW, C, R)) return VMTL_ERR_ARG;
+  const int Cs = ceil4i(C), Rs = ceil4i(R);
+  SeFwdP p{x, wr, br, we, be, pooled, z1, h, z2, g, HW, C, R, Cs, Rs, act1, act2, se_vec_ok(wr, C), se_vec_ok(we, R)};
+  hipLaunchKernelGGL(se_gate_fwd_kernel, dim3(B), dim3(SE_THREADS), (Cs + Rs) * sizeof(float), (hipStream_t)stream, p);
+  return vmtl_check_launch();
+}
+
+extern "C" int vmtl_se_gate_bwd(const float* dy, const float* x, const float* z1, const float* z2, const float* wr,
+                                const float* we, float* dg, float* dh, float* dmean, int B, int HW, int C, int R, int act1,
+                                int act2, void* stream) {
+  VMTL_ENTER();
+  if (!dy || !x || !z1 || !z2 || !wr || !we || !dg || !dh || !se_shape_ok(B, HW, C, R)) return VMTL_ERR_ARG;
+  const int Cs = ceil4i(C), Rs = ceil4i(R);
+  SeBwdP p{dy, x, z1, z2, wr, we, dg, dh, dmean, HW, C, R, Cs, Rs, act1, act2, se_vec_ok(wr, C), se_vec_ok(we, R)};
+  hipLaunchKernelGGL(se_gate_bwd_kernel, dim3(B), dim3(SE_THREADS), (Cs + Rs) * sizeof(float), (hipStream_t)stream, p);
+  return vmtl_check_launch();
+}
+
+extern "C" int vmtl_se_wgrad(const float* pooled, const float* h, const float* dg, const float* dh, const float* z1,
+                             const float* z2, float* dwr, float* dbr, float* dwe, float* dbe, int B, int C, int R,
+                             int act1, int act2, void* stream) {
+  VMTL_ENTER();
+  if (!pooled || !h || !dg || !dh || !z1 || !z2 || !dwr || !dwe || B <= 0 || B > 64 || C <= 0 || R <= 0)
+    return VMTL_ERR_ARG;
+  const int Cs = ceil4i(C), Rs = ceil4i(R);
+  FcWgP pe{h, dg, z2, dwe, dbe, 0, 0, 1.f, 1, 1, B, R, C, Rs, Cs, act2};
+  FcWgP pr{pooled, dh, z1, dwr, dbr, 0, 0, 1.f, 1, 1, B, C, R, Cs, Rs, act1};
+  const int nbe = cdiv(C, 8);
+  hipLaunchKernelGGL(se_wgrad_kernel, dim3(nbe + cdiv(R, 8)), dim3(256), 0, (hipStream_t)stream, pe, pr, nbe);
   return vmtl_check_launch();
 }

@@ -2034,12 +2034,15 @@ def channel_scale(x, s):
 # ----------------------------------------------------------------------------- cross-stitch (diagonal scale)
 class _SqueezeExcite(torch.autograd.Function):
     """y = x * act2(W_e act1(W_r mean_hw(x) + b_r) + b_e) - timm SqueezeExcite (ReLU / hard-sigmoid in
-    MobileNetV3), the gate of the `basic` encoder's inverted-residual blocks - as four launches: per-image
-    partial sums over HW, two batch-sized GEMMs (vmtl_fc_fwd: the first one finishes the mean while it loads
-    its operand), one scale pass.  Backward: partial sums of dy*x, two GEMMs with the activation backward
-    applied on load, one pass dx = dy*g + dmean/HW; the four parameter gradients come from two small
-    launches in the torch layout (side stream when they go to arena slots).  Weights are the torch
-    (R, C, 1, 1) / (C, R, 1, 1) conv parameters."""
+    MobileNetV3), the gate of the `basic` encoder's inverted-residual blocks - as two launches: the gate of every
+    image (spatial mean and both GEMVs, vmtl_se_gate_fwd) and one scale pass.  Backward: the gate's gradient
+    (sum_hw dy*x and both transposed GEMVs with the activation backward, vmtl_se_gate_bwd), one pass
+    dx = dy*g + dmean/HW; the four parameter gradients come from one small launch in the torch layout (side
+    stream when they go to arena slots).  Weights are the torch (R, C, 1, 1) / (C, R, 1, 1) conv parameters, read
+    as they are.  vmtl_se_gate_supported decides per shape and direction: the forward gate of the blocks with large
+    weights (480 channels and up) stays on the earlier sequence - per-image partial sums over HW, two batch-sized GEMMs
+    (vmtl_fc_fwd) - which reads the weights once instead of once per image.  VMTL_SE_FUSED=0 restores that sequence
+    everywhere (backward: the GEMMs on packed transposes, two vmtl_fc_wgrad), VMTL_SE_FUSED=2 fuses everything."""
 
     @staticmethod
     def forward(ctx, x, wr, br, we, be, act1, act2):
@@ -2052,6 +2055,19 @@ class _SqueezeExcite(torch.autograd.Function):
         if B > lib().raw("vmtl_fc_max_rows")():
             raise ValueError("squeeze_excite: batch too large for the batch-sized GEMM kernels")
         Rs = ceil4(R)
+        ctx.acts = (act1, act2)
+        ctx.slots = (_slot(wr), _slot(br), _slot(we), _slot(be))
+        route = lib().raw("vmtl_se_gate_supported")(B, C, R)  # bit 0: backward + weight gradient, bit 1: forward
+        ctx.fused = bool(route & 1)
+        if route & 2:
+            pooled, z1, h = _empty((B, Cs), x), _empty((B, Rs), x), _empty((B, Rs), x)
+            z2, g = _empty((B, Cs), x), _empty((B, Cs), x)
+            _k("vmtl_se_gate_fwd", x=x, wr=wr, br=br, we=we, be=be, pooled=pooled, z1=z1, h=h, z2=z2, g=g, B=B, HW=HW,
+               C=C, R=R, act1=act1, act2=act2)
+            y = _empty(x.shape, x)
+            _k("vmtl_channel_scale_add", x=x, s=g, t=None, t_scale=0.0, y=y, B=B, HW=HW, Cs=Cs)
+            ctx.save_for_backward(x, pooled, z1, h, z2, g, wr, we)
+            return y
         S = lib().raw("vmtl_hw_reduce_parts")(B, HW, Cs)
         parts = _empty((S, B, Cs), x)
         _k("vmtl_hw_reduce", x=x, y=None, part=parts, B=B, HW=HW, Cs=Cs)
@@ -2066,8 +2082,6 @@ class _SqueezeExcite(torch.autograd.Function):
         _k("vmtl_channel_scale_add", x=x, s=g, t=None, t_scale=0.0, y=y, B=B, HW=HW, Cs=Cs)
         ctx.save_for_backward(x, pooled, z1, h, z2, g, wr, we)
         ctx.S = S
-        ctx.acts = (act1, act2)
-        ctx.slots = (_slot(wr), _slot(br), _slot(we), _slot(be))
         return y
 
     @staticmethod
@@ -2078,7 +2092,29 @@ class _SqueezeExcite(torch.autograd.Function):
         B, H, W, Cs = x.shape
         HW = H * W
         R, C = wr.shape[0], wr.shape[1]
-        Rs, S = ceil4(R), ctx.S
+        Rs = ceil4(R)
+        slots = ctx.slots
+        all_slots = all(s is not None for s in slots)
+        if ctx.fused:
+            dg, dh = _empty((B, Cs), x), _empty((B, Rs), x)  # both finished, for the weight gradients
+            dmean = _empty((B, Cs), x) if ctx.needs_input_grad[0] else None
+            _k("vmtl_se_gate_bwd", dy=dy, x=x, z1=z1, z2=z2, wr=wr, we=we, dg=dg, dh=dh, dmean=dmean, B=B, HW=HW, C=C, R=R,
+               act1=act1, act2=act2)
+            fork = side.mark()
+            dx = None
+            if dmean is not None:
+                dx = _empty(x.shape, x)
+                _k("vmtl_channel_scale_add", x=dy, s=g, t=dmean, t_scale=1.0 / HW, y=dx, B=B, HW=HW, Cs=Cs)
+            with side.branch(all_slots, B, fork, dg, dh, pooled, z1, h, z2):
+                dwr = _empty(wr.shape, x) if slots[0] is None else slots[0]
+                dbr = _empty((R,), x) if slots[1] is None else slots[1]
+                dwe = _empty(we.shape, x) if slots[2] is None else slots[2]
+                dbe = _empty((C,), x) if slots[3] is None else slots[3]
+                _k("vmtl_se_wgrad", pooled=pooled, h=h, dg=dg, dh=dh, z1=z1, z2=z2, dwr=dwr, dbr=dbr, dwe=dwe, dbe=dbe,
+                   B=B, C=C, R=R, act1=act1, act2=act2)
+            ret = [None if sl is not None else t for t, sl in zip((dwr, dbr, dwe, dbe), slots)]
+            return dx, ret[0], ret[1], ret[2], ret[3], None, None
+        S = ctx.S
         # dg[b][c] = sum_hw dy*x, left as per-slice partial sums for the GEMM to finish
         dparts = _empty((S, B, Cs), x)
         _k("vmtl_hw_reduce", x=dy, y=x, part=dparts, B=B, HW=HW, Cs=Cs)
@@ -2096,8 +2132,6 @@ class _SqueezeExcite(torch.autograd.Function):
                bias=None, z=None, y=dmean, M=B, K=R, N=C, lda=Rs, ldw=Rs, ldy=Cs, act=0)
             dx = _empty(x.shape, x)
             _k("vmtl_channel_scale_add", x=dy, s=g, t=dmean, t_scale=1.0 / HW, y=dx, B=B, HW=HW, Cs=Cs)
-        slots = ctx.slots
-        all_slots = all(s is not None for s in slots)
         with side.branch(all_slots, B, fork, dg, dh, pooled, z1, h, z2):
             dwr = _empty(wr.shape, x) if slots[0] is None else slots[0]
             dbr = _empty((R,), x) if slots[1] is None else slots[1]
