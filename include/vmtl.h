@@ -438,6 +438,19 @@ int vmtl_stitch(const float* x, const float* w, float* y, long long M, int C, in
  * partial: (vmtl_reduce_rows(M) + 1) * Cs floats of scratch */
 int vmtl_stitch_bwd(const float* x, const float* dy, const float* w, float* dx, float* partial, float* dw, int M,
                     int C, int Cs, int wstride, int reduce_all, void* stream);
+/* The full 2x2 cross-stitch unit of Misra et al. (csrc/stitch_mix.hip) - the opt-in mode that models/cross_stitch_model.py's
+ * einsum never reaches (it only uses the diagonal: vmtl_stitch).  Two tasks: y0 = w00*x0 + w01*x1, y1 = w10*x0 + w11*x1 on
+ * [M][Cs] activations, lanes c >= C written as zeros.  w is the parameter as stored: entry (a,b,c) at (a*2+b)*C + c
+ * (wstride 1, channel-wise) or (a,b) at a*2+b (wstride 0, layer-wise).  Not in place: an output may not overlap an input
+ * or the other output. */
+int vmtl_stitch_mix(const float* x0, const float* x1, const float* w, float* y0, float* y1, int M, int C, int Cs,
+                    int wstride, void* stream);
+/* its backward in one sweep: dx0 = w00*dy0 + w10*dy1, dx1 = w01*dy0 + w11*dy1 (nullable together), dw (nullable) = the
+ * whole gradient in parameter layout, block (a,b) = sum_m dy_a * x_b (4*C floats, or 4 when wstride 0), overwritten,
+ * fp64 fixed-order finalize, no atomics.  dw NULL: data gradients only, no reduction is launched (x0, x1, partial unused).
+ * partial: (4 * vmtl_reduce_rows(M) + 4) * Cs floats of scratch */
+int vmtl_stitch_mix_bwd(const float* x0, const float* x1, const float* dy0, const float* dy1, const float* w, float* dx0,
+                        float* dx1, float* partial, float* dw, int M, int C, int Cs, int wstride, void* stream);
 /* mode 0 add, 1 sigmoid, 2 sigmoid-backward-from-output, 3 scale by *b */
 int vmtl_eltwise(const float* a, const float* b, float* y, int mode, long long total, void* stream);
 /* y = a + b (+ c) (+ d), c / d nullable, total % 4 == 0: the gradient sum of an activation with 2..4 consumers - what

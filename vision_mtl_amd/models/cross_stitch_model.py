@@ -3,6 +3,8 @@
 CrossStitchLayer keeps the reference's parameter shapes ((T,T,C) or (T,T), U(0,1) init) and its
 exact arithmetic: the einsum "aac,abcij->abcij" only ever touches the DIAGONAL w[a,a,(c)], i.e.
 a per-task (per-channel) scale with zero gradient for off-diagonal entries.
+mixing="full" (opt-in, never the default) is the cross-stitch unit of Misra et al. instead:
+y_a = sum_b w[a,b,(c)] * x_b over the same parameter, a deliberate deviation from the reference.
 
 CSNet follows the reference's forward literally: walk every named module of the task networks in
 registration order, apply only leaves, save / pad-concat skips at encoder / decoder block entries,
@@ -36,11 +38,25 @@ def get_joint_layer_names_before_stitch_for_unet(joint_layer_names: t.List[str])
     return out
 
 
-class CrossStitchLayer(nn.Module):
-    """reference models/cross_stitch_model.py:15-37."""
+STITCH_MIXINGS = ("diagonal", "full")
 
-    def __init__(self, num_tasks: int, num_channels: t.Optional[int] = None):
+
+def check_stitch_mixing(mixing: str) -> str:
+    if mixing not in STITCH_MIXINGS:
+        raise ValueError(f"unknown cross-stitch mixing {mixing!r}: expected one of {STITCH_MIXINGS}")
+    return mixing
+
+
+class CrossStitchLayer(nn.Module):
+    """reference models/cross_stitch_model.py:15-37.  mixing="diagonal" is the reference's arithmetic; mixing="full" mixes
+    the two tasks with the whole matrix (einsum "abc,bncij->ancij" / "ab,bncij->ancij"), same parameter."""
+
+    def __init__(self, num_tasks: int, num_channels: t.Optional[int] = None, mixing: str = "diagonal"):
         super().__init__()
+        check_stitch_mixing(mixing)
+        if mixing == "full" and num_tasks != 2:
+            raise NotImplementedError(f"CrossStitchLayer(mixing='full') mixes exactly two tasks, got {num_tasks}")
+        self.mixing = mixing
         self.num_tasks = num_tasks
         self.channel_wise_stitching = num_channels is not None
         shape = (num_tasks, num_tasks, num_channels) if self.channel_wise_stitching else (num_tasks, num_tasks)
@@ -51,9 +67,15 @@ class CrossStitchLayer(nn.Module):
         nn.init.uniform_(self.weights)
 
     def run(self, acts: t.List[L.Act]) -> t.List[L.Act]:
+        if self.mixing == "full":
+            a0, a1 = acts
+            y0, y1 = ops.stitch_mix(a0.t, a1.t, self.weights, a0.C)
+            return [L.Act(y0, a0.C), L.Act(y1, a0.C)]
         return [self.run_task(i, a) for i, a in enumerate(acts)]
 
     def run_task(self, i: int, a: L.Act) -> L.Act:
+        if self.mixing != "diagonal":
+            raise RuntimeError("CrossStitchLayer.run_task: full mixing needs both tasks' activations, use run()")
         return L.Act(ops.stitch(a.t, self.weights, i, a.C), a.C)
 
     def forward(self, mt_activations: torch.Tensor) -> torch.Tensor:
@@ -67,10 +89,14 @@ _ACT_OF = {nn.ReLU: ops.ACT_RELU, nn.Hardswish: ops.ACT_HSWISH, nn.Hardsigmoid: 
 
 
 class CSNet(nn.Module):
-    """reference models/cross_stitch_model.py:40-201."""
+    """reference models/cross_stitch_model.py:40-201.  stitch_mixing="full": every stitch site mixes the two task networks
+    (CrossStitchLayer) instead of scaling each one - one launch per site for both tasks, never folded into a conv."""
 
-    def __init__(self, models: dict, channel_wise_stitching: bool = False):
+    def __init__(self, models: dict, channel_wise_stitching: bool = False, stitch_mixing: str = "diagonal"):
         super().__init__()
+        self.stitch_mixing = check_stitch_mixing(stitch_mixing)
+        if stitch_mixing == "full" and len(models) != 2:
+            raise NotImplementedError(f"CSNet(stitch_mixing='full') mixes exactly two tasks, got {len(models)}")
         for task, m in models.items():  # the stitch sites below are the timm MobileNetV3 encoder's blocks
             enc = getattr(m[0], "encoder", None) if isinstance(m, nn.Sequential) and len(m) > 0 else None
             if enc is not None and not isinstance(enc, MobileNetV3Encoder):
@@ -91,10 +117,10 @@ class CSNet(nn.Module):
         self.true_cross_stitch_layer_names = list(self.joint_layer_names_before_stitch)
         if channel_wise_stitching:
             self.stitch_channels = self.get_stitch_channels(first, self.joint_layer_names_before_stitch)
-            layers = {n: CrossStitchLayer(self.num_tasks, self.stitch_channels[i])
+            layers = {n: CrossStitchLayer(self.num_tasks, self.stitch_channels[i], mixing=stitch_mixing)
                       for i, n in enumerate(self.valid_cross_stitch_layer_names)}
         else:
-            layers = {n: CrossStitchLayer(self.num_tasks) for n in self.valid_cross_stitch_layer_names}
+            layers = {n: CrossStitchLayer(self.num_tasks, mixing=stitch_mixing) for n in self.valid_cross_stitch_layer_names}
         self.cross_stitch_layers = nn.ModuleDict(layers)
         self._program = None
         self.debug_acts = None  # set to a list to capture (op, arg, task, NCHW tensor) after every op (diagnostics)
@@ -141,8 +167,8 @@ class CSNet(nn.Module):
                 prog.append(("merge", idx) if self.consider_decoder_layer_at_idx(idx) else ("up", None))
             if not any(True for _ in layer.named_children()) and not isinstance(layer, nn.Identity):
                 prog.append(("leaf", name))
-            if name in stitch_sites:
-                prog.append(("stitch", name.replace(".", "_")))
+            if name in stitch_sites:  # "mix": both tasks in one op (the full unit), "stitch": each task on its own
+                prog.append(("mix" if self.stitch_mixing == "full" else "stitch", name.replace(".", "_")))
         # peephole: conv -> plain BatchNorm2d -> ReLU leaves (decoder Conv2dReLU) become one fused call
         fused, i = [], 0
         while i < len(prog):
@@ -189,15 +215,16 @@ class CSNet(nn.Module):
             self._compile()
         # task streams only with a gradient arena (or no gradients at all): torch's AccumulateGrad nodes would otherwise
         # run on a stream other than the one they were created on (extra syncs, a warning, trouble under capture)
+        # (and never in full mixing mode: there the two networks exchange data at every stitch site)
         task_par = (x.is_cuda and ops.side.enabled and ops.side.task_parallel and self.num_tasks == 2
-                    and self.debug_acts is None
+                    and self.debug_acts is None and self.stitch_mixing == "diagonal"
                     and (not torch.is_grad_enabled()
                          or getattr(next(self.parameters()), "_vmtl_gslot", None) is not None))
         ops.packs.refresh(task_mode=task_par)  # one batched weight-packing launch for the whole step
         x0 = L.from_nchw(x)
         feats = {task: x0 for task in self.model_names}
         skips = {task: [] for task in self.model_names}
-        # Two task networks that never exchange data (the stitch only scales a task's own features): the
+        # Diagonal mixing: two task networks that never exchange data (the stitch only scales a task's own features): the
         # second one runs on its own stream - a parallel branch of the captured graph - and is joined at the end.
         main = torch.cuda.current_stream() if x.is_cuda else None
         streams = {task: None for task in self.model_names}
@@ -207,6 +234,10 @@ class CSNet(nn.Module):
             x0.t.record_stream(s1)
             streams[self.model_names[1]] = s1
         for op, arg in self._program:
+            if op == "mix":  # the full cross-stitch unit: one launch reads and writes both tasks' features
+                mixed = self.cross_stitch_layers[arg].run([feats[task] for task in self.model_names])
+                feats = dict(zip(self.model_names, mixed))
+                continue
             for ti, task in enumerate(self.model_names):
                 with (torch.cuda.stream(streams[task]) if streams[task] is not None else contextlib.nullcontext()):
                     net, f = self.models[task], feats[task]

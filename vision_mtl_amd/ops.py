@@ -132,7 +132,8 @@ class _SideBranch:
 
     def task_stream(self, device):
         """Stream for the second of two independent task networks (CSNet: the cross-stitch layers of the
-        reference only scale each task's own features, so the two U-Nets never exchange data).  join() also
+        reference only scale each task's own features, so the two U-Nets never exchange data; a CSNet with the opt-in
+        full stitch mixing does exchange data at every site and keeps both networks on the calling stream).  join() also
         waits for it: gradients written into arena slots from that stream have no AccumulateGrad node the
         autograd engine could synchronise on."""
         s = self.task_streams.get(device.index)
@@ -2204,6 +2205,58 @@ class _Stitch(torch.autograd.Function):
 
 def stitch(x, weights, task, C):
     return _Stitch.apply(x, weights, task, C)
+
+
+class _StitchMix(torch.autograd.Function):
+    """The full cross-stitch unit of two tasks (csrc/stitch_mix.hip): y_a = sum_b w[a, b, (c)] * x_b, `weights` the whole
+    (2,2[,C]) parameter.  The opt-in mode the reference's einsum never reaches: every entry of the
+    parameter gets a gradient, written by ONE launch (into the arena slot when there is one - overwritten, not added)."""
+
+    @staticmethod
+    def forward(ctx, x0, x1, weights, C):
+        x0, x1 = _req(x0, "x0"), _req(x1, "x1")
+        weights = _req(weights, "weights")
+        if weights.shape[:2] != (2, 2):
+            raise NotImplementedError(f"stitch_mix: two tasks only, got weights of shape {tuple(weights.shape)}")
+        channel_wise = weights.dim() == 3
+        if channel_wise and weights.shape[2] != C:
+            raise ValueError(f"stitch_mix: the stitch layer has {weights.shape[2]} channels, the activations {C}")
+        if x0.shape != x1.shape:
+            raise ValueError(f"stitch_mix: the two tasks' activations differ in shape: {tuple(x0.shape)} / {tuple(x1.shape)}")
+        B, H, W, Cs = x0.shape
+        y0, y1 = _empty(x0.shape, x0), _empty(x0.shape, x0)
+        # no _flop: bench.py files every recorded name it does not know under the conv forward family
+        _k("vmtl_stitch_mix", x0=x0, x1=x1, w=weights, y0=y0, y1=y1, M=B * H * W, C=C, Cs=Cs, wstride=1 if channel_wise else 0)
+        ctx.save_for_backward(x0, x1, weights)
+        ctx.cfg = (C, channel_wise)
+        ctx.slot = _slot(weights)
+        return y0, y1
+
+    @staticmethod
+    def backward(ctx, dy0, dy1):
+        x0, x1, weights = ctx.saved_tensors
+        C, channel_wise = ctx.cfg
+        dy0, dy1 = _req(dy0, "dy0"), _req(dy1, "dy1")
+        B, H, W, Cs = x0.shape
+        M = B * H * W
+        want_dx = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        dx0 = dx1 = dw = out = partial = None
+        if want_dx:
+            dx0, dx1 = _empty(x0.shape, x0), _empty(x0.shape, x0)
+        if ctx.needs_input_grad[2]:
+            out = ctx.slot
+            if out is None:
+                out = dw = _empty(weights.shape, weights)
+            partial = _empty((4 * _reduce_rows(M) + 4, Cs), x0)
+        if want_dx or out is not None:  # one sweep: both data gradients and the four weight-gradient blocks
+            _k("vmtl_stitch_mix_bwd", x0=x0, x1=x1, dy0=dy0, dy1=dy1, w=weights, dx0=dx0, dx1=dx1, partial=partial, dw=out,
+               M=M, C=C, Cs=Cs, wstride=1 if channel_wise else 0)
+        return (dx0 if ctx.needs_input_grad[0] else None, dx1 if ctx.needs_input_grad[1] else None, dw, None)
+
+
+def stitch_mix(x0, x1, weights, C):
+    """(y0, y1) = the full 2x2 cross-stitch mix of two tasks' activations."""
+    return _StitchMix.apply(x0, x1, weights, C)
 
 
 # ----------------------------------------------------------------------------- boundary layout + postprocess

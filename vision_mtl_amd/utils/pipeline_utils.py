@@ -8,7 +8,7 @@ import torch
 
 from ..lit_module import MTLModule
 from ..models.basic_model import BasicMTLModel
-from ..models.cross_stitch_model import CSNet
+from ..models.cross_stitch_model import CSNet, check_stitch_mixing
 from ..models.mtan_model import MTANMiniUnet
 from ..models.unet_mobilenetv3 import get_model_with_dense_preds
 
@@ -27,6 +27,7 @@ def build_model(args: argparse.Namespace, data_cfg: DataConfig) -> t.Union[Basic
         return MTANMiniUnet(in_channels=3, map_tasks_to_num_channels={"depth": 1, "segm": data_cfg.num_classes},
                             task_subnets_hidden_channels=128, encoder_first_channel=32, encoder_num_channels=4)
     if args.model_name == "csnet":
+        mixing = check_stitch_mixing(getattr(args, "cross_stitch_mixing", "diagonal"))  # before the networks are built
         backbone_params = dict(encoder_name="timm-mobilenetv3_large_100", encoder_weights=encoder_weights,
                                decoder_first_channel=256, num_decoder_layers=5)
         models = {
@@ -34,7 +35,9 @@ def build_model(args: argparse.Namespace, data_cfg: DataConfig) -> t.Union[Basic
             "segm": get_model_with_dense_preds(segm_classes=data_cfg.num_classes, activation=None,
                                                backbone_params=backbone_params),
         }
-        return CSNet(models, channel_wise_stitching=getattr(args, "channel_wise_stitching", True))
+        # "diagonal": the reference's arithmetic; "full": the opt-in cross-stitch unit proper
+        return CSNet(models, channel_wise_stitching=getattr(args, "channel_wise_stitching", True),
+                     stitch_mixing=mixing)
     raise NotImplementedError(f"Unknown model name: {args.model_name}")
 
 
