@@ -28,10 +28,12 @@ extern "C" {
 #define VMTL_ACT_HSIGMOID 3
 #define VMTL_ACT_SIGMOID 4
 
-/* operand precision of the implicit-GEMM convolutions (the *_p entry points below; their namesakes without the suffix
- * are VMTL_PREC_FP32).  VMTL_PREC_BF16: every product term is bf16(a)*bf16(b) (round-to-nearest-even, NaN stays NaN),
- * accumulated in fp32; tensors in memory, epilogues (bias, activation, statistics, BatchNorm backward) stay fp32.  Tile
- * choice, K split, statistics layout and weight-gradient slab counts do not depend on it.  Unknown values: -1. */
+/* operand precision of the implicit-GEMM convolutions and the pointwise GEMMs (the *_p entry points below; their
+ * namesakes without the suffix are VMTL_PREC_FP32).  VMTL_PREC_BF16: every product term is bf16(a)*bf16(b)
+ * (round-to-nearest-even, NaN stays NaN), accumulated in fp32; tensors in memory, epilogues (bias, activation, statistics,
+ * BatchNorm backward and its addend) stay fp32.  Tile choice, K split, persistent-program count, statistics layout and
+ * weight-gradient slab counts do not depend on it.  Unknown values: -1, checked before anything else.  The value is per
+ * call: which launches of a model run in which precision is the caller's routing (vision_mtl_amd/precision.py). */
 #define VMTL_PREC_FP32 0
 #define VMTL_PREC_BF16 1
 
@@ -84,12 +86,21 @@ int vmtl_conv1x1_stats_block(int M, int ldy, int Ks, int variant);
 int vmtl_conv1x1_stats_rows(int M, int ldy, int Ks, int variant);
 int vmtl_conv1x1_fwd(const float* x, const float* wp, const float* bias, float* y, float* stats, int M, int Ks, int ldy,
                      int Nw, int Cout, void* stream);
+/* the pointwise GEMMs with the operand precision chosen per call (VMTL_PREC_BF16: bf16(x)*bf16(wp) products on the bf16
+ * matrix cores, fp32 accumulation and epilogue; with a prologue the rounded operand is the fp32 value a_out receives).
+ * vmtl_conv1x1_stats_block / _rows take no precision: the geometry is the same in both. */
+int vmtl_conv1x1_fwd_p(const float* x, const float* wp, const float* bias, float* y, float* stats, int M, int Ks, int ldy,
+                       int Nw, int Cout, int precision, void* stream);
 /* conv1x1(cat[x, x2]) without the concat (mtan_model.py:57-59,139-141): x [M][K1] (K1 % 4 == 0), x2 [M][K2s], packed
  * weight rows [Nw][K1 + K2s]; and its data gradient writing [dx | dx2] (dx [M][N1], dx2 [M][N2s]) without a split pass */
 int vmtl_conv1x1_cat_fwd(const float* x, int K1, const float* x2, int K2s, const float* wp, const float* bias, float* y,
                          float* stats, int M, int ldy, int Nw, int Cout, void* stream);
 int vmtl_conv1x1_cat_dgrad(const float* dy, const float* wp, float* dx, int N1, float* dx2, int N2s, int N2, int M,
                            int Ks, void* stream);
+int vmtl_conv1x1_cat_fwd_p(const float* x, int K1, const float* x2, int K2s, const float* wp, const float* bias, float* y,
+                           float* stats, int M, int ldy, int Nw, int Cout, int precision, void* stream);
+int vmtl_conv1x1_cat_dgrad_p(const float* dy, const float* wp, float* dx, int N1, float* dx2, int N2s, int N2, int M,
+                             int Ks, int precision, void* stream);
 /* and its weight gradient in one launch: slabs [splits][Nw][K1 + K2s], splits = vmtl_conv2d_wgrad_splits(M, Nw, K1 + K2s) */
 int vmtl_conv1x1_cat_wgrad(const float* x, int K1, const float* x2, int K2s, const float* dy, float* slabs, int splits,
                            int M, int ldy, int Nw, void* stream);
@@ -106,6 +117,12 @@ int vmtl_conv1x1_bn_fwd(const float* x, const float* coef_a, const float* coef_c
 int vmtl_conv1x1_bnbwd(const float* dy, const float* wp, float* dz, float* stats, const float* ez_x,
                        const float* ez_mean, const float* ez_invstd, const float* ez_gamma, const float* ez_beta,
                        int ez_act, int M, int Ks, int ldy, int Nw, int Cout, void* stream);
+int vmtl_conv1x1_bn_fwd_p(const float* x, const float* coef_a, const float* coef_c, int act_in, float* a_out,
+                          const float* wp, const float* bias, float* y, float* stats, int M, int Ks, int ldy, int Nw,
+                          int Cout, int precision, void* stream);
+int vmtl_conv1x1_bnbwd_p(const float* dy, const float* wp, float* dz, float* stats, const float* ez_x,
+                         const float* ez_mean, const float* ez_invstd, const float* ez_gamma, const float* ez_beta,
+                         int ez_act, int M, int Ks, int ldy, int Nw, int Cout, int precision, void* stream);
 /* with a residual operand: the GEMM input is a = act(coef_a*x + coef_c) + res (an inverted-residual block's bn3 output +
  * skip connection consumed by the next block's expand conv; a_out receives a), and with a second gradient of the
  * differentiated tensor added before the backward: dz = (dy*W + addend) * act'(...) */
@@ -115,6 +132,13 @@ int vmtl_conv1x1_bn_res_fwd(const float* x, const float* coef_a, const float* co
 int vmtl_conv1x1_bnbwd_add(const float* dy, const float* wp, const float* addend, float* dz, float* stats,
                            const float* ez_x, const float* ez_mean, const float* ez_invstd, const float* ez_gamma,
                            const float* ez_beta, int ez_act, int M, int Ks, int ldy, int Nw, int Cout, void* stream);
+int vmtl_conv1x1_bn_res_fwd_p(const float* x, const float* coef_a, const float* coef_c, int act_in, const float* res,
+                              float* a_out, const float* wp, const float* bias, float* y, float* stats, int M, int Ks,
+                              int ldy, int Nw, int Cout, int precision, void* stream);
+int vmtl_conv1x1_bnbwd_add_p(const float* dy, const float* wp, const float* addend, float* dz, float* stats,
+                             const float* ez_x, const float* ez_mean, const float* ez_invstd, const float* ez_gamma,
+                             const float* ez_beta, int ez_act, int M, int Ks, int ldy, int Nw, int Cout, int precision,
+                             void* stream);
 
 /* vmtl_conv2d_fwd used as a DATA GRADIENT with the BatchNorm + activation backward of the layer that produced the
  * differentiated tensor fused into the epilogue (reference utils/model_utils.py:72-76 run backwards): y = conv *

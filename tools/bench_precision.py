@@ -1,7 +1,7 @@
-"""Training-step time of the captured step (vision_mtl_amd.graphed.GraphedStep) in fp32 and bf16 convolution precision
-(GPU box only: there is no CPU fallback).  Both modes are captured on the same model, then timed in alternating blocks;
-each configuration reports ms/step and img/s per mode, the bf16 speed-up, and the loss of the last bf16 replay against
-the fp32 one.  Prints ONE JSON line.
+"""Training-step time of the captured step (vision_mtl_amd.graphed.GraphedStep) in the three convolution precisions:
+fp32, bf16 and bf16_pw (bf16 plus the pointwise GEMMs; GPU box only: there is no CPU fallback).  All modes are captured on
+the same model, then timed in alternating blocks; each configuration reports ms/step and img/s per mode, the speed-up of
+bf16 and bf16_pw over fp32, and the loss of the last replay of each against the fp32 one.  Prints ONE JSON line.
 
     python tools/bench_precision.py [--steps 20] [--rounds 3] [--only basic_bs32]
 """
@@ -22,7 +22,7 @@ CONFIGS = [("basic_bs32", "basic", 32, 128, 256, 19), ("basic_bs8", "basic", 8, 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20, help="replays per timed block")
-    ap.add_argument("--rounds", type=int, default=3, help="alternating (fp32, bf16) block pairs; the median is reported")
+    ap.add_argument("--rounds", type=int, default=3, help="alternating (fp32, bf16, bf16_pw) blocks; the median is reported")
     ap.add_argument("--only", default="")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -34,6 +34,7 @@ def main():
     from vision_mtl_amd.utils.pipeline_utils import build_model
 
     dev = torch.device("cuda:0")
+    PRECS = ("fp32", "bf16", "bf16_pw")
     out = {}
     for tag, name, bs, H, W, C in CONFIGS:
         if args.only and args.only not in tag:
@@ -47,13 +48,13 @@ def main():
         arena = dp.FlatArena(model)
         module.dp_arena = None
         steps = {}
-        for prec in ("fp32", "bf16"):
+        for prec in PRECS:
             with conv_precision(prec):
                 steps[prec] = GraphedStep(module, batch, arena=arena, warmup=1)
-        times = {"fp32": [], "bf16": []}
+        times = {prec: [] for prec in PRECS}
         losses = {}
         for _ in range(args.rounds):
-            for prec in ("fp32", "bf16"):
+            for prec in PRECS:
                 g = steps[prec].graph
                 g.replay()
                 torch.cuda.synchronize()
@@ -66,11 +67,12 @@ def main():
                 times[prec].append(e0.elapsed_time(e1) / args.steps)
                 losses[prec] = float(steps[prec]._loss)
         res = {}
-        for prec in ("fp32", "bf16"):
+        for prec in PRECS:
             ms = statistics.median(times[prec])
             res[prec] = {"ms_per_step": round(ms, 3), "img_per_s": round(bs / ms * 1e3, 1), "final_loss": losses[prec]}
-        res["bf16_speedup"] = round(res["fp32"]["ms_per_step"] / res["bf16"]["ms_per_step"], 3)
-        res["bf16_loss_rel_diff"] = abs(losses["bf16"] - losses["fp32"]) / abs(losses["fp32"])
+        for prec in PRECS[1:]:
+            res[prec + "_speedup"] = round(res["fp32"]["ms_per_step"] / res[prec]["ms_per_step"], 3)
+            res[prec + "_loss_rel_diff"] = abs(losses[prec] - losses["fp32"]) / abs(losses["fp32"])
         out[tag] = res
         print(f"{tag}: {res}", file=sys.stderr, flush=True)
         del steps, module, model, arena

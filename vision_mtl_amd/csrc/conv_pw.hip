@@ -16,7 +16,25 @@
 //     through LDS once at the end - 4x the waves for the tile-starved deep layers (M = 1024 / 4096);
 //   * the output tile goes through LDS so that y is written as coalesced float4 rows, with the bias add and the
 //     BatchNorm (mean, M2) partials of the tile taken on the way.
+//
+// BF16 (VMTL_PREC_BF16, the *_p entry points; the contract of conv_igemm.hip): every product term is bf16(a) * bf16(b)
+// - both operands rounded to nearest even by a plain cast (v_cvt_pk_bf16_f32, NaN stays NaN) - accumulated in fp32 by
+// v_mfma_f32_16x16x32_bf16.  Memory stays fp32 and every epilogue (bias, pad-channel zeros, statistics, split store,
+// BatchNorm backward with its unrounded addend) works on the fp32 accumulators unchanged.  With the pre-activation
+// prologue the fp32 a = act(pa*x + pc) [+ res] is what a_out receives, and the product operand is the bf16 image of that
+// very value.  Tile choice, persistent-program count and statistics geometry do not depend on the precision.
 #include "common.h"
+
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ u32x2 pw_round_bf16x4(f32x4 v) {
+  return __builtin_bit_cast(u32x2, __builtin_convertvector(v, bf16x4));
+}
+// a lane's eight k values of one v_mfma_f32_16x16x32_bf16 operand: two fp32 quads, rounded
+__device__ __forceinline__ bf16x8 pw_round_bf16x8(f32x4 lo, f32x4 hi) {
+  const u32x2 l = pw_round_bf16x4(lo), h = pw_round_bf16x4(hi);
+  return __builtin_bit_cast(bf16x8, (u32x4){l[0], l[1], h[0], h[1]});
+}
 
 struct PwP {
   const float* x;     // [M][Ks]
@@ -53,7 +71,10 @@ struct PwP {
 };
 
 // wave tile 32 rows x (16*TN) columns; KW waves of the workgroup split K, the other 4/KW stack along M
-template <int TN, int KW, bool SRC2 = false, bool PRO = false>
+// BF16: the global loads are the same 16-byte quads; two consecutive k-groups of the wave's own sequence (g and g + KW)
+// supply a lane's eight k values of one v_mfma_f32_16x16x32_bf16 per (i, j) - A and B assign k values to MFMA k slots
+// alike, which is all the sum needs.  An odd group count pairs the last group with the loader's zero fill of g >= G.
+template <int TN, int KW, bool SRC2 = false, bool PRO = false, bool BF16 = false>
 __global__ __launch_bounds__(256) void pw_gemm_kernel(PwP p) {
   constexpr int TM = 2;
   constexpr int RG = 4 / KW;        // row groups (waves along M)
@@ -115,7 +136,7 @@ __global__ __launch_bounds__(256) void pw_gemm_kernel(PwP p) {
     for (int j = 0; j < TN; ++j)
       f.b[j] = (kok && bok[j]) ? *reinterpret_cast<const f32x4*>(bp[j] + 16 * g) : (f32x4){0.f, 0.f, 0.f, 0.f};
   };
-  auto mma = [&](Frag& f, int g) {
+  auto prologue = [&](Frag& f, int g) {
     if (PRO) {  // the producer's BatchNorm + activation, on the fragments (k >= Ks: pa = pc = 0 and B is zero there)
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
@@ -128,6 +149,9 @@ __global__ __launch_bounds__(256) void pw_gemm_kernel(PwP p) {
           *reinterpret_cast<f32x4*>(p.a_out + (size_t)(m0 + rg * 32 + 16 * i + l15) * p.Ks + 16 * g + 4 * lq) = v;
       }
     }
+  };
+  auto mma = [&](Frag& f, int g) {
+    prologue(f, g);
 #pragma unroll
     for (int e = 0; e < 4; ++e)
 #pragma unroll
@@ -136,20 +160,56 @@ __global__ __launch_bounds__(256) void pw_gemm_kernel(PwP p) {
         for (int j = 0; j < TN; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.a[i][e], f.b[j][e], acc[i][j], 0, 0, 0);
   };
-  // this wave's k-groups: ks, ks + KW, ...; three in flight
-  Frag f0, f1, f2;
-  int g = ks;
-  load(g, f0);
-  load(g + KW, f1);
-  for (; g < G; g += 3 * KW) {
-    load(g + 2 * KW, f2);
-    mma(f0, g);
-    if (g + KW >= G) break;
-    load(g + 3 * KW, f0);
-    mma(f1, g + KW);
-    if (g + 2 * KW >= G) break;
-    load(g + 4 * KW, f1);
-    mma(f2, g + 2 * KW);
+  if constexpr (!BF16) {
+    // this wave's k-groups: ks, ks + KW, ...; three in flight
+    Frag f0, f1, f2;
+    int g = ks;
+    load(g, f0);
+    load(g + KW, f1);
+    for (; g < G; g += 3 * KW) {
+      load(g + 2 * KW, f2);
+      mma(f0, g);
+      if (g + KW >= G) break;
+      load(g + 3 * KW, f0);
+      mma(f1, g + KW);
+      if (g + 2 * KW >= G) break;
+      load(g + 4 * KW, f1);
+      mma(f2, g + 2 * KW);
+    }
+  } else {
+    // this wave's k-groups in PAIRS (g, g + KW), (g + 2 KW, g + 3 KW), ...: one bf16 MFMA per (i, j) and pair.  TWO pairs
+    // (four k-groups, one more than the fp32 loop) are in flight: with three the 64-column instantiations need 288-414
+    // VGPRs - one wave per SIMD - where two pairs keep the fp32 kernel's occupancy.
+    // A group at or past G is the loader's zeros on both operands (and act(0) = 0 for the prologue's activations).
+    constexpr int S = 2 * KW;
+    auto load2 = [&](int g, Frag* f) {
+      load(g, f[0]);
+      load(g + KW, f[1]);
+    };
+    auto mma2 = [&](Frag* f, int g) {
+      prologue(f[0], g);  // fp32, and a_out receives it; the MFMA operand is the rounded image of that value
+      prologue(f[1], g + KW);
+      bf16x8 fa[TM], fb[TN];
+#pragma unroll
+      for (int i = 0; i < TM; ++i) fa[i] = pw_round_bf16x8(f[0].a[i], f[1].a[i]);
+#pragma unroll
+      for (int j = 0; j < TN; ++j) fb[j] = pw_round_bf16x8(f[0].b[j], f[1].b[j]);
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
+    };
+    Frag f0[2], f1[2];
+    int g = ks;
+    load2(g, f0);
+    for (; g < G; g += 2 * S) {
+      load2(g + S, f1);
+      mma2(f0, g);
+      if (g + S >= G) break;
+      load2(g + 2 * S, f0);
+      mma2(f1, g + S);
+    }
+    (void)mma;
   }
 
   // ---- C layout -> LDS (one plane per K slice); C: column = lane & 15, row = 4 * (lane >> 4) + reg ----
@@ -293,12 +353,18 @@ __global__ __launch_bounds__(256) void pw_gemm_kernel(PwP p) {
 //   * epilogue as above (bias, pad-channel zeros, per-tile BatchNorm (mean, M2), two-destination split store).
 // LDS images are [K chunk of 32][row][32 floats] with the 16-byte slot XOR-swizzled by (row & 7): the layout of
 // conv_igemm.hip's staging tiles (0 bank-conflict cycles measured there), for A and B alike.
+// BF16: both images are [K chunk of 32][row][32 bf16] planes (64-byte rows, half the size) with the 16-byte slot
+// XOR-swizzled by ((row >> 2) & 3) as conv_igemm.hip's bf16 planes are; operands are rounded ONCE, when they are staged
+// (A: after the prologue and the a_out store), and the K loop is one 16-byte fragment read per operand row and one
+// v_mfma_f32_16x16x32_bf16 per (i, j) and 32-deep chunk.  It reads whole chunks, so the zero fill of k >= Ks in the last
+// chunk (Ks = 40, 72, 136, ...) - B and A staging both write it - is what makes a half-full chunk exact.  Barriers,
+// prefetch and epilogue are the fp32 kernel's; the output tile may now be LARGER than the A image it aliases.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // wave tile (TM*16) x (TN*16), WM x WN waves; KC = K chunks of 32 the instantiation can hold (Ks <= 32 * KC)
 // EZ: BatchNorm-backward epilogue (see PwP::ez_x; no addend): dz = acc * act'(gamma * xhat + beta) and (sum dz, sum dz * xhat);
 // the ez_x values of a tile's epilogue are prefetched one tile ahead like A.
-template <int TM, int TN, int WM, int WN, int KC, bool SRC2, bool PRO, bool EZ = false>
+template <int TM, int TN, int WM, int WN, int KC, bool SRC2, bool PRO, bool EZ = false, bool BF16 = false>
 __global__ __launch_bounds__(WM* WN * 64) void pw_big_kernel(PwP p, int nprog) {
   static_assert(WM * WN == 4 || WM * WN == 8, "4 or 8 waves");
   constexpr int NTHR = WM * WN * 64;
@@ -307,11 +373,13 @@ __global__ __launch_bounds__(WM* WN * 64) void pw_big_kernel(PwP p, int nprog) {
   static_assert(BM % SR == 0, "whole staging passes");
   constexpr int RA = BM / SR, RB = (BN + SR - 1) / SR;  // staging rows per thread and chunk
   constexpr int OS = BN + 4;                         // output tile row stride (floats)
-  constexpr int A_FLOATS = KC * BM * 32, O_FLOATS = BM * OS;
+  constexpr int KF = BF16 ? 16 : 32;  // floats one row of a K chunk takes in LDS (bf16: 32 values in 64 bytes)
+  static_assert(!BF16 || SR % 16 == 0, "bf16 planes: a thread's staging rows share ((row >> 2) & 3)");
+  constexpr int A_FLOATS = KC * BM * KF, O_FLOATS = BM * OS;
   constexpr int AO_FLOATS = A_FLOATS > O_FLOATS ? A_FLOATS : O_FLOATS;  // the output tile aliases the A image
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* Bs = smem;                 // [KC][BN][32]
-  float* As = smem + KC * BN * 32;  // [KC][BM][32]  | output tile [BM][OS]
+  float* As = smem + KC * BN * KF;  // [KC][BM][32]  | output tile [BM][OS]
   f32x4* red = reinterpret_cast<f32x4*>(As + AO_FLOATS);  // [2][NTHR]
 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -322,6 +390,11 @@ __global__ __launch_bounds__(WM* WN * 64) void pw_big_kernel(PwP p, int nprog) {
   const int nkg = (p.Ks + 15) >> 4;   // 16-wide k-groups in use
   const int r0 = tid >> 3, kq = tid & 7;
   const int ks = (kq ^ (r0 & 7)) * 4;  // swizzled slot of this thread's k-quad ((r0 + SR i) & 7 == r0 & 7)
+  // bf16 planes: byte offset of this thread's four rounded values in its 64-byte row - k = 4 kq .. + 3 is half (kq & 1)
+  // of the natural 16-byte slot kq >> 1, which the swizzle moves ((r0 + SR i) >> 2 & 3 == r0 >> 2 & 3)
+  const int ksb = (((kq >> 1) ^ ((r0 >> 2) & 3)) << 4) + ((kq & 1) << 3);
+  char* const Bb = reinterpret_cast<char*>(Bs);
+  char* const Ab = reinterpret_cast<char*>(As);
   const int lda = SRC2 ? p.K1 : p.Ks;
 
   // ---- B: the whole [BN][Ks] weight tile, once ----
@@ -333,7 +406,8 @@ __global__ __launch_bounds__(WM* WN * 64) void pw_big_kernel(PwP p, int nprog) {
       if (BN % SR == 0 || row < BN) {
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         if (c < nkc && n < p.Nw && k < p.Ks) v = *reinterpret_cast<const f32x4*>(p.wp + (size_t)n * p.Ks + k);
-        *reinterpret_cast<f32x4*>(Bs + (c * BN + row) * 32 + ks) = v;
+        if constexpr (BF16) *reinterpret_cast<u32x2*>(Bb + (c * BN + row) * 64 + ksb) = pw_round_bf16x4(v);
+        else *reinterpret_cast<f32x4*>(Bs + (c * BN + row) * 32 + ks) = v;
       }
     }
   // prologue coefficients of this thread's k-quads (fixed per thread: one quad per chunk)
@@ -385,7 +459,8 @@ __global__ __launch_bounds__(WM* WN * 64) void pw_big_kernel(PwP p, int nprog) {
               *reinterpret_cast<f32x4*>(p.a_out + (size_t)m * p.Ks + k) = v;
             if (m >= p.M) v = (f32x4){0.f, 0.f, 0.f, 0.f};  // rows past M: act(pc) need not be 0
           }
-          *reinterpret_cast<f32x4*>(As + (c * BM + r0 + SR * i) * 32 + ks) = v;
+          if constexpr (BF16) *reinterpret_cast<u32x2*>(Ab + (c * BM + r0 + SR * i) * 64 + ksb) = pw_round_bf16x4(v);
+          else *reinterpret_cast<f32x4*>(As + (c * BM + r0 + SR * i) * 32 + ks) = v;
         }
       }
     }
@@ -458,23 +533,42 @@ __global__ __launch_bounds__(WM* WN * 64) void pw_big_kernel(PwP p, int nprog) {
 #pragma unroll
       for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
     // ---- K loop: no barrier, no global traffic ----
-    const float* a = As + ((wm * TM * 16 + l15) * 32);
-    const float* b = Bs + ((wn * TN * 16 + l15) * 32);
-    for (int g = 0; g < nkg; ++g) {
-      const int c = g >> 1;
-      const int so = ((((g & 1) << 2) + lq) ^ (l15 & 7)) * 4;
-      f32x4 fa[TM], fb[TN];
+    if constexpr (!BF16) {
+      const float* a = As + ((wm * TM * 16 + l15) * 32);
+      const float* b = Bs + ((wn * TN * 16 + l15) * 32);
+      for (int g = 0; g < nkg; ++g) {
+        const int c = g >> 1;
+        const int so = ((((g & 1) << 2) + lq) ^ (l15 & 7)) * 4;
+        f32x4 fa[TM], fb[TN];
 #pragma unroll
-      for (int i = 0; i < TM; ++i) fa[i] = *reinterpret_cast<const f32x4*>(a + (c * BM + i * 16) * 32 + so);
+        for (int i = 0; i < TM; ++i) fa[i] = *reinterpret_cast<const f32x4*>(a + (c * BM + i * 16) * 32 + so);
 #pragma unroll
-      for (int j = 0; j < TN; ++j) fb[j] = *reinterpret_cast<const f32x4*>(b + (c * BN + j * 16) * 32 + so);
+        for (int j = 0; j < TN; ++j) fb[j] = *reinterpret_cast<const f32x4*>(b + (c * BN + j * 16) * 32 + so);
 #pragma unroll
-      for (int e = 0; e < 4; ++e)
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+          for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+              acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i][e], fb[j][e], acc[i][j], 0, 0, 0);
+      }
+    } else {
+      // lane (l15, lq) holds k = 8 lq .. + 7 of the chunk: the natural slot lq of its row ((row >> 2) & 3 == l15 >> 2:
+      // wave and fragment row offsets are multiples of 16)
+      const int so = (lq ^ ((l15 >> 2) & 3)) << 4;
+      const char* a = Ab + (wm * TM * 16 + l15) * 64 + so;
+      const char* b = Bb + (wn * TN * 16 + l15) * 64 + so;
+      for (int c = 0; c < nkc; ++c) {
+        bf16x8 fa[TM], fb[TN];
+#pragma unroll
+        for (int i = 0; i < TM; ++i) fa[i] = *reinterpret_cast<const bf16x8*>(a + (c * BM + i * 16) * 64);
+#pragma unroll
+        for (int j = 0; j < TN; ++j) fb[j] = *reinterpret_cast<const bf16x8*>(b + (c * BN + j * 16) * 64);
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
-          for (int j = 0; j < TN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i][e], fb[j][e], acc[i][j], 0, 0, 0);
+          for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
+      }
     }
     lds_barrier();  // every wave is done reading the A image: it becomes the output tile
     float* tile = As;
@@ -618,6 +712,9 @@ __global__ __launch_bounds__(WM* WN * 64) void pw_big_kernel(PwP p, int nprog) {
     }
   }
   (void)first;
+  (void)nkg;
+  (void)ks;
+  (void)ksb;
 }
 
 // ---------------------------------------------------------------------------------------------- host side
@@ -673,7 +770,9 @@ static bool pw_big_cfg(int M, int ldy, int Ks, BigCfg* out) {
 static int pw_num_cus();
 
 // programs (persistent workgroups per column tile) of the large-M kernel for this problem: one per CU, two where the LDS
-// images of two workgroups fit a CU (their staging / epilogue phases then overlap the other's K loop)
+// images of two workgroups fit a CU (their staging / epilogue phases then overlap the other's K loop).
+// The occupancy is computed from the FP32 image sizes in BOTH precisions: the one-row-per-workgroup statistics layout
+// follows nprog, and the callers size their buffers (vmtl_conv1x1_stats_rows) without knowing the precision.
 static int pw_big_nprog(int M, int ldy, const BigCfg& c) {
   const int tiles_m = cdiv(M, c.bm), tiles_n = cdiv(ldy, c.bn);
   const int a_floats = c.kc * c.bm * 32, o_floats = c.bm * (c.bn + 4);
@@ -712,12 +811,13 @@ static int pw_num_cus() {
   return n;
 }
 
-template <int TM, int TN, int WM, int WN, int KC>
-static int launch_pw_big(PwP& p, hipStream_t st) {
+template <int TM, int TN, int WM, int WN, int KC, bool BF16>
+static int launch_pw_big_t(PwP& p, hipStream_t st) {
   constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
-  constexpr int A_FLOATS = KC * BM * 32, O_FLOATS = BM * (BN + 4);
+  constexpr int KF = BF16 ? 16 : 32;  // as in the kernel: floats per row and K chunk
+  constexpr int A_FLOATS = KC * BM * KF, O_FLOATS = BM * (BN + 4);
   constexpr int NTHR = WM * WN * 64;
-  constexpr size_t lds = ((size_t)KC * BN * 32 + (A_FLOATS > O_FLOATS ? A_FLOATS : O_FLOATS)) * 4 + 2 * NTHR * 16;
+  constexpr size_t lds = ((size_t)KC * BN * KF + (A_FLOATS > O_FLOATS ? A_FLOATS : O_FLOATS)) * 4 + 2 * NTHR * 16;
   static_assert(lds <= 160 * 1024, "LDS budget");
   p.tiles_m = cdiv(p.M, BM);
   p.tiles_n = cdiv(p.ldy, BN);
@@ -728,11 +828,11 @@ static int launch_pw_big(PwP& p, hipStream_t st) {
   {                                                                                                                     \
     static bool attr_set = false;                                                                                       \
     if (!attr_set) {                                                                                                    \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_big_kernel<TM, TN, WM, WN, KC, SRC2, PRO, EZ>),       \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_big_kernel<TM, TN, WM, WN, KC, SRC2, PRO, EZ, BF16>), \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                 \
       attr_set = true;                                                                                                  \
     }                                                                                                                   \
-    hipLaunchKernelGGL((pw_big_kernel<TM, TN, WM, WN, KC, SRC2, PRO, EZ>), grid, dim3(NTHR), lds, st, p, nprog);        \
+    hipLaunchKernelGGL((pw_big_kernel<TM, TN, WM, WN, KC, SRC2, PRO, EZ, BF16>), grid, dim3(NTHR), lds, st, p, nprog);  \
   }
   if (p.ez_x != nullptr) VMTL_PW_BIG_LAUNCH(false, false, true)
   else if (p.x2 != nullptr) VMTL_PW_BIG_LAUNCH(true, false, false)
@@ -742,38 +842,49 @@ static int launch_pw_big(PwP& p, hipStream_t st) {
   return vmtl_check_launch();
 }
 
-static int pw_big_dispatch(PwP& p, const BigCfg& c, hipStream_t st) {
+template <int TM, int TN, int WM, int WN, int KC>
+static int launch_pw_big(PwP& p, int prec, hipStream_t st) {
+  return prec == VMTL_PREC_BF16 ? launch_pw_big_t<TM, TN, WM, WN, KC, true>(p, st)
+                                : launch_pw_big_t<TM, TN, WM, WN, KC, false>(p, st);
+}
+
+static int pw_big_dispatch(PwP& p, const BigCfg& c, int prec, hipStream_t st) {
   static EnvInt e_w8{"VMTL_PW_BIG_WAVES", 8};  // tuning aid: 4 = the 4-wave workgroups (one wave per SIMD)
   const bool w8 = env_int(e_w8) == 8;
   switch (c.id) {
     case 0:  // 64 x 128
       if (w8)
-        return c.kc == 2 ? launch_pw_big<2, 2, 2, 4, 2>(p, st) : c.kc == 4 ? launch_pw_big<2, 2, 2, 4, 4>(p, st)
-                                                                          : launch_pw_big<2, 2, 2, 4, 6>(p, st);
-      return c.kc == 2 ? launch_pw_big<2, 4, 2, 2, 2>(p, st) : c.kc == 4 ? launch_pw_big<2, 4, 2, 2, 4>(p, st)
-                                                                        : launch_pw_big<2, 4, 2, 2, 6>(p, st);
+        return c.kc == 2 ? launch_pw_big<2, 2, 2, 4, 2>(p, prec, st) : c.kc == 4 ? launch_pw_big<2, 2, 2, 4, 4>(p, prec, st)
+                                                                          : launch_pw_big<2, 2, 2, 4, 6>(p, prec, st);
+      return c.kc == 2 ? launch_pw_big<2, 4, 2, 2, 2>(p, prec, st) : c.kc == 4 ? launch_pw_big<2, 4, 2, 2, 4>(p, prec, st)
+                                                                        : launch_pw_big<2, 4, 2, 2, 6>(p, prec, st);
     case 1:  // 64 x 64
-      if (w8) return c.kc == 4 ? launch_pw_big<2, 1, 2, 4, 4>(p, st) : launch_pw_big<2, 1, 2, 4, 8>(p, st);
-      return c.kc == 4 ? launch_pw_big<2, 2, 2, 2, 4>(p, st) : launch_pw_big<2, 2, 2, 2, 8>(p, st);
+      if (w8) return c.kc == 4 ? launch_pw_big<2, 1, 2, 4, 4>(p, prec, st) : launch_pw_big<2, 1, 2, 4, 8>(p, prec, st);
+      return c.kc == 4 ? launch_pw_big<2, 2, 2, 2, 4>(p, prec, st) : launch_pw_big<2, 2, 2, 2, 8>(p, prec, st);
     case 2:  // 64 x 32 (8 waves only)
-      return launch_pw_big<1, 1, 4, 2, 4>(p, st);
+      return launch_pw_big<1, 1, 4, 2, 4>(p, prec, st);
     default:  // 64 x 96
-      if (w8) return launch_pw_big<1, 3, 4, 2, 4>(p, st);
-      return launch_pw_big<2, 3, 2, 2, 4>(p, st);
+      if (w8) return launch_pw_big<1, 3, 4, 2, 4>(p, prec, st);
+      return launch_pw_big<2, 3, 2, 2, 4>(p, prec, st);
   }
 }
 
-template <int TN, int KW>
-static int launch_pw(PwP& p, hipStream_t st) {
+template <int TN, int KW, bool BF16>
+static int launch_pw_t(PwP& p, hipStream_t st) {
   p.tiles_m = cdiv(p.M, (4 / KW) * 32);
   p.tiles_n = cdiv(p.ldy, 16 * TN);
   if (p.x2 != nullptr)
-    hipLaunchKernelGGL((pw_gemm_kernel<TN, KW, true>), dim3(p.tiles_m * p.tiles_n), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((pw_gemm_kernel<TN, KW, true, false, BF16>), dim3(p.tiles_m * p.tiles_n), dim3(256), 0, st, p);
   else if (p.pa != nullptr)
-    hipLaunchKernelGGL((pw_gemm_kernel<TN, KW, false, true>), dim3(p.tiles_m * p.tiles_n), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((pw_gemm_kernel<TN, KW, false, true, BF16>), dim3(p.tiles_m * p.tiles_n), dim3(256), 0, st, p);
   else
-    hipLaunchKernelGGL((pw_gemm_kernel<TN, KW>), dim3(p.tiles_m * p.tiles_n), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((pw_gemm_kernel<TN, KW, false, false, BF16>), dim3(p.tiles_m * p.tiles_n), dim3(256), 0, st, p);
   return vmtl_check_launch();
+}
+
+template <int TN, int KW>
+static int launch_pw(PwP& p, int prec, hipStream_t st) {
+  return prec == VMTL_PREC_BF16 ? launch_pw_t<TN, KW, true>(p, st) : launch_pw_t<TN, KW, false>(p, st);
 }
 
 static void pw_plain(PwP& p) {  // no prologue, ordinary epilogue
@@ -781,33 +892,44 @@ static void pw_plain(PwP& p) {  // no prologue, ordinary epilogue
   p.ez_x = p.ez_mean = p.ez_invstd = p.ez_gamma = p.ez_beta = p.ez_add = nullptr; p.ez_act = 0;
 }
 
-static int pw_dispatch(PwP& p, hipStream_t st) {
+// kernel and tile choice do not look at the precision: the statistics geometry is the same in both
+static int pw_dispatch(PwP& p, int prec, hipStream_t st) {
   BigCfg c;
-  if (p.ez_add == nullptr && p.res == nullptr && pw_big_cfg(p.M, p.ldy, p.Ks, &c)) return pw_big_dispatch(p, c, st);
+  if (p.ez_add == nullptr && p.res == nullptr && pw_big_cfg(p.M, p.ldy, p.Ks, &c)) return pw_big_dispatch(p, c, prec, st);
   int tn, kw;
   pw_pick(p.M, p.ldy, p.Ks, &tn, &kw);
-  if (tn == 2) return kw == 4 ? launch_pw<2, 4>(p, st) : launch_pw<2, 1>(p, st);
-  return kw == 4 ? launch_pw<4, 4>(p, st) : launch_pw<4, 1>(p, st);
+  if (tn == 2) return kw == 4 ? launch_pw<2, 4>(p, prec, st) : launch_pw<2, 1>(p, prec, st);
+  return kw == 4 ? launch_pw<4, 4>(p, prec, st) : launch_pw<4, 1>(p, prec, st);
 }
 
-extern "C" int vmtl_conv1x1_fwd(const float* x, const float* wp, const float* bias, float* y, float* stats, int M, int Ks,
-                                int ldy, int Nw, int Cout, void* stream) {
+// Entry points.  Every vmtl_conv1x1_X_p takes X's arguments plus `precision` (VMTL_PREC_*) before the stream and checks it
+// first; X itself is the VMTL_PREC_FP32 call.
+extern "C" int vmtl_conv1x1_fwd_p(const float* x, const float* wp, const float* bias, float* y, float* stats, int M, int Ks,
+                                  int ldy, int Nw, int Cout, int precision, void* stream) {
   VMTL_ENTER();
+  if (!valid_prec(precision)) return VMTL_ERR_ARG;
   if (!x || !wp || !y || M <= 0 || Ks <= 0 || (Ks & 3) || ldy <= 0 || (ldy & 3)) return VMTL_ERR_ARG;
   if (Nw <= 0 || Nw > ldy || Cout <= 0 || Cout > Nw) return VMTL_ERR_ARG;
   PwP p;
   p.x = x; p.wp = wp; p.bias = bias; p.y = y; p.stats = stats; p.M = M; p.Ks = Ks; p.ldy = ldy; p.Nw = Nw; p.Cout = Cout;
   p.x2 = nullptr; p.y2 = nullptr; p.K1 = 0; p.N1 = 0;
   pw_plain(p);
-  return pw_dispatch(p, (hipStream_t)stream);
+  return pw_dispatch(p, precision, (hipStream_t)stream);
+}
+
+extern "C" int vmtl_conv1x1_fwd(const float* x, const float* wp, const float* bias, float* y, float* stats, int M, int Ks,
+                                int ldy, int Nw, int Cout, void* stream) {
+  return vmtl_conv1x1_fwd_p(x, wp, bias, y, stats, M, Ks, ldy, Nw, Cout, VMTL_PREC_FP32, stream);
 }
 
 // conv1x1(cat[x, x2]) without the concat: x is [M][K1] (K1 % 4 == 0), x2 is [M][K2s], the packed weight rows are
 // [Nw][K1 + K2s] (the ordinary packing of the (Nw, K1 + C2) weight).  Statistics geometry = vmtl_conv1x1_stats_*(M, ldy,
 // K1 + K2s).
-extern "C" int vmtl_conv1x1_cat_fwd(const float* x, int K1, const float* x2, int K2s, const float* wp, const float* bias,
-                                    float* y, float* stats, int M, int ldy, int Nw, int Cout, void* stream) {
+extern "C" int vmtl_conv1x1_cat_fwd_p(const float* x, int K1, const float* x2, int K2s, const float* wp, const float* bias,
+                                      float* y, float* stats, int M, int ldy, int Nw, int Cout, int precision,
+                                      void* stream) {
   VMTL_ENTER();
+  if (!valid_prec(precision)) return VMTL_ERR_ARG;
   if (!x || !x2 || !wp || !y || M <= 0 || K1 <= 0 || (K1 & 3) || K2s <= 0 || (K2s & 3) || ldy <= 0 || (ldy & 3))
     return VMTL_ERR_ARG;
   if (Nw <= 0 || Nw > ldy || Cout <= 0 || Cout > Nw) return VMTL_ERR_ARG;
@@ -815,14 +937,20 @@ extern "C" int vmtl_conv1x1_cat_fwd(const float* x, int K1, const float* x2, int
   p.x = x; p.wp = wp; p.bias = bias; p.y = y; p.stats = stats; p.M = M; p.Ks = K1 + K2s; p.ldy = ldy; p.Nw = Nw;
   p.Cout = Cout; p.x2 = x2; p.y2 = nullptr; p.K1 = K1; p.N1 = 0;
   pw_plain(p);
-  return pw_dispatch(p, (hipStream_t)stream);
+  return pw_dispatch(p, precision, (hipStream_t)stream);
+}
+
+extern "C" int vmtl_conv1x1_cat_fwd(const float* x, int K1, const float* x2, int K2s, const float* wp, const float* bias,
+                                    float* y, float* stats, int M, int ldy, int Nw, int Cout, void* stream) {
+  return vmtl_conv1x1_cat_fwd_p(x, K1, x2, K2s, wp, bias, y, stats, M, ldy, Nw, Cout, VMTL_PREC_FP32, stream);
 }
 
 // its data gradient: [dx | dx2] = dy * W without a split pass: output columns [0, N1) (N1 % 4 == 0) land in dx
 // ([M][N1]), columns [N1, N1 + N2s) in dx2 ([M][N2s]; columns past the N2 real ones are zero).  wp: [N1 + N2][Ks].
-extern "C" int vmtl_conv1x1_cat_dgrad(const float* dy, const float* wp, float* dx, int N1, float* dx2, int N2s, int N2,
-                                      int M, int Ks, void* stream) {
+extern "C" int vmtl_conv1x1_cat_dgrad_p(const float* dy, const float* wp, float* dx, int N1, float* dx2, int N2s, int N2,
+                                        int M, int Ks, int precision, void* stream) {
   VMTL_ENTER();
+  if (!valid_prec(precision)) return VMTL_ERR_ARG;
   if (!dy || !wp || !dx || !dx2 || M <= 0 || Ks <= 0 || (Ks & 3) || N1 <= 0 || (N1 & 3) || N2s <= 0 || (N2s & 3) ||
       N2 <= 0 || N2 > N2s)
     return VMTL_ERR_ARG;
@@ -830,7 +958,12 @@ extern "C" int vmtl_conv1x1_cat_dgrad(const float* dy, const float* wp, float* d
   p.x = dy; p.wp = wp; p.bias = nullptr; p.y = dx; p.stats = nullptr; p.M = M; p.Ks = Ks; p.ldy = N1 + N2s;
   p.Nw = N1 + N2; p.Cout = N1 + N2; p.x2 = nullptr; p.y2 = dx2; p.K1 = 0; p.N1 = N1;
   pw_plain(p);
-  return pw_dispatch(p, (hipStream_t)stream);
+  return pw_dispatch(p, precision, (hipStream_t)stream);
+}
+
+extern "C" int vmtl_conv1x1_cat_dgrad(const float* dy, const float* wp, float* dx, int N1, float* dx2, int N2s, int N2,
+                                      int M, int Ks, void* stream) {
+  return vmtl_conv1x1_cat_dgrad_p(dy, wp, dx, N1, dx2, N2s, N2, M, Ks, VMTL_PREC_FP32, stream);
 }
 
 // conv1x1(act(coef_a[k] * x + coef_c[k])): the BatchNorm + activation of the layer that produced x (coefficients from
@@ -838,7 +971,7 @@ extern "C" int vmtl_conv1x1_cat_dgrad(const float* dy, const float* wp, float* d
 // fragments; a_out (nullable, [M][Ks]) receives the activated matrix for the weight gradient.
 static int conv1x1_bn_fwd_impl(const float* x, const float* coef_a, const float* coef_c, int act_in, const float* res,
                                float* a_out, const float* wp, const float* bias, float* y, float* stats, int M, int Ks,
-                               int ldy, int Nw, int Cout, void* stream) {
+                               int ldy, int Nw, int Cout, int prec, void* stream) {
   if (!x || !coef_a || !coef_c || !wp || !y || M <= 0 || Ks <= 0 || (Ks & 3) || ldy <= 0 || (ldy & 3)) return VMTL_ERR_ARG;
   if (Nw <= 0 || Nw > ldy || Cout <= 0 || Cout > Nw) return VMTL_ERR_ARG;
   if (act_in != VMTL_ACT_NONE && act_in != VMTL_ACT_RELU && act_in != VMTL_ACT_HSWISH) return VMTL_ERR_ARG;
@@ -847,24 +980,43 @@ static int conv1x1_bn_fwd_impl(const float* x, const float* coef_a, const float*
   p.x2 = nullptr; p.y2 = nullptr; p.K1 = 0; p.N1 = 0;
   pw_plain(p);
   p.pa = coef_a; p.pc = coef_c; p.res = res; p.a_out = a_out; p.act_in = act_in;
-  return pw_dispatch(p, (hipStream_t)stream);
+  return pw_dispatch(p, prec, (hipStream_t)stream);
+}
+
+extern "C" int vmtl_conv1x1_bn_fwd_p(const float* x, const float* coef_a, const float* coef_c, int act_in, float* a_out,
+                                     const float* wp, const float* bias, float* y, float* stats, int M, int Ks, int ldy,
+                                     int Nw, int Cout, int precision, void* stream) {
+  VMTL_ENTER();
+  if (!valid_prec(precision)) return VMTL_ERR_ARG;
+  return conv1x1_bn_fwd_impl(x, coef_a, coef_c, act_in, nullptr, a_out, wp, bias, y, stats, M, Ks, ldy, Nw, Cout, precision,
+                             stream);
 }
 
 extern "C" int vmtl_conv1x1_bn_fwd(const float* x, const float* coef_a, const float* coef_c, int act_in, float* a_out,
                                    const float* wp, const float* bias, float* y, float* stats, int M, int Ks, int ldy,
                                    int Nw, int Cout, void* stream) {
-  VMTL_ENTER();
-  return conv1x1_bn_fwd_impl(x, coef_a, coef_c, act_in, nullptr, a_out, wp, bias, y, stats, M, Ks, ldy, Nw, Cout, stream);
+  return vmtl_conv1x1_bn_fwd_p(x, coef_a, coef_c, act_in, a_out, wp, bias, y, stats, M, Ks, ldy, Nw, Cout, VMTL_PREC_FP32,
+                               stream);
 }
 
 // the same with a residual operand: the GEMM's input is a = act(coef_a*x + coef_c) + res (an inverted-residual
 // block's bn3 output plus its skip connection, consumed by the next block's expand conv); a_out receives a.
+extern "C" int vmtl_conv1x1_bn_res_fwd_p(const float* x, const float* coef_a, const float* coef_c, int act_in,
+                                         const float* res, float* a_out, const float* wp, const float* bias, float* y,
+                                         float* stats, int M, int Ks, int ldy, int Nw, int Cout, int precision,
+                                         void* stream) {
+  VMTL_ENTER();
+  if (!valid_prec(precision)) return VMTL_ERR_ARG;
+  if (!res) return VMTL_ERR_ARG;
+  return conv1x1_bn_fwd_impl(x, coef_a, coef_c, act_in, res, a_out, wp, bias, y, stats, M, Ks, ldy, Nw, Cout, precision,
+                             stream);
+}
+
 extern "C" int vmtl_conv1x1_bn_res_fwd(const float* x, const float* coef_a, const float* coef_c, int act_in,
                                        const float* res, float* a_out, const float* wp, const float* bias, float* y,
                                        float* stats, int M, int Ks, int ldy, int Nw, int Cout, void* stream) {
-  VMTL_ENTER();
-  if (!res) return VMTL_ERR_ARG;
-  return conv1x1_bn_fwd_impl(x, coef_a, coef_c, act_in, res, a_out, wp, bias, y, stats, M, Ks, ldy, Nw, Cout, stream);
+  return vmtl_conv1x1_bn_res_fwd_p(x, coef_a, coef_c, act_in, res, a_out, wp, bias, y, stats, M, Ks, ldy, Nw, Cout,
+                                   VMTL_PREC_FP32, stream);
 }
 
 // data gradient of a 1x1 conv whose input was act(BN(ez_x)), ending with that activation's and BatchNorm's backward:
@@ -872,7 +1024,8 @@ extern "C" int vmtl_conv1x1_bn_res_fwd(const float* x, const float* coef_a, cons
 // per-row-block (sum dz, sum dz * xhat) for vmtl_bn_bwd_finalize / vmtl_bn_bwd_apply.
 static int conv1x1_bnbwd_impl(const float* dy, const float* wp, const float* addend, float* dz, float* stats,
                               const float* ez_x, const float* ez_mean, const float* ez_invstd, const float* ez_gamma,
-                              const float* ez_beta, int ez_act, int M, int Ks, int ldy, int Nw, int Cout, void* stream) {
+                              const float* ez_beta, int ez_act, int M, int Ks, int ldy, int Nw, int Cout, int prec,
+                              void* stream) {
   if (!dy || !wp || !dz || !stats || !ez_x || !ez_mean || !ez_invstd || M <= 0 || Ks <= 0 || (Ks & 3) || ldy <= 0 ||
       (ldy & 3))
     return VMTL_ERR_ARG;
@@ -883,26 +1036,45 @@ static int conv1x1_bnbwd_impl(const float* dy, const float* wp, const float* add
   pw_plain(p);
   p.ez_x = ez_x; p.ez_mean = ez_mean; p.ez_invstd = ez_invstd; p.ez_gamma = ez_gamma; p.ez_beta = ez_beta; p.ez_act = ez_act;
   p.ez_add = addend;
-  return pw_dispatch(p, (hipStream_t)stream);
+  return pw_dispatch(p, prec, (hipStream_t)stream);
+}
+
+extern "C" int vmtl_conv1x1_bnbwd_p(const float* dy, const float* wp, float* dz, float* stats, const float* ez_x,
+                                    const float* ez_mean, const float* ez_invstd, const float* ez_gamma,
+                                    const float* ez_beta, int ez_act, int M, int Ks, int ldy, int Nw, int Cout,
+                                    int precision, void* stream) {
+  VMTL_ENTER();
+  if (!valid_prec(precision)) return VMTL_ERR_ARG;
+  return conv1x1_bnbwd_impl(dy, wp, nullptr, dz, stats, ez_x, ez_mean, ez_invstd, ez_gamma, ez_beta, ez_act, M, Ks, ldy,
+                            Nw, Cout, precision, stream);
 }
 
 extern "C" int vmtl_conv1x1_bnbwd(const float* dy, const float* wp, float* dz, float* stats, const float* ez_x,
                                   const float* ez_mean, const float* ez_invstd, const float* ez_gamma,
                                   const float* ez_beta, int ez_act, int M, int Ks, int ldy, int Nw, int Cout,
                                   void* stream) {
-  VMTL_ENTER();
-  return conv1x1_bnbwd_impl(dy, wp, nullptr, dz, stats, ez_x, ez_mean, ez_invstd, ez_gamma, ez_beta, ez_act, M, Ks, ldy,
-                            Nw, Cout, stream);
+  return vmtl_conv1x1_bnbwd_p(dy, wp, dz, stats, ez_x, ez_mean, ez_invstd, ez_gamma, ez_beta, ez_act, M, Ks, ldy, Nw, Cout,
+                              VMTL_PREC_FP32, stream);
 }
 
 // the same with a second gradient of the differentiated tensor (the block's residual / skip consumers) added to the
-// GEMM result before the activation's and BatchNorm's backward: dz = (dy*W + addend) * act'(...)
+// GEMM result before the activation's and BatchNorm's backward: dz = (dy*W + addend) * act'(...); the addend is fp32
+// in both precisions
+extern "C" int vmtl_conv1x1_bnbwd_add_p(const float* dy, const float* wp, const float* addend, float* dz, float* stats,
+                                        const float* ez_x, const float* ez_mean, const float* ez_invstd,
+                                        const float* ez_gamma, const float* ez_beta, int ez_act, int M, int Ks, int ldy,
+                                        int Nw, int Cout, int precision, void* stream) {
+  VMTL_ENTER();
+  if (!valid_prec(precision)) return VMTL_ERR_ARG;
+  if (!addend) return VMTL_ERR_ARG;
+  return conv1x1_bnbwd_impl(dy, wp, addend, dz, stats, ez_x, ez_mean, ez_invstd, ez_gamma, ez_beta, ez_act, M, Ks, ldy,
+                            Nw, Cout, precision, stream);
+}
+
 extern "C" int vmtl_conv1x1_bnbwd_add(const float* dy, const float* wp, const float* addend, float* dz, float* stats,
                                       const float* ez_x, const float* ez_mean, const float* ez_invstd,
                                       const float* ez_gamma, const float* ez_beta, int ez_act, int M, int Ks, int ldy,
                                       int Nw, int Cout, void* stream) {
-  VMTL_ENTER();
-  if (!addend) return VMTL_ERR_ARG;
-  return conv1x1_bnbwd_impl(dy, wp, addend, dz, stats, ez_x, ez_mean, ez_invstd, ez_gamma, ez_beta, ez_act, M, Ks, ldy,
-                            Nw, Cout, stream);
+  return vmtl_conv1x1_bnbwd_add_p(dy, wp, addend, dz, stats, ez_x, ez_mean, ez_invstd, ez_gamma, ez_beta, ez_act, M, Ks,
+                                  ldy, Nw, Cout, VMTL_PREC_FP32, stream);
 }

@@ -19,7 +19,7 @@ from typing import NamedTuple
 import torch
 
 from ._lib import lib
-from .precision import conv_prec_code
+from .precision import conv_prec_code, pw_prec_code
 
 ACT_NONE, ACT_RELU, ACT_HSWISH, ACT_HSIGMOID, ACT_SIGMOID = 0, 1, 2, 3, 4
 ACT_CODES = {None: 0, "none": 0, "relu": 1, "hardswish": 2, "hardsigmoid": 3, "sigmoid": 4}
@@ -58,7 +58,9 @@ def _k(name, _flop=None, _xflop=None, **kw):
 def _kp(name, prec, _flop=None, _xflop=None, **kw):
     """A launch of an entry point that has a precision variant (include/vmtl.h VMTL_PREC_*).  fp32 (0) calls the legacy
     entry point with its legacy keywords - bench.py sorts the launches it records into families BY NAME - and only
-    bf16 calls the `_p` variant.  `prec` is what the autograd node recorded in its forward (precision.conv_prec_code)."""
+    bf16 calls the `_p` variant.  `prec` is what the autograd node recorded in its forward: precision.conv_prec_code for the
+    implicit-GEMM convolutions and the weight gradients, precision.pw_prec_code for the pointwise GEMMs (vmtl_conv1x1_*
+    forward and data gradient), which only the "bf16_pw" mode moves to bf16."""
     if prec:
         _k(name + "_p", _flop, _xflop, precision=prec, **kw)
     else:
@@ -704,17 +706,18 @@ def _mid_halo(x, wp, y, B, H, W, Cs, ldy, Nw, Cout, flop, pa=None, pc=None, act_
 
 
 def _conv_launch(x, wp, bias, y, B, H, W, Cs, Ho, Wo, ldy, Nw, Cout, KH, KW, stride, pad, shuffle=0, cin=None,
-                 algo_flop=None, prec=0, plan=None, stats=None):
+                 algo_flop=None, prec=0, plan=None, stats=None, pw_prec=0):
     """One dense conv launch, dispatched on its plan; a launch without an epilogue may leave the planning to this function.
-    stats: the [plan.stats_rows][2][ldy] rows of a plan with the statistics epilogue."""
+    stats: the [plan.stats_rows][2][ldy] rows of a plan with the statistics epilogue.  prec: the implicit GEMM's precision,
+    pw_prec: the pointwise GEMM's (the plan itself does not depend on pw_prec)."""
     if plan is None:
         plan = conv_plan(B, H, W, Cs, Ho, Wo, ldy, KH, KW, stride, pad, shuffle, prec)
     xflop = 2.0 * B * Ho * Wo * Nw * KH * KW * (Cs if cin is None else cin)
     flop = xflop if algo_flop is None else algo_flop
     ep_mode = 1 if stats is not None else 0
     if plan.route == "pw":
-        _k("vmtl_conv1x1_fwd", _flop=flop, _xflop=xflop, x=x, wp=wp, bias=bias, y=y, stats=stats, M=B * Ho * Wo, Ks=Cs,
-           ldy=ldy, Nw=Nw, Cout=Cout)
+        _kp("vmtl_conv1x1_fwd", pw_prec, _flop=flop, _xflop=xflop, x=x, wp=wp, bias=bias, y=y, stats=stats, M=B * Ho * Wo,
+            Ks=Cs, ldy=ldy, Nw=Nw, Cout=Cout)
     elif plan.route == "small":  # narrow full-resolution layer: the halo-tile kernel reads the input once
         _small(x, wp, y, B, H, W, Cs, ldy, Nw, Cout, flop, bias=bias, stats=stats, ep_mode=ep_mode)
     elif plan.route == "mid_halo":  # 64/68-channel layer: the halo-tile kernel reads each input pixel once
@@ -818,8 +821,9 @@ class _Conv2d(torch.autograd.Function):
         y = _empty((B, Ho, Wo, ldy), x)
         stats = _empty((plan.stats_rows, 2, ldy), x) if plan.stats_rows else None
         prec = ctx.prec = conv_prec_code()  # backward runs under the precision of this forward
+        pw_prec = ctx.pw_prec = pw_prec_code()  # (a 1x1 conv on the pointwise route: forward and data gradient)
         _conv_launch(x, wp, bias, y, B, H, W, Cs, Ho, Wo, ldy, Cout, Cout, KH, KW, stride, pad, cin=Cin, prec=prec, plan=plan,
-                     stats=stats)
+                     stats=stats, pw_prec=pw_prec)
         ctx.save_for_backward(x, weight, stitch_w)
         ctx.cfg = (stride, pad, bias is not None)
         ctx.zero_bias_grad = bool(zero_bias_grad)
@@ -863,7 +867,7 @@ class _Conv2d(torch.autograd.Function):
             if stride == 1:
                 dx = _empty((B, H, W, Cs), x)
                 _conv_launch(dy, wd, None, dx, B, Ho, Wo, ldy, H, W, Cs, Cin, Cin, KH, KW, 1, KH - 1 - pad, cin=Cout,
-                             prec=ctx.prec)
+                             prec=ctx.prec, pw_prec=ctx.pw_prec)
         if ctx.needs_input_grad[1] or (stitch_w is not None and ctx.needs_input_grad[7]):
             use_side = ctx.slots[0] is not None and (stitch_w is None or stitch_slot is not None)
             with side.branch(use_side, B * Ho * Wo, fork, x, dy):
@@ -935,15 +939,18 @@ class _BNActPw(torch.autograd.Function):
         ostats = None
         if want_stats:
             ostats = _empty((lib().raw("vmtl_conv1x1_stats_rows")(M, ldy, Cs, 0 if res is None else 1), 2, ldy), x)
+        # the weight gradient runs under conv_prec_code, the pointwise GEMMs (this one and the data gradient) under
+        # pw_prec_code: fp32 unless the mode is "bf16_pw"
+        ctx.prec, pw_prec = conv_prec_code(), pw_prec_code()
+        ctx.pw_prec = pw_prec
         if res is None:
-            _k("vmtl_conv1x1_bn_fwd", _flop=2.0 * M * Cout * Cin, x=x, coef_a=ca, coef_c=cc, act_in=act, a_out=a, wp=wp,
-               bias=bias, y=y, stats=ostats, M=M, Ks=Cs, ldy=ldy, Nw=Cout, Cout=Cout)
+            _kp("vmtl_conv1x1_bn_fwd", pw_prec, _flop=2.0 * M * Cout * Cin, x=x, coef_a=ca, coef_c=cc, act_in=act, a_out=a,
+                wp=wp, bias=bias, y=y, stats=ostats, M=M, Ks=Cs, ldy=ldy, Nw=Cout, Cout=Cout)
         else:
-            _k("vmtl_conv1x1_bn_res_fwd", _flop=2.0 * M * Cout * Cin, x=x, coef_a=ca, coef_c=cc, act_in=act, res=res, a_out=a,
-               wp=wp, bias=bias, y=y, stats=ostats, M=M, Ks=Cs, ldy=ldy, Nw=Cout, Cout=Cout)
+            _kp("vmtl_conv1x1_bn_res_fwd", pw_prec, _flop=2.0 * M * Cout * Cin, x=x, coef_a=ca, coef_c=cc, act_in=act, res=res,
+                a_out=a, wp=wp, bias=bias, y=y, stats=ostats, M=M, Ks=Cs, ldy=ldy, Nw=Cout, Cout=Cout)
         ctx.save_for_backward(x, a, weight, mean, invstd, gamma, beta)
         ctx.cfg = (C, training, act, bias is not None, bool(zero_bias_grad), res is not None)
-        ctx.prec = conv_prec_code()  # the weight gradient's (the pointwise GEMMs themselves stay fp32)
         ctx.slots = (_slot(gamma), _slot(beta), _slot(weight), _slot(bias))
         ctx.bias = bias
         ctx.set_materialize_grads(False)
@@ -976,14 +983,14 @@ class _BNActPw(torch.autograd.Function):
         rows = lib().raw("vmtl_conv1x1_stats_rows")(M, Cs, ldy, 0 if d_a is None else 1)
         part = _empty((rows, 2, Cs), x)
         if d_a is None:
-            _k("vmtl_conv1x1_bnbwd", _flop=2.0 * M * Cin * Cout, dy=dy, wp=wd, dz=dz, stats=part, ez_x=x, ez_mean=mean,
-               ez_invstd=invstd, ez_gamma=gamma, ez_beta=beta, ez_act=act, M=M, Ks=ldy, ldy=Cs, Nw=Cin, Cout=Cin)
+            _kp("vmtl_conv1x1_bnbwd", ctx.pw_prec, _flop=2.0 * M * Cin * Cout, dy=dy, wp=wd, dz=dz, stats=part, ez_x=x,
+                ez_mean=mean, ez_invstd=invstd, ez_gamma=gamma, ez_beta=beta, ez_act=act, M=M, Ks=ldy, ldy=Cs, Nw=Cin, Cout=Cin)
         else:  # + the gradient that reached a through its other consumers, added before act' and the reduction
             if act != ACT_NONE:
                 raise NotImplementedError("bn_act_conv1x1: a second consumer of the activation needs act = none")
-            _k("vmtl_conv1x1_bnbwd_add", _flop=2.0 * M * Cin * Cout, dy=dy, wp=wd, addend=_req(d_a, "d_a"), dz=dz, stats=part,
-               ez_x=x, ez_mean=mean, ez_invstd=invstd, ez_gamma=gamma, ez_beta=beta, ez_act=act, M=M, Ks=ldy, ldy=Cs, Nw=Cin,
-               Cout=Cin)
+            _kp("vmtl_conv1x1_bnbwd_add", ctx.pw_prec, _flop=2.0 * M * Cin * Cout, dy=dy, wp=wd, addend=_req(d_a, "d_a"), dz=dz,
+                stats=part, ez_x=x, ez_mean=mean, ez_invstd=invstd, ez_gamma=gamma, ez_beta=beta, ez_act=act, M=M, Ks=ldy,
+                ldy=Cs, Nw=Cin, Cout=Cin)
         _k("vmtl_bn_bwd_finalize", partial=part, nblk=rows, M=M, C=C, Cs=Cs, sum_dz=dbeta, sum_dzx=dgamma, mean=None,
            invstd=None, gamma=None, training=1 if training else 0, coef_a=None, coef_b=None, coef_c=None)
         dx = None
@@ -1052,11 +1059,12 @@ class _Conv1x1Cat(torch.autograd.Function):
         stats = None
         if want_stats:
             stats = _empty((lib().raw("vmtl_conv1x1_stats_rows")(M, ldy, Ks, 0), 2, ldy), xa)
-        _k("vmtl_conv1x1_cat_fwd", _flop=2.0 * M * Cout * Cin, x=xa, K1=Ca, x2=xb, K2s=Cbs, wp=wp, bias=bias, y=y, stats=stats,
-           M=M, ldy=ldy, Nw=Cout, Cout=Cout)
+        # the weight gradient's precision, and the pointwise GEMMs' (forward here, data gradient in backward)
+        ctx.prec, ctx.pw_prec = conv_prec_code(), pw_prec_code()
+        _kp("vmtl_conv1x1_cat_fwd", ctx.pw_prec, _flop=2.0 * M * Cout * Cin, x=xa, K1=Ca, x2=xb, K2s=Cbs, wp=wp, bias=bias, y=y,
+            stats=stats, M=M, ldy=ldy, Nw=Cout, Cout=Cout)
         ctx.save_for_backward(xa, xb, weight)
         ctx.cfg = (Cb, bias is not None, bool(zero_bias_grad))
-        ctx.prec = conv_prec_code()  # the weight gradient's (the pointwise GEMMs themselves stay fp32)
         ctx.slots = (_slot(weight), _slot(bias))
         ctx.bias = bias
         ctx.set_materialize_grads(False)
@@ -1081,8 +1089,8 @@ class _Conv1x1Cat(torch.autograd.Function):
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             wd = packs.get(weight, "dgrad", (1, Cin, 1, Cout, ldy, 0, 1, 1, Cin, 1))  # [Cin][ldy]
             dxa, dxb = _empty(xa.shape, xa), _empty(xb.shape, xa)
-            _k("vmtl_conv1x1_cat_dgrad", _flop=2.0 * M * Cin * Cout, dy=dy, wp=wd, dx=dxa, N1=Ca, dx2=dxb, N2s=Cbs, N2=Cb,
-               M=M, Ks=ldy)
+            _kp("vmtl_conv1x1_cat_dgrad", ctx.pw_prec, _flop=2.0 * M * Cin * Cout, dy=dy, wp=wd, dx=dxa, N1=Ca, dx2=dxb, N2s=Cbs,
+                N2=Cb, M=M, Ks=ldy)
         if ctx.needs_input_grad[2]:
             with side.branch(sw is not None, M, fork, xa, xb, dy):
                 dwt = _empty(weight.shape, xa) if sw is None else sw
@@ -2607,7 +2615,8 @@ class _DualHead(torch.autograd.Function):
         _copy_vec(bb, bias[Ca:], Cb)
         y = _empty((B, H, W, ldy), x)
         prec = ctx.prec = conv_prec_code()
-        _conv_launch(x, wp, bias, y, B, H, W, Cs, H, W, ldy, N, N, KH, KW, 1, pad, cin=Cin, prec=prec)
+        pw_prec = ctx.pw_prec = pw_prec_code()  # 1x1 heads take the pointwise route
+        _conv_launch(x, wp, bias, y, B, H, W, Cs, H, W, ldy, N, N, KH, KW, 1, pad, cin=Cin, prec=prec, pw_prec=pw_prec)
         oa, ob = _empty((B, Ca, H, W), x), _empty((B, Cb, H, W), x)
         yf = y.view(-1)
         _k("vmtl_nhwc_to_nchw", x=yf, y=oa, B=B, C=Ca, HW=H * W, Cs=ldy)
@@ -2643,7 +2652,7 @@ class _DualHead(torch.autograd.Function):
                sc=Cin * KK, flip=1)
             dx = _empty((B, H, W, Cs), x)
             _conv_launch(dy, wd, None, dx, B, H, W, ldy, H, W, Cs, Cin, Cin, KH, KW, 1, KH - 1 - pad, cin=N,
-                         prec=ctx.prec)
+                         prec=ctx.prec, pw_prec=ctx.pw_prec)
         with side.branch(all(s is not None for s in ctx.slots), B * H * W, fork, x, dy):
             slabs, ns = _wgrad(x, dy, B, H, W, Cs, H, W, ldy, N, KH, KW, 1, pad, 2.0 * B * H * W * N * KK * Cin,
                                prec=ctx.prec)
