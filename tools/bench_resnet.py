@@ -94,13 +94,14 @@ def bench_dgrad(B, H, W, steps, warmup, dev):
         wt = torch.randn(cout, cin, K, K, device=dev)
         Ho, Wo = (hh + 2 * pad - K) // 2 + 1, (ww + 2 * pad - K) // 2 + 1
         dy2 = torch.randn(B, Ho, Wo, ldy, device=dev)
-        s2 = _events(lambda: ops._dgrad_s2(dy2, wt, B, hh, ww, Cs, Ho, Wo, ldy, K, pad, 0), steps, warmup)
+        g2 = ops.ConvGeom.of((B, hh, ww, Cs), ldy, K, K, 2, pad)
+        s2 = _events(lambda: ops._dgrad_s2(dy2, wt, g2, 0), steps, warmup)
         dy1 = torch.randn(B, hh, ww, ldy, device=dev)
         KK = K * K
-        wd = ops.packs.get(wt, "dgrad", (1, cin, KK, cout, ldy, 0, KK, 1, cin * KK, 1))
+        wd = ops.packs.get(wt, "dgrad", ops.Layout.dgrad(cout, cin, KK, ldy))
         dx = torch.empty(B, hh, ww, Cs, device=dev)
-        s1 = _events(lambda: ops._conv_launch(dy1, wd, None, dx, B, hh, ww, ldy, hh, ww, Cs, cin, cin, K, K, 1, K - 1 - pad,
-                                              cin=cout), steps, warmup)
+        g1 = ops.ConvGeom.of((B, hh, ww, Cs), ldy, K, K, 1, pad).dgrad()
+        s1 = _events(lambda: ops._conv_launch(dy1, wd, None, dx, g1, Cout=cin, cin=cout), steps, warmup)
         f2, f1 = 2.0 * B * Ho * Wo * cout * KK * cin, 2.0 * B * hh * ww * cout * KK * cin
         out.append(dict(step="dgrad", layer=name, batch=B, in_hw=[hh, ww], K=K, cin=cin, cout=cout,
                         s2_ms=round(s2, 4), s2_tflops=round(f2 / s2 / 1e9, 2), s1_ms=round(s1, 4),

@@ -12,6 +12,7 @@ the calling module.
 from __future__ import annotations
 
 import contextlib
+import functools
 import os
 import weakref
 from typing import NamedTuple
@@ -100,6 +101,107 @@ def _empty(shape, like):
 
 def _reduce_rows(M: int) -> int:
     return lib().raw("vmtl_reduce_rows")(M)
+
+
+def _grad_buf(shape, slot, like):
+    """The buffer a parameter gradient is written into: the parameter's arena slot (_slot), else a fresh tensor."""
+    return _empty(shape, like) if slot is None else slot
+
+
+def _grad_ret(g, slot):
+    """What autograd is told about the gradient in _grad_buf's buffer: nothing when the slot took it (handing it back as
+    well would put it into the arena twice)."""
+    return None if slot is not None else g
+
+
+# ----------------------------------------------------------------------------- weight layouts / conv geometry
+class Layout(NamedTuple):
+    """How a torch-layout parameter becomes a packed GEMM operand (vmtl_pack_weights, formula in csrc/pack.hip) and how the
+    operand's gradient goes back (vmtl_unpack_weights, the exact inverse):
+        packed[r1 * R0 + r0][t' * Cs + c] = src[r1 * sr1 + r0 * sr0 + t * st + c * sc]  (c < C, else 0),  t' = T-1-t if flip.
+    A plain tuple to everything that consumes it: the pack-cache keys, the descriptor table, pack(src, *layout).
+    The constructors are pure functions of a few integers that a model repeats every step, so they are memoised: on the
+    eager launch path a layout is a dictionary lookup, not a tuple built per call.
+    The two heads of decoder_tail / dual_head use fwd / dgrad per head, with the GROUP's row width as Cs / ldy."""
+    R1: int
+    R0: int
+    T: int
+    C: int
+    Cs: int
+    sr1: int
+    sr0: int
+    st: int
+    sc: int
+    flip: int
+
+    @classmethod
+    @functools.lru_cache(maxsize=None)
+    def fwd(cls, Cout, Cin, KK, Cs, Cw=None):
+        """Forward operand [Cout][KK][Cs] of a dense conv with a (Cout, Cin, KH, KW) weight, KK = KH * KW.  Cw: the weight
+        holds Cw > Cin input channels and Cin consecutive ones are read (pack with offset = first channel * KK)."""
+        return cls(1, Cout, KK, Cin, Cs, 0, (Cin if Cw is None else Cw) * KK, 1, KK, 0)
+
+    @classmethod
+    @functools.lru_cache(maxsize=None)
+    def dgrad(cls, Cout, Cin, KK, ldy, Cw=None):
+        """Data-gradient operand [Cin][KK][ldy] of the same conv: transposed, taps flipped.  Cw as in fwd."""
+        return cls(1, Cin, KK, Cout, ldy, 0, KK, 1, (Cin if Cw is None else Cw) * KK, 1)
+
+    @classmethod
+    @functools.lru_cache(maxsize=None)
+    def ct_fwd(cls, Cin, Cout, Cs):
+        """ConvTranspose2d(k=2, s=2), (Cin, Cout, 2, 2) weight: one [Cout][Cs] block per output phase."""
+        return cls(4, Cout, 1, Cin, Cs, 1, 4, 0, Cout * 4, 0)
+
+    @classmethod
+    @functools.lru_cache(maxsize=None)
+    def ct_bwd(cls, Cin, Cout, ldy):
+        """Its data gradient, a 2x2 / stride-2 conv over dy: [Cin][4][ldy]."""
+        return cls(1, Cin, 4, Cout, ldy, 0, Cout * 4, 1, 4, 0)
+
+    @classmethod
+    @functools.lru_cache(maxsize=None)
+    def dw(cls, C, K, Cs):
+        """Depthwise (C, 1, K, K) weight as [K * K][Cs]."""
+        return cls(1, 1, K * K, C, Cs, 0, 0, 1, K * K, 0)
+
+    @classmethod
+    @functools.lru_cache(maxsize=None)
+    def vec(cls, n):
+        """A bias / per-channel vector of n entries, copied as it is."""
+        return cls(1, 1, 1, n, n, 0, 0, 0, 1, 0)
+
+
+class ConvGeom(NamedTuple):
+    """One dense conv launch [B, H, W, Cs] -> [B, Ho, Wo, ldy] (storage channel widths), KH x KW taps."""
+    B: int
+    H: int
+    W: int
+    Cs: int
+    Ho: int
+    Wo: int
+    ldy: int
+    KH: int
+    KW: int
+    stride: int
+    pad: int
+
+    @classmethod
+    def of(cls, xshape, ldy, KH, KW, stride=1, pad=0):
+        B, H, W, Cs = xshape
+        return cls(B, H, W, Cs, (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1, ldy, KH, KW, stride, pad)
+
+    @property
+    def M(self):
+        """Rows of the GEMM: output pixels."""
+        return self.B * self.Ho * self.Wo
+
+    def dgrad(self):
+        """The data gradient of this (stride-1) conv as a conv launch of its own, dy -> dx on the Layout.dgrad operand:
+        extents and channel widths swapped, pad K - 1 - pad."""
+        B, H, W, Cs, Ho, Wo, ldy, KH, KW, stride, pad = self
+        assert stride == 1, "ConvGeom.dgrad: stride-1 convs only (a stride-2 conv goes through _dgrad_s2)"
+        return ConvGeom(B, Ho, Wo, ldy, H, W, Cs, KH, KW, 1, KH - 1 - pad)
 
 
 # ----------------------------------------------------------------------------- weight-gradient branch
@@ -266,7 +368,7 @@ class _PackCache:
             self.dirty = True
 
     def get(self, weight, kind, params, offset=0, out=None, scale=None):
-        """params = (R1, R0, T, C, Cs, sr1, sr0, st, sc, flip); offset = first element of the weight to read;
+        """params = the operand's Layout; offset = first element of the weight to read;
         out: destination for a NEW entry (a slice of a caller-owned persistent buffer, see shared());
         scale = (tensor, first element, stride, smode): a cross-stitch factor folded into the operand
         (vmtl_pack_weights_scaled) - the entry is then also invalidated by a change of that tensor."""
@@ -546,16 +648,19 @@ def pack(src, R1, R0, T, C, Cs, sr1, sr0, st, sc, flip=0, out=None):
     return dst
 
 
-def unpack(packed, shape, R1, R0, T, C, Cs, sr1, sr0, st, sc, flip=0, out=None, nslabs=1, slab_stride=0):
-    grad = _empty(shape, packed) if out is None else out
-    _k("vmtl_unpack_weights", packed=packed, grad=grad, R1=R1, R0=R0, T=T, C=C, Cs=Cs, sr1=sr1, sr0=sr0, st=st,
+def unpack(packed, layout, out, nslabs=1, slab_stride=0):
+    """Sum the nslabs weight-gradient slabs of an operand into `out` in the torch layout; `layout` is the Layout the
+    operand of that GEMM was (or would be) packed with - the unpack is its inverse."""
+    R1, R0, T, C, Cs, sr1, sr0, st, sc, flip = layout
+    _k("vmtl_unpack_weights", packed=packed, grad=out, R1=R1, R0=R0, T=T, C=C, Cs=Cs, sr1=sr1, sr0=sr0, st=st,
        sc=sc, flip=flip, nslabs=nslabs, slab_stride=slab_stride)
-    return grad
+    return out
 
 
-def _wgrad(x, dy, B, H, W, Cs, Ho, Wo, ldy, Nw, KH, KW, stride, pad, flop, xflop=None, prec=0):
-    """Weight-gradient slabs [splits][Nw][KH*KW*Cs] (summed later by unpack).  prec applies to the dense kernel only (the
-    narrow halo-tile kernel stays fp32)."""
+def _wgrad(x, dy, g, *, Nw, flop, xflop=None, prec=0):
+    """Weight-gradient slabs [splits][Nw][KH*KW*Cs] of the conv g (summed later by unpack).  prec applies to the dense
+    kernel only (the narrow halo-tile kernel stays fp32)."""
+    B, H, W, Cs, Ho, Wo, ldy, KH, KW, stride, pad = g
     if (KH == 3 and KW == 3 and stride == 1 and pad == 1 and B * H * W * max(Cs, ldy) * 4 < 1 << 32
             and lib().raw("vmtl_conv3x3_wgrad_small_supported")(Cs, ldy, W)):
         # narrow full-resolution layers: the strip-walking halo kernel reads x once instead of once per tap
@@ -577,6 +682,30 @@ def _colsum(a, b, M, C, Cs, mode=0, reduce_all=0, out=None):
         out = _empty((1 if reduce_all else C,), a)
     _k("vmtl_colsum", a=a, b=b, M=M, C=C, Cs=Cs, mode=mode, reduce_all=reduce_all, partial=partial, out=out)
     return out
+
+
+def _wgrad_into(x, dy, g, layout, dw, flop, prec=0):
+    """Weight gradient of the dense conv g into dw (torch layout): `layout` is the weight's FORWARD Layout in that conv."""
+    slabs, ns = _wgrad(x, dy, g, Nw=layout.R1 * layout.R0, flop=flop, prec=prec)
+    unpack(slabs, layout, dw, nslabs=ns)
+
+
+def _wgrad_two_heads(x, dy, g, lay_a, lay_b, wa, wb, slots, flop, prec):
+    """Parameter gradients of two heads run as ONE conv g of N = Ca + Cb output channels: one weight-gradient launch whose
+    slabs are unpacked per head (lay_a / lay_b: each head's forward Layout), one column sum of dy split into the two biases.
+    slots = the arena slots of (weight a, bias a, weight b, bias b); returns what autograd is told, in that order."""
+    swa, sba, swb, sbb = slots
+    Ca, Cb, row = lay_a.R0, lay_b.R0, lay_a.T * lay_a.Cs
+    N = Ca + Cb
+    slabs, ns = _wgrad(x, dy, g, Nw=N, flop=flop, prec=prec)
+    dwa, dwb = _grad_buf(wa.shape, swa, x), _grad_buf(wb.shape, swb, x)
+    unpack(slabs, lay_a, dwa, nslabs=ns, slab_stride=N * row)
+    unpack(slabs.view(-1)[Ca * row:], lay_b, dwb, nslabs=ns, slab_stride=N * row)
+    db = _colsum(dy, None, g.M, N, g.ldy)
+    dba, dbb = _grad_buf((Ca,), sba, x), _grad_buf((Cb,), sbb, x)
+    _copy_vec(db, dba, Ca)
+    _copy_vec(db[Ca:], dbb, Cb)
+    return _grad_ret(dwa, swa), _grad_ret(dba, sba), _grad_ret(dwb, swb), _grad_ret(dbb, sbb)
 
 
 def _bias_grad(bias, slot, dy, M, Cout, ldy, zero, fork):
@@ -705,23 +834,36 @@ def _mid_halo(x, wp, y, B, H, W, Cs, ldy, Nw, Cout, flop, pa=None, pc=None, act_
        W=W, Cs=Cs, ldy=ldy, Nw=Nw, Cout=Cout)
 
 
-def _conv_launch(x, wp, bias, y, B, H, W, Cs, Ho, Wo, ldy, Nw, Cout, KH, KW, stride, pad, shuffle=0, cin=None,
-                 algo_flop=None, prec=0, plan=None, stats=None, pw_prec=0):
-    """One dense conv launch, dispatched on its plan; a launch without an epilogue may leave the planning to this function.
+def _halo_launch(route, x, wp, y, g, Nw, Cout, flop, **kw):
+    """The conv g (3x3 / stride 1 / pad 1) on the halo-tile kernel of its plan's route: "small" narrow full-resolution
+    layers, "mid_halo" 64/68-channel layers; both read each input pixel once."""
+    (_small if route == "small" else _mid_halo)(x, wp, y, g.B, g.H, g.W, g.Cs, g.ldy, Nw, Cout, flop, **kw)
+
+
+def _conv_launch(x, wp, bias, y, g, *legacy, Cout=None, Nw=None, shuffle=0, cin=None, algo_flop=None, prec=0, plan=None, stats=None,
+                 pw_prec=0):
+    """One dense conv launch of geometry g, dispatched on its plan; a launch without an epilogue may leave the planning to
+    this function.  Cout: logical output channels, Nw: rows of the operand wp (Cout unless given).
     stats: the [plan.stats_rows][2][ldy] rows of a plan with the statistics epilogue.  prec: the implicit GEMM's precision,
-    pw_prec: the pointwise GEMM's (the plan itself does not depend on pw_prec)."""
+    pw_prec: the pointwise GEMM's (the plan itself does not depend on pw_prec).
+    The earlier all-positional run (..., y, B, H, W, Cs, Ho, Wo, ldy, Nw, Cout, KH, KW, stride, pad) is still accepted, for
+    one caller only: tests/test_pw_precision_cpu.py::test_conv_launch_routes_the_pointwise_precision.  Nothing in the package
+    or in tools/ uses it; new code passes a ConvGeom."""
+    if legacy:
+        B, H, W, Cs, Ho, Wo, ldy, Nw, Cout, KH, KW, stride, pad = (g, *legacy)
+        g = ConvGeom(B, H, W, Cs, Ho, Wo, ldy, KH, KW, stride, pad)
+    B, H, W, Cs, Ho, Wo, ldy, KH, KW, stride, pad = g
+    if Nw is None:
+        Nw = Cout
     if plan is None:
         plan = conv_plan(B, H, W, Cs, Ho, Wo, ldy, KH, KW, stride, pad, shuffle, prec)
     xflop = 2.0 * B * Ho * Wo * Nw * KH * KW * (Cs if cin is None else cin)
     flop = xflop if algo_flop is None else algo_flop
-    ep_mode = 1 if stats is not None else 0
     if plan.route == "pw":
         _kp("vmtl_conv1x1_fwd", pw_prec, _flop=flop, _xflop=xflop, x=x, wp=wp, bias=bias, y=y, stats=stats, M=B * Ho * Wo,
             Ks=Cs, ldy=ldy, Nw=Nw, Cout=Cout)
-    elif plan.route == "small":  # narrow full-resolution layer: the halo-tile kernel reads the input once
-        _small(x, wp, y, B, H, W, Cs, ldy, Nw, Cout, flop, bias=bias, stats=stats, ep_mode=ep_mode)
-    elif plan.route == "mid_halo":  # 64/68-channel layer: the halo-tile kernel reads each input pixel once
-        _mid_halo(x, wp, y, B, H, W, Cs, ldy, Nw, Cout, flop, bias=bias, stats=stats, ep_mode=ep_mode)
+    elif plan.route in ("small", "mid_halo"):
+        _halo_launch(plan.route, x, wp, y, g, Nw, Cout, flop, bias=bias, stats=stats, ep_mode=1 if stats is not None else 0)
     elif plan.route == "ksplit":  # tile-starved contraction: split K when the tile grid alone cannot fill the chip
         _kp("vmtl_conv2d_fwd_ws", prec, _flop=flop, _xflop=xflop, x=x, wp=wp, bias=bias, y=y,
             ws=_empty((plan.ksplit, B * Ho * Wo, ldy), x), B=B, H=H, W=W, Cs=Cs, Ho=Ho, Wo=Wo, ldy=ldy, Nw=Nw, Cout=Cout,
@@ -759,9 +901,9 @@ def _up2_dskip(dy, weight, skip, C0, prec):
     B, H, W, ldy = dy.shape
     Cout, Cin = weight.shape[0], weight.shape[1]
     C1, C1s = Cin - C0, skip.shape[3]
-    wds = packs.get(weight, "up2_dskip", (1, C1, 9, Cout, ldy, 0, 9, 1, Cin * 9, 1), offset=C0 * 9)
+    wds = packs.get(weight, "up2_dskip", Layout.dgrad(Cout, C1, 9, ldy, Cw=Cin), offset=C0 * 9)
     dskip = _empty((B, H, W, C1s), dy)
-    _conv_launch(dy, wds, None, dskip, B, H, W, ldy, H, W, C1s, C1, C1, 3, 3, 1, 1, cin=Cout, prec=prec)
+    _conv_launch(dy, wds, None, dskip, ConvGeom(B, H, W, ldy, H, W, C1s, 3, 3, 1, 1), Cout=C1, cin=Cout, prec=prec)
     return dskip
 
 
@@ -771,13 +913,13 @@ def _up2_wgrad(dy, xl, skip, weight, C0, dw, prec):
     B, H, W, ldy = dy.shape
     _, H2, W2, C0s = xl.shape
     Cout, Cin = weight.shape[0], weight.shape[1]
-    slabs, ns = _wgrad(dy, xl, B, H, W, ldy, H2, W2, C0s, C0, 4, 4, 2, 1, 2.0 * B * H * W * Cout * 9 * C0,
+    slabs, ns = _wgrad(dy, xl, ConvGeom(B, H, W, ldy, H2, W2, C0s, 4, 4, 2, 1), Nw=C0, flop=2.0 * B * H * W * Cout * 9 * C0,
                        xflop=2.0 * B * H2 * W2 * C0 * 16 * Cout, prec=prec)
     _k("vmtl_unpack_up2", slabs=slabs, grad=dw, Cout=Cout, Cos=ldy, C0=C0, Cin=Cin, nslabs=ns)
     if skip is not None:
         C1, C1s = Cin - C0, skip.shape[3]
-        slabs, ns = _wgrad(skip, dy, B, H, W, C1s, H, W, ldy, Cout, 3, 3, 1, 1, 2.0 * B * H * W * Cout * 9 * C1, prec=prec)
-        unpack(slabs, None, 1, Cout, 9, C1, C1s, 0, Cin * 9, 1, 9, out=dw.view(-1)[C0 * 9:], nslabs=ns)
+        _wgrad_into(skip, dy, ConvGeom(B, H, W, C1s, H, W, ldy, 3, 3, 1, 1), Layout.fwd(Cout, C1, 9, C1s, Cw=Cin),
+                    dw.view(-1)[C0 * 9:], 2.0 * B * H * W * Cout * 9 * C1, prec)
 
 
 # ----------------------------------------------------------------------------- conv2d
@@ -807,23 +949,20 @@ class _Conv2d(torch.autograd.Function):
         Cout, Cin, KH, KW = weight.shape
         if ceil4(Cin) != Cs:
             raise ValueError(f"conv2d: input has {Cs} storage channels, weight expects Cin={Cin}")
-        KK = KH * KW
-        Ho = (H + 2 * pad - KH) // stride + 1
-        Wo = (W + 2 * pad - KW) // stride + 1
         ldy = ceil4(Cout)
+        g = ConvGeom.of(x.shape, ldy, KH, KW, stride, pad)
         if stitch_w is None:
-            wp = packs.get(weight, "fwd", (1, Cout, KK, Cin, Cs, 0, Cin * KK, 1, KK, 0))
+            wp = packs.get(weight, "fwd", Layout.fwd(Cout, Cin, KH * KW, Cs))
         else:
             stitch_w = _req(stitch_w, "stitch weights")
             soff, sstride = _stitch_view(stitch_w, stitch_task, Cin)
-            wp = packs.get(weight, f"fwd_st{stitch_task}", (1, Cout, KK, Cin, Cs, 0, Cin * KK, 1, KK, 0),
+            wp = packs.get(weight, f"fwd_st{stitch_task}", Layout.fwd(Cout, Cin, KH * KW, Cs),
                            scale=(stitch_w, soff, sstride, 1))
-        y = _empty((B, Ho, Wo, ldy), x)
+        y = _empty((B, g.Ho, g.Wo, ldy), x)
         stats = _empty((plan.stats_rows, 2, ldy), x) if plan.stats_rows else None
         prec = ctx.prec = conv_prec_code()  # backward runs under the precision of this forward
         pw_prec = ctx.pw_prec = pw_prec_code()  # (a 1x1 conv on the pointwise route: forward and data gradient)
-        _conv_launch(x, wp, bias, y, B, H, W, Cs, Ho, Wo, ldy, Cout, Cout, KH, KW, stride, pad, cin=Cin, prec=prec, plan=plan,
-                     stats=stats, pw_prec=pw_prec)
+        _conv_launch(x, wp, bias, y, g, Cout=Cout, cin=Cin, prec=prec, plan=plan, stats=stats, pw_prec=pw_prec)
         ctx.save_for_backward(x, weight, stitch_w)
         ctx.cfg = (stride, pad, bias is not None)
         ctx.zero_bias_grad = bool(zero_bias_grad)
@@ -847,6 +986,7 @@ class _Conv2d(torch.autograd.Function):
         Cout, Cin, KH, KW = weight.shape
         KK = KH * KW
         _, Ho, Wo, ldy = dy.shape
+        g = ConvGeom(B, H, W, Cs, Ho, Wo, ldy, KH, KW, stride, pad)
         dx = dw = db = dst_w = None
         if stitch_w is not None:
             soff, sstride = _stitch_view(stitch_w, stitch_task, Cin)
@@ -858,27 +998,26 @@ class _Conv2d(torch.autograd.Function):
                 if stitch_w is not None or stride != 2 or KH != KW or not lib().raw("vmtl_conv2d_dgrad_s2_supported")(KH, pad):
                     raise NotImplementedError(f"data gradient of a stride-{stride} {KH}x{KW} / pad {pad} dense conv"
                                               + (" with a stitch scale" if stitch_w is not None else ""))
-                dx = _dgrad_s2(dy, weight, B, H, W, Cs, Ho, Wo, ldy, KH, pad, ctx.prec)
+                dx = _dgrad_s2(dy, weight, g, ctx.prec)
             elif stitch_w is None:
-                wd = packs.get(weight, "dgrad", (1, Cin, KK, Cout, ldy, 0, KK, 1, Cin * KK, 1))
+                wd = packs.get(weight, "dgrad", Layout.dgrad(Cout, Cin, KK, ldy))
             else:  # rows of the data-gradient operand are the input channels: d(x) = s * d(s * x)
-                wd = packs.get(weight, f"dgrad_st{stitch_task}", (1, Cin, KK, Cout, ldy, 0, KK, 1, Cin * KK, 1),
+                wd = packs.get(weight, f"dgrad_st{stitch_task}", Layout.dgrad(Cout, Cin, KK, ldy),
                                scale=(stitch_w, soff, sstride, 2))
             if stride == 1:
                 dx = _empty((B, H, W, Cs), x)
-                _conv_launch(dy, wd, None, dx, B, Ho, Wo, ldy, H, W, Cs, Cin, Cin, KH, KW, 1, KH - 1 - pad, cin=Cout,
-                             prec=ctx.prec, pw_prec=ctx.pw_prec)
+                _conv_launch(dy, wd, None, dx, g.dgrad(), Cout=Cin, cin=Cout, prec=ctx.prec, pw_prec=ctx.pw_prec)
         if ctx.needs_input_grad[1] or (stitch_w is not None and ctx.needs_input_grad[7]):
             use_side = ctx.slots[0] is not None and (stitch_w is None or stitch_slot is not None)
             with side.branch(use_side, B * Ho * Wo, fork, x, dy):
-                slabs, ns = _wgrad(x, dy, B, H, W, Cs, Ho, Wo, ldy, Cout, KH, KW, stride, pad,
-                                   2.0 * B * Ho * Wo * Cout * KK * Cin, prec=ctx.prec)
+                dw = _grad_buf(weight.shape, ctx.slots[0], x)
+                flop = 2.0 * B * Ho * Wo * Cout * KK * Cin
                 if stitch_w is None:
-                    dw = unpack(slabs, weight.shape, 1, Cout, KK, Cin, Cs, 0, Cin * KK, 1, KK, out=ctx.slots[0], nslabs=ns)
+                    _wgrad_into(x, dy, g, Layout.fwd(Cout, Cin, KK, Cs), dw, flop, ctx.prec)
                 else:
                     # the slabs hold dL/d(W*s): dW = slabs * s, and the stitch weight's gradient is their contraction
                     # with W (one small launch pair on the weight-sized tensor; off-diagonal entries stay zero)
-                    dw = _empty(weight.shape, x) if ctx.slots[0] is None else ctx.slots[0]
+                    slabs, ns = _wgrad(x, dy, g, Nw=Cout, flop=flop, prec=ctx.prec)
                     n = Cin if sstride else 1
                     if stitch_slot is not None:
                         ds = stitch_slot.view(-1)[soff:soff + n]
@@ -889,16 +1028,16 @@ class _Conv2d(torch.autograd.Function):
                        sstride=sstride, ds=ds, work=_empty((Cout * Cin * KK + Cin,), x), R0=Cout, T=KK, C=Cin, Cs=Cs,
                        nslabs=ns, slab_stride=0, reduce_all=0 if sstride else 1)
                 stamp(f"side conv M={B * Ho * Wo} N={Cout} K={KK * Cin}")
-            if ctx.slots[0] is not None:
-                dw = None
+            dw = _grad_ret(dw, ctx.slots[0])
         if has_bias and ctx.needs_input_grad[2]:
             db = _bias_grad(ctx.bias, ctx.slots[1], dy, B * Ho * Wo, Cout, ldy, ctx.zero_bias_grad, fork)
         return dx, dw, db, None, None, None, None, dst_w, None
 
 
-def _dgrad_s2(dy, weight, B, H, W, Cs, Ho, Wo, ldy, K, pad, prec):
-    """dx of a stride-2 K x K dense conv by phase decomposition (vmtl_conv2d_dgrad_s2): four stride-1 implicit-GEMM
+def _dgrad_s2(dy, weight, g, prec):
+    """dx of the stride-2 K x K dense conv g by phase decomposition (vmtl_conv2d_dgrad_s2): four stride-1 implicit-GEMM
     correlations of dy with the phases' tap subsets, interleaved into dx.  Runs under the forward's precision."""
+    B, H, W, Cs, Ho, Wo, ldy, K, _, _, pad = g
     Cout, Cin = weight.shape[0], weight.shape[1]
     n = lib().raw("vmtl_pack_dgrad_s2_size")(Cin, ldy, K, pad)
     wd = packs.get_custom(weight, "dgrad_s2", (n,), lambda w, dst: _k(
@@ -933,7 +1072,7 @@ class _BNActPw(torch.autograd.Function):
             if tuple(res.shape) != tuple(x.shape) or act != ACT_NONE:
                 raise ValueError("bn_act_conv1x1: the residual operand needs x's shape and no activation (bn3 + skip)")
         mean, invstd, ca, cc = _bn_fwd_coef(x, stats, rpb, gamma, beta, rm, rv, nbt, C, training, momentum, eps)
-        wp = packs.get(weight, "fwd", (1, Cout, 1, Cin, Cs, 0, Cin, 1, 1, 0))
+        wp = packs.get(weight, "fwd", Layout.fwd(Cout, Cin, 1, Cs))
         ldy = ceil4(Cout)
         a, y = _empty(x.shape, x), _empty((B, H, W, ldy), x)
         ostats = None
@@ -976,9 +1115,8 @@ class _BNActPw(torch.autograd.Function):
         ldy = dy.shape[3]
         fork = side.mark()
         # ---- data gradient w.r.t. a = act(BN(x)), with act' and the BatchNorm-backward column sums in the epilogue
-        wd = packs.get(weight, "dgrad", (1, Cin, 1, Cout, ldy, 0, 1, 1, Cin, 1))
-        dgamma = _empty((C,), x) if sg is None else sg
-        dbeta = _empty((C,), x) if sb is None else sb
+        wd = packs.get(weight, "dgrad", Layout.dgrad(Cout, Cin, 1, ldy))
+        dgamma, dbeta = _grad_buf((C,), sg, x), _grad_buf((C,), sb, x)
         dz = _empty(x.shape, x)
         rows = lib().raw("vmtl_conv1x1_stats_rows")(M, Cs, ldy, 0 if d_a is None else 1)
         part = _empty((rows, 2, Cs), x)
@@ -999,17 +1137,17 @@ class _BNActPw(torch.autograd.Function):
             _k("vmtl_bn_bwd_apply", x=x, dz=dz, mean=mean, invstd=invstd, gamma=gamma, sum_dz=dbeta, sum_dzx=dgamma, dx=dx,
                M=M, C=C, Cs=Cs, training=1 if training else 0)
         # ---- parameter gradients (side stream when they go to arena slots)
-        dw = _empty(weight.shape, x) if sw is None else sw
+        dw = _grad_buf(weight.shape, sw, x)
         with side.branch(sw is not None, M, fork, dy, a):
-            slabs, ns = _wgrad(a, dy, B, H, W, Cs, H, W, ldy, Cout, 1, 1, 1, 0, 2.0 * M * Cout * Cin, prec=ctx.prec)
-            unpack(slabs, weight.shape, 1, Cout, 1, Cin, Cs, 0, Cin, 1, 1, out=dw, nslabs=ns)
+            _wgrad_into(a, dy, ConvGeom(B, H, W, Cs, H, W, ldy, 1, 1, 1, 0), Layout.fwd(Cout, Cin, 1, Cs), dw,
+                        2.0 * M * Cout * Cin, ctx.prec)
         db = None
         if has_bias and ctx.needs_input_grad[9]:
             db = _bias_grad(ctx.bias, sbias, dy, M, Cout, ldy, zero_bias, fork)
-        nif = lambda g, slot: None if slot is not None else g
         # act = none with a residual: d(res) is the gradient w.r.t. a itself = dz (no activation derivative in it)
         dres = dz if has_res and ctx.needs_input_grad[10] else None
-        return dx, None, None, nif(dgamma, sg), nif(dbeta, sb), None, None, None, nif(dw, sw), db, dres, None
+        return (dx, None, None, _grad_ret(dgamma, sg), _grad_ret(dbeta, sb), None, None, None, _grad_ret(dw, sw), db, dres,
+                None)
 
 
 _BN_PW_MAX_ROWS = int(os.environ.get("VMTL_BN_PW_MAX_ROWS", str(1 << 30)))
@@ -1054,7 +1192,7 @@ class _Conv1x1Cat(torch.autograd.Function):
         if tuple(xb.shape[:3]) != (B, H, W) or tuple(weight.shape[2:]) != (1, 1) or Cin != Ca + Cb or ceil4(Cb) != Cbs:
             raise ValueError("conv1x1_cat: weight must be (Cout, Ca + Cb, 1, 1) over two maps of equal extent")
         M, Ks, ldy = B * H * W, Ca + Cbs, ceil4(Cout)
-        wp = packs.get(weight, "fwd", (1, Cout, 1, Cin, Ks, 0, Cin, 1, 1, 0))
+        wp = packs.get(weight, "fwd", Layout.fwd(Cout, Cin, 1, Ks))
         y = _empty((B, H, W, ldy), xa)
         stats = None
         if want_stats:
@@ -1087,21 +1225,20 @@ class _Conv1x1Cat(torch.autograd.Function):
         dxa = dxb = dw = db = None
         fork = side.mark()
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            wd = packs.get(weight, "dgrad", (1, Cin, 1, Cout, ldy, 0, 1, 1, Cin, 1))  # [Cin][ldy]
+            wd = packs.get(weight, "dgrad", Layout.dgrad(Cout, Cin, 1, ldy))  # [Cin][ldy]
             dxa, dxb = _empty(xa.shape, xa), _empty(xb.shape, xa)
             _kp("vmtl_conv1x1_cat_dgrad", ctx.pw_prec, _flop=2.0 * M * Cin * Cout, dy=dy, wp=wd, dx=dxa, N1=Ca, dx2=dxb, N2s=Cbs,
                 N2=Cb, M=M, Ks=ldy)
         if ctx.needs_input_grad[2]:
             with side.branch(sw is not None, M, fork, xa, xb, dy):
-                dwt = _empty(weight.shape, xa) if sw is None else sw
-                flat = dwt.view(-1)
+                dwt = _grad_buf(weight.shape, sw, xa)
                 Ks = Ca + Cbs
                 ns = lib().raw("vmtl_conv2d_wgrad_splits")(M, Cout, Ks)
                 slabs = _empty((ns, Cout, Ks), xa)
                 _kp("vmtl_conv1x1_cat_wgrad", ctx.prec, _flop=2.0 * M * Cout * Cin, x=xa, K1=Ca, x2=xb, K2s=Cbs, dy=dy, slabs=slabs,
                    splits=ns, M=M, ldy=ldy, Nw=Cout)
-                unpack(slabs, None, 1, Cout, 1, Cin, Ks, 0, Cin, 1, 1, out=flat, nslabs=ns)
-            dw = None if sw is not None else dwt
+                unpack(slabs, Layout.fwd(Cout, Cin, 1, Ks), dwt.view(-1), nslabs=ns)
+            dw = _grad_ret(dwt, sw)
         if has_bias and ctx.needs_input_grad[3]:
             db = _bias_grad(ctx.bias, sbias, dy, M, Cout, ldy, zero_bias, fork)
         return dxa, dxb, dw, db, None, None, None
@@ -1171,17 +1308,16 @@ class _Up2Conv(torch.autograd.Function):
             wd = packs.get_custom(weight, "up2_dgrad", (C0, 16 * ldy), lambda w, dst: _k(
                 "vmtl_pack_up2_dgrad", w=w, dst=dst, Cout=Cout, Cos=ldy, C0=C0, Cin=Cin))
             dxl = _empty((B, H2, W2, C0s), xl)
-            _conv_launch(dy, wd, None, dxl, B, H, W, ldy, H2, W2, C0s, C0, C0, 4, 4, 2, 1, cin=Cout,
+            _conv_launch(dy, wd, None, dxl, ConvGeom(B, H, W, ldy, H2, W2, C0s, 4, 4, 2, 1), Cout=C0, cin=Cout,
                          algo_flop=2.0 * B * H * W * C0 * 9 * Cout, prec=ctx.prec)
         if skip is not None and ctx.needs_input_grad[1]:
             dskip = _up2_dskip(dy, weight, skip, C0, ctx.prec)
         if ctx.needs_input_grad[2]:
-            dw = _empty(weight.shape, xl) if ctx.slot is None else ctx.slot
+            dw = _grad_buf(weight.shape, ctx.slot, xl)
             with side.branch(ctx.slot is not None, B * H * W, fork, dy, xl, skip):
                 _up2_wgrad(dy, xl, skip, weight, C0, dw, ctx.prec)
                 stamp(f"side up2 M={B * H * W} N={Cout} Cin={Cin}")
-            if ctx.slot is not None:
-                dw = None
+            dw = _grad_ret(dw, ctx.slot)
         return dxl, dskip, dw, None, None
 
 
@@ -1248,15 +1384,15 @@ class _BNActConv(torch.autograd.Function):
         else:
             if Cin != C or skip is not None:
                 raise ValueError("bn_act_conv: weight expects x's channels (skip only with up2)")
-            wp = packs.get(weight, "fwd", (1, Cout, 9, Cin, Cs, 0, Cin * 9, 1, 9, 0))
+            wp = packs.get(weight, "fwd", Layout.fwd(Cout, Cin, 9, Cs))
+            g = ConvGeom(B, H, W, Cs, H, W, ldy, 3, 3, 1, 1)
             y = _empty((B, H, W, ldy), x)
             ostats = _empty((plan.stats_rows, 2, ldy), x) if plan.stats_rows else None
             if pro:
-                _mid_halo(x, wp, y, B, H, W, Cs, ldy, Cout, Cout, 2.0 * M * Cout * 9 * Cin, pa=ca, pc=cc, act_in=act, a_out=a,
-                          stats=ostats, ep_mode=1 if ostats is not None else 0)
+                _halo_launch("mid_halo", x, wp, y, g, Cout, Cout, 2.0 * M * Cout * 9 * Cin, pa=ca, pc=cc, act_in=act, a_out=a,
+                             stats=ostats, ep_mode=1 if ostats is not None else 0)
             else:
-                _conv_launch(a, wp, None, y, B, H, W, Cs, H, W, ldy, Cout, Cout, 3, 3, 1, 1, cin=Cin, prec=prec, plan=plan,
-                             stats=ostats)
+                _conv_launch(a, wp, None, y, g, Cout=Cout, cin=Cin, prec=prec, plan=plan, stats=ostats)
         ctx.save_for_backward(x, a, skip, weight, mean, invstd, gamma, beta)
         ctx.cfg = (C, training, act, up2)
         ctx.slots = (_slot(gamma), _slot(beta), _slot(weight))
@@ -1279,33 +1415,31 @@ class _BNActConv(torch.autograd.Function):
         ldy = dy.shape[3]
         stamp(f"main bnconv M={dy.shape[0] * dy.shape[1] * dy.shape[2]} N={Cout} Cin={Cin}")
         fork = side.mark()
+        gfwd = ConvGeom(B, H, W, Cs, H, W, ldy, 3, 3, 1, 1)  # the plain (not up2) forward conv
         # ---- data gradient w.r.t. a = act(BN(x)), with act' and the BatchNorm-backward column sums in the epilogue
         if up2:
             Hd, Wd = 2 * H, 2 * W  # dy's extent
             wd = packs.get_custom(weight, "up2_dgrad", (C, 16 * ldy), lambda w, dst: _k(
                 "vmtl_pack_up2_dgrad", w=w, dst=dst, Cout=Cout, Cos=ldy, C0=C, Cin=Cin))
-            geo = dict(B=B, H=Hd, W=Wd, Cs=ldy, Ho=H, Wo=W, ldy=Cs, KH=4, KW=4, stride=2, pad=1)
+            geo = ConvGeom(B, Hd, Wd, ldy, H, W, Cs, 4, 4, 2, 1)
             flop, xflop = 2.0 * B * Hd * Wd * C * 9 * Cout, 2.0 * M * C * 16 * Cout
         else:
             Hd, Wd = H, W
-            wd = packs.get(weight, "dgrad", (1, Cin, 9, Cout, ldy, 0, 9, 1, Cin * 9, 1))
-            geo = dict(B=B, H=H, W=W, Cs=ldy, Ho=H, Wo=W, ldy=Cs, KH=3, KW=3, stride=1, pad=1)
+            wd = packs.get(weight, "dgrad", Layout.dgrad(Cout, Cin, 9, ldy))
+            geo = gfwd.dgrad()
             flop = xflop = 2.0 * M * Cin * 9 * Cout
-        dgamma = _empty((C,), x) if sg is None else sg
-        dbeta = _empty((C,), x) if sb is None else sb
+        dgamma, dbeta = _grad_buf((C,), sg, x), _grad_buf((C,), sb, x)
         dx = _empty(x.shape, x) if ctx.needs_input_grad[0] else None
-        plan = conv_plan(**geo, prec=ctx.prec, epilogue="bnbwd")
+        plan = conv_plan(*geo, prec=ctx.prec, epilogue="bnbwd")
         if plan.stats_rows:  # fused: the halo-tile kernels (ep_mode 2) or the implicit GEMM's BatchNorm-backward epilogue
             dz = _empty(x.shape, x)
             part = _empty((plan.stats_rows, 2, Cs), x)
             ez = (x, mean, invstd, gamma, beta, act)
-            if plan.route == "small":
-                _small(dy, wd, dz, B, H, W, ldy, Cs, C, C, flop, stats=part, ep_mode=2, ez=ez)
-            elif plan.route == "mid_halo":
-                _mid_halo(dy, wd, dz, B, H, W, ldy, Cs, C, C, flop, stats=part, ep_mode=2, ez=ez)
+            if plan.route in ("small", "mid_halo"):
+                _halo_launch(plan.route, dy, wd, dz, geo, C, C, flop, stats=part, ep_mode=2, ez=ez)
             else:
                 _kp("vmtl_conv2d_bnbwd", ctx.prec, _flop=flop, _xflop=xflop, x=dy, wp=wd, y=dz, stats=part, ez_x=x, ez_mean=mean,
-                    ez_invstd=invstd, ez_gamma=gamma, ez_beta=beta, ez_act=act, Nw=C, Cout=C, **geo)
+                    ez_invstd=invstd, ez_gamma=gamma, ez_beta=beta, ez_act=act, Nw=C, Cout=C, **geo._asdict())
             _k("vmtl_bn_bwd_finalize", partial=part, nblk=plan.stats_rows, M=M, C=C, Cs=Cs, sum_dz=dbeta, sum_dzx=dgamma,
                mean=None, invstd=None, gamma=None, training=1 if training else 0, coef_a=None, coef_b=None, coef_c=None)
             if dx is not None:
@@ -1313,7 +1447,7 @@ class _BNActConv(torch.autograd.Function):
                    dx=dx, M=M, C=C, Cs=Cs, training=1 if training else 0)
         else:  # split-K data gradient (tile-starved layers) or VMTL_BNBWD_FUSE=0: unfused BatchNorm backward
             da = _empty(x.shape, x)
-            _conv_launch(dy, wd, None, da, Nw=C, Cout=C, cin=Cout, algo_flop=flop, prec=ctx.prec, plan=plan, **geo)
+            _conv_launch(dy, wd, None, da, geo, Cout=C, cin=Cout, algo_flop=flop, prec=ctx.prec, plan=plan)
             part = _empty((_reduce_rows(M), 2, Cs), x)
             _k("vmtl_bn_bwd", x=x, dy=da, mean=mean, invstd=invstd, gamma=gamma, beta=beta, mul=None, dmul=None,
                partial=part, sum_dz=dbeta, sum_dzx=dgamma, dx=dx if dx is not None else _empty(x.shape, x), M=M, C=C, Cs=Cs,
@@ -1322,16 +1456,15 @@ class _BNActConv(torch.autograd.Function):
         if up2 and skip is not None and ctx.needs_input_grad[9]:
             dskip = _up2_dskip(dy, weight, skip, C, ctx.prec)
         # ---- weight gradient (side stream when it goes to an arena slot)
-        dw = _empty(weight.shape, x) if sw is None else sw
+        dw = _grad_buf(weight.shape, sw, x)
         with side.branch(sw is not None, B * Hd * Wd, fork, dy, a, skip):
             if up2:
                 _up2_wgrad(dy, a, skip, weight, C, dw, ctx.prec)
             else:
-                slabs, ns = _wgrad(a, dy, B, H, W, Cs, H, W, ldy, Cout, 3, 3, 1, 1, 2.0 * M * Cout * 9 * Cin, prec=ctx.prec)
-                unpack(slabs, weight.shape, 1, Cout, 9, Cin, Cs, 0, Cin * 9, 1, 9, out=dw, nslabs=ns)
+                _wgrad_into(a, dy, gfwd, Layout.fwd(Cout, Cin, 9, Cs), dw, 2.0 * M * Cout * 9 * Cin, ctx.prec)
             stamp(f"side bnconv N={Cout} Cin={Cin}")
-        nif = lambda g, slot: None if slot is not None else g
-        return dx, None, None, nif(dgamma, sg), nif(dbeta, sb), None, None, None, nif(dw, sw), dskip, None
+        return (dx, None, None, _grad_ret(dgamma, sg), _grad_ret(dbeta, sb), None, None, None, _grad_ret(dw, sw), dskip,
+                None)
 
 
 def bn_act_conv(x, stats, rpb, bn, C, act, weight, skip=None, up2=False, want_stats=True):
@@ -1366,10 +1499,8 @@ def up2_conv(xl, C0, skip, weight, want_stats=False):
 def conv2d(x, weight, bias=None, stride=1, pad=0, want_stats=False, zero_bias_grad=False, stitch=None):
     """zero_bias_grad: the caller normalises y with a TRAIN-mode BatchNorm next, which makes dL/dbias exactly zero.
     stitch = (CrossStitchLayer weights, task index): y = conv(w[task, task, (c)] * x), the scale folded into the operand."""
-    B, H, W, Cs = x.shape
     Cout, _, KH, KW = weight.shape
-    Ho, Wo = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
-    plan = conv_plan(B, H, W, Cs, Ho, Wo, ceil4(Cout), KH, KW, stride, pad, prec=conv_prec_code(),
+    plan = conv_plan(*ConvGeom.of(x.shape, ceil4(Cout), KH, KW, stride, pad), prec=conv_prec_code(),
                      epilogue="stats" if want_stats else None)
     y, stats = _Conv2d.apply(x, weight, bias, stride, pad, plan, zero_bias_grad,
                              None if stitch is None else stitch[0], 0 if stitch is None else int(stitch[1]))
@@ -1391,9 +1522,9 @@ class _ConvT2x2(torch.autograd.Function):
         if tuple(weight.shape[2:]) != (2, 2) or ceil4(Cin) != Cs:
             raise ValueError("conv_transpose2x2: weight must be (Cin, Cout, 2, 2) matching the input channels")
         ldy = ceil4(Cout)
-        wp = packs.get(weight, "ct_fwd", (4, Cout, 1, Cin, Cs, 1, 4, 0, Cout * 4, 0))
+        wp = packs.get(weight, "ct_fwd", Layout.ct_fwd(Cin, Cout, Cs))
         y = _empty((B, 2 * H, 2 * W, ldy), x)
-        _conv_launch(x, wp, bias, y, B, H, W, Cs, H, W, ldy, 4 * Cout, Cout, 1, 1, 1, 0, shuffle=1, cin=Cin)
+        _conv_launch(x, wp, bias, y, ConvGeom(B, H, W, Cs, H, W, ldy, 1, 1, 1, 0), Cout=Cout, Nw=4 * Cout, shuffle=1, cin=Cin)
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
         ctx.slots = (_slot(weight), _slot(bias))
@@ -1407,23 +1538,22 @@ class _ConvT2x2(torch.autograd.Function):
         Cin, Cout = weight.shape[0], weight.shape[1]
         ldy = dy.shape[3]
         dx = dw = db = None
+        # the data gradient is a 2x2 / stride-2 conv over dy
+        g, lay = ConvGeom(B, 2 * H, 2 * W, ldy, H, W, Cs, 2, 2, 2, 0), Layout.ct_bwd(Cin, Cout, ldy)
         fork = side.mark()
-        if ctx.needs_input_grad[0]:  # a 2x2 / stride-2 conv over dy
-            wd = packs.get(weight, "ct_bwd", (1, Cin, 4, Cout, ldy, 0, Cout * 4, 1, 4, 0))
+        if ctx.needs_input_grad[0]:
+            wd = packs.get(weight, "ct_bwd", lay)
             dx = _empty((B, H, W, Cs), x)
-            _conv_launch(dy, wd, None, dx, B, 2 * H, 2 * W, ldy, H, W, Cs, Cin, Cin, 2, 2, 2, 0, cin=Cout)
+            _conv_launch(dy, wd, None, dx, g, Cout=Cin, cin=Cout)
         if ctx.needs_input_grad[1]:  # weight gradient of that same conv, with x in the role of its output gradient
             with side.branch(ctx.slots[0] is not None, B * H * W, fork, x, dy):
-                slabs, ns = _wgrad(dy, x, B, 2 * H, 2 * W, ldy, H, W, Cs, Cin, 2, 2, 2, 0,
-                                   2.0 * B * H * W * Cin * 4 * Cout)
-                dw = unpack(slabs, weight.shape, 1, Cin, 4, Cout, ldy, 0, Cout * 4, 1, 4, out=ctx.slots[0], nslabs=ns)
-            if ctx.slots[0] is not None:
-                dw = None
+                dw = _grad_buf(weight.shape, ctx.slots[0], x)
+                _wgrad_into(dy, x, g, lay, dw, 2.0 * B * H * W * Cin * 4 * Cout)
+            dw = _grad_ret(dw, ctx.slots[0])
         if ctx.has_bias and ctx.needs_input_grad[2]:
             with side.branch(ctx.slots[1] is not None, B * 4 * H * W, fork, dy):
                 db = _colsum(dy, None, B * 4 * H * W, Cout, ldy, out=ctx.slots[1])
-            if ctx.slots[1] is not None:
-                db = None
+            db = _grad_ret(db, ctx.slots[1])
         return dx, dw, db
 
 
@@ -1443,7 +1573,7 @@ class _DwConv(torch.autograd.Function):
             raise ValueError("dwconv: weight must be (C, 1, K, K) matching the input channels")
         Ho = (H + 2 * pad - K) // stride + 1
         Wo = (W + 2 * pad - K) // stride + 1
-        wp = packs.get(weight, "dw", (1, 1, K * K, C, Cs, 0, 0, 1, K * K, 0))
+        wp = packs.get(weight, "dw", Layout.dw(C, K, Cs))
         y = _empty((B, Ho, Wo, Cs), x)
         _k("vmtl_dwconv_fwd", x=x, wp=wp, y=y, B=B, H=H, W=W, Cs=Cs, Ho=Ho, Wo=Wo, K=K, stride=stride, pad=pad)
         ctx.save_for_backward(x, weight, wp)
@@ -1469,12 +1599,11 @@ class _DwConv(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             with side.branch(ctx.slot is not None, B * Ho * Wo, fork, x, dy):
                 partial = _empty((lib().raw("vmtl_dwconv_bwd_weight_rows")(B * Ho * Wo, Cs), K * K, Cs), x)
-                dw = _empty(weight.shape, x) if ctx.slot is None else ctx.slot
+                dw = _grad_buf(weight.shape, ctx.slot, x)
                 _k("vmtl_dwconv_bwd_weight", x=x, dy=dy, partial=partial, dw=dw, B=B, H=H, W=W, C=C, Cs=Cs, Ho=Ho,
                    Wo=Wo, K=K, stride=stride, pad=pad)
                 stamp(f"side dw M={B * Ho * Wo} C={C}")
-            if ctx.slot is not None:
-                dw = None
+            dw = _grad_ret(dw, ctx.slot)
         return dx, dw, None, None
 
 
@@ -1496,7 +1625,7 @@ class _BNActDw(torch.autograd.Function):
         Ho = (H + 2 * pad - K) // stride + 1
         Wo = (W + 2 * pad - K) // stride + 1
         mean, invstd, ca, cc = _bn_fwd_coef(x, stats, rpb, gamma, beta, rm, rv, nbt, C, training, momentum, eps)
-        wp = packs.get(weight, "dw", (1, 1, K * K, C, Cs, 0, 0, 1, K * K, 0))
+        wp = packs.get(weight, "dw", Layout.dw(C, K, Cs))
         need_bwd = any(ctx.needs_input_grad)
         a = _empty(x.shape, x) if need_bwd or return_act else None
         y = _empty((B, Ho, Wo, Cs), x)
@@ -1537,20 +1666,18 @@ class _BNActDw(torch.autograd.Function):
                K=K, stride=stride, pad=pad)
         else:
             _k("vmtl_dwconv_bwd_data", dy=dy, wp=wp, dx=da, B=B, H=H, W=W, Cs=Cs, Ho=Ho, Wo=Wo, K=K, stride=stride, pad=pad)
-        dgamma = _empty((C,), x) if sg is None else sg
-        dbeta = _empty((C,), x) if sb is None else sb
+        dgamma, dbeta = _grad_buf((C,), sg, x), _grad_buf((C,), sb, x)
         dx = _empty(x.shape, x)
         part = _empty((_reduce_rows(M), 2, Cs), x)
         _k("vmtl_bn_bwd", x=x, dy=da, mean=mean, invstd=invstd, gamma=gamma, beta=beta, mul=None, dmul=None, partial=part,
            sum_dz=dbeta, sum_dzx=dgamma, dx=dx, M=M, C=C, Cs=Cs, act=act, training=1 if training else 0)
-        dw = _empty(weight.shape, x) if sw is None else sw
+        dw = _grad_buf(weight.shape, sw, x)
         with side.branch(sw is not None, B * Ho * Wo, fork, a, dy):
             partial = _empty((lib().raw("vmtl_dwconv_bwd_weight_rows")(B * Ho * Wo, Cs), K * K, Cs), x)
             _k("vmtl_dwconv_bwd_weight", x=a, dy=dy, partial=partial, dw=dw, B=B, H=H, W=W, C=C, Cs=Cs, Ho=Ho, Wo=Wo, K=K,
                stride=stride, pad=pad)
             stamp(f"side bndw C={C}")
-        nif = lambda g, slot: None if slot is not None else g
-        return dx, None, None, nif(dgamma, sg), nif(dbeta, sb), None, None, None, nif(dw, sw), None
+        return dx, None, None, _grad_ret(dgamma, sg), _grad_ret(dbeta, sb), None, None, None, _grad_ret(dw, sw), None
 
 
 def bn_act_dwconv(x, stats, rpb, bn, C, act, weight, stride=1, pad=1, want_stats=True, return_act=False):
@@ -1635,14 +1762,12 @@ class _BNAct(torch.autograd.Function):
         if need_sums or dmul is not None:
             partial = _empty((_reduce_rows(M), 2, Cs), x)
         if need_sums:  # the kernels write exactly C entries: [dbeta | dgamma] may be arena slots
-            sum_dzx = _empty((C,), x) if ctx.slots[0] is None else ctx.slots[0]
-            sum_dz = _empty((C,), x) if ctx.slots[1] is None else ctx.slots[1]
+            sum_dzx, sum_dz = _grad_buf((C,), ctx.slots[0], x), _grad_buf((C,), ctx.slots[1], x)
         dx = _empty(x.shape, x)
         _k("vmtl_bn_bwd", x=x, dy=dy, mean=mean, invstd=invstd, gamma=gamma, beta=beta, mul=mul, dmul=dmul,
            partial=partial, sum_dz=sum_dz, sum_dzx=sum_dzx, dx=dx, M=M, C=C, Cs=Cs, act=act,
            training=1 if training else 0)
-        dgamma = sum_dzx if (need_sums and ctx.slots[0] is None) else None
-        dbeta = sum_dz if (need_sums and ctx.slots[1] is None) else None
+        dgamma, dbeta = _grad_ret(sum_dzx, ctx.slots[0]), _grad_ret(sum_dz, ctx.slots[1])  # both None without a BatchNorm
         return (dx, dgamma, dbeta, None, None, None, dmul, dy if has_res else None, None, None, None, None, None,
                 None, None)
 
@@ -1693,14 +1818,12 @@ class _BNActPool(torch.autograd.Function):
         dyp = _req(dyp, "dy")
         B, H, W, Cs = x.shape
         partial = _empty((_reduce_rows(B * (H // 2) * (W // 2)), 2, Cs), x)
-        sum_dzx = _empty((C,), x) if ctx.slots[0] is None else ctx.slots[0]  # exactly C entries: may be arena slots
-        sum_dz = _empty((C,), x) if ctx.slots[1] is None else ctx.slots[1]
+        sum_dzx, sum_dz = _grad_buf((C,), ctx.slots[0], x), _grad_buf((C,), ctx.slots[1], x)  # exactly C entries each
         dx = _empty(x.shape, x)
         _k("vmtl_bn_act_pool2_bwd", x=x, dyp=dyp, mean=mean, invstd=invstd, gamma=gamma, beta=beta, partial=partial,
            sum_dz=sum_dz, sum_dzx=sum_dzx, dx=dx, B=B, H=H, W=W, C=C, Cs=Cs, act=act, training=1 if training else 0)
-        dgamma = sum_dzx if ctx.slots[0] is None else None
-        dbeta = sum_dz if ctx.slots[1] is None else None
-        return dx, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None
+        return (dx, _grad_ret(sum_dzx, ctx.slots[0]), _grad_ret(sum_dz, ctx.slots[1]), None, None, None, None, None, None, None,
+                None, None, None)
 
 
 FUSE_BN_POOL = os.environ.get("VMTL_FUSE_BN_POOL", "1") != "0"  # MTAN encoder attention: BN + ReLU + MaxPool2d as one node
@@ -1778,13 +1901,11 @@ class _BNActPool3(torch.autograd.Function):
         dgamma = dbeta = None
         if bn:
             M = B * H * W
-            dgamma = _empty((C,), x) if ctx.slots[0] is None else ctx.slots[0]  # exactly C entries: may be arena slots
-            dbeta = _empty((C,), x) if ctx.slots[1] is None else ctx.slots[1]
+            dgamma, dbeta = _grad_buf((C,), ctx.slots[0], x), _grad_buf((C,), ctx.slots[1], x)  # exactly C entries each
             _k("vmtl_bn_act_pool3s2_bwd", x=x, dskip=da, dyp=dp, idx=idx, mean=mean, invstd=invstd, gamma=gamma, beta=beta,
                dz=_empty(x.shape, x), partial=_empty((_reduce_rows(M), 2, Cs), x), sum_dz=dbeta, sum_dzx=dgamma, dx=dx,
                B=B, H=H, W=W, C=C, Cs=Cs, act=act, training=1 if training else 0)
-            dgamma = dgamma if ctx.slots[0] is None else None
-            dbeta = dbeta if ctx.slots[1] is None else None
+            dgamma, dbeta = _grad_ret(dgamma, ctx.slots[0]), _grad_ret(dbeta, ctx.slots[1])
         else:
             _k("vmtl_bn_act_pool3s2_bwd", x=x, dskip=None, dyp=dp, idx=idx, mean=None, invstd=None, gamma=None, beta=None,
                dz=None, partial=None, sum_dz=None, sum_dzx=None, dx=dx, B=B, H=H, W=W, C=C, Cs=Cs, act=act, training=0)
@@ -1854,21 +1975,18 @@ class _BNAddAct(torch.autograd.Function):
         B, H, W, Cs = z.shape
         M = B * H * W
         g = _empty(z.shape, z)
-        dga = _empty((C,), z) if sga is None else sga
-        dba = _empty((C,), z) if sba is None else sba
+        dga, dba = _grad_buf((C,), sga, z), _grad_buf((C,), sba, z)
         dgb = dbb = dzd = None
         if zd is not None:
-            dgb = _empty((C,), z) if sgb is None else sgb
-            dbb = _empty((C,), z) if sbb is None else sbb
+            dgb, dbb = _grad_buf((C,), sgb, z), _grad_buf((C,), sbb, z)
             dzd = _empty(z.shape, z)
         dz = _empty(z.shape, z)
         _k("vmtl_bn_add_act_bwd", z=z, mean_a=mean_a, invstd_a=invstd_a, gamma_a=ga, beta_a=ba, res=res, zd=zd,
            mean_b=mean_b, invstd_b=invstd_b, gamma_b=gb, beta_b=bb, dy=dy, g=g, partial=_empty((_reduce_rows(M), 3, Cs), z),
            sum_dz_a=dba, sum_dzx_a=dga, sum_dz_b=dbb, sum_dzx_b=dgb, dz=dz, dzd=dzd, M=M, C=C, Cs=Cs, act=act,
            training=1 if training else 0)
-        nif = lambda t, slot: None if slot is not None else t
-        return (dz, None, nif(dga, sga), nif(dba, sba), None, None, None, g if res is not None else None, dzd, None,
-                nif(dgb, sgb), nif(dbb, sbb), None, None, None, None)
+        return (dz, None, _grad_ret(dga, sga), _grad_ret(dba, sba), None, None, None, g if res is not None else None, dzd,
+                None, _grad_ret(dgb, sgb), _grad_ret(dbb, sbb), None, None, None, None)
 
 
 def bn_add_act(z, stats, rpb, bn, C, act, res=None, zd=None, statsd=None, rpbd=0, bn_d=None):
@@ -2102,7 +2220,7 @@ class _SqueezeExcite(torch.autograd.Function):
         HW = H * W
         R, C = wr.shape[0], wr.shape[1]
         Rs = ceil4(R)
-        slots = ctx.slots
+        slots, shapes = ctx.slots, (wr.shape, (R,), we.shape, (C,))
         all_slots = all(s is not None for s in slots)
         if ctx.fused:
             dg, dh = _empty((B, Cs), x), _empty((B, Rs), x)  # both finished, for the weight gradients
@@ -2115,19 +2233,15 @@ class _SqueezeExcite(torch.autograd.Function):
                 dx = _empty(x.shape, x)
                 _k("vmtl_channel_scale_add", x=dy, s=g, t=dmean, t_scale=1.0 / HW, y=dx, B=B, HW=HW, Cs=Cs)
             with side.branch(all_slots, B, fork, dg, dh, pooled, z1, h, z2):
-                dwr = _empty(wr.shape, x) if slots[0] is None else slots[0]
-                dbr = _empty((R,), x) if slots[1] is None else slots[1]
-                dwe = _empty(we.shape, x) if slots[2] is None else slots[2]
-                dbe = _empty((C,), x) if slots[3] is None else slots[3]
+                dwr, dbr, dwe, dbe = grads = [_grad_buf(s, sl, x) for s, sl in zip(shapes, slots)]
                 _k("vmtl_se_wgrad", pooled=pooled, h=h, dg=dg, dh=dh, z1=z1, z2=z2, dwr=dwr, dbr=dbr, dwe=dwe, dbe=dbe,
                    B=B, C=C, R=R, act1=act1, act2=act2)
-            ret = [None if sl is not None else t for t, sl in zip((dwr, dbr, dwe, dbe), slots)]
-            return dx, ret[0], ret[1], ret[2], ret[3], None, None
+            return (dx, *map(_grad_ret, grads, slots), None, None)
         S = ctx.S
         # dg[b][c] = sum_hw dy*x, left as per-slice partial sums for the GEMM to finish
         dparts = _empty((S, B, Cs), x)
         _k("vmtl_hw_reduce", x=dy, y=x, part=dparts, B=B, HW=HW, Cs=Cs)
-        weT = packs.get(we, "dgrad", (1, R, 1, C, Cs, 0, 1, 1, R, 1))   # [R][Cs]
+        weT = packs.get(we, "dgrad", Layout.dgrad(C, R, 1, Cs))   # [R][Cs]
         dh = _empty((B, Rs), x)
         dg = _empty((B, Cs), x)  # finished sum_hw dy*x (a_out), for the weight gradient
         _k("vmtl_fc_fwd", a=dparts, a_parts=S, a_part_stride=B * Cs, a_scale=1.0, a_z=z2, a_act=act2, a_out=dg, w=weT,
@@ -2135,23 +2249,19 @@ class _SqueezeExcite(torch.autograd.Function):
         fork = side.mark()
         dx = None
         if ctx.needs_input_grad[0]:
-            wrT = packs.get(wr, "dgrad", (1, C, 1, R, Rs, 0, 1, 1, C, 1))  # [C][Rs]
+            wrT = packs.get(wr, "dgrad", Layout.dgrad(R, C, 1, Rs))  # [C][Rs]
             dmean = _empty((B, Cs), x)
             _k("vmtl_fc_fwd", a=dh, a_parts=1, a_part_stride=0, a_scale=1.0, a_z=z1, a_act=act1, a_out=None, w=wrT,
                bias=None, z=None, y=dmean, M=B, K=R, N=C, lda=Rs, ldw=Rs, ldy=Cs, act=0)
             dx = _empty(x.shape, x)
             _k("vmtl_channel_scale_add", x=dy, s=g, t=dmean, t_scale=1.0 / HW, y=dx, B=B, HW=HW, Cs=Cs)
         with side.branch(all_slots, B, fork, dg, dh, pooled, z1, h, z2):
-            dwr = _empty(wr.shape, x) if slots[0] is None else slots[0]
-            dbr = _empty((R,), x) if slots[1] is None else slots[1]
-            dwe = _empty(we.shape, x) if slots[2] is None else slots[2]
-            dbe = _empty((C,), x) if slots[3] is None else slots[3]
+            dwr, dbr, dwe, dbe = grads = [_grad_buf(s, sl, x) for s, sl in zip(shapes, slots)]
             _k("vmtl_fc_wgrad", x=h, x_parts=1, x_part_stride=0, x_scale=1.0, dyo=dg, dy_parts=1, dy_part_stride=0,
                zo=z2, dw=dwe, db=dbe, M=B, K=R, N=C, lda=Rs, ldn=Cs, act=act2)
             _k("vmtl_fc_wgrad", x=pooled, x_parts=1, x_part_stride=0, x_scale=1.0, dyo=dh, dy_parts=1,
                dy_part_stride=0, zo=z1, dw=dwr, db=dbr, M=B, K=C, N=R, lda=Cs, ldn=Rs, act=act1)
-        ret = [None if sl is not None else t for t, sl in zip((dwr, dbr, dwe, dbe), slots)]
-        return dx, ret[0], ret[1], ret[2], ret[3], None, None
+        return (dx, *map(_grad_ret, grads, slots), None, None)
 
 
 def squeeze_excite(x, w_reduce, b_reduce, w_expand, b_expand, act1=ACT_RELU, act2=ACT_HSIGMOID):
@@ -2457,7 +2567,7 @@ class _DecoderTail(torch.autograd.Function):
         tiles = lib().raw("vmtl_conv3x3_small_stat_rows")(B, H, W)  # statistics rows ...
         rpb = lib().raw("vmtl_conv3x3_small_stat_block")(B, H, W)   # ... of this many pixels each
         mean1, invstd1, pa1, pc1 = _bn_fwd_coef(x1, stats1, rpb1, g1, b1, rm1, rv1, nbt1, C1, tr1, mom1, eps1)
-        wp2 = packs.get(w2, "fwd", (1, C2, 9, C1, Cs1, 0, C1 * 9, 1, 9, 0))
+        wp2 = packs.get(w2, "fwd", Layout.fwd(C2, C1, 9, Cs1))
         a1 = _empty(x1.shape, x1) if need_bwd else None
         x2 = _empty((B, H, W, ldy2), x1)
         stats2 = _empty((tiles, 2, ldy2), x1) if tr2 else None
@@ -2466,11 +2576,11 @@ class _DecoderTail(torch.autograd.Function):
         mean2, invstd2, pa2, pc2 = _bn_fwd_coef(x2, stats2, rpb, g2, b2, rm2, rv2, nbt2, C2, tr2, mom2, eps2)
         # both heads as ONE GEMM operand / bias vector, kept packed by the step's batched packing launch
         wph = packs.shared(wa, "heads_fwd", (N, 9 * ldy2))
-        packs.get(wa, "heads_fwd", (1, Ca, 9, C2, ldy2, 0, C2 * 9, 1, 9, 0), out=wph[:Ca])
-        packs.get(wb, "heads_fwd", (1, Cb, 9, C2, ldy2, 0, C2 * 9, 1, 9, 0), out=wph[Ca:])
+        packs.get(wa, "heads_fwd", Layout.fwd(Ca, C2, 9, ldy2), out=wph[:Ca])
+        packs.get(wb, "heads_fwd", Layout.fwd(Cb, C2, 9, ldy2), out=wph[Ca:])
         bias = packs.shared(wa, "heads_bias", (N,))
-        packs.get(ba, "heads_bias", (1, 1, 1, Ca, Ca, 0, 0, 0, 1, 0), out=bias[:Ca])
-        packs.get(bb, "heads_bias", (1, 1, 1, Cb, Cb, 0, 0, 0, 1, 0), out=bias[Ca:])
+        packs.get(ba, "heads_bias", Layout.vec(Ca), out=bias[:Ca])
+        packs.get(bb, "heads_bias", Layout.vec(Cb), out=bias[Ca:])
         a2 = _empty(x2.shape, x1) if need_bwd else None
         oa, ob = _empty((B, Ca, H, W), x1), _empty((B, Cb, H, W), x1)
         _small(x2, wph, oa, B, H, W, ldy2, ldyh, N, N, 2.0 * M * N * 9 * C2, pa=pa2, pc=pc2, act_in=ACT_RELU, a_out=a2,
@@ -2513,7 +2623,7 @@ class _DecoderTail(torch.autograd.Function):
         wb_ref = weakref.ref(wb)  # the cache entry must not keep a parameter (and through it the whole model) alive
 
         def pack_heads_dgrad(w, dst):  # both heads' flipped weights as ONE dgrad operand [C2][9][ldyh]
-            pack(w, 1, C2, 9, Ca, ldyh, 0, 9, 1, C2 * 9, flip=1, out=dst)
+            pack(w, *Layout.dgrad(Ca, C2, 9, ldyh), out=dst)
             _k("vmtl_pack_weights_slice", src=wb_ref(), dst=dst.view(-1)[Ca:], R0=C2, T=9, C=Cb, group=ldyh, sr0=9, st=1,
                sc=C2 * 9, flip=1)
 
@@ -2522,34 +2632,25 @@ class _DecoderTail(torch.autograd.Function):
         _small(dy, wd, dz2, B, H, W, ldyh, ldy2, C2, C2, 2.0 * M * C2 * 9 * N, stats=part2, ep_mode=2,
                ez=(x2, mean2, invstd2, g2, b2, ACT_RELU))
         with side.branch(all(s is not None for s in (swa, sba, swb, sbb)), M, fork, a2, dy):
-            slabs, ns = _wgrad(a2, dy, B, H, W, ldy2, H, W, ldyh, N, 3, 3, 1, 1, 2.0 * M * N * 9 * C2, prec=ctx.prec)
-            stride = N * 9 * ldy2
-            dwa = unpack(slabs, wa.shape, 1, Ca, 9, C2, ldy2, 0, C2 * 9, 1, 9, out=swa, nslabs=ns, slab_stride=stride)
-            dwb = unpack(slabs.view(-1)[Ca * 9 * ldy2:], wb.shape, 1, Cb, 9, C2, ldy2, 0, C2 * 9, 1, 9, out=swb, nslabs=ns,
-                         slab_stride=stride)
-            dbias = _colsum(dy, None, M, N, ldyh)
-            dba = _empty((Ca,), x1) if sba is None else sba
-            dbb = _empty((Cb,), x1) if sbb is None else sbb
-            _copy_vec(dbias, dba, Ca)
-            _copy_vec(dbias[Ca:], dbb, Cb)
+            dwa, dba, dwb, dbb = _wgrad_two_heads(
+                a2, dy, ConvGeom(B, H, W, ldy2, H, W, ldyh, 3, 3, 1, 1), Layout.fwd(Ca, C2, 9, ldy2),
+                Layout.fwd(Cb, C2, 9, ldy2), wa, wb, (swa, sba, swb, sbb), 2.0 * M * N * 9 * C2, ctx.prec)
             stamp("side tail heads")
         # BatchNorm-2 parameter gradients + its backward-apply as affine coefficients of (dz2, x2)
-        dbeta2 = _empty((C2,), x1) if sb2 is None else sb2
-        dgamma2 = _empty((C2,), x1) if sg2 is None else sg2
+        dbeta2, dgamma2 = _grad_buf((C2,), sb2, x1), _grad_buf((C2,), sg2, x1)
         cA, cB, cC = _empty((ldy2,), x1), _empty((ldy2,), x1), _empty((ldy2,), x1)
         _k("vmtl_bn_bwd_finalize", partial=part2, nblk=tiles, M=M, C=C2, Cs=ldy2, sum_dz=dbeta2, sum_dzx=dgamma2, mean=mean2,
            invstd=invstd2, gamma=g2, training=1 if tr2 else 0, coef_a=cA, coef_b=cB, coef_c=cC)
         stamp("main tail conv2")
         # conv2's data gradient: prologue dx2 = cA*dz2 + cB*x2 + cC (kept in dx2 for the weight gradient),
         # epilogue = ReLU + BatchNorm-1 backward reduction
-        wd2 = packs.get(w2, "dgrad", (1, C1, 9, C2, ldy2, 0, 9, 1, C1 * 9, 1))
+        wd2 = packs.get(w2, "dgrad", Layout.dgrad(C2, C1, 9, ldy2))
         dx2 = _empty(x2.shape, x1)
         dz1, part1 = _empty(x1.shape, x1), _empty((tiles, 2, Cs1), x1)
         _small(dz2, wd2, dz1, B, H, W, ldy2, Cs1, C1, C1, 2.0 * M * C1 * 9 * C2, x2=x2, pa=cA, pb=cB, pc=cC, a_out=dx2,
                stats=part1, ep_mode=2, ez=(x1, mean1, invstd1, g1, b1, ACT_RELU))
         fork = side.mark()  # AFTER the launch above: the weight gradient reads the dx2 it wrote
-        dbeta1 = _empty((C1,), x1) if sb1 is None else sb1
-        dgamma1 = _empty((C1,), x1) if sg1 is None else sg1
+        dbeta1, dgamma1 = _grad_buf((C1,), sb1, x1), _grad_buf((C1,), sg1, x1)
         _k("vmtl_bn_bwd_finalize", partial=part1, nblk=tiles, M=M, C=C1, Cs=Cs1, sum_dz=dbeta1, sum_dzx=dgamma1, mean=None,
            invstd=None, gamma=None, training=1 if tr1 else 0, coef_a=None, coef_b=None, coef_c=None)
         dx1 = None
@@ -2558,12 +2659,12 @@ class _DecoderTail(torch.autograd.Function):
             _k("vmtl_bn_bwd_apply", x=x1, dz=dz1, mean=mean1, invstd=invstd1, gamma=g1, sum_dz=dbeta1, sum_dzx=dgamma1,
                dx=dx1, M=M, C=C1, Cs=Cs1, training=1 if tr1 else 0)
         with side.branch(sw2 is not None, M, fork, a1, dx2):
-            slabs, ns = _wgrad(a1, dx2, B, H, W, Cs1, H, W, ldy2, C2, 3, 3, 1, 1, 2.0 * M * C2 * 9 * C1, prec=ctx.prec)
-            dw2 = unpack(slabs, w2.shape, 1, C2, 9, C1, Cs1, 0, C1 * 9, 1, 9, out=sw2, nslabs=ns)
+            dw2 = _grad_buf(w2.shape, sw2, x1)
+            _wgrad_into(a1, dx2, ConvGeom(B, H, W, Cs1, H, W, ldy2, 3, 3, 1, 1), Layout.fwd(C2, C1, 9, Cs1), dw2,
+                        2.0 * M * C2 * 9 * C1, ctx.prec)
             stamp("side tail conv2")
-        nif = lambda g, slot: None if slot is not None else g
-        return (dx1, None, None, nif(dgamma1, sg1), nif(dbeta1, sb1), None, None, None, nif(dw2, sw2), nif(dgamma2, sg2),
-                nif(dbeta2, sb2), None, None, None, nif(dwa, swa), nif(dba, sba), nif(dwb, swb), nif(dbb, sbb), None)
+        return (dx1, None, None, _grad_ret(dgamma1, sg1), _grad_ret(dbeta1, sb1), None, None, None, _grad_ret(dw2, sw2),
+                _grad_ret(dgamma2, sg2), _grad_ret(dbeta2, sb2), None, None, None, dwa, dba, dwb, dbb, None)
 
 
 def decoder_tail_supported(x1_shape, C1, C2, N) -> bool:
@@ -2589,7 +2690,7 @@ def decoder_tail(x1, stats1, rpb1, bn1, conv2_weight, bn2, wa, ba, wb, bb):
 
 def _copy_vec(src, dst, n):
     """dst[:n] = src[:n] for small per-channel vectors (the pack kernel in its degenerate 1x1x1 form)."""
-    _k("vmtl_pack_weights", src=src, dst=dst, R1=1, R0=1, T=1, C=n, Cs=n, sr1=0, sr0=0, st=0, sc=1, flip=0)
+    pack(src, *Layout.vec(n), out=dst)
 
 
 class _DualHead(torch.autograd.Function):
@@ -2608,15 +2709,16 @@ class _DualHead(torch.autograd.Function):
         N, KK = Ca + Cb, KH * KW
         ldy, Ktot = ceil4(N), KK * Cs
         wp = _empty((N, Ktot), x)
-        pack(wa, 1, Ca, KK, Cin, Cs, 0, Cin * KK, 1, KK, out=wp[:Ca])
-        pack(wb, 1, Cb, KK, Cin, Cs, 0, Cin * KK, 1, KK, out=wp[Ca:])
+        pack(wa, *Layout.fwd(Ca, Cin, KK, Cs), out=wp[:Ca])
+        pack(wb, *Layout.fwd(Cb, Cin, KK, Cs), out=wp[Ca:])
         bias = _empty((N,), x)
         _copy_vec(ba, bias, Ca)
         _copy_vec(bb, bias[Ca:], Cb)
         y = _empty((B, H, W, ldy), x)
         prec = ctx.prec = conv_prec_code()
         pw_prec = ctx.pw_prec = pw_prec_code()  # 1x1 heads take the pointwise route
-        _conv_launch(x, wp, bias, y, B, H, W, Cs, H, W, ldy, N, N, KH, KW, 1, pad, cin=Cin, prec=prec, pw_prec=pw_prec)
+        _conv_launch(x, wp, bias, y, ConvGeom(B, H, W, Cs, H, W, ldy, KH, KW, 1, pad), Cout=N, cin=Cin, prec=prec,
+                     pw_prec=pw_prec)
         oa, ob = _empty((B, Ca, H, W), x), _empty((B, Cb, H, W), x)
         yf = y.view(-1)
         _k("vmtl_nhwc_to_nchw", x=yf, y=oa, B=B, C=Ca, HW=H * W, Cs=ldy)
@@ -2636,6 +2738,7 @@ class _DualHead(torch.autograd.Function):
         Ca, Cin, KH, KW = wa.shape
         Cb = wb.shape[0]
         N, KK = Ca + Cb, KH * KW
+        g = ConvGeom(B, H, W, Cs, H, W, ldy, KH, KW, 1, pad)
         ga = torch.zeros((B, Ca, H, W), device=x.device) if ga is None else _req(ga, "grad a")
         gb = torch.zeros((B, Cb, H, W), device=x.device) if gb is None else _req(gb, "grad b")
         dy = _empty((B, H, W, ldy), x)
@@ -2647,29 +2750,16 @@ class _DualHead(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             # one tap-flipped, transposed operand [ci][tap'][co]: head a fills co < Ca and zeroes the rest of
             # every ldy-wide group, head b then fills co in [Ca, Ca+Cb)
-            wd = pack(wa, 1, Cin, KK, Ca, ldy, 0, KK, 1, Cin * KK, flip=1)
+            wd = pack(wa, *Layout.dgrad(Ca, Cin, KK, ldy))
             _k("vmtl_pack_weights_slice", src=wb, dst=wd.view(-1)[Ca:], R0=Cin, T=KK, C=Cb, group=ldy, sr0=KK, st=1,
                sc=Cin * KK, flip=1)
             dx = _empty((B, H, W, Cs), x)
-            _conv_launch(dy, wd, None, dx, B, H, W, ldy, H, W, Cs, Cin, Cin, KH, KW, 1, KH - 1 - pad, cin=N,
-                         prec=ctx.prec, pw_prec=ctx.pw_prec)
+            _conv_launch(dy, wd, None, dx, g.dgrad(), Cout=Cin, cin=N, prec=ctx.prec, pw_prec=ctx.pw_prec)
         with side.branch(all(s is not None for s in ctx.slots), B * H * W, fork, x, dy):
-            slabs, ns = _wgrad(x, dy, B, H, W, Cs, H, W, ldy, N, KH, KW, 1, pad, 2.0 * B * H * W * N * KK * Cin,
-                               prec=ctx.prec)
-            stride = N * KK * Cs
-            dwa = unpack(slabs, wa.shape, 1, Ca, KK, Cin, Cs, 0, Cin * KK, 1, KK, out=ctx.slots[0], nslabs=ns,
-                         slab_stride=stride)
-            dwb = unpack(slabs.view(-1)[Ca * KK * Cs:], wb.shape, 1, Cb, KK, Cin, Cs, 0, Cin * KK, 1, KK,
-                         out=ctx.slots[2], nslabs=ns, slab_stride=stride)
-            db = _colsum(dy, None, B * H * W, N, ldy)
-            dba = _empty((Ca,), x) if ctx.slots[1] is None else ctx.slots[1]
-            dbb = _empty((Cb,), x) if ctx.slots[3] is None else ctx.slots[3]
-            _copy_vec(db, dba, Ca)
-            _copy_vec(db[Ca:], dbb, Cb)
+            dwa, dba, dwb, dbb = _wgrad_two_heads(x, dy, g, Layout.fwd(Ca, Cin, KK, Cs), Layout.fwd(Cb, Cin, KK, Cs), wa, wb,
+                                                  ctx.slots, 2.0 * B * H * W * N * KK * Cin, ctx.prec)
             stamp("side head")
-        none_if = lambda g, slot: None if slot is not None else g
-        return (dx, none_if(dwa, ctx.slots[0]), none_if(dba, ctx.slots[1]), none_if(dwb, ctx.slots[2]),
-                none_if(dbb, ctx.slots[3]), None)
+        return dx, dwa, dba, dwb, dbb, None
 
 
 def dual_head(x, wa, ba, wb, bb, pad=1):
