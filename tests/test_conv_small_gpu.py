@@ -212,8 +212,94 @@ def test_decoder_tail_matches_torch(dev, training, shape):
         assert int(a.num_batches_tracked) == int(b.num_batches_tracked)
 
 
+@pytest.mark.parametrize("poisoned", [False, True], ids=["plain", "poison"])
+@pytest.mark.parametrize("training", [True, False])
+# Ca: the gradient rows hold ld = ceil4(Ca + 1) floats.  14 -> 16, row-per-pixel kernel, one pad lane behind head b;
+# 16 -> 20 = Ca + 4, quad-per-thread kernel, which leaves the last quad (head b's lane and three pad lanes) unwritten: the
+# tail's relayout of head b must write lanes Ca..ld;  19 -> 20, row-per-pixel kernel, no pad lane;  32 -> 36 > 32,
+# quad-per-thread kernel, the widest row the halo-tile kernel takes
+@pytest.mark.parametrize("Ca", [14, 16, 19, 32])
+def test_cross_entropy_gradient_consumed_in_place_by_the_decoder_tail(dev, Ca, training, poisoned):
+    """loss = cross_entropy(head a) + silog(sigmoid(head b)) through ops.decoder_tail, as the production step composes
+    them: the cross-entropy backward writes its gradient as [B][H][W][ceil4(Ca + 1)] rows and the tail's backward takes
+    that storage IN PLACE as the dY operand of the heads' data gradient, adding head b's lane and the zero pad lanes.
+    Every value against the same composition in torch fp64, plain and on poisoned buffers (tests/poison.py; guard mode
+    would give the gradient a storage offset, and the tail would relayout it instead)."""
+    import contextlib
+    import copy
+
+    from oracle.losses import silog
+    from tests import poison
+    from vision_mtl_amd import ops
+
+    B, C1, C2, Cb, H, W = 1, 16, 16, 1, 4, 32  # the smallest shape decoder_tail_supported admits
+    g = torch.Generator().manual_seed(100 + Ca)
+    x1 = torch.randn(B, C1, H, W, generator=g) * 2 + 0.5
+    bn1, bn2 = torch.nn.BatchNorm2d(C1), torch.nn.BatchNorm2d(C2)
+    for bn in (bn1, bn2):
+        bn.weight.data = torch.rand(bn.num_features, generator=g) + 0.5
+        bn.bias.data = torch.randn(bn.num_features, generator=g) * 0.2
+        bn.running_mean.data = torch.randn(bn.num_features, generator=g) * 0.1
+        bn.running_var.data = torch.rand(bn.num_features, generator=g) + 0.5
+        bn.train(training)
+    w2 = torch.randn(C2, C1, 3, 3, generator=g) / (C1 * 9) ** 0.5
+    wa, wb = torch.randn(Ca, C2, 3, 3, generator=g) * 0.1, torch.randn(Cb, C2, 3, 3, generator=g) * 0.1
+    ba, bb = torch.randn(Ca, generator=g), torch.randn(Cb, generator=g)
+    t = torch.randint(0, Ca, (B, H, W), generator=g)
+    depth = 0.002 + 0.498 * torch.rand(B, H, W, 1, generator=g)
+    depth[0, 1, 5:9] = 0.0  # masked pixels
+
+    bn1d, bn2d = copy.deepcopy(bn1).to(dev), copy.deepcopy(bn2).to(dev)
+    bn1, bn2 = bn1.double(), bn2.double()
+    ref = [v.double().requires_grad_(True) for v in (x1, w2, wa, ba, wb, bb)]
+    a2 = F.relu(bn2(F.conv2d(F.relu(bn1(ref[0])), ref[1], None, padding=1)))
+    ya, yb = F.conv2d(a2, ref[2], ref[3], padding=1), F.conv2d(a2, ref[4], ref[5], padding=1)
+    lr = F.cross_entropy(ya, t) + silog(torch.sigmoid(yb).permute(0, 2, 3, 1), depth.double(), interpolate=False)
+    lr.backward()
+
+    launches = []
+    orig_k = ops._k
+
+    def _k(name, _flop=None, _xflop=None, **kw):
+        launches.append((name, {k: v for k, v in kw.items() if isinstance(v, int)}))
+        return orig_k(name, _flop=_flop, _xflop=_xflop, **kw)
+
+    xd = to_dev_nhwc(x1, dev).requires_grad_(True)
+    d = [v.to(dev).requires_grad_(True) for v in (w2, wa, ba, wb, bb)]
+    assert ops.decoder_tail_supported(xd.shape, C1, C2, Ca + Cb)
+    with poison.patched("poison") if poisoned else contextlib.nullcontext():
+        oa, ob = ops.decoder_tail(xd, None, 0, bn1d, d[0], bn2d, d[1], d[2], d[3], d[4])
+        loss = ops.add_losses(ops.cross_entropy(oa, t.to(dev)),
+                              ops.silog(ops.sigmoid(ob).permute(0, 2, 3, 1), depth.to(dev)))
+        ops._k = _k
+        try:
+            loss.backward()
+        finally:
+            ops._k = orig_k
+        torch.cuda.synchronize()
+    # the in-place path: the tail's backward relayouts head b alone, into lanes Ca..ld of the cross-entropy's rows
+    # (the fallback launches vmtl_nchw_to_nhwc twice: head a into a fresh buffer first)
+    relayouts = [kw for name, kw in launches if name == "vmtl_nchw_to_nhwc"]
+    ld = ceil4(Ca + Cb)
+    assert len(relayouts) == 1, [name for name, _ in launches]
+    assert (relayouts[0]["C"], relayouts[0]["Cs"], relayouts[0]["Cw"]) == (Cb, ld, ld - Ca)
+    assert any(name == "vmtl_ce_bwd_strided" and kw["dsp"] == ld for name, kw in launches)
+    assert_close(oa.detach().cpu(), ya.detach(), what="tail head a")
+    assert_close(ob.detach().cpu(), yb.detach(), what="tail head b")
+    assert_close(loss.detach().cpu(), lr.detach(), what="loss")
+    assert_close(from_dev_nhwc(xd.grad, C1), ref[0].grad, tol=2e-4, what="tail dx1")
+    for i, name in enumerate(["w2", "wa", "ba", "wb", "bb"]):
+        assert_close(d[i].grad.cpu(), ref[i + 1].grad, tol=2e-4, what=f"tail d{name}")
+    for nm, a, b in (("bn1", bn1d, bn1), ("bn2", bn2d, bn2)):
+        assert_close(a.weight.grad.cpu(), b.weight.grad, tol=2e-4, what=f"tail d{nm}.weight")
+        assert_close(a.bias.grad.cpu(), b.bias.grad, tol=2e-4, what=f"tail d{nm}.bias")
+        assert_close(a.running_mean.cpu(), b.running_mean, tol=1e-5, what=f"{nm}.running_mean")
+        assert_close(a.running_var.cpu(), b.running_var, tol=1e-5, what=f"{nm}.running_var")
+        assert int(a.num_batches_tracked) == int(b.num_batches_tracked)
+
+
 # B, C (channels of x), Cout, C1 (skip channels, up2 only), H, W, up2
-BNCONV_CASES = [(2, 33, 33, 0, 16, 24, False), (2, 67, 33, 0, 12, 20, True), (1, 135, 67, 16, 8, 12, True),
+BNCONV_CASES =[(2, 33, 33, 0, 16, 24, False), (2, 67, 33, 0, 12, 20, True), (1, 135, 67, 16, 8, 12, True),
                 (2, 20, 67, 24, 9, 7, True), (1, 64, 128, 0, 8, 8, False)]  # last: split-K data gradient -> unfused fallback
 
 

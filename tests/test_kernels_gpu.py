@@ -856,22 +856,34 @@ def test_conv_with_folded_stitch_scale(dev, case, channel_wise):
     assert_close(y2, 0.5 * y.detach(), tol=1e-5, what="stitched conv after an in-place update of the stitch weights")
 
 
-@pytest.mark.parametrize("C", [19, 14, 5])
+# Class counts beyond the three the models use, against F.cross_entropy in fp64.  With the gradient laid out as
+# [B][H][W][ceil4(C+1)] rows: 1, 2 (Q = 1), 33 and 40 are further widths; 4, 16 and 32 are multiples of 4, where the row is
+# C + 4 wide, wider than the ceil4(C) the row-per-pixel kernel covers, so the quad-per-thread kernel runs and leaves the
+# last quad to the consumer; 33 and 40 (NYUv2) are past the 32 logits the register forms of forward and backward hold.
+CE_FP64_COUNTS = (1, 2, 4, 16, 32, 33, 40)
+
+
+@pytest.mark.parametrize("C", [19, 14, 5, *CE_FP64_COUNTS])
 def test_cross_entropy(dev, C):
     ops = _ops()
     g = torch.Generator().manual_seed(23)
-    B, H, W = 3, 17, 29
+    B, H, W = 3, 17, 29  # 1479 pixels: no multiple of a wave
     z = torch.randn(B, C, H, W, generator=g) * 3
     t = torch.randint(0, C, (B, H, W), generator=g)
-    zr = z.clone().requires_grad_(True)
+    zr = (z.double() if C in CE_FP64_COUNTS else z.clone()).requires_grad_(True)
     lr = F.cross_entropy(zr, t)
     (lr * 1.7).backward()
     zd = z.to(dev).requires_grad_(True)
     l = ops.cross_entropy(zd, t.to(dev))
     (l * 1.7).backward()
+    print(f"C={C}: loss {l.item():.8g} (reference {lr.item():.8g}), gradient max-abs error "
+          f"{float((zd.grad.cpu().double() - zr.grad.double()).abs().max()):.3e} of {float(zr.grad.abs().max()):.3e}")
     assert abs(l.item() - lr.item()) <= 1e-5 * abs(lr.item())
     assert_close(zd.grad.cpu(), zr.grad, tol=1e-5, what="CE grad")
     assert torch.equal(ops.argmax_channels(zd).cpu(), z.argmax(1))
+    if C == 1:  # one class: log_softmax is exactly 0, and so are the loss and the gradient
+        assert l.item() == 0.0 and lr.item() == 0.0
+        assert zd.grad.abs().max().item() == 0.0
 
 
 def test_cross_entropy_large_logits(dev):
@@ -930,6 +942,7 @@ def test_layout_roundtrip_and_adam(dev):
     xd = x.to(dev).requires_grad_(True)
     y = ops.to_nhwc(xd)
     assert torch.equal(from_dev_nhwc(y, 3), x) and y.shape[-1] == 4
+    assert y[..., 3:].abs().max().item() == 0.0  # the pad lane of a node's output (nothing below reads it)
     back = ops.to_nchw(y, 3)
     assert torch.equal(back.cpu(), x)
     back.backward(torch.ones_like(back))
