@@ -74,7 +74,17 @@ struct PwP {
 // BF16: the global loads are the same 16-byte quads; two consecutive k-groups of the wave's own sequence (g and g + KW)
 // supply a lane's eight k values of one v_mfma_f32_16x16x32_bf16 per (i, j) - A and B assign k values to MFMA k slots
 // alike, which is all the sum needs.  An odd group count pairs the last group with the loader's zero fill of g >= G.
-template <int TN, int KW, bool SRC2 = false, bool PRO = false, bool BF16 = false>
+// PIPE (the default route; VMTL_PW_PIPE=0 keeps the loader it replaced for same-build comparisons): every load of a
+// k-group is issued UNCONDITIONALLY and the bounds tests select the ADDRESS, not the value - raw buffer loads through
+// exact-size descriptors whose out-of-range offset returns zeros (single-source operands), a pointer select onto a 16-byte
+// zero page where the source differs per lane (SRC2).  A "condition ? *ptr : 0" select made hipcc branch around every
+// load and wait vmcnt(0) right behind the youngest group: the groups "in flight" in the source were drained once per
+// trip.  The steady-state loop runs while every group it loads exists; the last groups are a peeled tail.  Rows m >= M,
+// columns n >= Nw and k >= Ks contribute the same exact zeros and the MFMA order is unchanged: results are bit-identical.
+// Operands of 4 GB or more (32-bit buffer offsets) stay on the pointer loader (host: pw_pipe_ok).
+__device__ __attribute__((aligned(16))) float g_pw_zero_page[4] = {0.f, 0.f, 0.f, 0.f};
+
+template <int TN, int KW, bool SRC2 = false, bool PRO = false, bool BF16 = false, bool PIPE = true>
 __global__ __launch_bounds__(256) void pw_gemm_kernel(PwP p) {
   constexpr int TM = 2;
   constexpr int RG = 4 / KW;        // row groups (waves along M)
@@ -117,8 +127,54 @@ __global__ __launch_bounds__(256) void pw_gemm_kernel(PwP p) {
 #pragma unroll
     for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
+  // PIPE: byte offsets of this lane's quad in group 0 (32-bit: pw_pipe_ok) and the exact-size descriptors
+  unsigned aoff[TM], boff[TN];
+#pragma unroll
+  for (int i = 0; i < TM; ++i) aoff[i] = (unsigned)(ap[i] - p.x) * 4u;
+#pragma unroll
+  for (int j = 0; j < TN; ++j) boff[j] = (unsigned)(bp[j] - p.wp) * 4u;
+  constexpr unsigned OOB = 0xFFFFFFFFu;
+  const auto rsrc = [](const float* base, unsigned bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
+  };
+  const __amdgpu_buffer_rsrc_t rs_a = rsrc(p.x, (unsigned)p.M * (unsigned)lda * 4u);
+  const __amdgpu_buffer_rsrc_t rs_b = rsrc(p.wp, (unsigned)p.Nw * (unsigned)p.Ks * 4u);
+  const __amdgpu_buffer_rsrc_t rs_pa = rsrc(p.pa, (unsigned)p.Ks * 4u);
+  const __amdgpu_buffer_rsrc_t rs_pc = rsrc(p.pc, (unsigned)p.Ks * 4u);
+  // no residual: a zero-length descriptor, every load returns zeros
+  const __amdgpu_buffer_rsrc_t rs_res = rsrc(p.res, p.res != nullptr ? (unsigned)p.M * (unsigned)p.Ks * 4u : 0u);
+  const __amdgpu_buffer_rsrc_t rs_ao =
+      rsrc(p.a_out, (p.a_out != nullptr && tile_n == 0) ? (unsigned)p.M * (unsigned)p.Ks * 4u : 0u);
+  const auto bload = [](__amdgpu_buffer_rsrc_t r, unsigned off) -> f32x4 {
+    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
+  };
+
   struct Frag { f32x4 a[TM], b[TN], pa, pc, r[TM]; };
   auto load = [&](int g, Frag& f) {
+    if constexpr (PIPE) {
+      // k >= Ks covers g >= G; `&`, not `&&`: no short-circuit branches on per-lane conditions
+      const bool kok = 16 * g + 4 * lq < p.Ks;
+      const unsigned kb = 64u * (unsigned)g;
+      if (PRO) {
+        const unsigned ko = kok ? kb + 16u * (unsigned)lq : OOB;
+        f.pa = bload(rs_pa, ko);
+        f.pc = bload(rs_pc, ko);
+      }
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+        const bool ok = kok & aok[i];
+        if (SRC2) {
+          const float* src = 16 * g + 4 * lq >= p.K1 ? ap2[i] : ap[i];  // K1 % 4 == 0: a quad has one source
+          f.a[i] = *reinterpret_cast<const f32x4*>(ok ? src + 16 * g : g_pw_zero_page);
+        } else {
+          f.a[i] = bload(rs_a, ok ? aoff[i] + kb : OOB);
+        }
+        if (PRO) f.r[i] = bload(rs_res, ok ? aoff[i] + kb : OOB);  // lda == Ks: the residual's offsets are A's
+      }
+#pragma unroll
+      for (int j = 0; j < TN; ++j) f.b[j] = bload(rs_b, (kok & bok[j]) ? boff[j] + kb : OOB);
+      return;
+    }
     const bool kok = g < G && 16 * g + 4 * lq < p.Ks;
     if (PRO) {
       f.pa = kok ? *reinterpret_cast<const f32x4*>(p.pa + 16 * g + 4 * lq) : (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -145,7 +201,10 @@ __global__ __launch_bounds__(256) void pw_gemm_kernel(PwP p) {
         for (int e = 0; e < 4; ++e) v[e] = act_fwd(v[e], p.act_in);
         v += f.r[i];
         f.a[i] = v;
-        if (p.a_out != nullptr && tile_n == 0 && aok[i] && g < G && 16 * g + 4 * lq < p.Ks)
+        if constexpr (PIPE) {  // a store through a zero-length descriptor (no a_out, not column tile 0) is dropped
+          const bool ok = aok[i] & (16 * g + 4 * lq < p.Ks);
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs_ao, ok ? aoff[i] + 64u * (unsigned)g : OOB, 0, 0);
+        } else if (p.a_out != nullptr && tile_n == 0 && aok[i] && g < G && 16 * g + 4 * lq < p.Ks)
           *reinterpret_cast<f32x4*>(p.a_out + (size_t)(m0 + rg * 32 + 16 * i + l15) * p.Ks + 16 * g + 4 * lq) = v;
       }
     }
@@ -166,6 +225,31 @@ __global__ __launch_bounds__(256) void pw_gemm_kernel(PwP p) {
     int g = ks;
     load(g, f0);
     load(g + KW, f1);
+    if constexpr (PIPE) {
+      // FENCE: the scheduler otherwise sinks a stage's loads below the next stage's MFMAs, and the wait in front of
+      // those MFMAs then covers the younger group too
+#define FENCE() __builtin_amdgcn_sched_barrier(0)
+      // steady state: every group loaded exists, no test between the loop header and the back edge
+      for (; g + 4 * KW < G; g += 3 * KW) {
+        load(g + 2 * KW, f2); FENCE();
+        mma(f0, g); FENCE();
+        load(g + 3 * KW, f0); FENCE();
+        mma(f1, g + KW); FENCE();
+        load(g + 4 * KW, f1); FENCE();
+        mma(f2, g + 2 * KW); FENCE();
+      }
+      // tail: at most the four groups g .. g + 3 KW are left (f0, f1 in flight); a load past G is an out-of-range offset
+      load(g + 2 * KW, f2); FENCE();
+      if (g < G) mma(f0, g);
+      FENCE();
+      load(g + 3 * KW, f0); FENCE();
+      if (g + KW < G) mma(f1, g + KW);
+      FENCE();
+      if (g + 2 * KW < G) mma(f2, g + 2 * KW);
+      FENCE();
+      if (g + 3 * KW < G) mma(f0, g + 3 * KW);
+      g = G;
+    }
     for (; g < G; g += 3 * KW) {
       load(g + 2 * KW, f2);
       mma(f0, g);
@@ -202,6 +286,24 @@ __global__ __launch_bounds__(256) void pw_gemm_kernel(PwP p) {
     Frag f0[2], f1[2];
     int g = ks;
     load2(g, f0);
+    if constexpr (PIPE) {
+      for (; g + 2 * S + KW < G; g += 2 * S) {  // steady state: every group of both pairs loaded exists
+        load2(g + S, f1); FENCE();
+        mma2(f0, g); FENCE();
+        load2(g + 2 * S, f0); FENCE();
+        mma2(f1, g + S); FENCE();
+      }
+      // tail: at most the pairs at g, g + S and g + 2 S are left
+      load2(g + S, f1); FENCE();
+      if (g < G) mma2(f0, g);
+      FENCE();
+      load2(g + 2 * S, f0); FENCE();
+      if (g + S < G) mma2(f1, g + S);
+      FENCE();
+      if (g + 2 * S < G) mma2(f0, g + 2 * S);
+#undef FENCE
+      g = G;
+    }
     for (; g < G; g += 2 * S) {
       load2(g + S, f1);
       mma2(f0, g);
@@ -869,22 +971,34 @@ static int pw_big_dispatch(PwP& p, const BigCfg& c, int prec, hipStream_t st) {
   }
 }
 
-template <int TN, int KW, bool BF16>
+// the branch-free loader addresses its single-source operands with 32-bit byte offsets: every one below 4 GB
+static bool pw_pipe_ok(const PwP& p) {
+  static EnvInt e{"VMTL_PW_PIPE", 1};  // 0 = the pointer loader (same-build comparisons)
+  if (!env_int(e)) return false;
+  const unsigned long long lim = 1ull << 32;
+  const unsigned long long lda = p.x2 != nullptr ? p.K1 : p.Ks;
+  return (unsigned long long)p.M * lda * 4 < lim && (unsigned long long)p.Nw * p.Ks * 4 < lim &&
+         (unsigned long long)p.M * p.Ks * 4 < lim;
+}
+
+template <int TN, int KW, bool BF16, bool PIPE>
 static int launch_pw_t(PwP& p, hipStream_t st) {
   p.tiles_m = cdiv(p.M, (4 / KW) * 32);
   p.tiles_n = cdiv(p.ldy, 16 * TN);
   if (p.x2 != nullptr)
-    hipLaunchKernelGGL((pw_gemm_kernel<TN, KW, true, false, BF16>), dim3(p.tiles_m * p.tiles_n), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((pw_gemm_kernel<TN, KW, true, false, BF16, PIPE>), dim3(p.tiles_m * p.tiles_n), dim3(256), 0, st, p);
   else if (p.pa != nullptr)
-    hipLaunchKernelGGL((pw_gemm_kernel<TN, KW, false, true, BF16>), dim3(p.tiles_m * p.tiles_n), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((pw_gemm_kernel<TN, KW, false, true, BF16, PIPE>), dim3(p.tiles_m * p.tiles_n), dim3(256), 0, st, p);
   else
-    hipLaunchKernelGGL((pw_gemm_kernel<TN, KW, false, false, BF16>), dim3(p.tiles_m * p.tiles_n), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((pw_gemm_kernel<TN, KW, false, false, BF16, PIPE>), dim3(p.tiles_m * p.tiles_n), dim3(256), 0, st, p);
   return vmtl_check_launch();
 }
 
 template <int TN, int KW>
 static int launch_pw(PwP& p, int prec, hipStream_t st) {
-  return prec == VMTL_PREC_BF16 ? launch_pw_t<TN, KW, true>(p, st) : launch_pw_t<TN, KW, false>(p, st);
+  if (pw_pipe_ok(p))
+    return prec == VMTL_PREC_BF16 ? launch_pw_t<TN, KW, true, true>(p, st) : launch_pw_t<TN, KW, false, true>(p, st);
+  return prec == VMTL_PREC_BF16 ? launch_pw_t<TN, KW, true, false>(p, st) : launch_pw_t<TN, KW, false, false>(p, st);
 }
 
 static void pw_plain(PwP& p) {  // no prologue, ordinary epilogue

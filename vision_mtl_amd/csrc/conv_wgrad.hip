@@ -69,8 +69,15 @@ static_assert(wg_ld(16) == 16 && wg_ld(20) == 80 && wg_ld(144) == 144 && wg_ld(1
 // scalar chunk base + per-thread constant, its bounds test one add + one compare.  The general loader tracks
 // (b, ho, wo) per gather row in vector registers and rebuilds every offset with two quarter-rate multiplies: ~10
 // non-MFMA instructions per MFMA on the 32-row tile (ISA count), which is what bounded the narrow tiles.
+// PIPE (host: PD = 3 with the scalar-chunk loader; VMTL_WG_PIPE=0 keeps the guarded loop for same-build comparisons):
+// the steady-state loop issues load_tile and store_tile UNCONDITIONALLY and runs while every chunk it loads lies inside
+// the slice; the last chunks are a peeled tail whose loads past the slice end use the out-of-range offset (no traffic,
+// never stored or multiplied).
+// With the uniform guards `if (pp + PD * BP < p_end)` around load_tile inside the loop, the compiler's wait in front of
+// the staged slot's ds_write assumed the worst path and drained every younger chunk: PD bought one compute phase of
+// cover, not PD.  The order of the MFMAs is the same: bit-identical slabs.
 template <int TM, int NTR = 0, int PM = 1, int PD = (TM <= 2 ? 3 : (TM <= 4 && NTR == 0) ? 2 : 1), bool FAST = false,
-          bool BF16 = false>
+          bool BF16 = false, bool PIPE = false>
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradP p) {
   constexpr int TN = 2;
   constexpr int BMM = TM * 16;    // rows covered by MFMA tiles
@@ -166,17 +173,19 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradP p) {
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
   };
   // slot: compile-time index after unrolling (register arrays must not be indexed at run time)
-  auto load_tile = [&](int pp, f32x4* ry_s, f32x4* rx_s) {
+  // live (uniform): the chunk lies inside the slice; a dead chunk's loads are issued with the out-of-range offset
+  auto load_tile = [&](int pp, f32x4* ry_s, f32x4* rx_s, bool live = true) {
     if (FAST) {
       // every chunk is whole (M and the slice length are multiples of BP): no m < p_end test
       const unsigned ybase = (unsigned)pp * (unsigned)p.ldy * 4u;
 #pragma unroll
-      for (int it = 0; it < YIT; ++it) ry_s[it] = bload(rs_dy, tyoff[it] >= 0 ? ybase + (unsigned)tyoff[it] : OOB);
+      for (int it = 0; it < YIT; ++it)
+        ry_s[it] = bload(rs_dy, ((tyoff[it] >= 0) & live) ? ybase + (unsigned)tyoff[it] : OOB);
       const int hin = s_ho * p.stride;  // uniform: first input row / column of the chunk (before the tap shift)
       const int win = s_wo * p.stride;
       const unsigned xbase = (unsigned)((s_b * p.H + hin) * p.W + win) * (unsigned)p.Cs * 4u;
       // `&`, not `&&`: a short-circuit on a per-lane condition became divergent branches around duplicated loads
-      const bool hok = xok & ((unsigned)(hin + dh) < (unsigned)p.H);
+      const bool hok = xok & live & ((unsigned)(hin + dh) < (unsigned)p.H);
 #pragma unroll
       for (int i = 0; i < XP; ++i) {
         const bool ok = hok & ((unsigned)(win + tw[i]) < (unsigned)p.W);
@@ -252,8 +261,10 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradP p) {
   const int ntr = NTR > 0 ? max(0, min(NTR, p.Nw - (co0 + BMM))) : 0;
   // chunks pp = p_begin + it * BP; chunk it lives in register slot it % PD until it is stored to LDS buffer it & 1
 #pragma unroll
-  for (int d = 0; d < PD; ++d)
-    if (p_begin + d * BP < p_end) load_tile(p_begin + d * BP, ry[d], rx[d]);
+  for (int d = 0; d < PD; ++d) {
+    if constexpr (PIPE) load_tile(p_begin + d * BP, ry[d], rx[d], p_begin + d * BP < p_end);
+    else if (p_begin + d * BP < p_end) load_tile(p_begin + d * BP, ry[d], rx[d]);
+  }
   if (p_begin < p_end) store_tile(0, ry[0], rx[0]);
   __syncthreads();
   int cur = 0;
@@ -330,13 +341,30 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradP p) {
       }
     }
   };
-  for (int base = p_begin; base < p_end; base += PD * BP) {
+  int base = p_begin;
+  if constexpr (PIPE) {
+    // steady state: the PD steps of a trip all refill their slot with a chunk inside the slice (the last one loads
+    // base + (2 PD - 1) BP), so every step also has a next chunk to stage: no test inside the trip
+    for (; base + (2 * PD - 1) * BP < p_end; base += PD * BP) {
+#pragma unroll
+      for (int k = 0; k < PD; ++k) {
+        load_tile(base + (k + PD) * BP, ry[k], rx[k]);
+        compute(cur);
+        store_tile(cur ^ 1, ry[(k + 1) % PD], rx[(k + 1) % PD]);
+        __syncthreads();
+        cur ^= 1;
+      }
+    }
+  }
+  // PIPE: the tail, at most 2 PD - 1 chunks
+  for (; base < p_end; base += PD * BP) {
 #pragma unroll
     for (int k = 0; k < PD; ++k) {  // unrolled: slot indices k and (k + 1) % PD are compile-time constants
       const int pp = base + k * BP;
       if (pp < p_end) {  // uniform over the workgroup
         // slot k held chunk pp: it went to LDS one step ago (or in the prologue); refill it PD chunks ahead
-        if (pp + PD * BP < p_end) load_tile(pp + PD * BP, ry[k], rx[k]);
+        if constexpr (PIPE) load_tile(pp + PD * BP, ry[k], rx[k], pp + PD * BP < p_end);
+        else if (pp + PD * BP < p_end) load_tile(pp + PD * BP, ry[k], rx[k]);
         compute(cur);
         if (pp + BP < p_end) store_tile(cur ^ 1, ry[(k + 1) % PD], rx[(k + 1) % PD]);
         __syncthreads();
@@ -523,14 +551,30 @@ static int launch_wgrad(WgradP& p, int splits, hipStream_t st, int prec) {
   return launch_wgrad_pm<TM, NTR, PMD, false>(p, splits, st);
 }
 
+template <int TM, int NTR, int PM, bool FAST, bool BF16, bool PIPE>
+static int launch_wgrad_pipe(WgradP& p, int splits, hipStream_t st);
+
 template <int TM, int NTR, int PM, bool FAST, bool BF16>
 static int launch_wgrad_pm(WgradP& p, int splits, hipStream_t st) {
+  constexpr int PD = (TM <= 2 ? 3 : (TM <= 4 && NTR == 0) ? 2 : 1);
+  // PD == 3 only (tile heights 16 / 20 / 32 / 36): at PD = 2 (48 / 64 rows) the peeled loop measured 4-5 % SLOWER in
+  // the step (9.9 -> 10.4 us, 15.3 -> 15.9 us per launch, 66 launches each: its slices are four chunks, all prologue and
+  // tail, and the code is twice as long); the general loaders keep the guarded loop too
+  if constexpr (PD >= 3 && FAST) {
+    static EnvInt e{"VMTL_WG_PIPE", 1};  // 0 = the guarded loop (same-build comparisons)
+    if (env_int(e)) return launch_wgrad_pipe<TM, NTR, PM, FAST, BF16, true>(p, splits, st);
+  }
+  return launch_wgrad_pipe<TM, NTR, PM, FAST, BF16, false>(p, splits, st);
+}
+
+template <int TM, int NTR, int PM, bool FAST, bool BF16, bool PIPE>
+static int launch_wgrad_pipe(WgradP& p, int splits, hipStream_t st) {
   constexpr int BMC = TM * 16 + NTR;
   constexpr int PD = (TM <= 2 ? 3 : (TM <= 4 && NTR == 0) ? 2 : 1);
   const size_t lds = (size_t)2 * BP * (wg_ld(BMC, PM) + wg_ld(WG_BNK, PM)) * sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<TM, NTR, PM, PD, FAST, BF16>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<TM, NTR, PM, PD, FAST, BF16, PIPE>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_set = true;
   }
@@ -539,7 +583,7 @@ static int launch_wgrad_pm(WgradP& p, int splits, hipStream_t st) {
   p.tiles_kk = cdiv(p.Ktot, WG_BNK);
   p.tiles_co = cdiv(p.Nw, BMC);
   p.splits = splits;
-  hipLaunchKernelGGL((conv_wgrad_kernel<TM, NTR, PM, PD, FAST, BF16>), dim3(p.tiles_kk * p.tiles_co * splits), dim3(256), lds, st,
+  hipLaunchKernelGGL((conv_wgrad_kernel<TM, NTR, PM, PD, FAST, BF16, PIPE>), dim3(p.tiles_kk * p.tiles_co * splits), dim3(256), lds, st,
                      p);
   return vmtl_check_launch();
 }
