@@ -522,11 +522,35 @@ int vmtl_ce_bwd(const float* logits, const long long* target, const float* grad_
 int vmtl_ce_bwd_strided(const float* logits, const long long* target, const float* grad_out, float* dlogits, int B,
                         int HW, int C, long long sb, long long sc, long long sp, long long dsb, long long dsc,
                         long long dsp, void* stream);
+/* Weighted / ignoring cross entropy (torch's `weight` and `ignore_index`, reduction "mean"):
+ *   loss = sum_valid w[t_i] nll_i / sum_valid w[t_i],  valid: t_i != ignore_index.
+ * weight: C device floats, or null for all ones.  ignore_index: VMTL_NO_IGNORE when there is nothing to ignore.  A valid
+ * pixel whose target is outside [0, C) still makes the loss (and its gradient row) NaN; with every pixel ignored the loss
+ * is NaN (0/0), as in torch.  The denominator depends on the data and never visits the host: the forward leaves it in
+ * `stats` (2 device floats: stats[0] = sum of weights over valid pixels, stats[1] = the weighted nll sum), the backward
+ * reads stats[0].  workspace: vmtl_ce_ex_workspace_bytes(P) bytes, 8-byte aligned.  argmax: null, or the per-pixel
+ * prediction as vmtl_ce_fwd_argmax writes it (for ignored pixels too).
+ * Backward: dz_c = w[t] (softmax_c - 1[c == t]) grad_out / stats[0], exactly 0.0f in every written lane of an ignored
+ * pixel; the same three layouts and the same written lanes as vmtl_ce_bwd_strided. */
+#define VMTL_NO_IGNORE (-0x7fffffffffffffffLL - 1)
+long long vmtl_ce_ex_workspace_bytes(long long P);
+int vmtl_ce_fwd_ex(const float* logits, const long long* target, const float* weight, long long ignore_index,
+                   float* loss, float* stats, void* workspace, long long* argmax, int B, int HW, int C, long long sb,
+                   long long sc, long long sp, void* stream);
+int vmtl_ce_bwd_ex(const float* logits, const long long* target, const float* weight, long long ignore_index,
+                   const float* stats, const float* grad_out, float* dlogits, int B, int HW, int C, long long sb,
+                   long long sc, long long sp, long long dsb, long long dsc, long long dsp, void* stream);
 long long vmtl_silog_workspace_bytes(long long P);
 int vmtl_silog_fwd(const float* pred, const float* target, float min_depth, float* loss, float* stats,
                    void* workspace, long long P, void* stream);
 int vmtl_silog_bwd(const float* pred, const float* target, const float* stats, const float* grad_out,
                    float min_depth, float* dpred, long long P, void* stream);
+/* SILog over the pixels with mask[i] != 0 (P bytes) instead of those with target > min_depth (losses.py:29-31 with a
+ * mask given); same stats / workspace; masked-out pixels get gradient 0.0f */
+int vmtl_silog_fwd_mask(const float* pred, const float* target, const unsigned char* mask, float* loss, float* stats,
+                        void* workspace, long long P, void* stream);
+int vmtl_silog_bwd_mask(const float* pred, const float* target, const unsigned char* mask, const float* stats,
+                        const float* grad_out, float* dpred, long long P, void* stream);
 int vmtl_l1_fwd(const float* pred, const float* target, float* loss, void* workspace, long long P, void* stream);
 int vmtl_l1_bwd(const float* pred, const float* target, const float* grad_out, float* dpred, long long P,
                 void* stream);
@@ -535,6 +559,11 @@ int vmtl_l1_bwd(const float* pred, const float* target, const float* grad_out, f
 int vmtl_confusion_matrix(const long long* pred, const long long* target, int* cm, long long P, int C,
                           void* stream);
 int vmtl_segm_metrics(const int* cm, int C, float beta, float* out, void* stream);
+/* the same with torchmetrics' ignore_index: pixels whose target equals it are not counted; a class in [0, C) is left out
+ * of the Jaccard class mean (divide by C - 1) and has zero support in F-beta; accuracy is over the valid pixels */
+int vmtl_confusion_matrix_ex(const long long* pred, const long long* target, int* cm, long long P, int C,
+                             long long ignore_index, void* stream);
+int vmtl_segm_metrics_ex(const int* cm, int C, float beta, long long ignore_index, float* out, void* stream);
 
 /* ---- optimizer (training_lit.py:51,87: torch.optim.Adam) ---------------------------------- */
 int vmtl_adam_step(float* p, const float* g, float* m, float* v, const float* step_ptr, float lr, float b1,

@@ -1,13 +1,21 @@
 // Per-pixel losses of the multi-task step, forward and backward.
 //
 //   cross entropy : torch.nn.CrossEntropyLoss() as used at reference lit_module.py:31,123
-//                   (mean over B*H*W, no ignore_index / class weights / smoothing)
+//                   (mean over B*H*W); the *_ex entry points add torch's `weight` and `ignore_index`:
+//                   sum_valid w[t] nll / sum_valid w[t], valid = (t != ignore_index).  No smoothing.
 //   SILog         : reference vision_mtl/losses.py:14-36 on already-sigmoided predictions
-//                   (mask = target > min_depth, unbiased variance, 10*sqrt(var + 0.15*mean^2))
+//                   (mask = target > min_depth, or the caller's uint8 mask in the *_mask entry points;
+//                   unbiased variance, 10*sqrt(var + 0.15*mean^2))
 //   L1 / MAE      : the depth metric of reference lit_module.py:68,112 (mean |p - t|)
 //
 // Reductions are two-stage: per-workgroup partials in fp64, summed in a fixed order by a
 // single finalize workgroup, so results are run-to-run reproducible.
+//
+// The weighted / ignoring cross entropy divides by a sum that depends on the targets.  Its forward reduces
+// (numerator, denominator) pairs the same way and leaves the denominator in a two-float `stats` buffer on the device
+// (stats[0] = sum of weights over valid pixels, stats[1] = the weighted nll sum); the backward reads stats[0], so the
+// step never waits for the host.  Its kernels (ce_ex_*) stand next to the plain ones, which are untouched: the default
+// step launches exactly the code it launched before.
 #include "common.h"
 
 #define CE_THREADS 256
@@ -329,6 +337,325 @@ extern "C" int vmtl_ce_bwd_strided(const float* logits, const long long* target,
   return vmtl_check_launch();
 }
 
+// ------------------------------------------------------------------ weighted / ignoring cross entropy
+// The kernels above with torch's `weight` and `ignore_index`: the same thread-to-pixel maps, strides, launch shapes and
+// log-softmax numerics; what differs is named where it differs.
+
+// What a pixel adds to (numerator, denominator): nothing when its target is the ignore index; NaN to the numerator for
+// any other target outside [0, C) (see ce_fwd_kernel; such a target never indexes w); else w[t] * nll and w[t]
+// (w == null: all ones).
+__device__ __forceinline__ bool ce_ex_counts(long long t, int C, long long ignore, double& num) {
+  if (t == ignore) return false;
+  if (t < 0 || t >= C) {
+    num += (double)__int_as_float(0x7fc00000);
+    return false;
+  }
+  return true;
+}
+
+__device__ __forceinline__ void ce_ex_add(double& num, double& den, float nll, const float* __restrict__ w, long long t) {
+  const float wt = w != nullptr ? w[t] : 1.f;
+  num += (double)wt * (double)nll;
+  den += (double)wt;
+}
+
+__device__ __forceinline__ void ce_ex_store_partials(double num, double den, double* __restrict__ partial, double* shd) {
+  const double bn = block_sum_d(num, shd);
+  const double bd = block_sum_d(den, shd);
+  if (threadIdx.x == 0) {
+    partial[2 * blockIdx.x] = bn;
+    partial[2 * blockIdx.x + 1] = bd;
+  }
+}
+
+// ce_fwd_kernel; the argmax is written for ignored pixels too (the prediction does not depend on the target)
+__global__ __launch_bounds__(CE_THREADS) void ce_ex_fwd_kernel(const float* __restrict__ z,
+                                                               const long long* __restrict__ tgt,
+                                                               const float* __restrict__ weight, long long ignore,
+                                                               double* __restrict__ partial,
+                                                               long long* __restrict__ amax, long long P, int HW,
+                                                               int C, long long sb, long long sc, long long sp) {
+  __shared__ double shd[4];
+  double num = 0.0, den = 0.0;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long long)gridDim.x * blockDim.x) {
+    const long long b = i / HW, hw = i - b * HW;
+    const float* r = z + b * sb + hw * sp;
+    float m = r[0];
+    int am = 0;
+    for (int c = 1; c < C; ++c) {
+      const float v = r[c * sc];
+      if (v > m) { m = v; am = c; }  // first maximum wins, like torch.argmax on ties
+    }
+    if (amax != nullptr) amax[i] = am;
+    const long long t = tgt[i];
+    if (!ce_ex_counts(t, C, ignore, num)) continue;
+    float s = 0.f;
+    for (int c = 0; c < C; ++c) s += expf(r[c * sc] - m);
+    ce_ex_add(num, den, logf(s) - (r[t * sc] - m), weight, t);
+  }
+  ce_ex_store_partials(num, den, partial, shd);
+}
+
+// ce_fwd_regs_kernel (C <= 32)
+template <int Q>
+__global__ __launch_bounds__(CE_THREADS) void ce_ex_fwd_regs_kernel(const float* __restrict__ z,
+                                                                    const long long* __restrict__ tgt,
+                                                                    const float* __restrict__ weight, long long ignore,
+                                                                    double* __restrict__ partial,
+                                                                    long long* __restrict__ amax, long long P, int HW,
+                                                                    int C, long long sb, long long sc, long long sp) {
+  __shared__ double shd[4];
+  double num = 0.0, den = 0.0;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long long)gridDim.x * blockDim.x) {
+    const long long b = i / HW, hw = i - b * HW;
+    const float* r = z + b * sb + hw * sp;
+    float v[4 * Q];
+#pragma unroll
+    for (int c = 0; c < 4 * Q; ++c) v[c] = c < C ? r[c * sc] : 0.f;
+    const long long t = tgt[i];
+    float m = v[0];
+    int am = 0;
+#pragma unroll
+    for (int c = 1; c < 4 * Q; ++c)
+      if (c < C && v[c] > m) { m = v[c]; am = c; }  // first maximum wins, like torch.argmax on ties
+    if (amax != nullptr) amax[i] = am;
+    if (!ce_ex_counts(t, C, ignore, num)) continue;
+    float s = 0.f, zt = 0.f;
+#pragma unroll
+    for (int c = 0; c < 4 * Q; ++c) {
+      if (c < C) s += expf(v[c] - m);
+      if (c == t) zt = v[c];
+    }
+    ce_ex_add(num, den, logf(s) - (zt - m), weight, t);
+  }
+  ce_ex_store_partials(num, den, partial, shd);
+}
+
+// The (numerator, denominator) pairs summed in the fixed order of sum_finalize_kernel.
+// loss = num / den: NaN (0/0) when every pixel is ignored, as torch.  stats[0] = den, stats[1] = num.
+__global__ void ce_ex_finalize_kernel(const double* __restrict__ partial, int n, float* loss, float* stats) {
+  __shared__ double shd[4];
+  double num = 0.0, den = 0.0;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    num += partial[2 * i];
+    den += partial[2 * i + 1];
+  }
+  num = block_sum_d(num, shd);
+  den = block_sum_d(den, shd);
+  if (threadIdx.x == 0) {
+    loss[0] = (float)(num / den);
+    stats[0] = (float)den;
+    stats[1] = (float)num;
+  }
+}
+
+// The gradient of one pixel is dz_c = (softmax_c - 1[c == t]) * k + bad with k = w[t] * g, g = gout / den.  An ignored
+// pixel sets `zero`, and the kernels then store 0.0f in every lane they own (a select, never a product with g, which is
+// inf when every pixel is ignored).  bad: NaN for a target outside [0, C) that is not the ignore index - as the
+// forward: NaN, never a silent 0 - and such a target never indexes w.
+__device__ __forceinline__ float ce_ex_scale(long long t, int C, float g, const float* __restrict__ w, long long ignore,
+                                             float& bad, bool& zero) {
+  zero = t == ignore;
+  const bool oob = t < 0 || t >= C;
+  bad = (oob && !zero) ? __int_as_float(0x7fc00000) : 0.f;
+  return (!oob && w != nullptr) ? w[t] * g : g;
+}
+
+// ce_bwd_kernel
+__global__ __launch_bounds__(CE_THREADS) void ce_ex_bwd_kernel(const float* __restrict__ z,
+                                                               const long long* __restrict__ tgt,
+                                                               const float* __restrict__ weight, long long ignore,
+                                                               const float* __restrict__ stats,
+                                                               const float* __restrict__ gout, float* __restrict__ dz,
+                                                               long long P, int HW, int C, long long sb, long long sc,
+                                                               long long sp, long long dsb, long long dsc, long long dsp) {
+  const float g = gout[0] / stats[0];
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long long)gridDim.x * blockDim.x) {
+    const long long b = i / HW, hw = i - b * HW;
+    const long long off = b * sb + hw * sp, doff = b * dsb + hw * dsp;
+    float m = z[off];
+    for (int c = 1; c < C; ++c) m = fmaxf(m, z[off + c * sc]);
+    float s = 0.f;
+    for (int c = 0; c < C; ++c) s += expf(z[off + c * sc] - m);
+    const float inv = 1.f / s;
+    const long long t = tgt[i];
+    float bad;
+    bool zero;
+    const float k = ce_ex_scale(t, C, g, weight, ignore, bad, zero);
+    for (int c = 0; c < C; ++c)
+      dz[doff + c * dsc] = zero ? 0.f : (expf(z[off + c * sc] - m) * inv - (c == t ? 1.f : 0.f)) * k + bad;
+  }
+}
+
+// ce_bwd_nhwc_kernel: NHWC rows of ld >= ceil4(C) floats, of which the first ceil4(C) are written
+__global__ __launch_bounds__(CE_THREADS) void ce_ex_bwd_nhwc_kernel(const float* __restrict__ z,
+                                                                    const long long* __restrict__ tgt,
+                                                                    const float* __restrict__ weight, long long ignore,
+                                                                    const float* __restrict__ stats,
+                                                                    const float* __restrict__ gout,
+                                                                    float* __restrict__ dz, long long P, int HW, int C,
+                                                                    long long sb, long long sc, long long sp, int ld) {
+  const float g = gout[0] / stats[0];
+  const int Q = (C + 3) >> 2;
+  const long long total = P * Q;
+  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+    const long long i = idx / Q;
+    const int q = (int)(idx - i * Q);
+    const long long b = i / HW, hw = i - b * HW;
+    const long long off = b * sb + hw * sp;
+    float m = z[off];
+    for (int c = 1; c < C; ++c) m = fmaxf(m, z[off + c * sc]);
+    float s = 0.f;
+    for (int c = 0; c < C; ++c) s += expf(z[off + c * sc] - m);
+    const float inv = 1.f / s;
+    const long long t = tgt[i];
+    float bad;
+    bool zero;
+    const float k = ce_ex_scale(t, C, g, weight, ignore, bad, zero);
+    f32x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int c = 4 * q + e;
+      v[e] = (c < C && !zero) ? (expf(z[off + c * sc] - m) * inv - (c == t ? 1.f : 0.f)) * k + bad : 0.f;
+    }
+    *reinterpret_cast<f32x4*>(dz + i * ld + 4 * q) = v;
+  }
+}
+
+// ce_bwd_nhwc_rows_kernel: rows of exactly Q = ceil(C/4) quads, turned through LDS
+template <int Q>
+__global__ __launch_bounds__(256) void ce_ex_bwd_nhwc_rows_kernel(const float* __restrict__ z,
+                                                                  const long long* __restrict__ tgt,
+                                                                  const float* __restrict__ weight, long long ignore,
+                                                                  const float* __restrict__ stats,
+                                                                  const float* __restrict__ gout, float* __restrict__ dz,
+                                                                  long long P, int HW, int C, long long sb, long long sc,
+                                                                  long long sp) {
+  __shared__ f32x4 sm[4][64 * Q];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const float g = gout[0] / stats[0];
+  for (long long wg0 = (long long)blockIdx.x * 256; wg0 < P; wg0 += (long long)gridDim.x * 256) {  // uniform trip count
+    const long long base = wg0 + wave * 64, i = base + lane;
+    if (i < P) {
+      const long long b = i / HW, hw = i - b * HW;
+      const float* r = z + b * sb + hw * sp;
+      float v[4 * Q];
+#pragma unroll
+      for (int c = 0; c < 4 * Q; ++c) v[c] = c < C ? r[c * sc] : 0.f;
+      float m = v[0];
+#pragma unroll
+      for (int c = 1; c < 4 * Q; ++c) m = c < C ? fmaxf(m, v[c]) : m;
+      float s = 0.f;
+#pragma unroll
+      for (int c = 0; c < 4 * Q; ++c) {
+        v[c] = c < C ? expf(v[c] - m) : 0.f;
+        s += v[c];
+      }
+      const float inv = 1.f / s;
+      const long long t = tgt[i];
+      float bad;
+      bool zero;
+      const float k = ce_ex_scale(t, C, g, weight, ignore, bad, zero);
+#pragma unroll
+      for (int q = 0; q < Q; ++q) {
+        f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int c = 4 * q + e;
+          o[e] = (c < C && !zero) ? (v[c] * inv - (c == t ? 1.f : 0.f)) * k + bad : 0.f;
+        }
+        sm[wave][lane * Q + q] = o;
+      }
+    }
+    __syncthreads();
+    if (base < P) {
+      const int nf4 = (int)(P - base < 64 ? P - base : 64) * Q;
+      f32x4* out = reinterpret_cast<f32x4*>(dz + base * (4 * Q));
+#pragma unroll
+      for (int j = 0; j < Q; ++j) {
+        const int idx = j * 64 + lane;
+        if (idx < nf4) out[idx] = sm[wave][idx];
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// (numerator, denominator) per block
+extern "C" long long vmtl_ce_ex_workspace_bytes(long long P) { return 2 * (long long)ce_blocks(P) * (long long)sizeof(double); }
+
+// weight = C floats or null (all ones), ignore_index = VMTL_NO_IGNORE for none, argmax = null or the prediction output.
+// Writes loss and stats (2 floats); workspace: vmtl_ce_ex_workspace_bytes(P) bytes, 8-byte aligned.
+extern "C" int vmtl_ce_fwd_ex(const float* logits, const long long* target, const float* weight, long long ignore_index,
+                              float* loss, float* stats, void* workspace, long long* argmax, int B, int HW, int C,
+                              long long sb, long long sc, long long sp, void* stream) {
+  VMTL_ENTER();
+  if (!logits || !target || !loss || !stats || !workspace || B <= 0 || HW <= 0 || C <= 0) return VMTL_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const long long P = (long long)B * HW;
+  const int nblk = ce_blocks(P);
+  double* partial = (double*)workspace;
+#define CEF(QV)                                                                                                     \
+  hipLaunchKernelGGL((ce_ex_fwd_regs_kernel<QV>), dim3(nblk), dim3(CE_THREADS), 0, st, logits, target, weight, ignore_index, \
+                     partial, argmax, P, HW, C, sb, sc, sp)
+  switch (C <= 32 ? (C + 3) >> 2 : 0) {
+    case 1: CEF(1); break;
+    case 2: CEF(2); break;
+    case 3: CEF(3); break;
+    case 4: CEF(4); break;
+    case 5: CEF(5); break;
+    case 6: CEF(6); break;
+    case 7: CEF(7); break;
+    case 8: CEF(8); break;
+    default:
+      hipLaunchKernelGGL(ce_ex_fwd_kernel, dim3(nblk), dim3(CE_THREADS), 0, st, logits, target, weight, ignore_index,
+                         partial, argmax, P, HW, C, sb, sc, sp);
+  }
+#undef CEF
+  hipLaunchKernelGGL(ce_ex_finalize_kernel, dim3(1), dim3(256), 0, st, partial, nblk, loss, stats);
+  return vmtl_check_launch();
+}
+
+// dz_c = w[t] (softmax_c - 1[c == t]) gout / stats[0], 0.0f in every written lane of an ignored pixel; stats as
+// vmtl_ce_fwd_ex left it.  The three layouts of vmtl_ce_bwd_strided, chosen by the same tests, writing the same lanes.
+extern "C" int vmtl_ce_bwd_ex(const float* logits, const long long* target, const float* weight, long long ignore_index,
+                              const float* stats, const float* grad_out, float* dlogits, int B, int HW, int C,
+                              long long sb, long long sc, long long sp, long long dsb, long long dsc, long long dsp,
+                              void* stream) {
+  VMTL_ENTER();
+  if (!logits || !target || !stats || !grad_out || !dlogits || B <= 0 || HW <= 0 || C <= 0) return VMTL_ERR_ARG;
+  const long long P = (long long)B * HW;
+  if (dsc == 1 && dsp == ((C + 3) & ~3) && dsp <= 32 && dsb == dsp * HW) {
+    long long nb = cdivll(P, 256);
+    if (nb > 8192) nb = 8192;
+#define CALL(QV)                                                                                                   \
+  hipLaunchKernelGGL((ce_ex_bwd_nhwc_rows_kernel<QV>), dim3((int)nb), dim3(256), 0, (hipStream_t)stream, logits, target, \
+                     weight, ignore_index, stats, grad_out, dlogits, P, HW, C, sb, sc, sp)
+    switch ((int)dsp >> 2) {
+      case 1: CALL(1); break;
+      case 2: CALL(2); break;
+      case 3: CALL(3); break;
+      case 4: CALL(4); break;
+      case 5: CALL(5); break;
+      case 6: CALL(6); break;
+      case 7: CALL(7); break;
+      default: CALL(8); break;
+    }
+#undef CALL
+    return vmtl_check_launch();
+  }
+  if (dsc == 1 && (dsp & 3) == 0 && dsp >= ((C + 3) & ~3) && dsb == dsp * HW) {
+    long long nb = cdivll(P * ((C + 3) >> 2), CE_THREADS);
+    if (nb > 8192) nb = 8192;
+    hipLaunchKernelGGL(ce_ex_bwd_nhwc_kernel, dim3((int)nb), dim3(CE_THREADS), 0, (hipStream_t)stream, logits, target,
+                       weight, ignore_index, stats, grad_out, dlogits, P, HW, C, sb, sc, sp, (int)dsp);
+    return vmtl_check_launch();
+  }
+  hipLaunchKernelGGL(ce_ex_bwd_kernel, dim3(ce_blocks(P)), dim3(CE_THREADS), 0, (hipStream_t)stream, logits, target, weight,
+                     ignore_index, stats, grad_out, dlogits, P, HW, C, sb, sc, sp, dsb, dsc, dsp);
+  return vmtl_check_launch();
+}
+
 // ------------------------------------------------------------------ SILog
 #define SL_BLOCKS_MAX 1024
 
@@ -425,6 +752,73 @@ extern "C" int vmtl_silog_bwd(const float* pred, const float* target, const floa
   if (!pred || !target || !stats || !grad_out || !dpred || P <= 0) return VMTL_ERR_ARG;
   hipLaunchKernelGGL(silog_bwd_kernel, dim3(sl_blocks(P)), dim3(256), 0, (hipStream_t)stream, pred, target, stats,
                      grad_out, min_depth, P, dpred);
+  return vmtl_check_launch();
+}
+
+// SILog over the pixels of the caller's uint8 mask (reference losses.py:29-31 with `mask` given; min_depth is then not
+// applied) instead of those with target > min_depth: silog_fwd_kernel / silog_bwd_kernel with that one test exchanged,
+// the same partials, finalize and closed-form backward.
+__global__ __launch_bounds__(256) void silog_mask_fwd_kernel(const float* __restrict__ pred,
+                                                             const float* __restrict__ tgt,
+                                                             const unsigned char* __restrict__ mask, long long P,
+                                                             double* __restrict__ partial) {
+  __shared__ double shd[4];
+  double n = 0.0, s1 = 0.0, s2 = 0.0;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long long)gridDim.x * blockDim.x) {
+    if (mask[i] != 0) {
+      const float g = logf(pred[i]) - logf(tgt[i]);
+      n += 1.0;
+      s1 += (double)g;
+      s2 += (double)g * (double)g;
+    }
+  }
+  const double bn = block_sum_d(n, shd);
+  const double b1 = block_sum_d(s1, shd);
+  const double b2 = block_sum_d(s2, shd);
+  if (threadIdx.x == 0) {
+    partial[blockIdx.x * 3 + 0] = bn;
+    partial[blockIdx.x * 3 + 1] = b1;
+    partial[blockIdx.x * 3 + 2] = b2;
+  }
+}
+
+__global__ __launch_bounds__(256) void silog_mask_bwd_kernel(const float* __restrict__ pred,
+                                                             const float* __restrict__ tgt,
+                                                             const unsigned char* __restrict__ mask,
+                                                             const float* __restrict__ stats,
+                                                             const float* __restrict__ gout, long long P,
+                                                             float* __restrict__ dpred) {
+  const float n = stats[0], mu = stats[1], dg = stats[2];
+  const float k = gout[0] * 5.f / sqrtf(dg);
+  const float a = 2.f / (n - 1.f), b = 0.3f * mu / n;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long long)gridDim.x * blockDim.x) {
+    float r = 0.f;
+    if (mask[i] != 0) {
+      const float p = pred[i];
+      const float g = logf(p) - logf(tgt[i]);
+      r = k * (a * (g - mu) + b) / p;
+    }
+    dpred[i] = r;
+  }
+}
+
+extern "C" int vmtl_silog_fwd_mask(const float* pred, const float* target, const unsigned char* mask, float* loss,
+                                   float* stats, void* workspace, long long P, void* stream) {
+  VMTL_ENTER();
+  if (!pred || !target || !mask || !loss || !stats || !workspace || P <= 0) return VMTL_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const int nblk = sl_blocks(P);
+  hipLaunchKernelGGL(silog_mask_fwd_kernel, dim3(nblk), dim3(256), 0, st, pred, target, mask, P, (double*)workspace);
+  hipLaunchKernelGGL(silog_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)workspace, nblk, loss, stats);
+  return vmtl_check_launch();
+}
+
+extern "C" int vmtl_silog_bwd_mask(const float* pred, const float* target, const unsigned char* mask, const float* stats,
+                                   const float* grad_out, float* dpred, long long P, void* stream) {
+  VMTL_ENTER();
+  if (!pred || !target || !mask || !stats || !grad_out || !dpred || P <= 0) return VMTL_ERR_ARG;
+  hipLaunchKernelGGL(silog_mask_bwd_kernel, dim3(sl_blocks(P)), dim3(256), 0, (hipStream_t)stream, pred, target, mask,
+                     stats, grad_out, P, dpred);
   return vmtl_check_launch();
 }
 

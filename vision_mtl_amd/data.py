@@ -38,12 +38,14 @@ def synthetic_batch(B: int, H: int, W: int, C: int, seed: int = 11, masked: floa
     return {"img": img, "mask": mask, "depth": depth}
 
 
-def prepare_sample(raw: dict, num_classes: int, max_depth: float = 1.0, dataset: str = "cityscapes") -> dict:
+def prepare_sample(raw: dict, num_classes: int, max_depth: float = 1.0, dataset: str = "cityscapes",
+                   void_label: t.Optional[int] = None) -> dict:
     """Value rules of the reference's two datasets on one raw sample {"img": (H,W,3), "mask": (H,W), "depth": (H,W) or
     (H,W,1)} of numpy arrays / tensors, WITHOUT the CHW transpose.
 
     dataset="cityscapes" (reference data_modules/cityscapes.py:39-67): mask == -1 -> num_classes-1, img float32, mask
-    int64, depth float32 divided by max_depth when its maximum exceeds 1 (common_ds.py:47-50).
+    int64, depth float32 divided by max_depth when its maximum exceeds 1 (common_ds.py:47-50).  void_label: the value -1
+    maps to instead (e.g. 255, trained with MTLModule(segm_ignore_index=255)); None keeps the reference's rule.
     dataset="nyuv2" (reference data_modules/nyuv2.py:100-141): img divided by 255 when its maximum exceeds 1 (8-bit
     PNG), a mask that a ToTensor transform scaled into [0,1] is multiplied back by 255 (`mask.max() <= 1.0`), mask
     squeezed to (H,W) int64 with NO -1 remap, depth = uint16 PNG value / 1e4 and THEN the max_depth rule
@@ -53,6 +55,8 @@ def prepare_sample(raw: dict, num_classes: int, max_depth: float = 1.0, dataset:
     Both: depth comes back as (H, W, 1) (SILog needs the trailing 1)."""
     if dataset not in ("cityscapes", "nyuv2"):
         raise ValueError(f"prepare_sample: dataset must be 'cityscapes' or 'nyuv2', got {dataset!r}")
+    if void_label is not None and dataset != "cityscapes":
+        raise ValueError("prepare_sample: void_label remaps Cityscapes' -1; the nyuv2 loader has no such label")
     as_t = lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
     img, mask, depth = as_t(raw["img"]).float(), as_t(raw["mask"]).clone(), as_t(raw["depth"]).float().clone()
     if img.dim() != 3 or img.shape[-1] != 3:
@@ -66,7 +70,7 @@ def prepare_sample(raw: dict, num_classes: int, max_depth: float = 1.0, dataset:
         depth = depth / 1e4  # nyuv2.py:126-127: the depth PNG is uint16, 1e-4 m per count
     else:
         mask = mask.long()
-        mask[mask == -1] = num_classes - 1  # cityscapes.py:42
+        mask[mask == -1] = num_classes - 1 if void_label is None else int(void_label)  # cityscapes.py:42
     if depth.max() > 1.0:  # common_ds.py:47-50
         depth /= max_depth
     if depth.dim() == 3 and depth.shape[0] == 1 and depth.shape[-1] != 1:  # nyuv2.py:130-131: (1,H,W) -> (H,W,1)

@@ -22,13 +22,28 @@ from .utils.loss_utils import summarize_epoch_metrics
 class MTLModule(nn.Module):
     def __init__(self, model: nn.Module, num_classes: int, optim_dict: t.Optional[dict] = None,
                  lr: t.Optional[float] = None, device: str = "cuda", loss_segm_weight: float = 1.0,
-                 loss_depth_weight: float = 1.0):
+                 loss_depth_weight: float = 1.0, segm_ignore_index: t.Optional[int] = None,
+                 segm_class_weights: t.Optional[t.Sequence[float]] = None):
+        """segm_ignore_index / segm_class_weights (opt-in, INTEGRATION.md): the `ignore_index` and per-class `weight`
+        of the segmentation criterion; the ignore index also keeps those pixels out of the segmentation metrics."""
         super().__init__()
+        if segm_class_weights is not None:
+            segm_class_weights = torch.as_tensor(segm_class_weights, dtype=torch.float32).detach().flatten()
+            if segm_class_weights.numel() != num_classes:
+                raise ValueError(f"MTLModule: segm_class_weights must hold num_classes = {num_classes} floats, got "
+                                 f"{segm_class_weights.numel()}")
         self.hparams = {"num_classes": num_classes, "optim_dict": optim_dict, "lr": lr, "device": device,
-                        "loss_segm_weight": loss_segm_weight, "loss_depth_weight": loss_depth_weight}
+                        "loss_segm_weight": loss_segm_weight, "loss_depth_weight": loss_depth_weight,
+                        "segm_ignore_index": segm_ignore_index,
+                        "segm_class_weights": None if segm_class_weights is None else segm_class_weights.tolist()}
         self.num_classes = num_classes
         self.model = model
-        self.segm_criterion = CrossEntropyLoss()
+        self.segm_criterion = CrossEntropyLoss(weight=segm_class_weights, ignore_index=segm_ignore_index)
+        if segm_class_weights is not None:  # the model usually arrives on its device: the weights join it there
+            p = next(model.parameters(), None)
+            if p is not None:
+                self.segm_criterion.to(p.device)
+        self.segm_ignore_index = segm_ignore_index
         self.depth_criterion = SILogLoss()
         self.optim_dict = optim_dict
         self.loss_segm_weight = loss_segm_weight
@@ -36,8 +51,10 @@ class MTLModule(nn.Module):
         self.step_outputs = {k: {"loss": [], "accuracy": [], "jaccard_index": [], "fbeta_score": [], "mae": []}
                              for k in ["train", "val", "test", "predict"]}
         # reference lit_module.py:48-69 (torchmetrics 0.7.3 Accuracy-micro / FBeta-weighted / Jaccard / MAE)
-        self.metrics = {"accuracy": M.Accuracy(num_classes), "fbeta_score": M.FBetaScore(num_classes, beta=1.0),
-                        "jaccard_index": M.JaccardIndex(num_classes), "mae": M.MeanAbsoluteError()}
+        ign = segm_ignore_index
+        self.metrics = {"accuracy": M.Accuracy(num_classes, ignore_index=ign),
+                        "fbeta_score": M.FBetaScore(num_classes, beta=1.0, ignore_index=ign),
+                        "jaccard_index": M.JaccardIndex(num_classes, ignore_index=ign), "mae": M.MeanAbsoluteError()}
         self.automatic_optimization = False
         self.compute_metrics = True  # bench.py turns this off to time exactly fwd + losses + bwd
         self._nan = {}  # device -> the NaN placeholder of the skipped metrics (built once, not filled every step)
@@ -74,7 +91,11 @@ class MTLModule(nn.Module):
             if nan is None:
                 nan = self._nan[gt_mask.device] = torch.full((), float("nan"), device=gt_mask.device)
             return {"accuracy": nan, "jaccard_index": nan, "fbeta_score": nan, "mae": nan}
-        cm = M.confusion_matrix(out["segm_predictions"], gt_mask, self.num_classes)
+        if self.segm_ignore_index is None:  # the default step makes the call it always made
+            cm = M.confusion_matrix(out["segm_predictions"], gt_mask, self.num_classes)
+        else:
+            cm = M.confusion_matrix(out["segm_predictions"], gt_mask, self.num_classes,
+                                    ignore_index=self.segm_ignore_index)
         return {"accuracy": self.metrics["accuracy"].from_confusion(cm),
                 "jaccard_index": self.metrics["jaccard_index"].from_confusion(cm),
                 "fbeta_score": self.metrics["fbeta_score"].from_confusion(cm),

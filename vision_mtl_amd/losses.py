@@ -23,27 +23,43 @@ class SILogLoss(nn.Module):
 
     def forward(self, pred: torch.Tensor, target: torch.Tensor, mask: t.Optional[torch.Tensor] = None,
                 interpolate: bool = True, min_depth: t.Optional[float] = None) -> torch.Tensor:
-        if mask is not None:
-            raise NotImplementedError("explicit masks are not used on the reference's step path")
         if pred.dim() < 2 or target.dim() < 2:
             raise IndexError("SILogLoss expects at least 2-D pred/target (the reference indexes shape[-2:])")
         if interpolate and pred.shape[-2:] != target.shape[-2:]:
             raise NotImplementedError("SILogLoss: pred/target spatial sizes differ; resample before the loss")
         if pred.shape != target.shape:
             raise ValueError(f"SILogLoss: shape mismatch {tuple(pred.shape)} vs {tuple(target.shape)}")
-        return ops.silog(pred, target, self.min_depth if min_depth is None else min_depth)
+        # mask: the valid pixels (bool / uint8, target's shape); min_depth is then not applied (losses.py:29-31)
+        return ops.silog(pred, target, self.min_depth if min_depth is None else min_depth, mask=mask)
 
 
 class CrossEntropyLoss(nn.Module):
-    """torch.nn.CrossEntropyLoss() with default arguments (mean, no weights / ignore_index / smoothing):
-    logits (B,C,H,W), target int64 (B,H,W)."""
+    """torch.nn.CrossEntropyLoss (reduction "mean", no smoothing): logits (B,C,H,W), target int64 (B,H,W).
+
+    weight: one float per class (torch's `weight`); ignore_index: a target value whose pixels count neither in the sum
+    nor in the denominator.  Its default is None - NOT torch's -100: nothing is ignored, and a label outside [0, C)
+    makes the loss NaN instead of vanishing.  With both at their defaults this is the reference's criterion on the
+    unweighted kernels.  `weight` is a buffer (it follows .to(device)) that stays out of state_dict: checkpoints keep
+    the reference's keys."""
+
+    def __init__(self, weight: t.Optional[torch.Tensor] = None, ignore_index: t.Optional[int] = None):
+        super().__init__()
+        if ignore_index is not None and (isinstance(ignore_index, bool) or not isinstance(ignore_index, int)):
+            raise TypeError(f"CrossEntropyLoss: ignore_index must be an int or None, got {ignore_index!r}")
+        if weight is not None:
+            weight = torch.as_tensor(weight, dtype=torch.float32).detach().clone()
+            if weight.dim() != 1 or weight.numel() == 0:
+                raise ValueError(f"CrossEntropyLoss: weight must be a 1-D tensor of per-class floats, got shape "
+                                 f"{tuple(weight.shape)}")
+        self.ignore_index = ignore_index
+        self.register_buffer("weight", weight, persistent=False)
 
     def forward(self, logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
-        return ops.cross_entropy(logits, target)
+        return ops.cross_entropy(logits, target, weight=self.weight, ignore_index=self.ignore_index)
 
     def forward_with_predictions(self, logits: torch.Tensor, target: torch.Tensor):
         """(loss, argmax_c logits): the loss pass finds each pixel's maximum anyway (one launch instead of two)."""
-        return ops.cross_entropy_with_argmax(logits, target)
+        return ops.cross_entropy_with_argmax(logits, target, weight=self.weight, ignore_index=self.ignore_index)
 
 
 class L1Loss(nn.Module):

@@ -2903,13 +2903,87 @@ class _CrossEntropy(torch.autograd.Function):
         return dl, None, None
 
 
-def cross_entropy(logits, target):
-    return _CrossEntropy.apply(logits, target, False)
+NO_IGNORE = -(1 << 63)  # include/vmtl.h VMTL_NO_IGNORE: the ignore_index of "nothing to ignore"
 
 
-def cross_entropy_with_argmax(logits, target):
-    """(loss, argmax over the class axis) from one pass over the logits (reference lit_module.py:123 + 137-138)."""
-    return _CrossEntropy.apply(logits, target, True)
+def _ce_weight(weight, logits):
+    """The class-weight operand of the weighted cross entropy: C fp32 floats on the logits' device (None: all ones)."""
+    if weight is None:
+        return None
+    weight = _req(weight.detach(), "weight")
+    if weight.dim() != 1 or weight.numel() != logits.shape[1]:
+        raise ValueError(f"cross_entropy: weight must hold one float per class ({logits.shape[1]}), got shape "
+                         f"{tuple(weight.shape)}")
+    if weight.device != logits.device:
+        raise RuntimeError(f"cross_entropy: weight is on {weight.device}, the logits on {logits.device}")
+    return weight
+
+
+class _CrossEntropyEx(torch.autograd.Function):
+    """sum_valid w[t] nll / sum_valid w[t] with valid = (target != ignore_index): torch's `weight` / `ignore_index`
+    (reduction "mean").  The denominator depends on the targets: the forward leaves it in `stats` on the device and the
+    backward reads it there, so the node never waits for the host.  weight gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight, ignore_index, want_argmax=False):
+        logits = _req(logits, "logits")
+        if target.dtype != torch.int64:
+            raise TypeError("cross_entropy: target must be int64 class indices")
+        target = target.contiguous()
+        B, C, H, W = logits.shape
+        if tuple(target.shape) != (B, H, W):
+            raise ValueError(f"cross_entropy: target shape {tuple(target.shape)} does not match logits {(B, H, W)}")
+        weight = _ce_weight(weight, logits)
+        P = B * H * W
+        loss, stats = _empty((), logits), _empty((2,), logits)
+        ws = torch.empty((lib().raw("vmtl_ce_ex_workspace_bytes")(P) // 8,), dtype=torch.float64, device=logits.device)
+        pred = torch.empty((B, H, W), dtype=torch.int64, device=logits.device) if want_argmax else None
+        _k("vmtl_ce_fwd_ex", logits=logits, target=target, weight=weight, ignore_index=ignore_index, loss=loss,
+           stats=stats, workspace=ws, argmax=pred, B=B, HW=H * W, C=C, sb=C * H * W, sc=H * W, sp=1)
+        ctx.save_for_backward(logits, target, stats, *(() if weight is None else (weight,)))
+        ctx.ignore_index = ignore_index
+        if want_argmax:
+            ctx.mark_non_differentiable(pred)
+            return loss, pred
+        return loss
+
+    @staticmethod
+    def backward(ctx, g, _gpred=None):
+        logits, target, stats, *weight = ctx.saved_tensors
+        B, C, H, W = logits.shape
+        g = _req(g, "grad_output")
+        ld = ceil4(C + 1)  # the layout of _CrossEntropy.backward: NHWC rows with room for one more head
+        st = _empty((B, H, W, ld), logits)
+        _k("vmtl_ce_bwd_ex", logits=logits, target=target, weight=weight[0] if weight else None,
+           ignore_index=ctx.ignore_index, stats=stats, grad_out=g, dlogits=st, B=B, HW=H * W, C=C, sb=C * H * W,
+           sc=H * W, sp=1, dsb=H * W * ld, dsc=1, dsp=ld)
+        dl = st[..., :C].permute(0, 3, 1, 2)
+        dl._vmtl_nhwc = st
+        return dl, None, None, None, None
+
+
+def _ce_ignore(ignore_index):
+    if ignore_index is None:
+        return NO_IGNORE
+    if isinstance(ignore_index, bool) or not isinstance(ignore_index, int):
+        raise TypeError(f"cross_entropy: ignore_index must be an int or None, got {ignore_index!r}")
+    return ignore_index
+
+
+def cross_entropy(logits, target, weight=None, ignore_index=None):
+    """torch.nn.functional.cross_entropy(logits, target) (mean); `weight` (C fp32 floats on the device) and
+    `ignore_index` as torch's, except that the default ignores nothing: an unmapped label makes the loss NaN."""
+    if weight is None and ignore_index is None:
+        return _CrossEntropy.apply(logits, target, False)
+    return _CrossEntropyEx.apply(logits, target, weight, _ce_ignore(ignore_index), False)
+
+
+def cross_entropy_with_argmax(logits, target, weight=None, ignore_index=None):
+    """(loss, argmax over the class axis) from one pass over the logits (reference lit_module.py:123 + 137-138).  The
+    prediction is written for every pixel, ignored or not."""
+    if weight is None and ignore_index is None:
+        return _CrossEntropy.apply(logits, target, True)
+    return _CrossEntropyEx.apply(logits, target, weight, _ce_ignore(ignore_index), True)
 
 
 class _SILog(torch.autograd.Function):
@@ -2938,8 +3012,43 @@ class _SILog(torch.autograd.Function):
         return dp, None, None
 
 
-def silog(pred, target, min_depth=1e-3):
-    return _SILog.apply(pred, target, float(min_depth))
+class _SILogMasked(torch.autograd.Function):
+    """_SILog over the pixels of an explicit uint8 mask (reference losses.py:29-31 with `mask` given)."""
+
+    @staticmethod
+    def forward(ctx, pred, target, mask):
+        pred, target = _req(pred, "pred"), _req(target, "target")
+        if pred.numel() != target.numel():
+            raise ValueError("silog: pred and target must have the same number of elements")
+        P = pred.numel()
+        loss, stats = _empty((), pred), _empty((3,), pred)
+        ws = torch.empty((lib().raw("vmtl_silog_workspace_bytes")(P) // 8,), dtype=torch.float64, device=pred.device)
+        _k("vmtl_silog_fwd_mask", pred=pred, target=target, mask=mask, loss=loss, stats=stats, workspace=ws, P=P)
+        ctx.save_for_backward(pred, target, mask, stats)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, target, mask, stats = ctx.saved_tensors
+        g = _req(g, "grad_output")
+        dp = _empty(pred.shape, pred)
+        _k("vmtl_silog_bwd_mask", pred=pred, target=target, mask=mask, stats=stats, grad_out=g, dpred=dp, P=pred.numel())
+        return dp, None, None
+
+
+def silog(pred, target, min_depth=1e-3, mask=None):
+    """reference losses.py:14-36.  mask (bool or uint8, the shape of target): the valid pixels; min_depth is then not
+    applied, as in the reference."""
+    if mask is None:
+        return _SILog.apply(pred, target, float(min_depth))
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"silog: mask must be bool or uint8, got {mask.dtype}")
+    if tuple(mask.shape) != tuple(target.shape):
+        raise ValueError(f"silog: mask shape {tuple(mask.shape)} does not match target {tuple(target.shape)}")
+    if not mask.is_cuda or mask.device != target.device:
+        raise RuntimeError(f"silog: mask is on {mask.device}, the target on {target.device} (no CPU fallback)")
+    mask = mask.contiguous()
+    return _SILogMasked.apply(pred, target, mask.view(torch.uint8) if mask.dtype == torch.bool else mask)
 
 
 class _L1(torch.autograd.Function):

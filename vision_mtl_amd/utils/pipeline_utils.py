@@ -44,8 +44,11 @@ def build_model(args: argparse.Namespace, data_cfg: DataConfig) -> t.Union[Basic
 def init_model(args: argparse.Namespace, data_cfg: DataConfig) -> MTLModule:
     """reference utils/pipeline_utils.py:22-30."""
     model = build_model(args, data_cfg)
+    # opt-in (INTEGRATION.md): an ignored label / per-class weights (a sequence of num_classes floats) for the segmentation loss
     module = MTLModule(model=model, num_classes=data_cfg.num_classes, lr=getattr(args, "lr", None),
-                       device=getattr(args, "device", "cuda"))
+                       device=getattr(args, "device", "cuda"),
+                       segm_ignore_index=getattr(args, "segm_ignore_index", None),
+                       segm_class_weights=getattr(args, "segm_class_weights", None))
     if getattr(args, "ckpt_dir", None):
         from .ckpt import load_ckpt_model
 
