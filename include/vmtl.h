@@ -569,6 +569,31 @@ int vmtl_segm_metrics_ex(const int* cm, int C, float beta, long long ignore_inde
 int vmtl_adam_step(float* p, const float* g, float* m, float* v, const float* step_ptr, float lr, float b1,
                    float b2, float eps, float weight_decay, float grad_scale, long long n, void* stream);
 
+/* ---- global-norm clipping + extended Adam / AdamW (csrc/optim.hip) ------------------------
+ * Flat fp32 buffers of n >= 1 elements, any 4-byte-aligned pointers.  `workspace`: vmtl_grad_sumsq_workspace_bytes(n)
+ * bytes, 8-byte aligned.  `ctl`: the control block, 16 floats, zeroed once by the caller:
+ *   [0] total norm of g * grad_scale (NaN when no norm was computed)  [1] clip coefficient
+ *   [2] the norm is not finite  [3] this step is skipped  [4] running count of skipped steps
+ *   [5..10] bias corrections and betas for vmtl_adam_step_ex  [11..15] unused
+ * A beta is passed as the fp32 pair (hi, lo) with hi + lo == the double value.  max_norm 0: no clipping. */
+long long vmtl_grad_sumsq_workspace_bytes(long long n);
+/* per-workgroup fp64 partial sums of (g[i] * grad_scale)^2 into workspace; deterministic, no atomics */
+int vmtl_grad_sumsq(const float* g, float grad_scale, void* workspace, long long n, void* stream);
+/* partials -> ctl (norm, torch's clip coefficient min(1, max_norm / (norm + 1e-6)), flags); step_ptr[0] += 1 on the
+ * device unless skip_nonfinite is set and the norm is not finite (then ctl[4] += 1).  n: the element count workspace was
+ * filled for; n == 0 (workspace may be null): no norm, clipping and skip_nonfinite are then refused */
+int vmtl_optim_control(const void* workspace, long long n, float max_norm, int skip_nonfinite, float* step_ptr,
+                       float b1, float b1_lo, float b2, float b2_lo, float* ctl, void* stream);
+/* torch.optim.Adam (decoupled 0: g += wd * p) / AdamW (decoupled 1: p *= 1 - lr * wd) with the gradient read as
+ * g * grad_scale * ctl[1]; lr_ptr (nullable) overrides lr; a skipped step (ctl[3]) leaves p, m and v untouched; g is
+ * never written.  Runs after vmtl_optim_control on the same stream */
+int vmtl_adam_step_ex(float* p, const float* g, float* m, float* v, const float* ctl, float lr,
+                      const float* lr_ptr, float eps, float weight_decay, int decoupled, float grad_scale,
+                      long long n, void* stream);
+/* g *= grad_scale * clip coefficient in place, after vmtl_grad_sumsq with the same grad_scale and n; writes ctl[0..2] */
+int vmtl_grad_clip_(float* g, const void* workspace, float grad_scale, float max_norm, float* ctl, long long n,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,6 +73,7 @@ class FlatArena:
         self.numel = total
         self.model = model
         self._adam = None
+        self._optim = None  # (workspace, control block) of the clipping / extended-update launches
         self.pending_scale = 1.0  # 1/world still to be applied to flat_grad (see all_reduce_mean / ArenaAdam)
         if broadcast:
             self.broadcast_parameters()
@@ -184,24 +185,71 @@ class FlatArena:
             if consumer is not None:
                 # the attached ArenaAdam folds the factor into its fused update (no extra pass over 54 MB).  Until its
                 # step() - or adam_step() - runs, flat_grad holds the SUM over ranks: anything else that reads gradients
-                # in between (clipping, logging) must multiply by arena.pending_scale
+                # in between (clipping, logging) must multiply by arena.pending_scale - grad_norm() and
+                # clip_grad_norm_() below do, torch.nn.utils.clip_grad_norm_ does not
                 self.pending_scale = scale
             else:
                 self.flat_grad.mul_(scale)
 
-    def adam_step(self, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0):
-        """torch.optim.Adam semantics (reference training_lit.py:51,87) as ONE fused launch over the arena."""
+    # ---- global-norm clipping (csrc/optim.hip)
+    def _optim_buffers(self):
+        """(workspace, control block) of the norm / clip / extended-update launches, allocated once per arena."""
+        if self._optim is None:
+            self._optim = (ops.optim_workspace(self.numel, self.flat_param), ops.optim_control_block(self.flat_param))
+        return self._optim
+
+    def _adam_state(self):
         if self._adam is None:
             z = torch.zeros_like(self.flat_param)
             self._adam = {"m": z, "v": z.clone(), "step": torch.zeros(1, dtype=torch.float32, device=z.device)}
+        return self._adam
+
+    def grad_norm(self) -> torch.Tensor:
+        """2-norm of the TRUE gradient as a 0-dim device tensor (no host sync): a 1/world factor still owed to flat_grad
+        (pending_scale) is honoured, flat_grad is not written.  The tensor is a view of the arena's control block: the
+        next grad_norm() / clip_grad_norm_() / extended adam_step() overwrites it (clone() to keep a value)."""
+        ws, ctl = self._optim_buffers()
         ops.side.join()
-        st = self._adam
-        st["step"] += 1
+        return ops.grad_norm(self.flat_grad, self.pending_scale, ws, ctl)
+
+    def clip_grad_norm_(self, max_norm) -> torch.Tensor:
+        """torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm) over the arena in two launches (one read of the
+        gradient for the norm, one scale pass), for callers who keep torch.optim.Adam over the parameter views.  Returns
+        the norm before clipping (0-dim device tensor, a view like grad_norm()'s).  A pending 1/world factor is part of the
+        gradient that is measured and is CONSUMED by the scale pass: pending_scale is 1.0 afterwards, so a following
+        optimizer does not apply it again."""
+        if max_norm is None or not float(max_norm) >= 0.0:
+            raise ValueError(f"clip_grad_norm_: max_norm must be >= 0, got {max_norm}")
+        ws, ctl = self._optim_buffers()
+        ops.side.join()
+        scale, self.pending_scale = self.pending_scale, 1.0
+        return ops.scale_by_clip(self.flat_grad, float(max_norm), scale, ws, ctl)
+
+    def adam_step(self, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0, *, max_grad_norm=None,
+                  decoupled_weight_decay=False, skip_nonfinite=False):
+        """torch.optim.Adam semantics (reference training_lit.py:51,87) as ONE fused launch over the arena.
+
+        max_grad_norm (clip the global norm of the true gradient first), decoupled_weight_decay (AdamW),
+        skip_nonfinite (leave everything untouched when the gradient norm is inf / NaN) or a 0-dim device tensor as lr
+        select the extended path instead (ops.adam_step_ex: norm pass when clipping or skipping, control launch, update):
+        the step counter is then incremented on the device, in the same tensor."""
+        extended = (max_grad_norm is not None or decoupled_weight_decay or skip_nonfinite
+                    or isinstance(lr, torch.Tensor))
+        st = self._adam_state()
+        ops.side.join()
         # a 1/world factor still owed to the gradient (gloo: all_reduce_mean returned it to _end_of_backward) is consumed
         # HERE, whoever calls: a direct adam_step() after a discarded ArenaAdam cannot silently drop it
         grad_scale, self.pending_scale = grad_scale * self.pending_scale, 1.0
-        ops.adam_step(self.flat_param, self.flat_grad, st["m"], st["v"], st["step"], lr, betas, eps, weight_decay,
-                      grad_scale)
+        if extended:
+            ws, ctl = self._optim_buffers()
+            ops.adam_step_ex(self.flat_param, self.flat_grad, st["m"], st["v"], st["step"], lr, betas, eps,
+                             weight_decay, grad_scale, max_grad_norm=max_grad_norm,
+                             decoupled_weight_decay=decoupled_weight_decay, skip_nonfinite=skip_nonfinite,
+                             workspace=ws, ctl=ctl)
+        else:
+            st["step"] += 1
+            ops.adam_step(self.flat_param, self.flat_grad, st["m"], st["v"], st["step"], lr, betas, eps, weight_decay,
+                          grad_scale)
         self._kernel_written.clear()
         ops.packs.invalidate()  # parameters changed through raw pointers: packed operands are stale
 
@@ -214,18 +262,62 @@ class ArenaAdam(torch.optim.Optimizer):
     torch.optim.Adam(module.parameters()) uses), and load_state_dict() accepts exactly that - so the reference's
     scheduler (`ReduceLROnPlateau`, training_lit.py:51-55) drives it unchanged and session_{epoch}.pt files
     written by `save_ckpt` (pipeline_utils.py:139-167) move between this optimizer and torch.optim.Adam in both
-    directions.  Anything else raises (never a silent partial load)."""
+    directions.  Anything else raises (never a silent partial load).
 
-    def __init__(self, arena: "FlatArena", lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    decoupled_weight_decay=True is AdamW (torch.optim.AdamW is Adam with this flag): it lives in param_groups[0] as in
+    torch and travels with the state dict.  max_grad_norm clips the global norm of the true gradient (a pending 1/world
+    factor included) inside the update - the clipped gradient is never written back - and skip_nonfinite leaves
+    parameters, moments and the step counter untouched when that norm is inf / NaN; both are plain attributes, not
+    optimizer state (clipping is not optimizer state in torch either).  After a step() with any of these set, `grad_norm`
+    (before clipping; NaN when neither clipping nor skipping asked for a norm) and `skipped_steps` are 0-dim device
+    tensors, views of the arena's control block: reading them is the caller's choice of when to sync.
+
+    capturable=True: param_groups[0]["lr"] is a 0-dim fp32 DEVICE tensor handed to the kernel by pointer (torch's
+    schedulers fill_ a tensor lr in place, so a captured step() follows ReduceLROnPlateau); state_dict() emits it as a
+    float.  Moments, workspace and control block are allocated here, and step() issues nothing but the vmtl launches, so
+    it can be captured into a hipGraph on its own.  ops.packs.invalidate() stays host-side bookkeeping that a replay
+    does not repeat: whoever REPLAYS a captured step() must call ops.packs.invalidate() after it - or use GraphedStep,
+    whose graph re-packs the operands every step."""
+
+    def __init__(self, arena: "FlatArena", lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, *,
+                 decoupled_weight_decay=False, max_grad_norm=None, skip_nonfinite=False, capturable=False):
+        if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
+            raise ValueError(f"ArenaAdam: max_grad_norm must be >= 0 or None, got {max_grad_norm}")
+        if isinstance(lr, torch.Tensor):
+            if not capturable:
+                raise ValueError("ArenaAdam: a tensor lr needs capturable=True (as torch.optim.Adam has it)")
+            lr = float(lr)
         self.arena = arena
-        super().__init__([arena.flat_param], dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self.max_grad_norm = max_grad_norm
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.capturable = bool(capturable)
+        if capturable:
+            lr = torch.tensor(float(lr), dtype=torch.float32, device=arena.flat_param.device)
+            arena._adam_state()
+            arena._optim_buffers()
+        super().__init__([arena.flat_param], dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                                  decoupled_weight_decay=bool(decoupled_weight_decay)))
         arena._scale_consumer = weakref.ref(self)  # weak: a discarded optimizer stops deferring the 1/world factor
+
+    @property
+    def grad_norm(self):
+        """Norm of the last step's true gradient before clipping (None before the first extended step)."""
+        o = self.arena._optim
+        return None if o is None else o[1][ops.CTL_NORM]
+
+    @property
+    def skipped_steps(self):
+        """How many steps skip_nonfinite has skipped so far (None before the first extended step)."""
+        o = self.arena._optim
+        return None if o is None else o[1][ops.CTL_SKIPPED]
 
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
         g = self.param_groups[0]
-        self.arena.adam_step(lr=g["lr"], betas=tuple(g["betas"]), eps=g["eps"], weight_decay=g["weight_decay"])
+        self.arena.adam_step(lr=g["lr"], betas=tuple(g["betas"]), eps=g["eps"], weight_decay=g["weight_decay"],
+                             max_grad_norm=self.max_grad_norm, skip_nonfinite=self.skip_nonfinite,
+                             decoupled_weight_decay=bool(g["decoupled_weight_decay"]))
         return loss
 
     def zero_grad(self, set_to_none: bool = False):
@@ -234,7 +326,8 @@ class ArenaAdam(torch.optim.Optimizer):
 
     def state_dict(self):
         a, st = self.arena, self.arena._adam
-        group = {k: v for k, v in self.param_groups[0].items() if k != "params"}
+        group = {k: (float(v) if k == "lr" and isinstance(v, torch.Tensor) else v)
+                 for k, v in self.param_groups[0].items() if k != "params"}
         group["params"] = list(range(len(a.params)))
         state = {}
         if st is not None:
@@ -260,7 +353,10 @@ class ArenaAdam(torch.optim.Optimizer):
         for k in ("amsgrad", "maximize"):
             if hyper[0].get(k):
                 raise ValueError(f"ArenaAdam.load_state_dict: {k}=True is not implemented by the fused update")
+        lr_t = self.param_groups[0]["lr"] if self.capturable else None
         self.param_groups[0].update({k: v for k, v in hyper[0].items() if k in self.param_groups[0]})
+        if lr_t is not None:  # the kernel reads lr through this tensor's address: refill it, never rebind it
+            self.param_groups[0]["lr"] = lr_t.fill_(float(hyper[0].get("lr", lr_t)))
         state = sd["state"]
         if not state:
             a._adam = None
@@ -281,6 +377,13 @@ class ArenaAdam(torch.optim.Optimizer):
         if len(steps) != 1:
             raise ValueError("ArenaAdam.load_state_dict: parameters with different step counts cannot share the fused update")
         a._adam = {"m": m, "v": v, "step": torch.full((1,), steps.pop(), dtype=torch.float32, device=dev)}
+
+
+class ArenaAdamW(ArenaAdam):
+    """torch.optim.AdamW over the arena: ArenaAdam with decoupled weight decay and AdamW's default weight_decay."""
+
+    def __init__(self, arena: "FlatArena", lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, **kw):
+        super().__init__(arena, lr, betas, eps, weight_decay, decoupled_weight_decay=True, **kw)
 
 
 class _SyncGrads(torch.autograd.Function):

@@ -14,6 +14,7 @@ from __future__ import annotations
 import contextlib
 import functools
 import os
+import struct
 import weakref
 from typing import NamedTuple
 
@@ -3083,3 +3084,110 @@ def adam_step(p, g, m, v, step_t, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay
     tensor holding the (already incremented) step count."""
     _k("vmtl_adam_step", p=p, g=g, m=m, v=v, step_ptr=step_t, lr=lr, b1=betas[0], b2=betas[1], eps=eps,
        weight_decay=weight_decay, grad_scale=grad_scale, n=p.numel())
+
+
+# Global-norm clipping and the extended Adam / AdamW update (csrc/optim.hip).  Plain launches, not autograd nodes: they
+# run where torch.nn.utils.clip_grad_norm_ and optimizer.step() run, under no_grad, on flat fp32 buffers.
+OPTIM_CTL_FLOATS = 16  # control block (include/vmtl.h): [0] norm [1] clip coefficient [2] non-finite [3] skipped [4] count
+CTL_NORM, CTL_COEF, CTL_NONFINITE, CTL_SKIP, CTL_SKIPPED = 0, 1, 2, 3, 4
+
+
+def _flat(t, name):
+    """A flat fp32 device buffer exactly as given: these kernels write in place, so nothing may be copied."""
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} is on {t.device}: the vmtl hot path only runs as HIP kernels on an MI355X "
+                           "(there is deliberately no CPU fallback)")
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise TypeError(f"{name} must be a contiguous float32 buffer, got {t.dtype} with strides {t.stride()}")
+    return t
+
+
+def _max_norm(max_norm) -> float:
+    """None / 0: no clipping (coefficient 1); a negative or NaN bound is an error, not a silent no-op."""
+    if max_norm is None:
+        return 0.0
+    m = float(max_norm)
+    if not m >= 0.0:
+        raise ValueError(f"max_norm must be >= 0 or None, got {max_norm}")
+    return m
+
+
+@functools.lru_cache(maxsize=None)
+def _hi_lo(x: float):
+    """x as the fp32 pair the C ABI carries (hi + lo == x to double precision)."""
+    hi = struct.unpack("f", struct.pack("f", x))[0]
+    return hi, x - hi
+
+
+def optim_workspace(n: int, like):
+    """Workspace of grad_sumsq for n elements: one fp64 partial per workgroup."""
+    return torch.empty((lib().raw("vmtl_grad_sumsq_workspace_bytes")(n) // 8,), dtype=torch.float64, device=like.device)
+
+
+def optim_control_block(like):
+    """A zeroed control block (the skipped-step count starts at 0)."""
+    return torch.zeros(OPTIM_CTL_FLOATS, dtype=torch.float32, device=like.device)
+
+
+def grad_sumsq(g, workspace=None, grad_scale=1.0):
+    """Per-workgroup fp64 partial sums of (g * grad_scale)^2 into `workspace` (returned); deterministic."""
+    g = _flat(g, "g")
+    if workspace is None:
+        workspace = optim_workspace(g.numel(), g)
+    _k("vmtl_grad_sumsq", g=g, grad_scale=grad_scale, workspace=workspace, n=g.numel())
+    return workspace
+
+
+def optim_control(ctl, step_t, n, workspace=None, max_norm=None, skip_nonfinite=False, betas=(0.9, 0.999)):
+    """Partials -> control block; step_t += 1 ON THE DEVICE unless the step is skipped.  n: the element count the
+    partials cover, 0 when no norm was computed (then nothing is clipped and nothing can be skipped)."""
+    (b1, b1_lo), (b2, b2_lo) = _hi_lo(betas[0]), _hi_lo(betas[1])
+    _k("vmtl_optim_control", workspace=workspace if n else None, n=n, max_norm=_max_norm(max_norm),
+       skip_nonfinite=int(bool(skip_nonfinite)), step_ptr=_flat(step_t, "step_t"), b1=b1, b1_lo=b1_lo, b2=b2,
+       b2_lo=b2_lo, ctl=_flat(ctl, "ctl"))
+
+
+def grad_norm(g, grad_scale=1.0, workspace=None, ctl=None):
+    """Norm of g * grad_scale as a 0-dim device tensor (what clip_grad_norm_ returns); g is not written.  Two launches."""
+    ws = grad_sumsq(g, workspace, grad_scale)
+    ctl = optim_control_block(g) if ctl is None else ctl
+    # the clip launch with nothing to clip: it sums the partials, records the norm and returns before touching g
+    _k("vmtl_grad_clip_", g=g, workspace=ws, grad_scale=1.0, max_norm=0.0, ctl=_flat(ctl, "ctl"), n=g.numel())
+    return ctl[CTL_NORM]
+
+
+def scale_by_clip(g, max_norm, grad_scale=1.0, workspace=None, ctl=None):
+    """torch.nn.utils.clip_grad_norm_ on the flat gradient g * grad_scale, in place, as two launches: g becomes
+    g * grad_scale * min(1, max_norm / (norm + 1e-6)).  Returns the norm BEFORE clipping (0-dim device tensor)."""
+    max_norm = _max_norm(max_norm)
+    ws = grad_sumsq(g, workspace, grad_scale)
+    ctl = optim_control_block(g) if ctl is None else ctl
+    _k("vmtl_grad_clip_", g=g, workspace=ws, grad_scale=grad_scale, max_norm=max_norm, ctl=_flat(ctl, "ctl"),
+       n=g.numel())
+    return ctl[CTL_NORM]
+
+
+def adam_step_ex(p, g, m, v, step_t, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0, *,
+                 max_grad_norm=None, decoupled_weight_decay=False, skip_nonfinite=False, workspace=None, ctl=None):
+    """torch.optim.Adam / AdamW over flat fp32 buffers with global-norm clipping folded in: the gradient the update sees
+    is g * grad_scale * clip coefficient, g itself is only read.  step_t (1-element device tensor) holds the count of
+    steps taken so far and is incremented by the control launch, not by the caller; with skip_nonfinite a step whose
+    gradient norm is inf / NaN leaves p, m, v and step_t untouched and counts in ctl[CTL_SKIPPED].  lr: a float, or a
+    0-dim / 1-element fp32 device tensor read at run time (a captured launch follows a scheduler).
+    Launches: [sum of squares, when clipping or skipping] + control + update.  Returns the control block."""
+    p, g, m, v = _flat(p, "p"), _flat(g, "g"), _flat(m, "m"), _flat(v, "v")
+    n = p.numel()
+    if not (g.numel() == m.numel() == v.numel() == n):
+        raise ValueError("adam_step_ex: p, g, m and v must hold the same number of elements")
+    max_norm = _max_norm(max_grad_norm)
+    need_norm = max_norm > 0.0 or bool(skip_nonfinite)
+    ctl = optim_control_block(p) if ctl is None else ctl
+    if need_norm:
+        workspace = grad_sumsq(g, workspace, grad_scale)
+    optim_control(ctl, step_t, n if need_norm else 0, workspace, max_norm, skip_nonfinite, betas)
+    lr_ptr = None
+    if isinstance(lr, torch.Tensor):
+        lr_ptr, lr = _flat(lr, "lr"), 0.0
+    _k("vmtl_adam_step_ex", p=p, g=g, m=m, v=v, ctl=ctl, lr=lr, lr_ptr=lr_ptr, eps=eps, weight_decay=weight_decay,
+       decoupled=int(bool(decoupled_weight_decay)), grad_scale=grad_scale, n=n)
+    return ctl
