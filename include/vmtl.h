@@ -555,6 +555,41 @@ int vmtl_l1_fwd(const float* pred, const float* target, float* loss, void* works
 int vmtl_l1_bwd(const float* pred, const float* target, const float* grad_out, float* dpred, long long P,
                 void* stream);
 
+/* ---- task-loss balancing (csrc/balance.hip) ------------------------------------------------
+ * Opt-in replacements of lit_module.py:120-131 (loss = w_segm * loss_segm + w_depth * loss_depth with two host floats):
+ * T = 1..4 scalar task losses L_k, given as the pointers l0..l3 (the first T non-null, in the style of vmtl_add_n), become
+ * `total`, and weights_k = d total / d L_k (T floats) is kept for the backward.  Losses, param and grad_out are read by
+ * pointer at run time, so a captured launch follows an optimizer step or an epoch update without a recapture.
+ *   VMTL_BALANCE_UNCERTAINTY  total = sum_k exp(-s_k) L_k + s_k, s_k = log sigma_k^2 = param[k] (Kendall et al. 2018);
+ *                             weights_k = exp(-s_k); d total / d s_k = 1 - exp(-s_k) L_k.  s = 0 is the reference's default.
+ *   VMTL_BALANCE_DWA          total = sum_k w_k L_k, w = param (Liu et al. 2019, set by vmtl_dwa_epoch_update); with
+ *                             `accumulate` the forward adds L_k to the epoch's sums in `state` and 1 to its step count -
+ *                             only when every L_k is finite.  No parameter gradient.
+ *   VMTL_BALANCE_GEOMETRIC    total = exp(mean_k log L_k) (Chennupati et al. 2019), weights_k = total / (T L_k); param may
+ *                             be null.  A loss that is not positive makes total and every weight NaN.
+ * state (DWA only; may be null without `accumulate`): vmtl_task_balance_state_bytes(T) bytes, 8-byte aligned, zeroed once
+ * by the caller, 3 T + 2 doubles:
+ *   [0, T) sums of L_k over the epoch's accumulated steps   [T] their number   [T + 1] completed epochs
+ *   [T + 2, 2T + 2) prev: mean losses of the last completed epoch   [2T + 2, 3T + 2) prev2: of the one before
+ * (a data-parallel caller sum-reduces the first T + 1 doubles over its ranks before the epoch update). */
+#define VMTL_BALANCE_UNCERTAINTY 0
+#define VMTL_BALANCE_DWA 1
+#define VMTL_BALANCE_GEOMETRIC 2
+long long vmtl_task_balance_state_bytes(int T); /* host only; 0 for T outside 1..4 */
+int vmtl_task_balance_fwd(const float* l0, const float* l1, const float* l2, const float* l3, int T, int mode,
+                          const float* param, void* state, int accumulate, float* total, float* weights, void* stream);
+/* g_k = grad_out * weights_k (each nullable) and dparam (T floats, nullable) = grad_out * (1 - weights_k L_k) for
+ * VMTL_BALANCE_UNCERTAINTY, zeros otherwise; dparam is overwritten, not accumulated.  One launch. */
+int vmtl_task_balance_bwd(const float* grad_out, const float* weights, const float* l0, const float* l1, const float* l2,
+                          const float* l3, const float* param, int mode, int T, float* g0, float* g1, float* g2, float* g3,
+                          float* dparam, void* stream);
+/* End of a training epoch (the reference has no such hook: its weights come from hyperparam_tuning.py).  mean = sums /
+ * steps; prev2 <- prev, prev <- mean; completed epochs += 1; sums and step count <- 0.  From the second completed epoch on
+ * param[k] = T exp(r_k / temperature) / sum_j exp(r_j / temperature) with r_k = prev_k / prev2_k, before that 1.  A step
+ * count of zero changes nothing; an r_k that is not finite or not positive drops the epoch (sums and step count are
+ * zeroed; param, history and the epoch count stay as they were). */
+int vmtl_dwa_epoch_update(void* state, float* param, int T, float temperature, void* stream);
+
 /* ---- per-step metrics (lit_module.py:48-69,106-118: torchmetrics Accuracy / Jaccard / FBeta) ---- */
 int vmtl_confusion_matrix(const long long* pred, const long long* target, int* cm, long long P, int C,
                           void* stream);

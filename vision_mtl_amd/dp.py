@@ -44,12 +44,25 @@ class FlatArena:
 
     COLLECTIVE CONSTRUCTOR: with an initialised process group, FlatArena(model) broadcasts rank 0's parameters and
     buffers (broadcast=True, the default) - EVERY rank must construct its arena, in the same order, or the ranks that do
-    wait forever.  Pass broadcast=False for a rank-local arena (and call broadcast_parameters() yourself later)."""
+    wait forever.  Pass broadcast=False for a rank-local arena (and call broadcast_parameters() yourself later).
 
-    def __init__(self, model: torch.nn.Module, broadcast: bool = True):
+    extra_params: trainable parameters that live outside `model` (the log-variances of a balancing.TaskBalancer, which
+    belongs to the MTLModule around the model).  They are appended AFTER the model's, so the model's offsets are those
+    of FlatArena(model) and the parameter order is MTLModule.parameters()': ArenaAdam.state_dict() then matches
+    torch.optim.Adam(module.parameters()) parameter for parameter."""
+
+    def __init__(self, model: torch.nn.Module, broadcast: bool = True, extra_params=None):
         params = [p for p in model.parameters() if p.requires_grad]
         if not params:
             raise ValueError("model has no trainable parameters")
+        for p in extra_params or ():
+            if not isinstance(p, torch.nn.Parameter) or not p.requires_grad or p.dtype != torch.float32:
+                raise ValueError("FlatArena: extra_params must be trainable float32 nn.Parameters")
+            if any(p is q for q in params):
+                raise ValueError("FlatArena: an extra parameter is already in the arena")
+            if p.device != params[0].device:
+                raise ValueError(f"FlatArena: an extra parameter is on {p.device}, the model on {params[0].device}")
+            params.append(p)
         dev = params[0].device  # build the arena AFTER model.to(device): .to() would drop the views
         total = sum(p.numel() for p in params)
         self.flat_param = torch.empty(total, dtype=torch.float32, device=dev)

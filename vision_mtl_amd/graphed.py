@@ -93,7 +93,9 @@ class GraphedStep(_StaticBatch):
     data.upload_batch inside the graph).  arena: an existing dp.FlatArena of module.model (default: module.dp_arena,
     else a new one - built here, so construct the GraphedStep on every rank).  warmup: eager steps before capture
     (allocator pools, code objects, packed-operand table).  NOTE: the warm-up steps and the capture rehearsal run real
-    training steps on `example_batch` (BatchNorm running statistics move, no optimizer step is taken).  The step is captured
+    training steps on `example_batch` (BatchNorm running statistics move, no optimizer step is taken; the buffers of a
+    module.task_balancer - DWA weights, accumulators, history - are put back as they were, and its parameters join the
+    default arena: a caller's arena must hold them, dp.FlatArena(model, extra_params=...)).  The step is captured
     under the convolution precision in force at construction (recorded as `conv_precision`), and every replay keeps it
     whatever vision_mtl_amd.set_conv_precision says later.  Likewise `module.device_transform` (data.DeviceTransform)
     at construction: the static buffers then hold raw batches (data.collate_raw) and the transform is captured too."""
@@ -103,11 +105,20 @@ class GraphedStep(_StaticBatch):
         if not torch.cuda.is_available():
             raise RuntimeError("GraphedStep needs an MI355X: the hot path has no CPU fallback")
         self.module, self.stage = module, stage
+        balancer = getattr(module, "task_balancer", None)
+        extra = [] if balancer is None else [p for p in balancer.parameters() if p.requires_grad]
         if arena is None:
-            arena = module.dp_arena if module.dp_arena is not None else dp.FlatArena(module.model)
+            arena = module.dp_arena
+        if arena is None:
+            arena = dp.FlatArena(module.model, extra_params=extra)
+        elif any(getattr(p, "_vmtl_arena", None) is not arena for p in extra):
+            raise ValueError("GraphedStep: the arena does not hold the task balancer's parameters; build it as "
+                             "dp.FlatArena(module.model, extra_params=list(module.task_balancer.parameters()))")
         self.arena = arena
         self._init_static(module, example_batch)  # static buffers; conv precision and module.device_transform recorded
         attached, module.dp_arena = module.dp_arena, None  # the collective stays outside the graph (see __call__)
+        # the warm-up and rehearsal steps run with gradients enabled: a "dwa" balancer would count them into its epoch
+        snap = [] if balancer is None else [(b, b.clone()) for b in balancer.buffers()]
         try:
             so = module.step_outputs[stage]
             mark = {k: len(v) for k, v in so.items()}
@@ -137,6 +148,9 @@ class GraphedStep(_StaticBatch):
             self._pack_tables = (ops.packs.table, ops.packs.table_side)
         finally:
             module.dp_arena = attached
+            with torch.no_grad():
+                for b, v in snap:
+                    b.copy_(v)
         self._anchor = torch.zeros((), device=self.device, requires_grad=True)
         self.replays = 0
 

@@ -15,6 +15,7 @@ from torch import nn
 
 from . import metrics as M
 from . import ops
+from .balancing import TaskBalancer
 from .losses import CrossEntropyLoss, SILogLoss
 from .utils.loss_utils import summarize_epoch_metrics
 
@@ -23,10 +24,25 @@ class MTLModule(nn.Module):
     def __init__(self, model: nn.Module, num_classes: int, optim_dict: t.Optional[dict] = None,
                  lr: t.Optional[float] = None, device: str = "cuda", loss_segm_weight: float = 1.0,
                  loss_depth_weight: float = 1.0, segm_ignore_index: t.Optional[int] = None,
-                 segm_class_weights: t.Optional[t.Sequence[float]] = None):
+                 segm_class_weights: t.Optional[t.Sequence[float]] = None,
+                 loss_balancing: t.Union[None, str, TaskBalancer] = None, dwa_temperature: float = 2.0):
         """segm_ignore_index / segm_class_weights (opt-in, INTEGRATION.md): the `ignore_index` and per-class `weight`
-        of the segmentation criterion; the ignore index also keeps those pixels out of the segmentation metrics."""
+        of the segmentation criterion; the ignore index also keeps those pixels out of the segmentation metrics.
+        loss_balancing (opt-in): "uncertainty" | "dwa" | "geometric" or a balancing.TaskBalancer
+        over the tasks ("segm", "depth"); it becomes the submodule `task_balancer` and takes the place of the two static
+        weights, which must then stay 1.0.  dwa_temperature: the softmax temperature of "dwa"."""
         super().__init__()
+        if loss_balancing is not None:
+            if loss_segm_weight != 1.0 or loss_depth_weight != 1.0:
+                raise ValueError("MTLModule: loss_balancing replaces the static loss weights: leave loss_segm_weight and "
+                                 f"loss_depth_weight at 1.0 (got {loss_segm_weight}, {loss_depth_weight})")
+            if isinstance(loss_balancing, str):
+                loss_balancing = TaskBalancer(loss_balancing, temperature=dwa_temperature)
+            elif not isinstance(loss_balancing, TaskBalancer):
+                raise ValueError(f"MTLModule: loss_balancing must be None, a method name or a TaskBalancer, got "
+                                 f"{type(loss_balancing).__name__}")
+            if loss_balancing.tasks != ("segm", "depth"):
+                raise ValueError(f"MTLModule: the balancer's tasks must be ('segm', 'depth'), got {loss_balancing.tasks}")
         if segm_class_weights is not None:
             segm_class_weights = torch.as_tensor(segm_class_weights, dtype=torch.float32).detach().flatten()
             if segm_class_weights.numel() != num_classes:
@@ -36,6 +52,8 @@ class MTLModule(nn.Module):
                         "loss_segm_weight": loss_segm_weight, "loss_depth_weight": loss_depth_weight,
                         "segm_ignore_index": segm_ignore_index,
                         "segm_class_weights": None if segm_class_weights is None else segm_class_weights.tolist()}
+        if loss_balancing is not None:  # the default module keeps the hparams it always had
+            self.hparams.update(loss_balancing=loss_balancing.method, dwa_temperature=loss_balancing.temperature)
         self.num_classes = num_classes
         self.model = model
         self.segm_criterion = CrossEntropyLoss(weight=segm_class_weights, ignore_index=segm_ignore_index)
@@ -45,6 +63,9 @@ class MTLModule(nn.Module):
                 self.segm_criterion.to(p.device)
         self.segm_ignore_index = segm_ignore_index
         self.depth_criterion = SILogLoss()
+        if loss_balancing is not None:  # absent by default: state_dict() keys and parameters() stay the reference's
+            p = next(model.parameters(), None)
+            self.task_balancer = loss_balancing if p is None else loss_balancing.to(p.device)
         self.optim_dict = optim_dict
         self.loss_segm_weight = loss_segm_weight
         self.loss_depth_weight = loss_depth_weight
@@ -107,7 +128,10 @@ class MTLModule(nn.Module):
         else:
             loss_segm = self.segm_criterion(out["segm_logits"], gt_mask)
         loss_depth = self.depth_criterion(out["depth_predictions"], gt_depth)
-        if loss_segm.is_cuda and loss_segm.dim() == 0 and loss_depth.dim() == 0:
+        balancer = getattr(self, "task_balancer", None)
+        if balancer is not None:  # learned / dynamic weights, read on the device (csrc/balance.hip)
+            loss = balancer({"segm": loss_segm, "depth": loss_depth})
+        elif loss_segm.is_cuda and loss_segm.dim() == 0 and loss_depth.dim() == 0:
             loss = ops.add_losses(loss_segm, loss_depth, self.loss_segm_weight, self.loss_depth_weight)
         else:
             loss = self.loss_segm_weight * loss_segm + self.loss_depth_weight * loss_depth
@@ -141,6 +165,9 @@ class MTLModule(nn.Module):
         return summarize_epoch_metrics(self.step_outputs[stage], metric_name_prefix=stage)
 
     def on_train_epoch_end(self):
+        balancer = getattr(self, "task_balancer", None)
+        if balancer is not None:  # "dwa": the epoch's mean losses become the next epoch's weights
+            balancer.on_train_epoch_end()
         return self.shared_epoch_end("train")
 
     def on_validation_epoch_end(self):
@@ -177,3 +204,7 @@ class MTLModule(nn.Module):
     def parameters(self, recurse: bool = True):  # reference lit_module.py:232-234
         for p in self.model.parameters():
             yield p
+        balancer = getattr(self, "task_balancer", None)
+        if balancer is not None:  # the log-variances of "uncertainty" train with the model, after its parameters
+            for p in balancer.parameters():
+                yield p

@@ -2847,6 +2847,94 @@ def add_losses(a, b, wa=1.0, wb=1.0):
     return _AddScalars.apply(a, b, float(wa), float(wb))
 
 
+BALANCE_MODES = {"uncertainty": 0, "dwa": 1, "geometric": 2}  # include/vmtl.h VMTL_BALANCE_*
+BALANCE_MAX_TASKS = 4
+
+
+def balance_state_doubles(T: int) -> int:
+    """Length of the fp64 DWA state of T tasks (layout: include/vmtl.h)."""
+    n = lib().raw("vmtl_task_balance_state_bytes")(int(T))
+    if n <= 0:
+        raise ValueError(f"task balancing takes 1..{BALANCE_MAX_TASKS} tasks, got {T}")
+    return n // 8
+
+
+class _BalanceLosses(torch.autograd.Function):
+    """The T scalar task losses -> the loss that is differentiated (csrc/balance.hip), in place of add_losses' two host
+    floats (reference lit_module.py:127-129): one launch per direction, and every number the kernels use - losses,
+    log-variances or DWA weights, grad_out - is read by pointer, so a replayed graph follows the optimizer and the epoch
+    update.  Returns (total, weights) with weights_k = d total / d L_k; the gradient of the log-variances goes straight
+    into their arena slot when they have one."""
+
+    @staticmethod
+    def forward(ctx, param, state, mode, accumulate, *losses):
+        T = len(losses)
+        losses = [_req(l, f"losses[{k}]") for k, l in enumerate(losses)]
+        l4 = losses + [None] * (BALANCE_MAX_TASKS - T)
+        total, weights = _empty((), losses[0]), _empty((T,), losses[0])
+        _k("vmtl_task_balance_fwd", l0=l4[0], l1=l4[1], l2=l4[2], l3=l4[3], T=T, mode=mode, param=param, state=state,
+           accumulate=1 if accumulate else 0, total=total, weights=weights)
+        ctx.mark_non_differentiable(weights)
+        ctx.save_for_backward(weights, *losses)
+        ctx.param = param  # read again by the backward kernel, in place: never a saved copy
+        ctx.cfg = (mode, T)
+        ctx.slot = _slot(param) if param is not None and param.requires_grad else None
+        return total, weights
+
+    @staticmethod
+    def backward(ctx, g, _gw):
+        weights, *losses = ctx.saved_tensors
+        mode, T = ctx.cfg
+        g = _req(g, "grad")
+        l4 = list(losses) + [None] * (BALANCE_MAX_TASKS - T)
+        gs = [_empty((), g) if ctx.needs_input_grad[4 + k] else None for k in range(T)] + [None] * (BALANCE_MAX_TASKS - T)
+        dparam = _grad_buf((T,), ctx.slot, g) if ctx.needs_input_grad[0] else None
+        if dparam is not None or any(x is not None for x in gs):
+            _k("vmtl_task_balance_bwd", grad_out=g, weights=weights, l0=l4[0], l1=l4[1], l2=l4[2], l3=l4[3], param=ctx.param,
+               mode=mode, T=T, g0=gs[0], g1=gs[1], g2=gs[2], g3=gs[3], dparam=dparam)
+        return (None if dparam is None else _grad_ret(dparam, ctx.slot), None, None, None, *gs[:T])
+
+
+def balance_losses(losses, mode, param=None, state=None, accumulate=False):
+    """(total, weights) of the scalar task losses under `mode` ("uncertainty": param = the log-variances; "dwa": param =
+    the weights, state = the fp64 accumulators of balance_state_doubles(T), accumulate = add this step to them;
+    "geometric": neither - a loss that is not positive gives NaN).  See vision_mtl_amd.balancing.TaskBalancer."""
+    if mode not in BALANCE_MODES:
+        raise ValueError(f"balance_losses: mode must be one of {sorted(BALANCE_MODES)}, got {mode!r}")
+    losses = list(losses)
+    T = len(losses)
+    if not 1 <= T <= BALANCE_MAX_TASKS:
+        raise ValueError(f"balance_losses: 1..{BALANCE_MAX_TASKS} losses, got {T}")
+    if any(l.dim() != 0 for l in losses):
+        raise ValueError("balance_losses: every loss must be a 0-dim tensor")
+    if mode != "geometric":
+        if param is None:
+            raise ValueError(f"balance_losses: mode {mode!r} needs `param` ({T} floats)")
+        _req(param, "param")
+        if param.numel() != T or not param.is_contiguous():
+            raise ValueError(f"balance_losses: param must hold {T} contiguous floats, got shape {tuple(param.shape)}")
+    else:
+        param = None
+    if mode == "dwa" and accumulate:
+        if state is None or not state.is_cuda or state.dtype != torch.float64 or not state.is_contiguous() \
+                or state.numel() != balance_state_doubles(T):
+            raise ValueError(f"balance_losses: state must be {balance_state_doubles(T)} contiguous float64 on the GPU")
+    else:
+        state, accumulate = (state if mode == "dwa" else None), False
+    return _BalanceLosses.apply(param, state, BALANCE_MODES[mode], bool(accumulate), *losses)
+
+
+def dwa_epoch_update(state, weights, temperature):
+    """End of a training epoch for the "dwa" mode: one launch (vmtl_dwa_epoch_update), nothing visits the host."""
+    T = weights.numel()
+    _req(weights, "weights")
+    if not state.is_cuda or state.dtype != torch.float64 or state.numel() != balance_state_doubles(T):
+        raise ValueError(f"dwa_epoch_update: state must be {balance_state_doubles(T)} float64 on the GPU")
+    if not float(temperature) > 0.0:
+        raise ValueError(f"dwa_epoch_update: temperature must be > 0, got {temperature}")
+    _k("vmtl_dwa_epoch_update", state=state, param=weights, T=T, temperature=float(temperature))
+
+
 def argmax_channels(logits):
     """argmax over dim 1 of (B,C,H,W) logits -> int64 (B,H,W); reads NCHW or channels-last strides in place."""
     if not logits.is_cuda:

@@ -48,7 +48,10 @@ def init_model(args: argparse.Namespace, data_cfg: DataConfig) -> MTLModule:
     module = MTLModule(model=model, num_classes=data_cfg.num_classes, lr=getattr(args, "lr", None),
                        device=getattr(args, "device", "cuda"),
                        segm_ignore_index=getattr(args, "segm_ignore_index", None),
-                       segm_class_weights=getattr(args, "segm_class_weights", None))
+                       segm_class_weights=getattr(args, "segm_class_weights", None),
+                       # opt-in: "uncertainty" | "dwa" | "geometric" task-loss balancing
+                       loss_balancing=getattr(args, "loss_balancing", None),
+                       dwa_temperature=getattr(args, "dwa_temperature", 2.0))
     if getattr(args, "ckpt_dir", None):
         from .ckpt import load_ckpt_model
 
