@@ -505,6 +505,23 @@ int vmtl_nyuv2_resize_parts(int B, int Hi, int Wi, int Ho, int Wo, int depth_dty
 int vmtl_nyuv2_resize(const void* img, const void* mask, const void* depth, int depth_dtype, float* img_out,
                       long long* mask_out, float* depth_out, float* part, int B, int Hi, int Wi, int Ho, int Wo,
                       float max_depth, void* stream);
+/* Joint training augmentation on the device (csrc/augment.hip): random scale-crop + horizontal
+ * flip (+ brightness gain) of image, mask and depth together.  Two launches, no allocation, no synchronisation.
+ * vmtl_augment_draw: state int64[2] = {seed, counter}; fills params int32 [B][8] = {scale_idx, top, left, flip, gain
+ * (float bits), 0, 0, 0} with the counter-based generator of DESIGN.md section 19 and then stores counter + 1, so a
+ * replayed graph draws fresh rows.  crop_hw int32 [S][2] = {int(H / s), int(W / s)} per scale (computed by the host in
+ * double precision), S <= 8; flip_threshold = round(p_flip * 2^24) in [0, 2^24]; 0 <= brightness < 1.  params is
+ * 16-byte aligned.
+ * vmtl_augment_apply: img float with pixel stride ld = 3 ([B][H][W][3], dataset sample layout) or 4 (the model's NHWC
+ * input storage, 16-byte aligned), mask int64 [B][H][W], depth float [B][H][W]; scales float [S].  Outputs: img_out
+ * NHWC storage [B][H][W][4] (pad lane 0), mask_out int64, depth_out float (depth / s).  Image: bilinear,
+ * align_corners=True; mask and depth: nearest; both as torch's CPU F.interpolate of the crop window.  Every parameter
+ * row is clamped into range before use.  -1 when an output overlaps its input. */
+int vmtl_augment_draw(long long* state, int* params, const int* crop_hw, int B, int H, int W, int S, int flip_threshold,
+                      float brightness, void* stream);
+int vmtl_augment_apply(const float* img, int ld, const long long* mask, const float* depth, const int* params,
+                       const float* scales, const int* crop_hw, float* img_out, long long* mask_out, float* depth_out,
+                       int B, int H, int W, int S, void* stream);
 
 /* ---- losses ------------------------------------------------------------------------------
  * lit_module.py:31,123 (CrossEntropyLoss); losses.py:14-36 (SILogLoss); lit_module.py:68,112 (MAE). */

@@ -10,12 +10,16 @@ C-1, dtypes, depth normalisation, depth as (H, W, 1)), `collate` stacks into PIN
 `upload_batch` copies asynchronously and re-lays the image with ONE kernel (vmtl_hwc_to_nhwc_pad) straight into
 the model's input storage.  What the caller sees stays the reference's contract: batch["img"] is a (B, 3, H, W)
 float tensor (a channels-last view over that storage; the models pick the storage up without another copy).
-Dataset file I/O, augmentation and DataLoader workers stay out of scope (host code).
+Dataset file I/O and DataLoader workers stay out of scope (host code).
 
 NYUv2's host transform also resizes (cfg.py:144-155: ToTensor + Resize((256, 256), antialias=True)), the expensive part
 of its input side.  `collate_raw` stacks the samples as the files decode (uint8 image and mask, uint16 / int32 depth),
 and `DeviceTransform`, handed to `upload_batch` (or set as `MTLModule.device_transform`), runs that resize and the
 loader's value rules as HIP kernels on the uploaded batch.  PNG decode and file reading stay on the host.
+
+Training augmentation (the reference has none: cfg.py:103-155 sets train_transform == test_transform): `DeviceAugment`,
+set as `MTLModule.train_augment`, runs the joint random scale-crop + horizontal flip of the multi-task literature on
+the batch that is already on the device, with its random parameters drawn on the device (csrc/augment.hip).
 """
 from __future__ import annotations
 
@@ -191,3 +195,166 @@ class DeviceTransform:
 
     def __repr__(self) -> str:
         return f"DeviceTransform(size={self.size}, max_depth={self.max_depth}, dataset={self.dataset!r})"
+
+
+# ---- joint training augmentation on the device (csrc/augment.hip)
+_M64 = (1 << 64) - 1
+_GOLDEN = 0x9E3779B97F4A7C15
+
+
+def _mix64(z: int) -> int:
+    z ^= z >> 30
+    z = (z * 0xBF58476D1CE4E5B9) & _M64
+    z ^= z >> 27
+    z = (z * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def augment_crop_table(H: int, W: int, scales: t.Sequence[float]) -> t.List[t.Tuple[int, int]]:
+    """Crop size (int(H / s), int(W / s)) per scale, in Python's double arithmetic: the device reads this table and
+    never recomputes it ((int)(H / 1.2f) can differ from the double result)."""
+    return [(int(H / s), int(W / s)) for s in scales]
+
+
+def augment_params_host(seed: int, counter: int, B: int, H: int, W: int, scales: t.Sequence[float] = (1.0, 1.2, 1.5),
+                        p_flip: float = 0.5, brightness: float = 0.0) -> torch.Tensor:
+    """What vmtl_augment_draw writes for the state {seed, counter}, restated on the host: int32 (B, 8) rows of
+    {scale_idx, top, left, flip, gain (float32 bit pattern), 0, 0, 0}.  Counter-based (all arithmetic mod 2^64):
+
+        r24(b, k) = mix(mix(seed + G * (counter + 1)) + G * (8 * b + k + 1)) >> 40
+
+    with mix the splitmix64 finaliser and G = 0x9E3779B97F4A7C15; every range reduction is (r24 * n) >> 24 in integers.
+    Columns 0-3 match the device bit for bit; the gain to a rounding of its float expression.  For tests and for users
+    who log their augmentations."""
+    crops = augment_crop_table(H, W, scales)
+    S = len(crops)
+    thr = int(round(float(p_flip) * (1 << 24)))
+    base = _mix64((seed + _GOLDEN * (counter + 1)) & _M64)
+    f32 = np.float32
+    out = np.zeros((B, 8), dtype=np.int32)
+    for b in range(B):
+        r = [_mix64((base + _GOLDEN * (8 * b + k + 1)) & _M64) >> 40 for k in range(5)]
+        si = (r[0] * S) >> 24
+        h, w = min(max(crops[si][0], 1), H), min(max(crops[si][1], 1), W)
+        gain = f32(1.0) + (f32(2.0) * (f32(r[4]) * f32(2.0 ** -24)) - f32(1.0)) * f32(brightness)
+        out[b, :4] = (si, (r[1] * (H - h + 1)) >> 24, (r[2] * (W - w + 1)) >> 24, int(r[3] < thr))
+        out[b, 4] = np.array([gain], dtype=np.float32).view(np.int32)[0]
+    return torch.from_numpy(out)
+
+
+class DeviceAugment:
+    """Joint training augmentation as two HIP launches on a device batch (csrc/augment.hip): MTAN's recipe of the
+    multi-task literature.  Per sample one scale s is drawn from `scales`, a window of int(H / s) x int(W / s) is cropped
+    at a random offset and resampled back to H x W, and the sample is flipped horizontally with probability `p_flip`.
+    Image, mask and depth move together: the image bilinear (align_corners=True), mask and depth nearest, depth divided
+    by s.  Nearest sampling blends no labels, so ignore_index pixels and invalid (zero) depth stay what the loss kernels
+    expect.  brightness > 0 also multiplies the image by a gain drawn from [1 - brightness, 1 + brightness), clamped to
+    [0, 1].
+
+    Called on a device batch in the model's input contract (img as data.upload_batch / DeviceTransform return it, a
+    (B,H,W,3) sample-layout tensor, or plain (B,3,H,W); mask int64 (B,H,W); depth (B,H,W,1)) it returns a new dict with
+    img / mask / depth replaced; other keys pass through.  Set it as `MTLModule.train_augment`: training_step applies it,
+    validation / test / predict never do, and graphed.GraphedStep captures it.
+
+    The random parameters are drawn ON THE DEVICE from the state {seed, counter}; every call (and every replay of a
+    captured step) advances the counter by one, with no host involvement.  The rows used by the latest call stay
+    readable as `last_params` (one buffer per batch size, overwritten by the next call - static under capture);
+    augment_params_host(seed, counter, ...) restates them.  `counter` reads the device (a synchronisation: for logging
+    and checkpoints, not for the step loop); set_counter(n) is a device fill.  state_dict() / load_state_dict() carry
+    seed and counter, so a resumed run continues the stream.  Data-parallel runs: pass seed + rank, or every rank draws
+    the same augmentations."""
+
+    def __init__(self, scales: t.Sequence[float] = (1.0, 1.2, 1.5), p_flip: float = 0.5, brightness: float = 0.0,
+                 seed: int = 0):
+        from .ops import AUGMENT_MAX_SCALES
+
+        try:
+            scales = tuple(float(s) for s in scales)
+        except TypeError:
+            raise ValueError(f"DeviceAugment: scales must be a sequence of floats, got {scales!r}") from None
+        if not 1 <= len(scales) <= AUGMENT_MAX_SCALES:
+            raise ValueError(f"DeviceAugment: between 1 and {AUGMENT_MAX_SCALES} scales, got {len(scales)}")
+        if not all(np.isfinite(s) and s >= 1.0 for s in scales):
+            raise ValueError(f"DeviceAugment: every scale must be finite and >= 1 (a crop is upsampled), got {scales}")
+        if not 0.0 <= p_flip <= 1.0:
+            raise ValueError(f"DeviceAugment: p_flip must be in [0, 1], got {p_flip!r}")
+        if not 0.0 <= brightness < 1.0:
+            raise ValueError(f"DeviceAugment: brightness must be in [0, 1), got {brightness!r}")
+        self.scales, self.p_flip, self.brightness = scales, float(p_flip), float(brightness)
+        self.seed, self._counter = self._check_word("seed", seed), 0
+        self._state = None    # int64 (2,) on the batch's device, created by the first call
+        self._tables = {}     # (device, H, W) -> (scales float32 (S,), crop_hw int32 (S, 2))
+        self._params = {}     # (device, B) -> int32 (B, 8)
+        self.last_params = None
+
+    @staticmethod
+    def _check_word(name: str, v) -> int:
+        if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v < (1 << 63):
+            raise ValueError(f"DeviceAugment: {name} must be an int in [0, 2^63), got {v!r}")
+        return v
+
+    # ---- state
+    def _device_state(self, device) -> torch.Tensor:
+        if self._state is None or self._state.device != device:
+            if self._state is not None:
+                self._counter = self.counter
+            self._state = torch.tensor([self.seed, self._counter], dtype=torch.int64).to(device)
+        return self._state
+
+    @property
+    def counter(self) -> int:
+        """Calls made so far plus the start value (reads the device state: synchronises)."""
+        return self._counter if self._state is None else int(self._state[1].item())
+
+    def set_counter(self, n: int) -> None:
+        self._counter = self._check_word("counter", n)
+        if self._state is not None:
+            self._state[1].fill_(n)  # a device fill on the current stream, no synchronisation
+
+    def state_dict(self) -> dict:
+        return {"seed": self.seed, "counter": self.counter}
+
+    def load_state_dict(self, sd: dict) -> None:
+        seed, counter = self._check_word("seed", sd["seed"]), self._check_word("counter", sd["counter"])
+        self.seed = seed
+        if self._state is not None:
+            self._state[0].fill_(seed)
+        self.set_counter(counter)
+
+    # ---- the transform
+    def _table(self, device, H: int, W: int):
+        key = (device, H, W)
+        tab = self._tables.get(key)
+        if tab is None:
+            crops = augment_crop_table(H, W, self.scales)
+            if any(h < 1 or w < 1 for h, w in crops):
+                raise ValueError(f"DeviceAugment: a {H}x{W} batch is too small for the scales {self.scales}")
+            tab = self._tables[key] = (torch.tensor(self.scales, dtype=torch.float32).to(device),
+                                       torch.tensor(crops, dtype=torch.int32).to(device))
+        return tab
+
+    def __call__(self, batch: dict) -> dict:
+        from . import ops
+
+        img = batch["img"]
+        if not img.is_cuda:
+            raise RuntimeError(f"DeviceAugment: the batch is on {img.device}: the augmentation only runs as HIP kernels "
+                               "on an MI355X (there is deliberately no CPU fallback)")
+        if img.dim() != 4:
+            raise ValueError(f"DeviceAugment: img must be (B, 3, H, W) or (B, H, W, 3), got {tuple(img.shape)}")
+        sample_layout = img.shape[-1] == 3 and img.shape[1] != 3
+        B, (H, W) = img.shape[0], (img.shape[1:3] if sample_layout else img.shape[2:])
+        scales, crop_hw = self._table(img.device, int(H), int(W))
+        params = self._params.get((img.device, B))
+        if params is None:
+            params = self._params[(img.device, B)] = torch.zeros((B, 8), dtype=torch.int32, device=img.device)
+        ops.augment_draw(self._device_state(img.device), params, crop_hw, H, W, self.p_flip, self.brightness)
+        aimg, amask, adepth = ops.augment_apply(img, batch["mask"], batch["depth"], params, scales, crop_hw)
+        self.last_params = params
+        out = dict(batch)
+        out.update(img=aimg, mask=amask, depth=adepth)
+        return out
+
+    def __repr__(self) -> str:
+        return (f"DeviceAugment(scales={self.scales}, p_flip={self.p_flip}, brightness={self.brightness}, "
+                f"seed={self.seed})")

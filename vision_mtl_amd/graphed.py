@@ -98,7 +98,9 @@ class GraphedStep(_StaticBatch):
     default arena: a caller's arena must hold them, dp.FlatArena(model, extra_params=...)).  The step is captured
     under the convolution precision in force at construction (recorded as `conv_precision`), and every replay keeps it
     whatever vision_mtl_amd.set_conv_precision says later.  Likewise `module.device_transform` (data.DeviceTransform)
-    at construction: the static buffers then hold raw batches (data.collate_raw) and the transform is captured too."""
+    at construction: the static buffers then hold raw batches (data.collate_raw) and the transform is captured too.
+    `module.train_augment` (data.DeviceAugment) at construction is captured as well, after the transform or re-layout
+    (stage "train" only); construction leaves its counter as it was, every replay advances it by one on the device."""
 
     def __init__(self, module, example_batch: dict, arena: "dp.FlatArena | None" = None, warmup: int = 2,
                  stage: str = "train"):
@@ -116,9 +118,13 @@ class GraphedStep(_StaticBatch):
                              "dp.FlatArena(module.model, extra_params=list(module.task_balancer.parameters()))")
         self.arena = arena
         self._init_static(module, example_batch)  # static buffers; conv precision and module.device_transform recorded
+        # a data.DeviceAugment, recorded like the transform: its two launches join the graph, its counter lives on the
+        # device, so every replay draws fresh parameters
+        self.train_augment = getattr(module, "train_augment", None) if stage == "train" else None
         attached, module.dp_arena = module.dp_arena, None  # the collective stays outside the graph (see __call__)
         # the warm-up and rehearsal steps run with gradients enabled: a "dwa" balancer would count them into its epoch
         snap = [] if balancer is None else [(b, b.clone()) for b in balancer.buffers()]
+        aug_counter = None if self.train_augment is None else self.train_augment.counter
         try:
             so = module.step_outputs[stage]
             mark = {k: len(v) for k, v in so.items()}
@@ -151,12 +157,16 @@ class GraphedStep(_StaticBatch):
             with torch.no_grad():
                 for b, v in snap:
                     b.copy_(v)
+            if aug_counter is not None:  # the warm-up and rehearsal steps drew: the stream continues where it was
+                self.train_augment.set_counter(aug_counter)
         self._anchor = torch.zeros((), device=self.device, requires_grad=True)
         self.replays = 0
 
     # ---- helpers
     def _step(self) -> torch.Tensor:
-        return self.module.shared_step(self._model_batch(), self.stage)
+        if self.train_augment is None:
+            return self.module.shared_step(self._model_batch(), self.stage)
+        return self.module.shared_step(self.train_augment(self._model_batch()), self.stage)
 
     # ---- the step
     def __call__(self, batch: dict) -> torch.Tensor:

@@ -83,6 +83,9 @@ class MTLModule(nn.Module):
         # a data.DeviceTransform: transfer_batch_to_device then takes raw batches (data.collate_raw) and runs the sample
         # transform on the device (GraphedStep records it at construction)
         self.device_transform = None
+        # a data.DeviceAugment: training_step applies it to the device batch (validation, test and predict never do;
+        # GraphedStep(stage="train") records it at construction and captures it)
+        self.train_augment = None
 
     def forward(self, x: torch.Tensor) -> dict:
         return self.model(x)
@@ -145,6 +148,8 @@ class MTLModule(nn.Module):
                 "depth_predictions": ops.sigmoid(depth_logits).permute(0, 2, 3, 1)}
 
     def training_step(self, batch: dict, batch_idx: Any = 0):
+        if self.train_augment is not None:
+            batch = self.train_augment(batch)
         return self.shared_step(batch=batch, stage="train")
 
     def validation_step(self, batch: dict, batch_idx: Any = 0):

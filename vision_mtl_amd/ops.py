@@ -2469,6 +2469,69 @@ def nyuv2_resize(img, mask, depth, size, max_depth: float = 10.0):
     view._vmtl_nhwc = st
     return view, m, d
 
+
+AUGMENT_MAX_SCALES = 8  # csrc/augment.hip AUG_MAX_S
+
+
+def augment_draw(state, params, crop_hw, H: int, W: int, p_flip: float = 0.5, brightness: float = 0.0):
+    """One launch (csrc/augment.hip): fill params int32 (B, 8) = {scale_idx, top, left, flip, gain bits, 0, 0, 0} from
+    the device state int64 (2,) = {seed, counter} and advance the counter on the device.  crop_hw int32 (S, 2): the crop
+    size per scale.  The generator is restated on the host by data.augment_params_host."""
+    for name, v, dt in (("state", state, torch.int64), ("params", params, torch.int32)):
+        if _req_dtype(v, name, (dt,)) is not v:  # both are written: a contiguous, aligned copy would take the result
+            raise ValueError(f"augment_draw: {name} must be contiguous and 16-byte aligned")
+    crop_hw = _req_dtype(crop_hw, "crop_hw", (torch.int32,))
+    if state.numel() != 2 or params.dim() != 2 or params.shape[1] != 8 or crop_hw.dim() != 2 or crop_hw.shape[1] != 2:
+        raise ValueError(f"augment_draw: state (2,), params (B, 8), crop_hw (S, 2) expected, got {tuple(state.shape)}, "
+                         f"{tuple(params.shape)}, {tuple(crop_hw.shape)}")
+    _k("vmtl_augment_draw", state=state, params=params, crop_hw=crop_hw, B=params.shape[0], H=int(H), W=int(W),
+       S=crop_hw.shape[0], flip_threshold=int(round(float(p_flip) * (1 << 24))), brightness=float(brightness))
+    return params
+
+
+def augment_apply(img, mask, depth, params, scales, crop_hw):
+    """Random scale-crop + flip (+ gain) of one batch by the rows of `params`, as one launch (csrc/augment.hip).
+
+    img: a (B,3,H,W) view over the model's NHWC input storage (hwc_to_model_input, nyuv2_resize), a (B,H,W,3) tensor in
+    dataset sample layout, or a plain (B,3,H,W) tensor (re-laid first by the existing kernel); mask int64 (B,H,W); depth
+    float32 (B,H,W,1) or (B,H,W); params int32 (B,8); scales float32 (S,); crop_hw int32 (S,2).  Returns (img, mask, depth)
+    in the model's input contract: img a (B,3,H,W) view of a NEW NHWC storage (pad lane 0), mask int64 (B,H,W), depth
+    (B,H,W,1)."""
+    st = getattr(img, "_vmtl_nhwc", None)
+    if (st is not None and img.dim() == 4 and st.dim() == 4 and st.shape[-1] == 4 and st.shape[0] == img.shape[0]
+            and tuple(st.shape[1:3]) == tuple(img.shape[2:])):
+        src, ld = _req(st, "img"), 4
+    elif img.dim() == 4 and img.shape[-1] == 3 and img.shape[1] != 3:
+        src, ld = _req(img, "img"), 3
+    elif img.dim() == 4 and img.shape[1] == 3:
+        src, ld = to_nhwc(_req(img, "img")), 4
+    else:
+        raise ValueError(f"augment_apply: img must be (B, 3, H, W) or (B, H, W, 3), got {tuple(img.shape)}")
+    B, H, W, _ = src.shape
+    mask = _req_dtype(mask, "mask", (torch.int64,))
+    depth = _req(depth, "depth")
+    params = _req_dtype(params, "params", (torch.int32,))
+    scales = _req(scales, "scales")
+    crop_hw = _req_dtype(crop_hw, "crop_hw", (torch.int32,))
+    if tuple(mask.shape) != (B, H, W) or tuple(depth.shape) not in ((B, H, W, 1), (B, H, W)):
+        raise ValueError(f"augment_apply: mask {tuple(mask.shape)} must be {(B, H, W)} and depth {tuple(depth.shape)} "
+                         f"{(B, H, W, 1)}")
+    S = scales.numel()
+    if (tuple(params.shape) != (B, 8) or scales.dim() != 1 or tuple(crop_hw.shape) != (S, 2)
+            or not 1 <= S <= AUGMENT_MAX_SCALES):
+        raise ValueError(f"augment_apply: params {(B, 8)}, scales (S,), crop_hw (S, 2) with 1 <= S <= "
+                         f"{AUGMENT_MAX_SCALES} expected, got {tuple(params.shape)}, {tuple(scales.shape)}, "
+                         f"{tuple(crop_hw.shape)}")
+    out = _empty((B, H, W, 4), src)
+    m = torch.empty((B, H, W), dtype=torch.int64, device=src.device)
+    d = _empty((B, H, W, 1), src)
+    _k("vmtl_augment_apply", img=src, ld=ld, mask=mask, depth=depth, params=params, scales=scales, crop_hw=crop_hw,
+       img_out=out, mask_out=m, depth_out=d, B=B, H=H, W=W, S=S)
+    view = out[..., :3].permute(0, 3, 1, 2)
+    view._vmtl_nhwc = out
+    return view, m, d
+
+
 class _ToNCHW(torch.autograd.Function):
     """internal [B,H,W,Cs] -> (B,C,H,W) contiguous, the reference's output layout."""
 
