@@ -617,6 +617,49 @@ int vmtl_confusion_matrix_ex(const long long* pred, const long long* target, int
                              long long ignore_index, void* stream);
 int vmtl_segm_metrics_ex(const int* cm, int C, float beta, long long ignore_index, float* out, void* stream);
 
+/* ---- dataset-level evaluation metrics (csrc/eval_accum.hip) ------------
+ * Opt-in; the reference only averages the per-step metrics above.  The caller owns the state, zeroes it once per epoch and
+ * keeps it on the device; every evaluation step ADDS its batch to it (no allocation, no memset, no host sync in the call):
+ *   cm   int64   [C][C]   confusion matrix, target row, prediction column (C <= 64)
+ *   acc  float64 [16]     over the valid depth pixels, with p = max(prediction, min_depth), t = target:
+ *     [0] valid-pixel count   [1] sum |p - t|   [2] sum |p - t| / t   [3] sum (p - t)^2 / t   [4] sum (p - t)^2
+ *     [5] sum g^2 and [6] sum g, g = ln p - ln t   [7] sum |log10 p - log10 t|
+ *     [8] [9] [10] counts of max(p / t, t / p) < 1.25, 1.25^2, 1.25^3   [11..15] reserved, left at zero
+ * The prediction is clamped below at min_depth before EVERY term (Eigen-style evaluation: a prediction at or below zero
+ * would make the log terms meaningless), whichever validity rule is in use.  Every term is computed in fp64 from the fp32
+ * inputs (g as the fp64 log of the correctly rounded fp64 quotient p / t, |log10 p - log10 t| as |g| / ln 10).  cm and the counts are integers all the way (a count enters acc as one exact fp64 addition); the floating sums go
+ * through one fp64 partial row per workgroup in `workspace` and a fixed-order fold by a single workgroup: no floating-point
+ * atomics, the state after a given sequence of batches is bit-identical from run to run.
+ *
+ * vmtl_eval_accumulate.  Segmentation part, one of two forms (the other null), or absent (all three null):
+ *   pred / target: int64, P pixels; a pixel whose target equals ignore_index (-1: none) or whose target or prediction is
+ *                  outside [0, C) is skipped, as vmtl_confusion_matrix_ex does;
+ *   step_cm:       a ready int32 [C][C] matrix of this step (what vmtl_confusion_matrix* built), added element-wise.
+ * Depth part (absent: dpred, dtarget null): float dpred / dtarget of Pd pixels at any 4-byte alignment; a pixel is valid
+ * when valid[i] != 0 (uint8, Pd bytes), or with valid null when dtarget[i] > min_depth (SILog's rule).  With a valid mask
+ * the caller answers for t > 0 on the valid pixels.  workspace: vmtl_eval_accum_workspace_bytes(Pd) bytes, 8-byte aligned,
+ * contents don't matter; needed by the depth part only. */
+#define VMTL_EVAL_ACC_SIZE 16
+long long vmtl_eval_accum_workspace_bytes(long long P); /* host only */
+int vmtl_eval_accumulate(const long long* pred, const long long* target, const int* step_cm, long long P, int C,
+                         long long ignore_index, const float* dpred, const float* dtarget, const unsigned char* valid,
+                         float min_depth, long long Pd, long long* cm, double* acc, void* workspace, void* stream);
+/* State -> metrics, one single-workgroup launch.  out: float64 [16]
+ *   [0] pixel accuracy  [1] mean class accuracy  [2] mIoU  [3] F-beta, support weighted
+ *   [4] abs_err = E|p - t|  [5] rel_err = E|p - t| / t  [6] sq_rel = E (p - t)^2 / t  [7] rmse  [8] rmse_log = sqrt(E g^2)
+ *   [9] log10 = E|log10 p - log10 t|  [10] silog = sqrt(max(E g^2 - (E g)^2, 0))  [11] [12] [13] delta1..3 (fractions)
+ *   [14] n_valid (depth pixels)  [15] n_pixels (the sum of cm)
+ * iou: float64 [C], per-class intersection over union.
+ * The two class means run over the classes whose union tp + fp + fn (mIoU), or support (mean accuracy), is non-zero, and
+ * never over a class named by ignore_index; iou[c] is NaN for a class left out.  This is the convention of the Cityscapes
+ * evaluation scripts and of MTAN's ConfMatrix, and it DIFFERS ON PURPOSE from the per-step Jaccard of vmtl_segm_metrics,
+ * which (as torchmetrics' absent_score = 0) scores an absent class 0: over a whole evaluation set an absent class says
+ * nothing about the model, within one batch the reference counts it.  Pixel accuracy and F-beta are over all of cm (the row
+ * of an ignored class is empty when cm was built with the same ignore_index).  [0..3] and iou are NaN when cm is all zero,
+ * [4..13] are NaN when acc[0] == 0; nothing divides by zero. */
+int vmtl_eval_finalize(const long long* cm, const double* acc, int C, float beta, long long ignore_index, double* out,
+                       double* iou, void* stream);
+
 /* ---- optimizer (training_lit.py:51,87: torch.optim.Adam) ---------------------------------- */
 int vmtl_adam_step(float* p, const float* g, float* m, float* v, const float* step_ptr, float lr, float b1,
                    float b2, float eps, float weight_decay, float grad_scale, long long n, void* stream);
