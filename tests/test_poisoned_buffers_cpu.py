@@ -164,32 +164,43 @@ def _collect(paths):
 
 
 def test_sweep_covers_exactly_what_pytest_collects():
-    """A renamed, added or newly parametrised test of a swept module must not drop out of the sweep silently: the ids
-    pytest collects from the swept modules, and the ids of the sweep mapped back to their originals, are the same set
-    (apart from the explicit exclusion list, which is bounded)."""
+    """A renamed, added or newly parametrised test of a swept module must not drop out of a sweep silently: the ids
+    pytest collects from the swept modules, and the ids of each sweep (test_guarded, test_launch_guarded) mapped back to
+    their originals, are the same set (apart from that sweep's explicit exclusion list, which is bounded)."""
     from tests import test_poisoned_buffers_gpu as sweep
 
     mods = [f"tests/{m}.py" for m in sweep.SWEPT_MODULES]
     ids = _collect(mods + [f"tests/{m}.py" for m in sweep.SWEPT_FUNCTIONS] + ["tests/test_poisoned_buffers_gpu.py"])
-    swept, originals, listed = set(), set(), set()
+    sweeps = {"test_guarded": (set(), sweep.EXCLUDED), "test_launch_guarded": (set(), sweep.EXCLUDED_LAUNCH)}
+    originals, listed, others = set(), set(), []
     for i in ids:
         path, rest = i.split("::", 1)
         if path == "tests/test_poisoned_buffers_gpu.py":
-            orig = sweep.original_id(rest)
-            assert orig not in swept, f"{orig} is swept twice"
-            swept.add(orig)
+            name = rest.split("[")[0]
+            if name not in sweeps:
+                others.append(rest)
+                continue
+            orig = sweep.original_id(rest, name)
+            assert orig not in sweeps[name][0], f"{orig} is swept twice by {name}"
+            sweeps[name][0].add(orig)
         elif path in mods:
             originals.add(i)
         elif rest.split("[")[0] in sweep.SWEPT_FUNCTIONS[path[len("tests/"):-len(".py")]]:
             listed.add(i)
-    excluded = {e for e, _ in sweep.EXCLUDED}
-    assert excluded <= originals | listed, f"excluded ids that do not exist: {sorted(excluded - originals - listed)}"
-    assert all(reason.strip() for _, reason in sweep.EXCLUDED)
-    assert len(excluded) <= 0.05 * len(originals | listed)
-    missing, extra = (originals | listed) - excluded - swept, swept - ((originals | listed) - excluded)
-    assert not missing, f"collected but not swept: {sorted(missing)}"
-    assert not extra, f"swept but not collected (or excluded): {sorted(extra)}"
+    # the tally of the second sweep is collected, and after every case of it
+    assert others == ["test_launch_guarded_leaves_few_pointers_in_place"] and ids[-1].endswith(others[0]), others
+    for name, (swept, exclusions) in sweeps.items():
+        excluded = {e for e, _ in exclusions}
+        assert len(excluded) == len(exclusions), f"{name}: an id is excluded twice"
+        assert excluded <= originals | listed, f"{name}: excluded ids that do not exist: {sorted(excluded - originals - listed)}"
+        assert all(reason.strip() for _, reason in exclusions)
+        assert len(excluded) <= 0.05 * len(originals | listed), name
+        missing, extra = (originals | listed) - excluded - swept, swept - ((originals | listed) - excluded)
+        assert not missing, f"{name}: collected but not swept: {sorted(missing)}"
+        assert not extra, f"{name}: swept but not collected (or excluded): {sorted(extra)}"
     assert len(originals) >= 348  # the five modules at the commit that introduced the sweep
+    assert len(listed) >= 219     # the listed functions at the commit that introduced the second sweep
     for m, names in sweep.SWEPT_FUNCTIONS.items():  # every listed function exists and contributed a case
         for n in names:
             assert any(i.startswith(f"tests/{m}.py::{n}") for i in listed), f"{m}.{n} is listed but not collected"
+    assert sweep.LEFT_IN_PLACE_CAP == 0.05
