@@ -860,7 +860,9 @@ def test_conv_with_folded_stitch_scale(dev, case, channel_wise):
 # [B][H][W][ceil4(C+1)] rows: 1, 2 (Q = 1), 33 and 40 are further widths; 4, 16 and 32 are multiples of 4, where the row is
 # C + 4 wide, wider than the ceil4(C) the row-per-pixel kernel covers, so the quad-per-thread kernel runs and leaves the
 # last quad to the consumer; 33 and 40 (NYUv2) are past the 32 logits the register forms of forward and backward hold.
-CE_FP64_COUNTS = (1, 2, 4, 16, 32, 33, 40)
+# 9, 22, 26 and 30 are the Q = ceil(C/4) = 3, 6, 7, 8 that 19 (5), 14 (4), 5 (2) and 1 leave out, at C % 4 != 0, so the
+# row-per-pixel kernel runs them: every case of the launchers' Q switches, which the weighted variant shares.
+CE_FP64_COUNTS = (1, 2, 4, 16, 32, 33, 40, 9, 22, 26, 30)
 
 
 @pytest.mark.parametrize("C", [19, 14, 5, *CE_FP64_COUNTS])

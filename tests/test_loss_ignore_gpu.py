@@ -22,9 +22,10 @@ pytestmark = pytest.mark.gpu
 IGN = 255
 GOUT = 1.7  # the loss is scaled before backward: grad_output is not 1
 # name: (C, B, H, W).  a: ragged last wave; b, c: the rows kernel at ld = 16 / 20; d: ld = 24 != 4*ceil(C/4), the wide-ld
-# NHWC kernel; e: past the 32 logits the register forms hold; f: P = 526 683 > 2048 * 256, the grid-stride loop and block cap
+# NHWC kernel; e: past the 32 logits the register forms hold; f: P = 526 683 > 2048 * 256, the grid-stride loop and block cap;
+# g, h, i, j: Q = ceil(C/4) = 3, 6, 7, 8 at C % 4 != 0 (the rows kernel), the cases of the Q switches that a, b, c leave out
 CASES = {"a": (3, 2, 5, 13), "b": (14, 2, 5, 13), "c": (19, 2, 5, 13), "d": (20, 2, 5, 13), "e": (33, 2, 5, 13),
-         "f": (3, 3, 419, 419)}
+         "f": (3, 3, 419, 419), "g": (9, 2, 5, 13), "h": (22, 2, 5, 13), "i": (26, 2, 5, 13), "j": (30, 2, 5, 13)}
 COMBOS = ("ignore", "weight", "both")
 
 
@@ -68,8 +69,8 @@ def _bits(x):
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_forward_argmax_and_backward_match_torch(dev, name, combo):
     """Forward, fused-argmax forward and the backward the node runs (NHWC rows of ceil4(C+1) floats: the rows kernel for
-    a, b, c, f; the wide-ld kernel for d and e) against torch in fp64; the argmax at every pixel, ignored ones included;
-    ignored rows bitwise 0.0; no NaN anywhere."""
+    a, b, c, f, g, h, i, j; the wide-ld kernel for d and e) against torch in fp64; the argmax at every pixel, ignored
+    ones included; ignored rows bitwise 0.0; no NaN anywhere."""
     ops = _ops()
     c = _case(name, combo)
     z, t, w = _dev_inputs(c, dev)

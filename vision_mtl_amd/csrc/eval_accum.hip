@@ -59,7 +59,7 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   return v;
 }
 
-// Segmentation part (P > 0): confusion_ex_kernel's LDS histogram, flushed into the int64 matrix.
+// Segmentation part (P > 0): the LDS histogram of metrics.hip's confusion_kernel<true>, flushed into the int64 matrix.
 // Depth part (Pd > 0): the first nblk_d workgroups sweep the pixels and leave one row of partials each.
 // VEC: dpred / dtgt are 16-byte aligned (valid 4-byte aligned): float4 loads over Pd / 4 quads, scalar tail.
 template <bool VEC, bool MASK>

@@ -11,11 +11,18 @@
 // Reductions are two-stage: per-workgroup partials in fp64, summed in a fixed order by a
 // single finalize workgroup, so results are run-to-run reproducible.
 //
+// Every cross-entropy kernel is written once as a template over `bool EX` and compiled twice.  EX = false is the plain
+// mean over all pixels; EX = true takes the operands of CeEx<true>: class weights, an ignore index and, in the backward,
+// the denominator the forward left on the device.  What the two variants do differently is stated once, in the ce_*<EX>
+// helpers in front of the kernels; everything else - thread-to-pixel maps, strides, launch shapes, the log-softmax - is
+// the one kernel body.  The plain instantiations compile to the instruction sequence a kernel without the parameter
+// compiles to, so the default step pays nothing for the variant.  The SILog kernels take their
+// validity test (target > min_depth, or the caller's mask) as a functor in the same way.
+//
 // The weighted / ignoring cross entropy divides by a sum that depends on the targets.  Its forward reduces
-// (numerator, denominator) pairs the same way and leaves the denominator in a two-float `stats` buffer on the device
+// (numerator, denominator) pairs and leaves the denominator in a two-float `stats` buffer on the device
 // (stats[0] = sum of weights over valid pixels, stats[1] = the weighted nll sum); the backward reads stats[0], so the
-// step never waits for the host.  Its kernels (ce_ex_*) stand next to the plain ones, which are untouched: the default
-// step launches exactly the code it launched before.
+// step never waits for the host.
 #include "common.h"
 
 #define CE_THREADS 256
@@ -32,6 +39,93 @@ __device__ __forceinline__ double block_sum_d(double v, double* sh) {
   return s;
 }
 
+// ------------------------------------------------------------------ cross entropy: what the variants do differently
+// The operands only the weighted / ignoring variant has.  weight: C floats or null (all ones); ignore: VMTL_NO_IGNORE
+// for none; stats: what the forward left for the backward (null in the forward itself).  The plain variant's struct is
+// empty and never read, but as a kernel argument it still takes 8 bytes: the backward kernels take it LAST, so that
+// the plain ones find their arguments where they were without it (behind `tgt` the gap split their one load of the
+// four pointers in two).  The forward kernels take it behind `tgt`, where the gap costs the plain ones nothing.
+template <bool EX>
+struct CeEx {};
+template <>
+struct CeEx<true> {
+  const float* __restrict__ weight;
+  long long ignore;
+  const float* __restrict__ stats;
+};
+
+// Forward, before the pixel's sum of exponentials: false when the pixel adds no nll.  EX: its target is the ignore index
+// (adds nothing), or any other target outside [0, C), which adds NaN to the numerator and never indexes w.
+// torch raises on an out-of-range class index; raising here would need a host sync on the step path, so such a pixel
+// contributes NaN: the loss (and, in the backward, the gradient) fails the step VISIBLY instead of silently adding 0.
+// The plain variant skips nothing and applies the same rule in ce_add.
+template <bool EX>
+__device__ __forceinline__ bool ce_counts(long long t, int C, CeEx<EX> ex, double& num) {
+  if constexpr (EX) {
+    if (t == ex.ignore) return false;
+    if (t < 0 || t >= C) {
+      num += (double)__int_as_float(0x7fc00000);
+      return false;
+    }
+  }
+  return true;
+}
+
+// What a pixel that counts adds: w[t] * nll and w[t] to (numerator, denominator), or nll to the plain variant's single
+// sum (kept in num; den stays unused).  nll() is only evaluated for a target inside [0, C).
+template <bool EX, class Nll>
+__device__ __forceinline__ void ce_add(double& num, double& den, long long t, int C, CeEx<EX> ex, Nll nll) {
+  if constexpr (EX) {
+    const float wt = ex.weight != nullptr ? ex.weight[t] : 1.f;
+    num += (double)wt * (double)nll();
+    den += (double)wt;
+  } else {
+    if (t < 0 || t >= C) num += (double)__int_as_float(0x7fc00000);  // see ce_counts
+    else num += (double)nll();
+  }
+}
+
+// partial: one double per block, or (numerator, denominator) per block
+template <bool EX>
+__device__ __forceinline__ void ce_store_partials(double num, double den, double* __restrict__ partial, double* shd) {
+  const double bn = block_sum_d(num, shd);
+  if constexpr (EX) {
+    const double bd = block_sum_d(den, shd);
+    if (threadIdx.x == 0) {
+      partial[2 * blockIdx.x] = bn;
+      partial[2 * blockIdx.x + 1] = bd;
+    }
+  } else {
+    if (threadIdx.x == 0) partial[blockIdx.x] = bn;
+  }
+}
+
+// Backward: the gradient of one pixel is dz_c = (softmax_c - 1[c == t]) * k + bad, with k = g = gout / P in the plain
+// variant and k = w[t] * g, g = gout / stats[0] in the other.  bad: NaN for a target outside [0, C) that is not the
+// ignore index - as the forward: NaN, never a silent 0 - and such a target never indexes w.  An ignored pixel sets
+// `zero`, and the kernels then store 0.0f in every lane they own (a select, never a product with g, which is inf when
+// every pixel is ignored).
+template <bool EX>
+__device__ __forceinline__ float ce_grad_unit(const float* __restrict__ gout, long long P, CeEx<EX> ex) {
+  if constexpr (EX) return gout[0] / ex.stats[0];
+  else return gout[0] / (float)P;
+}
+
+template <bool EX>
+__device__ __forceinline__ float ce_scale(long long t, int C, float g, CeEx<EX> ex, float& bad, bool& zero) {
+  if constexpr (EX) {
+    zero = t == ex.ignore;
+    const bool oob = t < 0 || t >= C;
+    bad = (oob && !zero) ? __int_as_float(0x7fc00000) : 0.f;
+    return (!oob && ex.weight != nullptr) ? ex.weight[t] * g : g;
+  } else {
+    zero = false;
+    bad = (t < 0 || t >= C) ? __int_as_float(0x7fc00000) : 0.f;
+    return g;
+  }
+}
+
+// ------------------------------------------------------------------ cross entropy: kernels
 // Element (b, c, hw) of the logits sits at z[b*sb + c*sc + hw*sp]:
 //   NCHW (the reference's layout at the boundary): sb = C*HW, sc = HW, sp = 1  -> every channel
 //   read of a wave is 256 contiguous bytes;  NHWC: sb = HW*ld, sc = 1, sp = ld.
@@ -39,13 +133,15 @@ __device__ __forceinline__ double block_sum_d(double v, double* sh) {
 // Numerics: log-softmax is evaluated as (z - max) - log(sum exp(z - max)), subtracting the max FIRST
 // (exact for nearby floats).  Forming lse = max + log(sum) and then z - lse would lose ~ulp(max)
 // per pixel when the logits are large, a systematic error the backward pass of a deep net amplifies.
+// The argmax is written for ignored pixels too (the prediction does not depend on the target).
+template <bool EX>
 __global__ __launch_bounds__(CE_THREADS) void ce_fwd_kernel(const float* __restrict__ z,
-                                                            const long long* __restrict__ tgt,
+                                                            const long long* __restrict__ tgt, CeEx<EX> ex,
                                                             double* __restrict__ partial,
                                                             long long* __restrict__ amax, long long P, int HW,
                                                             int C, long long sb, long long sc, long long sp) {
   __shared__ double shd[4];
-  double loss = 0.0;
+  double num = 0.0, den = 0.0;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long long)gridDim.x * blockDim.x) {
     const long long b = i / HW, hw = i - b * HW;
     const float* r = z + b * sb + hw * sp;
@@ -56,29 +152,25 @@ __global__ __launch_bounds__(CE_THREADS) void ce_fwd_kernel(const float* __restr
       if (v > m) { m = v; am = c; }  // first maximum wins, like torch.argmax on ties
     }
     if (amax != nullptr) amax[i] = am;
+    if (!ce_counts<EX>(tgt[i], C, ex, num)) continue;
     float s = 0.f;
     for (int c = 0; c < C; ++c) s += expf(r[c * sc] - m);
     const long long t = tgt[i];
-    // torch raises on an out-of-range class index; raising here would need a host sync on the step path, so the
-    // pixel contributes NaN: the loss (and, in ce_bwd, the gradient) fails the step VISIBLY instead of silently
-    // adding 0 to a loss still divided by P
-    if (t < 0 || t >= C) loss += (double)__int_as_float(0x7fc00000);
-    else loss += (double)(logf(s) - (r[t * sc] - m));
+    ce_add<EX>(num, den, t, C, ex, [&] { return logf(s) - (r[t * sc] - m); });
   }
-  const double bs = block_sum_d(loss, shd);
-  if (threadIdx.x == 0) partial[blockIdx.x] = bs;
+  ce_store_partials<EX>(num, den, partial, shd);
 }
 
 // The same pass with the pixel's logits held in registers (C <= 32: one load per logit instead of three sweeps over
 // the channel planes for max / sum-exp / target): 44 -> ~30 us for 32x19x128x256.
-template <int Q>
+template <int Q, bool EX>
 __global__ __launch_bounds__(CE_THREADS) void ce_fwd_regs_kernel(const float* __restrict__ z,
-                                                                 const long long* __restrict__ tgt,
+                                                                 const long long* __restrict__ tgt, CeEx<EX> ex,
                                                                  double* __restrict__ partial,
                                                                  long long* __restrict__ amax, long long P, int HW,
                                                                  int C, long long sb, long long sc, long long sp) {
   __shared__ double shd[4];
-  double loss = 0.0;
+  double num = 0.0, den = 0.0;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long long)gridDim.x * blockDim.x) {
     const long long b = i / HW, hw = i - b * HW;
     const float* r = z + b * sb + hw * sp;
@@ -92,17 +184,16 @@ __global__ __launch_bounds__(CE_THREADS) void ce_fwd_regs_kernel(const float* __
     for (int c = 1; c < 4 * Q; ++c)
       if (c < C && v[c] > m) { m = v[c]; am = c; }  // first maximum wins, like torch.argmax on ties
     if (amax != nullptr) amax[i] = am;
+    if (!ce_counts<EX>(t, C, ex, num)) continue;
     float s = 0.f, zt = 0.f;
 #pragma unroll
     for (int c = 0; c < 4 * Q; ++c) {
       if (c < C) s += expf(v[c] - m);
       if (c == t) zt = v[c];
     }
-    if (t < 0 || t >= C) loss += (double)__int_as_float(0x7fc00000);  // see ce_fwd_kernel
-    else loss += (double)(logf(s) - (zt - m));
+    ce_add<EX>(num, den, t, C, ex, [&] { return logf(s) - (zt - m); });
   }
-  const double bs = block_sum_d(loss, shd);
-  if (threadIdx.x == 0) partial[blockIdx.x] = bs;
+  ce_store_partials<EX>(num, den, partial, shd);
 }
 
 // err (may be null): the result becomes NaN when the flag is set.
@@ -113,322 +204,6 @@ __global__ void sum_finalize_kernel(const double* __restrict__ partial, int n, d
   for (int i = threadIdx.x; i < n; i += blockDim.x) s += partial[i];
   const double t = block_sum_d(s, shd);
   if (threadIdx.x == 0) out[0] = (err != nullptr && err[0] != 0) ? __int_as_float(0x7fc00000) : (float)(t * scale);
-}
-
-// dz = (softmax(z) - onehot(y)) * gout / P, written with the same strides as z.  The softmax is
-// recomputed from the logits (max-subtracted, see above); nothing is saved by the forward pass.
-__global__ __launch_bounds__(CE_THREADS) void ce_bwd_kernel(const float* __restrict__ z,
-                                                            const long long* __restrict__ tgt,
-                                                            const float* __restrict__ gout, float* __restrict__ dz,
-                                                            long long P, int HW, int C, long long sb, long long sc,
-                                                            long long sp, long long dsb, long long dsc, long long dsp) {
-  const float g = gout[0] / (float)P;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long long)gridDim.x * blockDim.x) {
-    const long long b = i / HW, hw = i - b * HW;
-    const long long off = b * sb + hw * sp, doff = b * dsb + hw * dsp;
-    float m = z[off];
-    for (int c = 1; c < C; ++c) m = fmaxf(m, z[off + c * sc]);
-    float s = 0.f;
-    for (int c = 0; c < C; ++c) s += expf(z[off + c * sc] - m);
-    const float inv = 1.f / s;
-    const long long t = tgt[i];
-    const float bad = (t < 0 || t >= C) ? __int_as_float(0x7fc00000) : 0.f;  // as the forward: NaN, never a silent 0
-    for (int c = 0; c < C; ++c) dz[doff + c * dsc] = (expf(z[off + c * sc] - m) * inv - (c == t ? 1.f : 0.f)) * g + bad;
-  }
-}
-
-// vmtl_ce_bwd_strided with a channel-contiguous gradient (NHWC rows of ld >= ceil4(C) floats): one thread per
-// (pixel, channel quad), so a wave writes 1 KB of CONTIGUOUS gradient (one thread per pixel left every store
-// instruction touching 64 lanes x 16 bytes at an 80-byte stride: 2-4x slower than the NCHW form).  The softmax
-// statistics of a pixel are recomputed by its Q = ceil(C/4) threads (reads hit L1; ~2*C expf each).
-__global__ __launch_bounds__(CE_THREADS) void ce_bwd_nhwc_kernel(const float* __restrict__ z,
-                                                                 const long long* __restrict__ tgt,
-                                                                 const float* __restrict__ gout, float* __restrict__ dz,
-                                                                 long long P, int HW, int C, long long sb, long long sc,
-                                                                 long long sp, int ld) {
-  const float g = gout[0] / (float)P;
-  const int Q = (C + 3) >> 2;
-  const long long total = P * Q;
-  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
-    const long long i = idx / Q;
-    const int q = (int)(idx - i * Q);
-    const long long b = i / HW, hw = i - b * HW;
-    const long long off = b * sb + hw * sp;
-    float m = z[off];
-    for (int c = 1; c < C; ++c) m = fmaxf(m, z[off + c * sc]);
-    float s = 0.f;
-    for (int c = 0; c < C; ++c) s += expf(z[off + c * sc] - m);
-    const float inv = 1.f / s;
-    const long long t = tgt[i];
-    const float bad = (t < 0 || t >= C) ? __int_as_float(0x7fc00000) : 0.f;  // as the forward: NaN, never a silent 0
-    f32x4 v;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int c = 4 * q + e;
-      v[e] = c < C ? (expf(z[off + c * sc] - m) * inv - (c == t ? 1.f : 0.f)) * g + bad : 0.f;
-    }
-    *reinterpret_cast<f32x4*>(dz + i * ld + 4 * q) = v;
-  }
-}
-
-// The same gradient when the NHWC rows are exactly the Q = ceil(C/4) quads (ld == 4*Q, the layout
-// ops._CrossEntropy.backward allocates): one thread per PIXEL - logits read once, coalesced along the pixel axis of
-// each channel plane, softmax evaluated once - and the wave's 64 finished rows (64*ld contiguous floats) turned
-// through LDS so every store instruction writes 1 KB of consecutive gradient.  138 -> ~60 us for 32x19x128x256 on
-// MI355X (the quad-per-thread form above re-reads the pixel's logits and re-evaluates 2*C expf in each of its Q threads).
-template <int Q>
-__global__ __launch_bounds__(256) void ce_bwd_nhwc_rows_kernel(const float* __restrict__ z,
-                                                               const long long* __restrict__ tgt,
-                                                               const float* __restrict__ gout, float* __restrict__ dz,
-                                                               long long P, int HW, int C, long long sb, long long sc,
-                                                               long long sp) {
-  __shared__ f32x4 sm[4][64 * Q];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const float g = gout[0] / (float)P;
-  for (long long wg0 = (long long)blockIdx.x * 256; wg0 < P; wg0 += (long long)gridDim.x * 256) {  // uniform trip count
-    const long long base = wg0 + wave * 64, i = base + lane;
-    if (i < P) {
-      const long long b = i / HW, hw = i - b * HW;
-      const float* r = z + b * sb + hw * sp;
-      float v[4 * Q];
-#pragma unroll
-      for (int c = 0; c < 4 * Q; ++c) v[c] = c < C ? r[c * sc] : 0.f;
-      float m = v[0];
-#pragma unroll
-      for (int c = 1; c < 4 * Q; ++c) m = c < C ? fmaxf(m, v[c]) : m;
-      float s = 0.f;
-#pragma unroll
-      for (int c = 0; c < 4 * Q; ++c) {
-        v[c] = c < C ? expf(v[c] - m) : 0.f;
-        s += v[c];
-      }
-      const float inv = 1.f / s;
-      const long long t = tgt[i];
-      const float bad = (t < 0 || t >= C) ? __int_as_float(0x7fc00000) : 0.f;  // as the forward: NaN, never a silent 0
-#pragma unroll
-      for (int q = 0; q < Q; ++q) {
-        f32x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int c = 4 * q + e;
-          o[e] = c < C ? (v[c] * inv - (c == t ? 1.f : 0.f)) * g + bad : 0.f;
-        }
-        sm[wave][lane * Q + q] = o;
-      }
-    }
-    __syncthreads();
-    if (base < P) {
-      const int nf4 = (int)(P - base < 64 ? P - base : 64) * Q;
-      f32x4* out = reinterpret_cast<f32x4*>(dz + base * (4 * Q));
-#pragma unroll
-      for (int j = 0; j < Q; ++j) {
-        const int idx = j * 64 + lane;
-        if (idx < nf4) out[idx] = sm[wave][idx];
-      }
-    }
-    __syncthreads();
-  }
-}
-
-static inline int ce_blocks(long long P) {
-  long long nb = cdivll(P, CE_THREADS);
-  if (nb > 2048) nb = 2048;
-  if (nb < 1) nb = 1;
-  return (int)nb;
-}
-
-extern "C" long long vmtl_ce_workspace_bytes(long long P) { return ((long long)ce_blocks(P) + 1) * (long long)sizeof(double); }
-
-// workspace: vmtl_ce_workspace_bytes(P) bytes, 8-byte aligned (per-block partial sums).  A target outside [0, C)
-// makes the loss NaN.
-static int ce_fwd_impl(const float* logits, const long long* target, float* loss, void* workspace, long long* amax,
-                       int B, int HW, int C, long long sb, long long sc, long long sp, void* stream) {
-  if (!logits || !target || !loss || !workspace || B <= 0 || HW <= 0 || C <= 0) return VMTL_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const long long P = (long long)B * HW;
-  const int nblk = ce_blocks(P);
-  double* partial = (double*)workspace;
-#define CEF(QV)                                                                                              \
-  hipLaunchKernelGGL((ce_fwd_regs_kernel<QV>), dim3(nblk), dim3(CE_THREADS), 0, st, logits, target, partial, amax, P, \
-                     HW, C, sb, sc, sp)
-  switch (C <= 32 ? (C + 3) >> 2 : 0) {
-    case 1: CEF(1); break;
-    case 2: CEF(2); break;
-    case 3: CEF(3); break;
-    case 4: CEF(4); break;
-    case 5: CEF(5); break;
-    case 6: CEF(6); break;
-    case 7: CEF(7); break;
-    case 8: CEF(8); break;
-    default:
-      hipLaunchKernelGGL(ce_fwd_kernel, dim3(nblk), dim3(CE_THREADS), 0, st, logits, target, partial, amax, P, HW, C, sb,
-                         sc, sp);
-  }
-#undef CEF
-  hipLaunchKernelGGL(sum_finalize_kernel, dim3(1), dim3(256), 0, st, partial, nblk, 1.0 / (double)P, loss,
-                     (const int*)nullptr);
-  return vmtl_check_launch();
-}
-
-extern "C" int vmtl_ce_fwd(const float* logits, const long long* target, float* loss, void* workspace, int B, int HW,
-                           int C, long long sb, long long sc, long long sp, void* stream) {
-  VMTL_ENTER();
-  return ce_fwd_impl(logits, target, loss, workspace, nullptr, B, HW, C, sb, sc, sp, stream);
-}
-
-// vmtl_ce_fwd that also emits argmax_c logits (= the segmentation prediction of lit_module.py:137-138): the loss
-// pass finds every pixel's maximum anyway, so the prediction costs one 8-byte store instead of a second sweep
-// over the logits in its own launch
-extern "C" int vmtl_ce_fwd_argmax(const float* logits, const long long* target, float* loss, void* workspace,
-                                  long long* argmax, int B, int HW, int C, long long sb, long long sc, long long sp,
-                                  void* stream) {
-  VMTL_ENTER();
-  if (!argmax) return VMTL_ERR_ARG;
-  return ce_fwd_impl(logits, target, loss, workspace, argmax, B, HW, C, sb, sc, sp, stream);
-}
-
-extern "C" int vmtl_ce_bwd(const float* logits, const long long* target, const float* grad_out, float* dlogits, int B,
-                           int HW, int C, long long sb, long long sc, long long sp, void* stream) {
-  VMTL_ENTER();
-  if (!logits || !target || !grad_out || !dlogits || B <= 0 || HW <= 0 || C <= 0) return VMTL_ERR_ARG;
-  const long long P = (long long)B * HW;
-  hipLaunchKernelGGL(ce_bwd_kernel, dim3(ce_blocks(P)), dim3(CE_THREADS), 0, (hipStream_t)stream, logits, target,
-                     grad_out, dlogits, P, HW, C, sb, sc, sp, sb, sc, sp);
-  return vmtl_check_launch();
-}
-
-// vmtl_ce_bwd with its own strides for dlogits: element (b, c, hw) of the gradient goes to dlogits[b*dsb + c*dsc +
-// hw*dsp].  With (HW*ld, 1, ld) the gradient lands in the NHWC storage the head's data-gradient conv reads (one
-// 76-byte run per pixel) and the NCHW -> NHWC relayout of an 80 MB tensor disappears from the step.
-extern "C" int vmtl_ce_bwd_strided(const float* logits, const long long* target, const float* grad_out, float* dlogits,
-                                   int B, int HW, int C, long long sb, long long sc, long long sp, long long dsb,
-                                   long long dsc, long long dsp, void* stream) {
-  VMTL_ENTER();
-  if (!logits || !target || !grad_out || !dlogits || B <= 0 || HW <= 0 || C <= 0) return VMTL_ERR_ARG;
-  const long long P = (long long)B * HW;
-  if (dsc == 1 && dsp == ((C + 3) & ~3) && dsp <= 32 && dsb == dsp * HW) {
-    long long nb = cdivll(P, 256);
-    if (nb > 8192) nb = 8192;
-#define CALL(QV)                                                                                                  \
-  hipLaunchKernelGGL((ce_bwd_nhwc_rows_kernel<QV>), dim3((int)nb), dim3(256), 0, (hipStream_t)stream, logits, target, \
-                     grad_out, dlogits, P, HW, C, sb, sc, sp)
-    switch ((int)dsp >> 2) {
-      case 1: CALL(1); break;
-      case 2: CALL(2); break;
-      case 3: CALL(3); break;
-      case 4: CALL(4); break;
-      case 5: CALL(5); break;
-      case 6: CALL(6); break;
-      case 7: CALL(7); break;
-      default: CALL(8); break;
-    }
-#undef CALL
-    return vmtl_check_launch();
-  }
-  if (dsc == 1 && (dsp & 3) == 0 && dsp >= ((C + 3) & ~3) && dsb == dsp * HW) {
-    long long nb = cdivll(P * ((C + 3) >> 2), CE_THREADS);
-    if (nb > 8192) nb = 8192;
-    hipLaunchKernelGGL(ce_bwd_nhwc_kernel, dim3((int)nb), dim3(CE_THREADS), 0, (hipStream_t)stream, logits, target,
-                       grad_out, dlogits, P, HW, C, sb, sc, sp, (int)dsp);
-    return vmtl_check_launch();
-  }
-  hipLaunchKernelGGL(ce_bwd_kernel, dim3(ce_blocks(P)), dim3(CE_THREADS), 0, (hipStream_t)stream, logits, target,
-                     grad_out, dlogits, P, HW, C, sb, sc, sp, dsb, dsc, dsp);
-  return vmtl_check_launch();
-}
-
-// ------------------------------------------------------------------ weighted / ignoring cross entropy
-// The kernels above with torch's `weight` and `ignore_index`: the same thread-to-pixel maps, strides, launch shapes and
-// log-softmax numerics; what differs is named where it differs.
-
-// What a pixel adds to (numerator, denominator): nothing when its target is the ignore index; NaN to the numerator for
-// any other target outside [0, C) (see ce_fwd_kernel; such a target never indexes w); else w[t] * nll and w[t]
-// (w == null: all ones).
-__device__ __forceinline__ bool ce_ex_counts(long long t, int C, long long ignore, double& num) {
-  if (t == ignore) return false;
-  if (t < 0 || t >= C) {
-    num += (double)__int_as_float(0x7fc00000);
-    return false;
-  }
-  return true;
-}
-
-__device__ __forceinline__ void ce_ex_add(double& num, double& den, float nll, const float* __restrict__ w, long long t) {
-  const float wt = w != nullptr ? w[t] : 1.f;
-  num += (double)wt * (double)nll;
-  den += (double)wt;
-}
-
-__device__ __forceinline__ void ce_ex_store_partials(double num, double den, double* __restrict__ partial, double* shd) {
-  const double bn = block_sum_d(num, shd);
-  const double bd = block_sum_d(den, shd);
-  if (threadIdx.x == 0) {
-    partial[2 * blockIdx.x] = bn;
-    partial[2 * blockIdx.x + 1] = bd;
-  }
-}
-
-// ce_fwd_kernel; the argmax is written for ignored pixels too (the prediction does not depend on the target)
-__global__ __launch_bounds__(CE_THREADS) void ce_ex_fwd_kernel(const float* __restrict__ z,
-                                                               const long long* __restrict__ tgt,
-                                                               const float* __restrict__ weight, long long ignore,
-                                                               double* __restrict__ partial,
-                                                               long long* __restrict__ amax, long long P, int HW,
-                                                               int C, long long sb, long long sc, long long sp) {
-  __shared__ double shd[4];
-  double num = 0.0, den = 0.0;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long long)gridDim.x * blockDim.x) {
-    const long long b = i / HW, hw = i - b * HW;
-    const float* r = z + b * sb + hw * sp;
-    float m = r[0];
-    int am = 0;
-    for (int c = 1; c < C; ++c) {
-      const float v = r[c * sc];
-      if (v > m) { m = v; am = c; }  // first maximum wins, like torch.argmax on ties
-    }
-    if (amax != nullptr) amax[i] = am;
-    const long long t = tgt[i];
-    if (!ce_ex_counts(t, C, ignore, num)) continue;
-    float s = 0.f;
-    for (int c = 0; c < C; ++c) s += expf(r[c * sc] - m);
-    ce_ex_add(num, den, logf(s) - (r[t * sc] - m), weight, t);
-  }
-  ce_ex_store_partials(num, den, partial, shd);
-}
-
-// ce_fwd_regs_kernel (C <= 32)
-template <int Q>
-__global__ __launch_bounds__(CE_THREADS) void ce_ex_fwd_regs_kernel(const float* __restrict__ z,
-                                                                    const long long* __restrict__ tgt,
-                                                                    const float* __restrict__ weight, long long ignore,
-                                                                    double* __restrict__ partial,
-                                                                    long long* __restrict__ amax, long long P, int HW,
-                                                                    int C, long long sb, long long sc, long long sp) {
-  __shared__ double shd[4];
-  double num = 0.0, den = 0.0;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long long)gridDim.x * blockDim.x) {
-    const long long b = i / HW, hw = i - b * HW;
-    const float* r = z + b * sb + hw * sp;
-    float v[4 * Q];
-#pragma unroll
-    for (int c = 0; c < 4 * Q; ++c) v[c] = c < C ? r[c * sc] : 0.f;
-    const long long t = tgt[i];
-    float m = v[0];
-    int am = 0;
-#pragma unroll
-    for (int c = 1; c < 4 * Q; ++c)
-      if (c < C && v[c] > m) { m = v[c]; am = c; }  // first maximum wins, like torch.argmax on ties
-    if (amax != nullptr) amax[i] = am;
-    if (!ce_ex_counts(t, C, ignore, num)) continue;
-    float s = 0.f, zt = 0.f;
-#pragma unroll
-    for (int c = 0; c < 4 * Q; ++c) {
-      if (c < C) s += expf(v[c] - m);
-      if (c == t) zt = v[c];
-    }
-    ce_ex_add(num, den, logf(s) - (zt - m), weight, t);
-  }
-  ce_ex_store_partials(num, den, partial, shd);
 }
 
 // The (numerator, denominator) pairs summed in the fixed order of sum_finalize_kernel.
@@ -449,27 +224,16 @@ __global__ void ce_ex_finalize_kernel(const double* __restrict__ partial, int n,
   }
 }
 
-// The gradient of one pixel is dz_c = (softmax_c - 1[c == t]) * k + bad with k = w[t] * g, g = gout / den.  An ignored
-// pixel sets `zero`, and the kernels then store 0.0f in every lane they own (a select, never a product with g, which is
-// inf when every pixel is ignored).  bad: NaN for a target outside [0, C) that is not the ignore index - as the
-// forward: NaN, never a silent 0 - and such a target never indexes w.
-__device__ __forceinline__ float ce_ex_scale(long long t, int C, float g, const float* __restrict__ w, long long ignore,
-                                             float& bad, bool& zero) {
-  zero = t == ignore;
-  const bool oob = t < 0 || t >= C;
-  bad = (oob && !zero) ? __int_as_float(0x7fc00000) : 0.f;
-  return (!oob && w != nullptr) ? w[t] * g : g;
-}
-
-// ce_bwd_kernel
-__global__ __launch_bounds__(CE_THREADS) void ce_ex_bwd_kernel(const float* __restrict__ z,
-                                                               const long long* __restrict__ tgt,
-                                                               const float* __restrict__ weight, long long ignore,
-                                                               const float* __restrict__ stats,
-                                                               const float* __restrict__ gout, float* __restrict__ dz,
-                                                               long long P, int HW, int C, long long sb, long long sc,
-                                                               long long sp, long long dsb, long long dsc, long long dsp) {
-  const float g = gout[0] / stats[0];
+// dz = (softmax(z) - onehot(y)) * k + bad (see ce_scale), written with its own strides.  The softmax is
+// recomputed from the logits (max-subtracted, see above); nothing but the denominator is saved by the forward pass.
+template <bool EX>
+__global__ __launch_bounds__(CE_THREADS) void ce_bwd_kernel(const float* __restrict__ z,
+                                                            const long long* __restrict__ tgt,
+                                                            const float* __restrict__ gout, float* __restrict__ dz,
+                                                            long long P, int HW, int C, long long sb, long long sc,
+                                                            long long sp, long long dsb, long long dsc, long long dsp,
+                                                            CeEx<EX> ex) {
+  const float g = ce_grad_unit<EX>(gout, P, ex);
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long long)gridDim.x * blockDim.x) {
     const long long b = i / HW, hw = i - b * HW;
     const long long off = b * sb + hw * sp, doff = b * dsb + hw * dsp;
@@ -481,21 +245,23 @@ __global__ __launch_bounds__(CE_THREADS) void ce_ex_bwd_kernel(const float* __re
     const long long t = tgt[i];
     float bad;
     bool zero;
-    const float k = ce_ex_scale(t, C, g, weight, ignore, bad, zero);
-    for (int c = 0; c < C; ++c)
-      dz[doff + c * dsc] = zero ? 0.f : (expf(z[off + c * sc] - m) * inv - (c == t ? 1.f : 0.f)) * k + bad;
+    const float k = ce_scale<EX>(t, C, g, ex, bad, zero);
+    for (int c = 0; c < C; ++c)  // "EX &&": the plain variant's `zero` is gone before the loop is laid out
+      dz[doff + c * dsc] = (EX && zero) ? 0.f : (expf(z[off + c * sc] - m) * inv - (c == t ? 1.f : 0.f)) * k + bad;
   }
 }
 
-// ce_bwd_nhwc_kernel: NHWC rows of ld >= ceil4(C) floats, of which the first ceil4(C) are written
-__global__ __launch_bounds__(CE_THREADS) void ce_ex_bwd_nhwc_kernel(const float* __restrict__ z,
-                                                                    const long long* __restrict__ tgt,
-                                                                    const float* __restrict__ weight, long long ignore,
-                                                                    const float* __restrict__ stats,
-                                                                    const float* __restrict__ gout,
-                                                                    float* __restrict__ dz, long long P, int HW, int C,
-                                                                    long long sb, long long sc, long long sp, int ld) {
-  const float g = gout[0] / stats[0];
+// The same gradient, channel-contiguous (NHWC rows of ld >= ceil4(C) floats, of which the first ceil4(C) are written):
+// one thread per (pixel, channel quad), so a wave writes 1 KB of CONTIGUOUS gradient (one thread per pixel left every
+// store instruction touching 64 lanes x 16 bytes at an 80-byte stride: 2-4x slower than the NCHW form).  The softmax
+// statistics of a pixel are recomputed by its Q = ceil(C/4) threads (reads hit L1; ~2*C expf each).
+template <bool EX>
+__global__ __launch_bounds__(CE_THREADS) void ce_bwd_nhwc_kernel(const float* __restrict__ z,
+                                                                 const long long* __restrict__ tgt,
+                                                                 const float* __restrict__ gout, float* __restrict__ dz,
+                                                                 long long P, int HW, int C, long long sb, long long sc,
+                                                                 long long sp, int ld, CeEx<EX> ex) {
+  const float g = ce_grad_unit<EX>(gout, P, ex);
   const int Q = (C + 3) >> 2;
   const long long total = P * Q;
   for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
@@ -511,7 +277,7 @@ __global__ __launch_bounds__(CE_THREADS) void ce_ex_bwd_nhwc_kernel(const float*
     const long long t = tgt[i];
     float bad;
     bool zero;
-    const float k = ce_ex_scale(t, C, g, weight, ignore, bad, zero);
+    const float k = ce_scale<EX>(t, C, g, ex, bad, zero);
     f32x4 v;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -522,18 +288,20 @@ __global__ __launch_bounds__(CE_THREADS) void ce_ex_bwd_nhwc_kernel(const float*
   }
 }
 
-// ce_bwd_nhwc_rows_kernel: rows of exactly Q = ceil(C/4) quads, turned through LDS
-template <int Q>
-__global__ __launch_bounds__(256) void ce_ex_bwd_nhwc_rows_kernel(const float* __restrict__ z,
-                                                                  const long long* __restrict__ tgt,
-                                                                  const float* __restrict__ weight, long long ignore,
-                                                                  const float* __restrict__ stats,
-                                                                  const float* __restrict__ gout, float* __restrict__ dz,
-                                                                  long long P, int HW, int C, long long sb, long long sc,
-                                                                  long long sp) {
+// The same gradient when the NHWC rows are exactly the Q = ceil(C/4) quads (ld == 4*Q, the layout
+// ops._CrossEntropy.backward allocates): one thread per PIXEL - logits read once, coalesced along the pixel axis of
+// each channel plane, softmax evaluated once - and the wave's 64 finished rows (64*ld contiguous floats) turned
+// through LDS so every store instruction writes 1 KB of consecutive gradient.  138 -> ~60 us for 32x19x128x256 on
+// MI355X (the quad-per-thread form above re-reads the pixel's logits and re-evaluates 2*C expf in each of its Q threads).
+template <int Q, bool EX>
+__global__ __launch_bounds__(256) void ce_bwd_nhwc_rows_kernel(const float* __restrict__ z,
+                                                               const long long* __restrict__ tgt,
+                                                               const float* __restrict__ gout, float* __restrict__ dz,
+                                                               long long P, int HW, int C, long long sb, long long sc,
+                                                               long long sp, CeEx<EX> ex) {
   __shared__ f32x4 sm[4][64 * Q];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const float g = gout[0] / stats[0];
+  const float g = ce_grad_unit<EX>(gout, P, ex);
   for (long long wg0 = (long long)blockIdx.x * 256; wg0 < P; wg0 += (long long)gridDim.x * 256) {  // uniform trip count
     const long long base = wg0 + wave * 64, i = base + lane;
     if (i < P) {
@@ -555,7 +323,7 @@ __global__ __launch_bounds__(256) void ce_ex_bwd_nhwc_rows_kernel(const float* _
       const long long t = tgt[i];
       float bad;
       bool zero;
-      const float k = ce_ex_scale(t, C, g, weight, ignore, bad, zero);
+      const float k = ce_scale<EX>(t, C, g, ex, bad, zero);
 #pragma unroll
       for (int q = 0; q < Q; ++q) {
         f32x4 o;
@@ -581,23 +349,22 @@ __global__ __launch_bounds__(256) void ce_ex_bwd_nhwc_rows_kernel(const float* _
   }
 }
 
-// (numerator, denominator) per block
-extern "C" long long vmtl_ce_ex_workspace_bytes(long long P) { return 2 * (long long)ce_blocks(P) * (long long)sizeof(double); }
+// ------------------------------------------------------------------ cross entropy: launchers and entry points
+static inline int ce_blocks(long long P) {
+  long long nb = cdivll(P, CE_THREADS);
+  if (nb > 2048) nb = 2048;
+  if (nb < 1) nb = 1;
+  return (int)nb;
+}
 
-// weight = C floats or null (all ones), ignore_index = VMTL_NO_IGNORE for none, argmax = null or the prediction output.
-// Writes loss and stats (2 floats); workspace: vmtl_ce_ex_workspace_bytes(P) bytes, 8-byte aligned.
-extern "C" int vmtl_ce_fwd_ex(const float* logits, const long long* target, const float* weight, long long ignore_index,
-                              float* loss, float* stats, void* workspace, long long* argmax, int B, int HW, int C,
-                              long long sb, long long sc, long long sp, void* stream) {
-  VMTL_ENTER();
-  if (!logits || !target || !loss || !stats || !workspace || B <= 0 || HW <= 0 || C <= 0) return VMTL_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const long long P = (long long)B * HW;
+// The per-block partials of the loss into `partial` (ce_blocks(P) entries): logits in registers for C <= 32.
+template <bool EX>
+static void ce_fwd_launch(const float* logits, const long long* target, CeEx<EX> ex, double* partial, long long* amax,
+                          long long P, int HW, int C, long long sb, long long sc, long long sp, hipStream_t st) {
   const int nblk = ce_blocks(P);
-  double* partial = (double*)workspace;
-#define CEF(QV)                                                                                                     \
-  hipLaunchKernelGGL((ce_ex_fwd_regs_kernel<QV>), dim3(nblk), dim3(CE_THREADS), 0, st, logits, target, weight, ignore_index, \
-                     partial, argmax, P, HW, C, sb, sc, sp)
+#define CEF(QV)                                                                                                    \
+  hipLaunchKernelGGL((ce_fwd_regs_kernel<QV, EX>), dim3(nblk), dim3(CE_THREADS), 0, st, logits, target, ex, partial, \
+                     amax, P, HW, C, sb, sc, sp)
   switch (C <= 32 ? (C + 3) >> 2 : 0) {
     case 1: CEF(1); break;
     case 2: CEF(2); break;
@@ -608,29 +375,34 @@ extern "C" int vmtl_ce_fwd_ex(const float* logits, const long long* target, cons
     case 7: CEF(7); break;
     case 8: CEF(8); break;
     default:
-      hipLaunchKernelGGL(ce_ex_fwd_kernel, dim3(nblk), dim3(CE_THREADS), 0, st, logits, target, weight, ignore_index,
-                         partial, argmax, P, HW, C, sb, sc, sp);
+      hipLaunchKernelGGL(ce_fwd_kernel<EX>, dim3(nblk), dim3(CE_THREADS), 0, st, logits, target, ex, partial, amax, P, HW,
+                         C, sb, sc, sp);
   }
 #undef CEF
-  hipLaunchKernelGGL(ce_ex_finalize_kernel, dim3(1), dim3(256), 0, st, partial, nblk, loss, stats);
-  return vmtl_check_launch();
 }
 
-// dz_c = w[t] (softmax_c - 1[c == t]) gout / stats[0], 0.0f in every written lane of an ignored pixel; stats as
-// vmtl_ce_fwd_ex left it.  The three layouts of vmtl_ce_bwd_strided, chosen by the same tests, writing the same lanes.
-extern "C" int vmtl_ce_bwd_ex(const float* logits, const long long* target, const float* weight, long long ignore_index,
-                              const float* stats, const float* grad_out, float* dlogits, int B, int HW, int C,
-                              long long sb, long long sc, long long sp, long long dsb, long long dsc, long long dsp,
-                              void* stream) {
-  VMTL_ENTER();
-  if (!logits || !target || !stats || !grad_out || !dlogits || B <= 0 || HW <= 0 || C <= 0) return VMTL_ERR_ARG;
-  const long long P = (long long)B * HW;
+template <bool EX>
+static void ce_bwd_launch_strided(const float* logits, const long long* target, const float* grad_out, float* dlogits,
+                                  CeEx<EX> ex, long long P, int HW, int C, long long sb, long long sc, long long sp,
+                                  long long dsb, long long dsc, long long dsp, hipStream_t st) {
+  hipLaunchKernelGGL(ce_bwd_kernel<EX>, dim3(ce_blocks(P)), dim3(CE_THREADS), 0, st, logits, target, grad_out, dlogits, P,
+                     HW, C, sb, sc, sp, dsb, dsc, dsp, ex);
+}
+
+// Element (b, c, hw) of the gradient goes to dlogits[b*dsb + c*dsc + hw*dsp].  With (HW*ld, 1, ld) the gradient lands
+// in the NHWC storage the head's data-gradient conv reads (one 76-byte run per pixel) and the NCHW -> NHWC relayout of
+// an 80 MB tensor disappears from the step.  Three layouts: rows of exactly ceil4(C) floats (turned through LDS), NHWC
+// with a wider ld (only the first ceil4(C) lanes are written), generic strides (C lanes).
+template <bool EX>
+static void ce_bwd_launch(const float* logits, const long long* target, const float* grad_out, float* dlogits,
+                          CeEx<EX> ex, long long P, int HW, int C, long long sb, long long sc, long long sp,
+                          long long dsb, long long dsc, long long dsp, hipStream_t st) {
   if (dsc == 1 && dsp == ((C + 3) & ~3) && dsp <= 32 && dsb == dsp * HW) {
     long long nb = cdivll(P, 256);
     if (nb > 8192) nb = 8192;
-#define CALL(QV)                                                                                                   \
-  hipLaunchKernelGGL((ce_ex_bwd_nhwc_rows_kernel<QV>), dim3((int)nb), dim3(256), 0, (hipStream_t)stream, logits, target, \
-                     weight, ignore_index, stats, grad_out, dlogits, P, HW, C, sb, sc, sp)
+#define CALL(QV)                                                                                                 \
+  hipLaunchKernelGGL((ce_bwd_nhwc_rows_kernel<QV, EX>), dim3((int)nb), dim3(256), 0, st, logits, target, grad_out, \
+                     dlogits, P, HW, C, sb, sc, sp, ex)
     switch ((int)dsp >> 2) {
       case 1: CALL(1); break;
       case 2: CALL(2); break;
@@ -642,32 +414,125 @@ extern "C" int vmtl_ce_bwd_ex(const float* logits, const long long* target, cons
       default: CALL(8); break;
     }
 #undef CALL
-    return vmtl_check_launch();
-  }
-  if (dsc == 1 && (dsp & 3) == 0 && dsp >= ((C + 3) & ~3) && dsb == dsp * HW) {
+  } else if (dsc == 1 && (dsp & 3) == 0 && dsp >= ((C + 3) & ~3) && dsb == dsp * HW) {
     long long nb = cdivll(P * ((C + 3) >> 2), CE_THREADS);
     if (nb > 8192) nb = 8192;
-    hipLaunchKernelGGL(ce_ex_bwd_nhwc_kernel, dim3((int)nb), dim3(CE_THREADS), 0, (hipStream_t)stream, logits, target,
-                       weight, ignore_index, stats, grad_out, dlogits, P, HW, C, sb, sc, sp, (int)dsp);
-    return vmtl_check_launch();
+    hipLaunchKernelGGL(ce_bwd_nhwc_kernel<EX>, dim3((int)nb), dim3(CE_THREADS), 0, st, logits, target, grad_out, dlogits,
+                       P, HW, C, sb, sc, sp, (int)dsp, ex);
+  } else {
+    ce_bwd_launch_strided<EX>(logits, target, grad_out, dlogits, ex, P, HW, C, sb, sc, sp, dsb, dsc, dsp, st);
   }
-  hipLaunchKernelGGL(ce_ex_bwd_kernel, dim3(ce_blocks(P)), dim3(CE_THREADS), 0, (hipStream_t)stream, logits, target, weight,
-                     ignore_index, stats, grad_out, dlogits, P, HW, C, sb, sc, sp, dsb, dsc, dsp);
+}
+
+extern "C" long long vmtl_ce_workspace_bytes(long long P) { return ((long long)ce_blocks(P) + 1) * (long long)sizeof(double); }
+
+// (numerator, denominator) per block
+extern "C" long long vmtl_ce_ex_workspace_bytes(long long P) { return 2 * (long long)ce_blocks(P) * (long long)sizeof(double); }
+
+// workspace: vmtl_ce_workspace_bytes(P) bytes, 8-byte aligned (per-block partial sums).  A target outside [0, C)
+// makes the loss NaN.
+static int ce_fwd_impl(const float* logits, const long long* target, float* loss, void* workspace, long long* amax,
+                       int B, int HW, int C, long long sb, long long sc, long long sp, void* stream) {
+  if (!logits || !target || !loss || !workspace || B <= 0 || HW <= 0 || C <= 0) return VMTL_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const long long P = (long long)B * HW;
+  double* partial = (double*)workspace;
+  ce_fwd_launch<false>(logits, target, {}, partial, amax, P, HW, C, sb, sc, sp, st);
+  hipLaunchKernelGGL(sum_finalize_kernel, dim3(1), dim3(256), 0, st, partial, ce_blocks(P), 1.0 / (double)P, loss,
+                     (const int*)nullptr);
+  return vmtl_check_launch();
+}
+
+extern "C" int vmtl_ce_fwd(const float* logits, const long long* target, float* loss, void* workspace, int B, int HW,
+                           int C, long long sb, long long sc, long long sp, void* stream) {
+  VMTL_ENTER();
+  return ce_fwd_impl(logits, target, loss, workspace, nullptr, B, HW, C, sb, sc, sp, stream);
+}
+
+// vmtl_ce_fwd that also emits argmax_c logits (= the segmentation prediction of lit_module.py:137-138): the loss
+// pass finds every pixel's maximum anyway, so the prediction costs one 8-byte store instead of a second sweep
+// over the logits in its own launch
+extern "C" int vmtl_ce_fwd_argmax(const float* logits, const long long* target, float* loss, void* workspace,
+                                  long long* argmax, int B, int HW, int C, long long sb, long long sc, long long sp,
+                                  void* stream) {
+  VMTL_ENTER();
+  if (!argmax) return VMTL_ERR_ARG;
+  return ce_fwd_impl(logits, target, loss, workspace, argmax, B, HW, C, sb, sc, sp, stream);
+}
+
+// weight = C floats or null (all ones), ignore_index = VMTL_NO_IGNORE for none, argmax = null or the prediction output.
+// Writes loss and stats (2 floats); workspace: vmtl_ce_ex_workspace_bytes(P) bytes, 8-byte aligned.
+extern "C" int vmtl_ce_fwd_ex(const float* logits, const long long* target, const float* weight, long long ignore_index,
+                              float* loss, float* stats, void* workspace, long long* argmax, int B, int HW, int C,
+                              long long sb, long long sc, long long sp, void* stream) {
+  VMTL_ENTER();
+  if (!logits || !target || !loss || !stats || !workspace || B <= 0 || HW <= 0 || C <= 0) return VMTL_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const long long P = (long long)B * HW;
+  double* partial = (double*)workspace;
+  ce_fwd_launch<true>(logits, target, {weight, ignore_index, nullptr}, partial, argmax, P, HW, C, sb, sc, sp, st);
+  hipLaunchKernelGGL(ce_ex_finalize_kernel, dim3(1), dim3(256), 0, st, partial, ce_blocks(P), loss, stats);
+  return vmtl_check_launch();
+}
+
+// The gradient with the strides of the logits (generic-stride kernel, C lanes per pixel, whatever the strides are).
+extern "C" int vmtl_ce_bwd(const float* logits, const long long* target, const float* grad_out, float* dlogits, int B,
+                           int HW, int C, long long sb, long long sc, long long sp, void* stream) {
+  VMTL_ENTER();
+  if (!logits || !target || !grad_out || !dlogits || B <= 0 || HW <= 0 || C <= 0) return VMTL_ERR_ARG;
+  ce_bwd_launch_strided<false>(logits, target, grad_out, dlogits, {}, (long long)B * HW, HW, C, sb, sc, sp, sb, sc, sp,
+                               (hipStream_t)stream);
+  return vmtl_check_launch();
+}
+
+// vmtl_ce_bwd with its own strides for dlogits (see ce_bwd_launch)
+extern "C" int vmtl_ce_bwd_strided(const float* logits, const long long* target, const float* grad_out, float* dlogits,
+                                   int B, int HW, int C, long long sb, long long sc, long long sp, long long dsb,
+                                   long long dsc, long long dsp, void* stream) {
+  VMTL_ENTER();
+  if (!logits || !target || !grad_out || !dlogits || B <= 0 || HW <= 0 || C <= 0) return VMTL_ERR_ARG;
+  ce_bwd_launch<false>(logits, target, grad_out, dlogits, {}, (long long)B * HW, HW, C, sb, sc, sp, dsb, dsc, dsp,
+                       (hipStream_t)stream);
+  return vmtl_check_launch();
+}
+
+// dz_c = w[t] (softmax_c - 1[c == t]) gout / stats[0], 0.0f in every written lane of an ignored pixel; stats as
+// vmtl_ce_fwd_ex left it.  The three layouts of vmtl_ce_bwd_strided, chosen by the same tests, writing the same lanes.
+extern "C" int vmtl_ce_bwd_ex(const float* logits, const long long* target, const float* weight, long long ignore_index,
+                              const float* stats, const float* grad_out, float* dlogits, int B, int HW, int C,
+                              long long sb, long long sc, long long sp, long long dsb, long long dsc, long long dsp,
+                              void* stream) {
+  VMTL_ENTER();
+  if (!logits || !target || !stats || !grad_out || !dlogits || B <= 0 || HW <= 0 || C <= 0) return VMTL_ERR_ARG;
+  ce_bwd_launch<true>(logits, target, grad_out, dlogits, {weight, ignore_index, stats}, (long long)B * HW, HW, C, sb, sc,
+                      sp, dsb, dsc, dsp, (hipStream_t)stream);
   return vmtl_check_launch();
 }
 
 // ------------------------------------------------------------------ SILog
 #define SL_BLOCKS_MAX 1024
 
+// Which pixels count: those with target > min_depth, or those of the caller's uint8 mask (reference losses.py:29-31
+// with `mask` given; min_depth is then not applied).  The kernels take either as their `valid` operand; partials,
+// finalize and the closed-form backward are the same, and with mask == (target > min_depth) the two agree bit for bit.
+struct SlAboveMinDepth {
+  float min_depth;
+  __device__ __forceinline__ bool operator()(const float* __restrict__ tgt, long long i) const { return tgt[i] > min_depth; }
+};
+struct SlMasked {
+  const unsigned char* __restrict__ mask;
+  __device__ __forceinline__ bool operator()(const float* __restrict__, long long i) const { return mask[i] != 0; }
+};
+
+template <class Valid>
 __global__ __launch_bounds__(256) void silog_fwd_kernel(const float* __restrict__ pred,
-                                                        const float* __restrict__ tgt, float min_depth, long long P,
+                                                        const float* __restrict__ tgt, Valid valid, long long P,
                                                         double* __restrict__ partial) {
   __shared__ double shd[4];
   double n = 0.0, s1 = 0.0, s2 = 0.0;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long long)gridDim.x * blockDim.x) {
-    const float t = tgt[i];
-    if (t > min_depth) {
-      const float g = logf(pred[i]) - logf(t);
+    if (valid(tgt, i)) {
+      const float g = logf(pred[i]) - logf(tgt[i]);
       n += 1.0;
       s1 += (double)g;
       s2 += (double)g * (double)g;
@@ -707,19 +572,19 @@ __global__ void silog_finalize_kernel(const double* __restrict__ partial, int nb
 }
 
 // dL/dpred_i = gout * (5/sqrt(Dg)) * (2 (g_i - mu)/(N-1) + 0.3 mu / N) / pred_i   on valid pixels, else 0
+template <class Valid>
 __global__ __launch_bounds__(256) void silog_bwd_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
                                                         const float* __restrict__ stats,
-                                                        const float* __restrict__ gout, float min_depth, long long P,
+                                                        const float* __restrict__ gout, Valid valid, long long P,
                                                         float* __restrict__ dpred) {
   const float n = stats[0], mu = stats[1], dg = stats[2];
   const float k = gout[0] * 5.f / sqrtf(dg);
   const float a = 2.f / (n - 1.f), b = 0.3f * mu / n;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long long)gridDim.x * blockDim.x) {
-    const float t = tgt[i];
     float r = 0.f;
-    if (t > min_depth) {
+    if (valid(tgt, i)) {
       const float p = pred[i];
-      const float g = logf(p) - logf(t);
+      const float g = logf(p) - logf(tgt[i]);
       r = k * (a * (g - mu) + b) / p;
     }
     dpred[i] = r;
@@ -735,91 +600,50 @@ static inline int sl_blocks(long long P) {
 
 extern "C" long long vmtl_silog_workspace_bytes(long long P) { return (long long)sl_blocks(P) * 3 * sizeof(double); }
 
+template <class Valid>
+static int silog_fwd_launch(const float* pred, const float* target, Valid valid, float* loss, float* stats,
+                            void* workspace, long long P, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const int nblk = sl_blocks(P);
+  hipLaunchKernelGGL(silog_fwd_kernel<Valid>, dim3(nblk), dim3(256), 0, st, pred, target, valid, P, (double*)workspace);
+  hipLaunchKernelGGL(silog_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)workspace, nblk, loss, stats);
+  return vmtl_check_launch();
+}
+
+template <class Valid>
+static int silog_bwd_launch(const float* pred, const float* target, Valid valid, const float* stats,
+                            const float* grad_out, float* dpred, long long P, void* stream) {
+  hipLaunchKernelGGL(silog_bwd_kernel<Valid>, dim3(sl_blocks(P)), dim3(256), 0, (hipStream_t)stream, pred, target, stats,
+                     grad_out, valid, P, dpred);
+  return vmtl_check_launch();
+}
+
 extern "C" int vmtl_silog_fwd(const float* pred, const float* target, float min_depth, float* loss, float* stats,
                               void* workspace, long long P, void* stream) {
   VMTL_ENTER();
   if (!pred || !target || !loss || !stats || !workspace || P <= 0) return VMTL_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const int nblk = sl_blocks(P);
-  hipLaunchKernelGGL(silog_fwd_kernel, dim3(nblk), dim3(256), 0, st, pred, target, min_depth, P, (double*)workspace);
-  hipLaunchKernelGGL(silog_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)workspace, nblk, loss, stats);
-  return vmtl_check_launch();
+  return silog_fwd_launch(pred, target, SlAboveMinDepth{min_depth}, loss, stats, workspace, P, stream);
 }
 
 extern "C" int vmtl_silog_bwd(const float* pred, const float* target, const float* stats, const float* grad_out,
                               float min_depth, float* dpred, long long P, void* stream) {
   VMTL_ENTER();
   if (!pred || !target || !stats || !grad_out || !dpred || P <= 0) return VMTL_ERR_ARG;
-  hipLaunchKernelGGL(silog_bwd_kernel, dim3(sl_blocks(P)), dim3(256), 0, (hipStream_t)stream, pred, target, stats,
-                     grad_out, min_depth, P, dpred);
-  return vmtl_check_launch();
-}
-
-// SILog over the pixels of the caller's uint8 mask (reference losses.py:29-31 with `mask` given; min_depth is then not
-// applied) instead of those with target > min_depth: silog_fwd_kernel / silog_bwd_kernel with that one test exchanged,
-// the same partials, finalize and closed-form backward.
-__global__ __launch_bounds__(256) void silog_mask_fwd_kernel(const float* __restrict__ pred,
-                                                             const float* __restrict__ tgt,
-                                                             const unsigned char* __restrict__ mask, long long P,
-                                                             double* __restrict__ partial) {
-  __shared__ double shd[4];
-  double n = 0.0, s1 = 0.0, s2 = 0.0;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long long)gridDim.x * blockDim.x) {
-    if (mask[i] != 0) {
-      const float g = logf(pred[i]) - logf(tgt[i]);
-      n += 1.0;
-      s1 += (double)g;
-      s2 += (double)g * (double)g;
-    }
-  }
-  const double bn = block_sum_d(n, shd);
-  const double b1 = block_sum_d(s1, shd);
-  const double b2 = block_sum_d(s2, shd);
-  if (threadIdx.x == 0) {
-    partial[blockIdx.x * 3 + 0] = bn;
-    partial[blockIdx.x * 3 + 1] = b1;
-    partial[blockIdx.x * 3 + 2] = b2;
-  }
-}
-
-__global__ __launch_bounds__(256) void silog_mask_bwd_kernel(const float* __restrict__ pred,
-                                                             const float* __restrict__ tgt,
-                                                             const unsigned char* __restrict__ mask,
-                                                             const float* __restrict__ stats,
-                                                             const float* __restrict__ gout, long long P,
-                                                             float* __restrict__ dpred) {
-  const float n = stats[0], mu = stats[1], dg = stats[2];
-  const float k = gout[0] * 5.f / sqrtf(dg);
-  const float a = 2.f / (n - 1.f), b = 0.3f * mu / n;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long long)gridDim.x * blockDim.x) {
-    float r = 0.f;
-    if (mask[i] != 0) {
-      const float p = pred[i];
-      const float g = logf(p) - logf(tgt[i]);
-      r = k * (a * (g - mu) + b) / p;
-    }
-    dpred[i] = r;
-  }
+  return silog_bwd_launch(pred, target, SlAboveMinDepth{min_depth}, stats, grad_out, dpred, P, stream);
 }
 
 extern "C" int vmtl_silog_fwd_mask(const float* pred, const float* target, const unsigned char* mask, float* loss,
                                    float* stats, void* workspace, long long P, void* stream) {
   VMTL_ENTER();
   if (!pred || !target || !mask || !loss || !stats || !workspace || P <= 0) return VMTL_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const int nblk = sl_blocks(P);
-  hipLaunchKernelGGL(silog_mask_fwd_kernel, dim3(nblk), dim3(256), 0, st, pred, target, mask, P, (double*)workspace);
-  hipLaunchKernelGGL(silog_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)workspace, nblk, loss, stats);
-  return vmtl_check_launch();
+  return silog_fwd_launch(pred, target, SlMasked{mask}, loss, stats, workspace, P, stream);
 }
 
 extern "C" int vmtl_silog_bwd_mask(const float* pred, const float* target, const unsigned char* mask, const float* stats,
                                    const float* grad_out, float* dpred, long long P, void* stream) {
   VMTL_ENTER();
   if (!pred || !target || !mask || !stats || !grad_out || !dpred || P <= 0) return VMTL_ERR_ARG;
-  hipLaunchKernelGGL(silog_mask_bwd_kernel, dim3(sl_blocks(P)), dim3(256), 0, (hipStream_t)stream, pred, target, mask,
-                     stats, grad_out, P, dpred);
-  return vmtl_check_launch();
+  return silog_bwd_launch(pred, target, SlMasked{mask}, stats, grad_out, dpred, P, stream);
 }
 
 // ------------------------------------------------------------------ L1 (mean absolute error)

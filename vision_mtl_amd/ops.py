@@ -3012,49 +3012,6 @@ def argmax_channels(logits):
 
 
 # ----------------------------------------------------------------------------- losses
-class _CrossEntropy(torch.autograd.Function):
-    """mean_{b,h,w} -log_softmax(logits)[target]; logits (B,C,H,W) NCHW-contiguous."""
-
-    @staticmethod
-    def forward(ctx, logits, target, want_argmax=False):
-        logits = _req(logits, "logits")
-        if target.dtype != torch.int64:
-            raise TypeError("cross_entropy: target must be int64 class indices")
-        target = target.contiguous()
-        B, C, H, W = logits.shape
-        if tuple(target.shape) != (B, H, W):
-            raise ValueError(f"cross_entropy: target shape {tuple(target.shape)} does not match logits {(B, H, W)}")
-        P = B * H * W
-        loss = _empty((), logits)
-        ws = torch.empty((lib().raw("vmtl_ce_workspace_bytes")(P) // 8,), dtype=torch.float64, device=logits.device)
-        ctx.save_for_backward(logits, target)
-        if want_argmax:
-            pred = torch.empty((B, H, W), dtype=torch.int64, device=logits.device)
-            _k("vmtl_ce_fwd_argmax", logits=logits, target=target, loss=loss, workspace=ws, argmax=pred, B=B, HW=H * W,
-               C=C, sb=C * H * W, sc=H * W, sp=1)
-            ctx.mark_non_differentiable(pred)
-            return loss, pred
-        _k("vmtl_ce_fwd", logits=logits, target=target, loss=loss, workspace=ws, B=B, HW=H * W, C=C,
-           sb=C * H * W, sc=H * W, sp=1)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g, _gpred=None):
-        logits, target = ctx.saved_tensors
-        B, C, H, W = logits.shape
-        g = _req(g, "grad_output")
-        # the gradient is laid out NHWC with room for one more head ([B][H][W][ceil4(C+1)]) and returned as its
-        # (B,C,H,W) view: a head conv that consumes it (ops.decoder_tail) takes the storage as its dY operand without
-        # the NCHW -> NHWC relayout of this 80 MB tensor; any other consumer sees an ordinary strided tensor
-        ld = ceil4(C + 1)
-        st = _empty((B, H, W, ld), logits)
-        _k("vmtl_ce_bwd_strided", logits=logits, target=target, grad_out=g, dlogits=st, B=B, HW=H * W, C=C,
-           sb=C * H * W, sc=H * W, sp=1, dsb=H * W * ld, dsc=1, dsp=ld)
-        dl = st[..., :C].permute(0, 3, 1, 2)
-        dl._vmtl_nhwc = st
-        return dl, None, None
-
-
 NO_IGNORE = -(1 << 63)  # include/vmtl.h VMTL_NO_IGNORE: the ignore_index of "nothing to ignore"
 
 
@@ -3071,13 +3028,16 @@ def _ce_weight(weight, logits):
     return weight
 
 
-class _CrossEntropyEx(torch.autograd.Function):
-    """sum_valid w[t] nll / sum_valid w[t] with valid = (target != ignore_index): torch's `weight` / `ignore_index`
-    (reduction "mean").  The denominator depends on the targets: the forward leaves it in `stats` on the device and the
-    backward reads it there, so the node never waits for the host.  weight gets no gradient."""
+class _CrossEntropy(torch.autograd.Function):
+    """mean_{b,h,w} -log_softmax(logits)[target]; logits (B,C,H,W) NCHW-contiguous.
+
+    ignore_index None (and then no weight) is that plain mean.  An int (NO_IGNORE for none) selects torch's `weight` /
+    `ignore_index` form (reduction "mean"): sum_valid w[t] nll / sum_valid w[t] with valid = (target != ignore_index).
+    Its denominator depends on the targets: the forward leaves it in `stats` on the device and the backward reads it
+    there, so the node never waits for the host.  weight gets no gradient."""
 
     @staticmethod
-    def forward(ctx, logits, target, weight, ignore_index, want_argmax=False):
+    def forward(ctx, logits, target, weight, ignore_index, want_argmax):
         logits = _req(logits, "logits")
         if target.dtype != torch.int64:
             raise TypeError("cross_entropy: target must be int64 class indices")
@@ -3087,12 +3047,22 @@ class _CrossEntropyEx(torch.autograd.Function):
             raise ValueError(f"cross_entropy: target shape {tuple(target.shape)} does not match logits {(B, H, W)}")
         weight = _ce_weight(weight, logits)
         P = B * H * W
-        loss, stats = _empty((), logits), _empty((2,), logits)
-        ws = torch.empty((lib().raw("vmtl_ce_ex_workspace_bytes")(P) // 8,), dtype=torch.float64, device=logits.device)
+        dims = dict(B=B, HW=H * W, C=C, sb=C * H * W, sc=H * W, sp=1)
+        loss = _empty((), logits)
+        ws_bytes = lib().raw("vmtl_ce_workspace_bytes" if ignore_index is None else "vmtl_ce_ex_workspace_bytes")(P)
+        ws = torch.empty((ws_bytes // 8,), dtype=torch.float64, device=logits.device)
         pred = torch.empty((B, H, W), dtype=torch.int64, device=logits.device) if want_argmax else None
-        _k("vmtl_ce_fwd_ex", logits=logits, target=target, weight=weight, ignore_index=ignore_index, loss=loss,
-           stats=stats, workspace=ws, argmax=pred, B=B, HW=H * W, C=C, sb=C * H * W, sc=H * W, sp=1)
-        ctx.save_for_backward(logits, target, stats, *(() if weight is None else (weight,)))
+        if ignore_index is not None:
+            stats = _empty((2,), logits)
+            _k("vmtl_ce_fwd_ex", logits=logits, target=target, weight=weight, ignore_index=ignore_index, loss=loss,
+               stats=stats, workspace=ws, argmax=pred, **dims)
+            ctx.save_for_backward(logits, target, stats, *(() if weight is None else (weight,)))
+        else:
+            if want_argmax:
+                _k("vmtl_ce_fwd_argmax", logits=logits, target=target, loss=loss, workspace=ws, argmax=pred, **dims)
+            else:
+                _k("vmtl_ce_fwd", logits=logits, target=target, loss=loss, workspace=ws, **dims)
+            ctx.save_for_backward(logits, target)
         ctx.ignore_index = ignore_index
         if want_argmax:
             ctx.mark_non_differentiable(pred)
@@ -3101,22 +3071,29 @@ class _CrossEntropyEx(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g, _gpred=None):
-        logits, target, stats, *weight = ctx.saved_tensors
+        logits, target, *ex = ctx.saved_tensors  # ex: (stats[, weight]) of the weighted / ignoring form
         B, C, H, W = logits.shape
         g = _req(g, "grad_output")
-        ld = ceil4(C + 1)  # the layout of _CrossEntropy.backward: NHWC rows with room for one more head
+        # the gradient is laid out NHWC with room for one more head ([B][H][W][ceil4(C+1)]) and returned as its
+        # (B,C,H,W) view: a head conv that consumes it (ops.decoder_tail) takes the storage as its dY operand without
+        # the NCHW -> NHWC relayout of this 80 MB tensor; any other consumer sees an ordinary strided tensor
+        ld = ceil4(C + 1)
         st = _empty((B, H, W, ld), logits)
-        _k("vmtl_ce_bwd_ex", logits=logits, target=target, weight=weight[0] if weight else None,
-           ignore_index=ctx.ignore_index, stats=stats, grad_out=g, dlogits=st, B=B, HW=H * W, C=C, sb=C * H * W,
-           sc=H * W, sp=1, dsb=H * W * ld, dsc=1, dsp=ld)
+        dims = dict(B=B, HW=H * W, C=C, sb=C * H * W, sc=H * W, sp=1, dsb=H * W * ld, dsc=1, dsp=ld)
+        if ctx.ignore_index is None:
+            _k("vmtl_ce_bwd_strided", logits=logits, target=target, grad_out=g, dlogits=st, **dims)
+        else:
+            _k("vmtl_ce_bwd_ex", logits=logits, target=target, weight=ex[1] if len(ex) > 1 else None,
+               ignore_index=ctx.ignore_index, stats=ex[0], grad_out=g, dlogits=st, **dims)
         dl = st[..., :C].permute(0, 3, 1, 2)
         dl._vmtl_nhwc = st
         return dl, None, None, None, None
 
 
-def _ce_ignore(ignore_index):
+def _ce_ignore(weight, ignore_index):
+    """The node's ignore_index: None for the plain mean (nothing given), else an int (NO_IGNORE: weights only)."""
     if ignore_index is None:
-        return NO_IGNORE
+        return None if weight is None else NO_IGNORE
     if isinstance(ignore_index, bool) or not isinstance(ignore_index, int):
         raise TypeError(f"cross_entropy: ignore_index must be an int or None, got {ignore_index!r}")
     return ignore_index
@@ -3125,74 +3102,55 @@ def _ce_ignore(ignore_index):
 def cross_entropy(logits, target, weight=None, ignore_index=None):
     """torch.nn.functional.cross_entropy(logits, target) (mean); `weight` (C fp32 floats on the device) and
     `ignore_index` as torch's, except that the default ignores nothing: an unmapped label makes the loss NaN."""
-    if weight is None and ignore_index is None:
-        return _CrossEntropy.apply(logits, target, False)
-    return _CrossEntropyEx.apply(logits, target, weight, _ce_ignore(ignore_index), False)
+    return _CrossEntropy.apply(logits, target, weight, _ce_ignore(weight, ignore_index), False)
 
 
 def cross_entropy_with_argmax(logits, target, weight=None, ignore_index=None):
     """(loss, argmax over the class axis) from one pass over the logits (reference lit_module.py:123 + 137-138).  The
     prediction is written for every pixel, ignored or not."""
-    if weight is None and ignore_index is None:
-        return _CrossEntropy.apply(logits, target, True)
-    return _CrossEntropyEx.apply(logits, target, weight, _ce_ignore(ignore_index), True)
+    return _CrossEntropy.apply(logits, target, weight, _ce_ignore(weight, ignore_index), True)
 
 
 class _SILog(torch.autograd.Function):
-    """reference losses.py:29-36 on predictions in (0,1); pred and target hold the same number of elements."""
+    """reference losses.py:29-36 on predictions in (0,1); pred and target hold the same number of elements.  The valid
+    pixels are those with target > min_depth, or those of an explicit uint8 mask (losses.py:29-31 with `mask` given)."""
 
     @staticmethod
-    def forward(ctx, pred, target, min_depth):
+    def forward(ctx, pred, target, min_depth, mask):
         pred, target = _req(pred, "pred"), _req(target, "target")
         if pred.numel() != target.numel():
             raise ValueError("silog: pred and target must have the same number of elements")
         P = pred.numel()
         loss, stats = _empty((), pred), _empty((3,), pred)
         ws = torch.empty((lib().raw("vmtl_silog_workspace_bytes")(P) // 8,), dtype=torch.float64, device=pred.device)
-        _k("vmtl_silog_fwd", pred=pred, target=target, min_depth=min_depth, loss=loss, stats=stats, workspace=ws, P=P)
-        ctx.save_for_backward(pred, target, stats)
+        if mask is None:
+            _k("vmtl_silog_fwd", pred=pred, target=target, min_depth=min_depth, loss=loss, stats=stats, workspace=ws, P=P)
+            ctx.save_for_backward(pred, target, stats)
+        else:
+            _k("vmtl_silog_fwd_mask", pred=pred, target=target, mask=mask, loss=loss, stats=stats, workspace=ws, P=P)
+            ctx.save_for_backward(pred, target, stats, mask)
         ctx.min_depth = min_depth
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        pred, target, stats = ctx.saved_tensors
+        pred, target, stats, *mask = ctx.saved_tensors
         g = _req(g, "grad_output")
         dp = _empty(pred.shape, pred)
-        _k("vmtl_silog_bwd", pred=pred, target=target, stats=stats, grad_out=g, min_depth=ctx.min_depth, dpred=dp,
-           P=pred.numel())
-        return dp, None, None
-
-
-class _SILogMasked(torch.autograd.Function):
-    """_SILog over the pixels of an explicit uint8 mask (reference losses.py:29-31 with `mask` given)."""
-
-    @staticmethod
-    def forward(ctx, pred, target, mask):
-        pred, target = _req(pred, "pred"), _req(target, "target")
-        if pred.numel() != target.numel():
-            raise ValueError("silog: pred and target must have the same number of elements")
-        P = pred.numel()
-        loss, stats = _empty((), pred), _empty((3,), pred)
-        ws = torch.empty((lib().raw("vmtl_silog_workspace_bytes")(P) // 8,), dtype=torch.float64, device=pred.device)
-        _k("vmtl_silog_fwd_mask", pred=pred, target=target, mask=mask, loss=loss, stats=stats, workspace=ws, P=P)
-        ctx.save_for_backward(pred, target, mask, stats)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        pred, target, mask, stats = ctx.saved_tensors
-        g = _req(g, "grad_output")
-        dp = _empty(pred.shape, pred)
-        _k("vmtl_silog_bwd_mask", pred=pred, target=target, mask=mask, stats=stats, grad_out=g, dpred=dp, P=pred.numel())
-        return dp, None, None
+        if mask:
+            _k("vmtl_silog_bwd_mask", pred=pred, target=target, mask=mask[0], stats=stats, grad_out=g, dpred=dp,
+               P=pred.numel())
+        else:
+            _k("vmtl_silog_bwd", pred=pred, target=target, stats=stats, grad_out=g, min_depth=ctx.min_depth, dpred=dp,
+               P=pred.numel())
+        return dp, None, None, None
 
 
 def silog(pred, target, min_depth=1e-3, mask=None):
     """reference losses.py:14-36.  mask (bool or uint8, the shape of target): the valid pixels; min_depth is then not
     applied, as in the reference."""
     if mask is None:
-        return _SILog.apply(pred, target, float(min_depth))
+        return _SILog.apply(pred, target, float(min_depth), None)
     if mask.dtype not in (torch.bool, torch.uint8):
         raise TypeError(f"silog: mask must be bool or uint8, got {mask.dtype}")
     if tuple(mask.shape) != tuple(target.shape):
@@ -3200,7 +3158,7 @@ def silog(pred, target, min_depth=1e-3, mask=None):
     if not mask.is_cuda or mask.device != target.device:
         raise RuntimeError(f"silog: mask is on {mask.device}, the target on {target.device} (no CPU fallback)")
     mask = mask.contiguous()
-    return _SILogMasked.apply(pred, target, mask.view(torch.uint8) if mask.dtype == torch.bool else mask)
+    return _SILog.apply(pred, target, float(min_depth), mask.view(torch.uint8) if mask.dtype == torch.bool else mask)
 
 
 class _L1(torch.autograd.Function):
