@@ -557,6 +557,27 @@ int vmtl_ce_fwd_ex(const float* logits, const long long* target, const float* we
 int vmtl_ce_bwd_ex(const float* logits, const long long* target, const float* weight, long long ignore_index,
                    const float* stats, const float* grad_out, float* dlogits, int B, int HW, int C, long long sb,
                    long long sc, long long sp, long long dsb, long long dsc, long long dsp, void* stream);
+/* Online hard example mining (OHEM, bootstrapped cross entropy) on the weighted / ignoring cross entropy (ce_ohem.hip):
+ *   nll_i = -log softmax(z_i)[t_i] (unweighted; NaN for a valid pixel with a label outside [0, C) or non-finite logits,
+ *   which ranks as the hardest), K = min(min_kept_total, V) with V the number of valid pixels, kappa = the K-th largest
+ *   nll among the valid pixels, cut = min(nll_thresh, kappa); kept: valid and not (nll_i < cut), ties included.
+ *   loss = sum_kept w[t_i] nll_i / sum_kept w[t_i]  (NaN when V = 0).
+ * nll_thresh = -log(thresh) >= 0 for a probability threshold in (0, 1] (+inf: pure top-K); min_kept_total = min_kept * B
+ * >= 1.  weight, ignore_index, argmax as vmtl_ce_fwd_ex.  The selection is exact (a three-round radix select over the
+ * fp32 bits of nll, integer atomics only) and neither K, the cut nor the denominator visits the host.  The forward writes
+ * loss, stats (4 device floats: sum_kept w, sum_kept w nll, cut, 0), counts (2 device int64: V, kept) and nll (P floats;
+ * -1 for ignored pixels).  workspace: vmtl_ce_ohem_workspace_bytes(P) bytes, 8-byte aligned.
+ * Backward: dz_c = w[t] (softmax_c - 1[c == t]) grad_out / stats[0] on the kept pixels, decided from the SAVED nll and
+ * stats[2]; exactly 0.0f in every written lane of every other pixel; layouts and written lanes as vmtl_ce_bwd_strided. */
+long long vmtl_ce_ohem_workspace_bytes(long long P);
+int vmtl_ce_ohem_fwd(const float* logits, const long long* target, const float* weight, long long ignore_index,
+                     float nll_thresh, long long min_kept_total, float* loss, float* stats, long long* counts,
+                     float* nll, void* workspace, long long* argmax, int B, int HW, int C, long long sb, long long sc,
+                     long long sp, void* stream);
+int vmtl_ce_ohem_bwd(const float* logits, const long long* target, const float* weight, long long ignore_index,
+                     const float* stats, const float* nll, const float* grad_out, float* dlogits, int B, int HW, int C,
+                     long long sb, long long sc, long long sp, long long dsb, long long dsc, long long dsp,
+                     void* stream);
 long long vmtl_silog_workspace_bytes(long long P);
 int vmtl_silog_fwd(const float* pred, const float* target, float min_depth, float* loss, float* stats,
                    void* workspace, long long P, void* stream);

@@ -25,12 +25,16 @@ class MTLModule(nn.Module):
                  lr: t.Optional[float] = None, device: str = "cuda", loss_segm_weight: float = 1.0,
                  loss_depth_weight: float = 1.0, segm_ignore_index: t.Optional[int] = None,
                  segm_class_weights: t.Optional[t.Sequence[float]] = None,
-                 loss_balancing: t.Union[None, str, TaskBalancer] = None, dwa_temperature: float = 2.0):
+                 loss_balancing: t.Union[None, str, TaskBalancer] = None, dwa_temperature: float = 2.0,
+                 segm_ohem_min_kept: t.Optional[int] = None, segm_ohem_thresh: t.Optional[float] = None):
         """segm_ignore_index / segm_class_weights (opt-in, INTEGRATION.md): the `ignore_index` and per-class `weight`
         of the segmentation criterion; the ignore index also keeps those pixels out of the segmentation metrics.
         loss_balancing (opt-in): "uncertainty" | "dwa" | "geometric" or a balancing.TaskBalancer
         over the tasks ("segm", "depth"); it becomes the submodule `task_balancer` and takes the place of the two static
-        weights, which must then stay 1.0.  dwa_temperature: the softmax temperature of "dwa"."""
+        weights, which must then stay 1.0.  dwa_temperature: the softmax temperature of "dwa".
+        segm_ohem_min_kept / segm_ohem_thresh (opt-in): online hard example mining in the
+        segmentation loss of the TRAINING step - it becomes the submodule `segm_train_criterion`; validation, test and
+        predict keep reporting the un-mined loss of `segm_criterion` with the same weights and ignore index."""
         super().__init__()
         if loss_balancing is not None:
             if loss_segm_weight != 1.0 or loss_depth_weight != 1.0:
@@ -61,6 +65,12 @@ class MTLModule(nn.Module):
             p = next(model.parameters(), None)
             if p is not None:
                 self.segm_criterion.to(p.device)
+        if segm_ohem_min_kept is not None or segm_ohem_thresh is not None:  # absent by default, as the balancer
+            self.hparams.update(segm_ohem_min_kept=segm_ohem_min_kept, segm_ohem_thresh=segm_ohem_thresh)
+            self.segm_train_criterion = CrossEntropyLoss(weight=segm_class_weights, ignore_index=segm_ignore_index,
+                                                         ohem_min_kept=segm_ohem_min_kept, ohem_thresh=segm_ohem_thresh)
+            if segm_class_weights is not None:
+                self.segm_train_criterion.to(self.segm_criterion.weight.device)
         self.segm_ignore_index = segm_ignore_index
         self.depth_criterion = SILogLoss()
         if loss_balancing is not None:  # absent by default: state_dict() keys and parameters() stay the reference's
@@ -86,6 +96,7 @@ class MTLModule(nn.Module):
         # a data.DeviceAugment: training_step applies it to the device batch (validation, test and predict never do;
         # GraphedStep(stage="train") records it at construction and captures it)
         self.train_augment = None
+        self._mining = False  # True inside a training step's calc_losses
 
     def forward(self, x: torch.Tensor) -> dict:
         return self.model(x)
@@ -96,7 +107,11 @@ class MTLModule(nn.Module):
         raw_out = self(img)
         # the segmentation prediction comes out of the cross-entropy pass (calc_losses) when the criterion can emit it
         out = self.postprocess_raw_out(raw_out, defer_segm_predictions=hasattr(self.segm_criterion, "forward_with_predictions"))
-        all_losses = self.calc_losses(gt_mask, gt_depth, out)
+        self._mining = stage == "train"  # calc_losses keeps its signature: the training step alone mines
+        try:
+            all_losses = self.calc_losses(gt_mask, gt_depth, out)
+        finally:
+            self._mining = False
         all_metrics = self.calc_metrics(gt_mask, gt_depth, out)
         self.update_step_stats(stage, all_losses, all_metrics)
         if stage == "train" and self.dp_arena is not None and torch.is_grad_enabled():
@@ -126,10 +141,13 @@ class MTLModule(nn.Module):
                 "mae": self.metrics["mae"](out["depth_predictions"].detach(), gt_depth)}
 
     def calc_losses(self, gt_mask, gt_depth, out: dict) -> dict:  # reference lit_module.py:120-131
-        if out.get("segm_predictions") is None and hasattr(self.segm_criterion, "forward_with_predictions"):
-            loss_segm, out["segm_predictions"] = self.segm_criterion.forward_with_predictions(out["segm_logits"], gt_mask)
+        criterion = self.segm_criterion
+        if self._mining:  # a training step: the mining criterion, when there is one
+            criterion = getattr(self, "segm_train_criterion", criterion)
+        if out.get("segm_predictions") is None and hasattr(criterion, "forward_with_predictions"):
+            loss_segm, out["segm_predictions"] = criterion.forward_with_predictions(out["segm_logits"], gt_mask)
         else:
-            loss_segm = self.segm_criterion(out["segm_logits"], gt_mask)
+            loss_segm = criterion(out["segm_logits"], gt_mask)
         loss_depth = self.depth_criterion(out["depth_predictions"], gt_depth)
         balancer = getattr(self, "task_balancer", None)
         if balancer is not None:  # learned / dynamic weights, read on the device (csrc/balance.hip)

@@ -40,10 +40,26 @@ class CrossEntropyLoss(nn.Module):
     nor in the denominator.  Its default is None - NOT torch's -100: nothing is ignored, and a label outside [0, C)
     makes the loss NaN instead of vanishing.  With both at their defaults this is the reference's criterion on the
     unweighted kernels.  `weight` is a buffer (it follows .to(device)) that stays out of state_dict: checkpoints keep
-    the reference's keys."""
+    the reference's keys.
 
-    def __init__(self, weight: t.Optional[torch.Tensor] = None, ignore_index: t.Optional[int] = None):
+    ohem_min_kept (opt-in): online hard example mining - the mean runs over the valid pixels whose true-class probability
+    is below ohem_thresh (in (0, 1]; None: pure top-K), and never over fewer than ohem_min_kept pixels per image
+    (ops.cross_entropy_ohem).  Mining is on iff ohem_min_kept is given."""
+
+    def __init__(self, weight: t.Optional[torch.Tensor] = None, ignore_index: t.Optional[int] = None,
+                 ohem_min_kept: t.Optional[int] = None, ohem_thresh: t.Optional[float] = None):
         super().__init__()
+        if ohem_min_kept is None:
+            if ohem_thresh is not None:
+                raise ValueError("CrossEntropyLoss: ohem_thresh needs ohem_min_kept (mining is on iff ohem_min_kept is set)")
+        else:
+            if isinstance(ohem_min_kept, bool) or not isinstance(ohem_min_kept, int):
+                raise TypeError(f"CrossEntropyLoss: ohem_min_kept must be an int or None, got {ohem_min_kept!r}")
+            if ohem_min_kept < 1:
+                raise ValueError(f"CrossEntropyLoss: ohem_min_kept must be at least 1, got {ohem_min_kept}")
+            ops.ohem_tau(ohem_thresh)  # TypeError / ValueError for anything but None or a float in (0, 1]
+        self.ohem_min_kept = ohem_min_kept
+        self.ohem_thresh = ohem_thresh
         if ignore_index is not None and (isinstance(ignore_index, bool) or not isinstance(ignore_index, int)):
             raise TypeError(f"CrossEntropyLoss: ignore_index must be an int or None, got {ignore_index!r}")
         if weight is not None:
@@ -55,10 +71,16 @@ class CrossEntropyLoss(nn.Module):
         self.register_buffer("weight", weight, persistent=False)
 
     def forward(self, logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        if self.ohem_min_kept is not None:
+            return ops.cross_entropy_ohem(logits, target, self.ohem_min_kept, self.ohem_thresh, weight=self.weight,
+                                          ignore_index=self.ignore_index)
         return ops.cross_entropy(logits, target, weight=self.weight, ignore_index=self.ignore_index)
 
     def forward_with_predictions(self, logits: torch.Tensor, target: torch.Tensor):
         """(loss, argmax_c logits): the loss pass finds each pixel's maximum anyway (one launch instead of two)."""
+        if self.ohem_min_kept is not None:
+            return ops.cross_entropy_ohem_with_argmax(logits, target, self.ohem_min_kept, self.ohem_thresh,
+                                                      weight=self.weight, ignore_index=self.ignore_index)
         return ops.cross_entropy_with_argmax(logits, target, weight=self.weight, ignore_index=self.ignore_index)
 
 

@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import contextlib
 import functools
+import math
 import os
 import struct
 import weakref
@@ -3109,6 +3110,91 @@ def cross_entropy_with_argmax(logits, target, weight=None, ignore_index=None):
     """(loss, argmax over the class axis) from one pass over the logits (reference lit_module.py:123 + 137-138).  The
     prediction is written for every pixel, ignored or not."""
     return _CrossEntropy.apply(logits, target, weight, _ce_ignore(weight, ignore_index), True)
+
+
+class _CrossEntropyOHEM(torch.autograd.Function):
+    """The weighted / ignoring cross entropy over the hard pixels only (csrc/ce_ohem.hip): a valid pixel is kept when
+    its unweighted nll is not below cut = min(tau, K-th largest nll), K = min(min_kept_total, valid pixels).  The
+    selection runs on the device: K, the cut and the denominator never visit the host, so the node captures like
+    _CrossEntropy.  The forward saves the per-pixel nll and stats = (den, num, cut, 0); the backward decides membership
+    from those - never from a recomputed nll.  No gradient flows through the selection; weight gets none."""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight, ignore_index, tau, min_kept_total, want_argmax):
+        logits = _req(logits, "logits")
+        if target.dtype != torch.int64:
+            raise TypeError("cross_entropy_ohem: target must be int64 class indices")
+        target = target.contiguous()
+        B, C, H, W = logits.shape
+        if tuple(target.shape) != (B, H, W):
+            raise ValueError(f"cross_entropy_ohem: target shape {tuple(target.shape)} does not match logits {(B, H, W)}")
+        weight = _ce_weight(weight, logits)
+        P = B * H * W
+        loss, stats, nll = _empty((), logits), _empty((4,), logits), _empty((B, H, W), logits)
+        counts = torch.empty((2,), dtype=torch.int64, device=logits.device)
+        ws = torch.empty((lib().raw("vmtl_ce_ohem_workspace_bytes")(P) // 8,), dtype=torch.float64, device=logits.device)
+        pred = torch.empty((B, H, W), dtype=torch.int64, device=logits.device) if want_argmax else None
+        _k("vmtl_ce_ohem_fwd", logits=logits, target=target, weight=weight, ignore_index=ignore_index, nll_thresh=tau,
+           min_kept_total=min_kept_total, loss=loss, stats=stats, counts=counts, nll=nll, workspace=ws, argmax=pred,
+           B=B, HW=H * W, C=C, sb=C * H * W, sc=H * W, sp=1)
+        ctx.save_for_backward(logits, target, stats, nll, *(() if weight is None else (weight,)))
+        ctx.ignore_index = ignore_index
+        if want_argmax:
+            ctx.mark_non_differentiable(pred)
+            return loss, pred
+        return loss
+
+    @staticmethod
+    def backward(ctx, g, _gpred=None):
+        logits, target, stats, nll, *w = ctx.saved_tensors
+        B, C, H, W = logits.shape
+        g = _req(g, "grad_output")
+        ld = ceil4(C + 1)  # the NHWC storage with room for one more head, as _CrossEntropy.backward lays it out
+        st = _empty((B, H, W, ld), logits)
+        _k("vmtl_ce_ohem_bwd", logits=logits, target=target, weight=w[0] if w else None, ignore_index=ctx.ignore_index,
+           stats=stats, nll=nll, grad_out=g, dlogits=st, B=B, HW=H * W, C=C, sb=C * H * W, sc=H * W, sp=1,
+           dsb=H * W * ld, dsc=1, dsp=ld)
+        dl = st[..., :C].permute(0, 3, 1, 2)
+        dl._vmtl_nhwc = st
+        return dl, None, None, None, None, None, None
+
+
+def ohem_tau(thresh) -> float:
+    """tau = -log(thresh), the nll above which a pixel counts as hard: thresh is a true-class probability in (0, 1];
+    None is +inf (pure top-K).  Computed in double, +0.0 at thresh = 1."""
+    if thresh is None:
+        return float("inf")
+    if isinstance(thresh, bool) or not isinstance(thresh, (int, float)):
+        raise TypeError(f"cross_entropy_ohem: thresh must be a float in (0, 1] or None, got {thresh!r}")
+    if not 0.0 < thresh <= 1.0:  # NaN fails both comparisons
+        raise ValueError(f"cross_entropy_ohem: thresh must be in (0, 1], got {thresh!r}")
+    return -math.log(thresh) + 0.0
+
+
+def _ohem_args(logits, min_kept, thresh, weight, ignore_index):
+    if isinstance(min_kept, bool) or not isinstance(min_kept, int):
+        raise TypeError(f"cross_entropy_ohem: min_kept must be an int, got {min_kept!r}")
+    if min_kept < 1:
+        raise ValueError(f"cross_entropy_ohem: min_kept must be at least 1 pixel per image, got {min_kept}")
+    tau = ohem_tau(thresh)
+    ign = _ce_ignore(weight, ignore_index)
+    return NO_IGNORE if ign is None else ign, tau, min_kept * logits.shape[0]
+
+
+def cross_entropy_ohem(logits, target, min_kept, thresh=None, weight=None, ignore_index=None):
+    """Cross entropy with online hard example mining (bootstrapped cross entropy): the mean, weighted as
+    ops.cross_entropy(weight=, ignore_index=) weights it, over the valid pixels whose true-class probability is below
+    `thresh` - and never fewer than min_kept per image (min_kept * B hardest pixels of the batch; every tie at the cut is
+    kept).  thresh None: pure top-K.  thresh = 1.0, or min_kept * B at least the number of valid pixels: every valid
+    pixel, i.e. ops.cross_entropy."""
+    ign, tau, total = _ohem_args(logits, min_kept, thresh, weight, ignore_index)
+    return _CrossEntropyOHEM.apply(logits, target, weight, ign, tau, total, False)
+
+
+def cross_entropy_ohem_with_argmax(logits, target, min_kept, thresh=None, weight=None, ignore_index=None):
+    """(loss, argmax over the class axis) from the one pass over the logits; the prediction is written for every pixel."""
+    ign, tau, total = _ohem_args(logits, min_kept, thresh, weight, ignore_index)
+    return _CrossEntropyOHEM.apply(logits, target, weight, ign, tau, total, True)
 
 
 class _SILog(torch.autograd.Function):

@@ -51,7 +51,10 @@ def init_model(args: argparse.Namespace, data_cfg: DataConfig) -> MTLModule:
                        segm_class_weights=getattr(args, "segm_class_weights", None),
                        # opt-in: "uncertainty" | "dwa" | "geometric" task-loss balancing
                        loss_balancing=getattr(args, "loss_balancing", None),
-                       dwa_temperature=getattr(args, "dwa_temperature", 2.0))
+                       dwa_temperature=getattr(args, "dwa_temperature", 2.0),
+                       # opt-in: online hard example mining in the training step's segmentation loss
+                       segm_ohem_min_kept=getattr(args, "segm_ohem_min_kept", None),
+                       segm_ohem_thresh=getattr(args, "segm_ohem_thresh", None))
     if getattr(args, "ckpt_dir", None):
         from .ckpt import load_ckpt_model
 
