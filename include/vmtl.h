@@ -593,6 +593,35 @@ int vmtl_l1_fwd(const float* pred, const float* target, float* loss, void* works
 int vmtl_l1_bwd(const float* pred, const float* target, const float* grad_out, float* dpred, long long P,
                 void* stream);
 
+/* ---- depth loss with multi-scale gradient matching (csrc/depth_grad.hip) --------------------
+ * MegaDepth's / MiDaS' scale-invariant gradient-matching term on log depth, next to SILog (no reference call site: the
+ * reference's depth criterion is SILogLoss alone, losses.py:7-36).  pred, target: [B][H][W] floats.  Valid pixels: those
+ * with mask[i] != 0 (B*H*W bytes), or, mask NULL, those with target > min_depth.  R = log(pred) - log(target) on valid
+ * pixels.  For k < scales (1..6), s = 2^k, G_k = pixels with y % s == 0 and x % s == 0:
+ *   N_k = #valid pixels of G_k (whole batch);  S_k = sum over G_k of |R(y,x+s) - R(y,x)| + |R(y+s,x) - R(y,x)|, each pair
+ *   counted when its neighbour is inside the image and both pixels are valid;  L_grad = sum_k (N_k > 0 ? S_k / N_k : 0)
+ *   loss = silog_weight * SILog + grad_weight * L_grad        (both weights finite and >= 0)
+ * R is evaluated as ONE log of the quotient pred / target (smaller rounding than a difference of two logs); it differs from
+ * log(pred) - log(target) only where the fp32 quotient under- or overflows (magnitudes 2^126 apart: no depth range).  Nothing
+ * is clamped: pred < 0 on a valid pixel gives R = NaN and a NaN loss, pred == 0 gives R = -inf: NaN with SILog on, +inf
+ * for the term alone, when the pixel is in a valid pair (no valid pair: the term does not see it).
+ * silog_weight == 0: SILog is neither evaluated nor differentiated (terms[0], stats[1], stats[2] are 0), so the term
+ * alone stays finite with fewer than two valid pixels.  H or W below a scale's step: that scale has no pair there.
+ * The forward writes loss, terms (2 floats: SILog, L_grad, unweighted), stats (3 floats: SILog's N, mu, Dg), counts
+ * (`scales` int64: N_k, exact) and resid (B*H*W floats: R, 0.0f at invalid pixels) in three launches: residual + SILog
+ * partials, stencil partials, a one-workgroup fp64 finalize in a fixed order (run-to-run bit-identical; no float
+ * atomics, no host sync).  workspace: vmtl_depth_grad_workspace_bytes(B, H, W, scales) bytes, 8-byte aligned.
+ * Backward, one launch, a gather: dpred_i = grad_out * dL/dR_i / pred_i with the signs of d|.| taken from the SAVED
+ * resid (0 at a tie) and 1/N_k from counts; +0.0f at invalid pixels; dpred is written for every pixel.  The validity
+ * predicate is evaluated again on target / mask. */
+long long vmtl_depth_grad_workspace_bytes(int B, int H, int W, int scales);
+int vmtl_depth_grad_fwd(const float* pred, const float* target, const unsigned char* mask, float min_depth, int B, int H,
+                        int W, int scales, float silog_weight, float grad_weight, float* loss, float* terms,
+                        float* stats, long long* counts, float* resid, void* workspace, void* stream);
+int vmtl_depth_grad_bwd(const float* pred, const float* target, const unsigned char* mask, float min_depth,
+                        const float* resid, const float* stats, const long long* counts, const float* grad_out, int B,
+                        int H, int W, int scales, float silog_weight, float grad_weight, float* dpred, void* stream);
+
 /* ---- task-loss balancing (csrc/balance.hip) ------------------------------------------------
  * Opt-in replacements of lit_module.py:120-131 (loss = w_segm * loss_segm + w_depth * loss_depth with two host floats):
  * T = 1..4 scalar task losses L_k, given as the pointers l0..l3 (the first T non-null, in the style of vmtl_add_n), become

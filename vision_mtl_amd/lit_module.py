@@ -7,6 +7,7 @@ synchronises with the host.
 """
 from __future__ import annotations
 
+import math
 import typing as t
 from typing import Any
 
@@ -16,7 +17,7 @@ from torch import nn
 from . import metrics as M
 from . import ops
 from .balancing import TaskBalancer
-from .losses import CrossEntropyLoss, SILogLoss
+from .losses import CrossEntropyLoss, SILogGradLoss, SILogLoss
 from .utils.loss_utils import summarize_epoch_metrics
 
 
@@ -26,7 +27,8 @@ class MTLModule(nn.Module):
                  loss_depth_weight: float = 1.0, segm_ignore_index: t.Optional[int] = None,
                  segm_class_weights: t.Optional[t.Sequence[float]] = None,
                  loss_balancing: t.Union[None, str, TaskBalancer] = None, dwa_temperature: float = 2.0,
-                 segm_ohem_min_kept: t.Optional[int] = None, segm_ohem_thresh: t.Optional[float] = None):
+                 segm_ohem_min_kept: t.Optional[int] = None, segm_ohem_thresh: t.Optional[float] = None,
+                 depth_grad_weight: t.Optional[float] = None, depth_grad_scales: int = 4):
         """segm_ignore_index / segm_class_weights (opt-in, INTEGRATION.md): the `ignore_index` and per-class `weight`
         of the segmentation criterion; the ignore index also keeps those pixels out of the segmentation metrics.
         loss_balancing (opt-in): "uncertainty" | "dwa" | "geometric" or a balancing.TaskBalancer
@@ -34,7 +36,10 @@ class MTLModule(nn.Module):
         weights, which must then stay 1.0.  dwa_temperature: the softmax temperature of "dwa".
         segm_ohem_min_kept / segm_ohem_thresh (opt-in): online hard example mining in the
         segmentation loss of the TRAINING step - it becomes the submodule `segm_train_criterion`; validation, test and
-        predict keep reporting the un-mined loss of `segm_criterion` with the same weights and ignore index."""
+        predict keep reporting the un-mined loss of `segm_criterion` with the same weights and ignore index.
+        depth_grad_weight / depth_grad_scales (opt-in): `depth_criterion` becomes
+        SILog + depth_grad_weight * the multi-scale gradient-matching term (losses.SILogGradLoss), in every stage: it is
+        part of the loss definition, like the class weights."""
         super().__init__()
         if loss_balancing is not None:
             if loss_segm_weight != 1.0 or loss_depth_weight != 1.0:
@@ -72,7 +77,18 @@ class MTLModule(nn.Module):
             if segm_class_weights is not None:
                 self.segm_train_criterion.to(self.segm_criterion.weight.device)
         self.segm_ignore_index = segm_ignore_index
-        self.depth_criterion = SILogLoss()
+        if depth_grad_weight is None:
+            self.depth_criterion = SILogLoss()
+        else:  # same child name, no parameters or buffers: checkpoints keep their keys
+            if (isinstance(depth_grad_weight, bool) or not isinstance(depth_grad_weight, (int, float))
+                    or not math.isfinite(depth_grad_weight) or depth_grad_weight <= 0):
+                raise ValueError(f"MTLModule: depth_grad_weight must be a finite float > 0, got {depth_grad_weight!r}")
+            if (isinstance(depth_grad_scales, bool) or not isinstance(depth_grad_scales, int)
+                    or not 1 <= depth_grad_scales <= ops.DEPTH_GRAD_SCALES_MAX):
+                raise ValueError(f"MTLModule: depth_grad_scales must be an int in 1..{ops.DEPTH_GRAD_SCALES_MAX}, got "
+                                 f"{depth_grad_scales!r}")
+            self.hparams.update(depth_grad_weight=float(depth_grad_weight), depth_grad_scales=depth_grad_scales)
+            self.depth_criterion = SILogGradLoss(grad_weight=float(depth_grad_weight), scales=depth_grad_scales)
         if loss_balancing is not None:  # absent by default: state_dict() keys and parameters() stay the reference's
             p = next(model.parameters(), None)
             self.task_balancer = loss_balancing if p is None else loss_balancing.to(p.device)

@@ -33,6 +33,53 @@ class SILogLoss(nn.Module):
         return ops.silog(pred, target, self.min_depth if min_depth is None else min_depth, mask=mask)
 
 
+def _check_depth_pair(who: str, pred: torch.Tensor, target: torch.Tensor, interpolate: bool) -> None:
+    """SILogLoss.forward's shape errors, under the caller's name"""
+    if pred.dim() < 2 or target.dim() < 2:
+        raise IndexError(f"{who} expects at least 2-D pred/target (the reference indexes shape[-2:])")
+    if interpolate and pred.shape[-2:] != target.shape[-2:]:
+        raise NotImplementedError(f"{who}: pred/target spatial sizes differ; resample before the loss")
+    if pred.shape != target.shape:
+        raise ValueError(f"{who}: shape mismatch {tuple(pred.shape)} vs {tuple(target.shape)}")
+
+
+class GradientMatchingLoss(nn.Module):
+    """The multi-scale scale-invariant gradient-matching term of MegaDepth (Li & Snavely 2018) / MiDaS, on log depth,
+    alone (ops.depth_loss with silog_weight = 0, grad_weight = 1): sum over scales s = 1, 2, .. 2^(scales-1) of the mean
+    absolute x- and y-difference of log(pred) - log(target) on the [::s, ::s] subsample, over valid pixel pairs, divided
+    by the subsample's valid pixel count of the whole batch.  pred: (B,H,W,1), (B,1,H,W) or (B,H,W)."""
+
+    def __init__(self, scales: int = 4, min_depth: float = 1e-3):
+        super().__init__()
+        self.scales = ops.depth_loss_scales(scales)
+        self.min_depth = min_depth
+
+    def forward(self, pred: torch.Tensor, target: torch.Tensor, mask: t.Optional[torch.Tensor] = None,
+                min_depth: t.Optional[float] = None) -> torch.Tensor:
+        return ops.depth_loss(pred, target, self.min_depth if min_depth is None else min_depth, mask=mask,
+                              grad_weight=1.0, scales=self.scales, silog_weight=0.0)
+
+
+class SILogGradLoss(nn.Module):
+    """SILogLoss + grad_weight * GradientMatchingLoss(scales) from one autograd node (one pass over pred / target, one
+    gradient buffer).  Same call signature and shape errors as SILogLoss; no parameters or buffers."""
+
+    def __init__(self, grad_weight: float = 0.5, scales: int = 4, min_depth: float = 1e-3):
+        super().__init__()
+        grad_weight = ops.depth_loss_weight(grad_weight, "grad_weight")
+        if grad_weight == 0.0:
+            raise ValueError("SILogGradLoss: grad_weight must be > 0 (SILogLoss is the criterion without the term)")
+        self.grad_weight = grad_weight
+        self.scales = ops.depth_loss_scales(scales)
+        self.min_depth = min_depth
+
+    def forward(self, pred: torch.Tensor, target: torch.Tensor, mask: t.Optional[torch.Tensor] = None,
+                interpolate: bool = True, min_depth: t.Optional[float] = None) -> torch.Tensor:
+        _check_depth_pair("SILogGradLoss", pred, target, interpolate)
+        return ops.depth_loss(pred, target, self.min_depth if min_depth is None else min_depth, mask=mask,
+                              grad_weight=self.grad_weight, scales=self.scales, silog_weight=1.0)
+
+
 class CrossEntropyLoss(nn.Module):
     """torch.nn.CrossEntropyLoss (reduction "mean", no smoothing): logits (B,C,H,W), target int64 (B,H,W).
 

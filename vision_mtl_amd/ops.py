@@ -3247,6 +3247,98 @@ def silog(pred, target, min_depth=1e-3, mask=None):
     return _SILog.apply(pred, target, float(min_depth), mask.view(torch.uint8) if mask.dtype == torch.bool else mask)
 
 
+DEPTH_GRAD_SCALES_MAX = 6  # csrc/depth_grad.hip
+
+
+class _DepthLoss(torch.autograd.Function):
+    """silog_weight * SILog + grad_weight * (multi-scale gradient matching on log depth), csrc/depth_grad.hip: one node,
+    one dpred.  pred / target are [B][H][W] in memory; the residual image, SILog's statistics and the per-scale valid
+    counts stay on the device between forward and backward."""
+
+    @staticmethod
+    def forward(ctx, pred, target, min_depth, mask, geom, scales, silog_weight, grad_weight):
+        pred, target = _req(pred, "pred"), _req(target, "target")
+        B, H, W = geom
+        loss, terms, stats = _empty((), pred), _empty((2,), pred), _empty((3,), pred)
+        resid = _empty((B, H, W), pred)
+        counts = torch.empty((scales,), dtype=torch.int64, device=pred.device)
+        ws = torch.empty((lib().raw("vmtl_depth_grad_workspace_bytes")(B, H, W, scales) // 8,), dtype=torch.float64,
+                         device=pred.device)
+        _k("vmtl_depth_grad_fwd", pred=pred, target=target, mask=mask, min_depth=min_depth, B=B, H=H, W=W, scales=scales,
+           silog_weight=silog_weight, grad_weight=grad_weight, loss=loss, terms=terms, stats=stats, counts=counts,
+           resid=resid, workspace=ws)
+        if mask is None:
+            ctx.save_for_backward(pred, target, resid, stats, counts)
+        else:
+            ctx.save_for_backward(pred, target, resid, stats, counts, mask)
+        ctx.args = (min_depth, geom, scales, silog_weight, grad_weight)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, target, resid, stats, counts, *mask = ctx.saved_tensors
+        min_depth, (B, H, W), scales, silog_weight, grad_weight = ctx.args
+        g = _req(g, "grad_output")
+        dp = _empty(pred.shape, pred)
+        _k("vmtl_depth_grad_bwd", pred=pred, target=target, mask=mask[0] if mask else None, min_depth=min_depth,
+           resid=resid, stats=stats, counts=counts, grad_out=g, B=B, H=H, W=W, scales=scales, silog_weight=silog_weight,
+           grad_weight=grad_weight, dpred=dp)
+        return dp, None, None, None, None, None, None, None
+
+
+def depth_loss_weight(w, name):
+    """A loss weight of the depth criterion as a float: finite and not negative."""
+    if isinstance(w, bool) or not isinstance(w, (int, float)):
+        raise TypeError(f"depth_loss: {name} must be a float, got {w!r}")
+    w = float(w)
+    if not math.isfinite(w) or w < 0.0:
+        raise ValueError(f"depth_loss: {name} must be finite and not negative, got {w}")
+    return w
+
+
+def depth_loss_scales(scales):
+    if isinstance(scales, bool) or not isinstance(scales, int):
+        raise TypeError(f"depth_loss: scales must be an int, got {scales!r}")
+    if not 1 <= scales <= DEPTH_GRAD_SCALES_MAX:
+        raise ValueError(f"depth_loss: scales must be in 1..{DEPTH_GRAD_SCALES_MAX}, got {scales}")
+    return scales
+
+
+def depth_loss(pred, target, min_depth=1e-3, mask=None, grad_weight=0.5, scales=4, silog_weight=1.0):
+    """silog_weight * SILog(pred, target) + grad_weight * L_grad, where L_grad is the scale-invariant gradient-matching
+    term of MegaDepth / MiDaS on R = log(pred) - log(target): for s = 1, 2, .. 2^(scales-1), the sum of |R(y,x+s) - R(y,x)|
+    and |R(y+s,x) - R(y,x)| over the pixels with y % s == x % s == 0 whose neighbour is inside the image, both valid,
+    divided by the number of valid pixels of that grid (batch-based reduction; a scale with none contributes 0).
+    pred: (B,H,W,1), (B,1,H,W) or (B,H,W); target: as many elements, in the same order.  Valid pixels and `mask` as
+    ops.silog.  silog_weight = 0 gives the term alone (finite also with fewer than two valid pixels)."""
+    scales = depth_loss_scales(scales)
+    silog_weight, grad_weight = depth_loss_weight(silog_weight, "silog_weight"), depth_loss_weight(grad_weight, "grad_weight")
+    if pred.dim() == 4 and pred.shape[3] == 1:
+        geom = tuple(pred.shape[:3])
+    elif pred.dim() == 4 and pred.shape[1] == 1:
+        geom = (pred.shape[0], pred.shape[2], pred.shape[3])
+    elif pred.dim() == 3:
+        geom = tuple(pred.shape)
+    else:
+        raise ValueError(f"depth_loss: pred must be (B,H,W,1), (B,1,H,W) or (B,H,W), got {tuple(pred.shape)}")
+    if pred.numel() != target.numel():
+        raise ValueError("depth_loss: pred and target must have the same number of elements")
+    if pred.numel() == 0:
+        raise ValueError(f"depth_loss: empty pred {tuple(pred.shape)}")
+    if mask is not None:
+        if mask.dtype not in (torch.bool, torch.uint8):
+            raise TypeError(f"depth_loss: mask must be bool or uint8, got {mask.dtype}")
+        if tuple(mask.shape) != tuple(target.shape):
+            raise ValueError(f"depth_loss: mask shape {tuple(mask.shape)} does not match target {tuple(target.shape)}")
+        if not mask.is_cuda or mask.device != target.device:
+            raise RuntimeError(f"depth_loss: mask is on {mask.device}, the target on {target.device} (no CPU fallback)")
+        mask = mask.contiguous()
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+    return _DepthLoss.apply(pred, target, float(min_depth), mask, tuple(int(v) for v in geom), scales, silog_weight,
+                            grad_weight)
+
+
 class _L1(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, target):

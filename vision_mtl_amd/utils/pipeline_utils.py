@@ -54,7 +54,10 @@ def init_model(args: argparse.Namespace, data_cfg: DataConfig) -> MTLModule:
                        dwa_temperature=getattr(args, "dwa_temperature", 2.0),
                        # opt-in: online hard example mining in the training step's segmentation loss
                        segm_ohem_min_kept=getattr(args, "segm_ohem_min_kept", None),
-                       segm_ohem_thresh=getattr(args, "segm_ohem_thresh", None))
+                       segm_ohem_thresh=getattr(args, "segm_ohem_thresh", None),
+                       # opt-in: SILog + weight * multi-scale gradient matching as the depth loss
+                       depth_grad_weight=getattr(args, "depth_grad_weight", None),
+                       depth_grad_scales=getattr(args, "depth_grad_scales", 4))
     if getattr(args, "ckpt_dir", None):
         from .ckpt import load_ckpt_model
 
