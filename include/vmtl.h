@@ -522,6 +522,36 @@ int vmtl_augment_draw(long long* state, int* params, const int* crop_hw, int B, 
 int vmtl_augment_apply(const float* img, int ld, const long long* mask, const float* depth, const int* params,
                        const float* scales, const int* crop_hw, float* img_out, long long* mask_out, float* depth_out,
                        int B, int H, int W, int S, void* stream);
+/* Test-time augmentation and output-size predictions (csrc/tta.hip): the model is run on resized
+ * and mirrored views of a batch, the views are merged at the base size (H, W), and the merged map is turned into
+ * predictions at any output size without the (B, C, Ho, Wo) map ever being written.  Forward only; one launch each, one
+ * thread per output pixel, no atomics, no workspace, bit-identical from run to run.  Every resampling is
+ * F.interpolate(mode="bilinear", align_corners=False, antialias=False): src = (dst + 0.5) * in / out - 0.5 clamped
+ * below at 0, the second tap clamped to the last index; equal sizes are an exact copy.  1 <= C <= 32, else -3.
+ * vmtl_tta_view: img float with pixel stride ld = 3 or 4 as vmtl_augment_apply takes it ([B][H][W][ld]; ld 4 is 16-byte
+ * aligned) -> out, the model's NHWC input storage [B][Ho][Wo][4] (16-byte aligned, pad lane +0.0f), resampled and then,
+ * with flip != 0, mirrored in x: out[.., x, :] = resized[.., Wo - 1 - x, :].
+ * vmtl_tta_accumulate: one view.  logits [B][C][h][w] and depth_logits [B][1][h][w] (NCHW, as the model returns them
+ * for that view) are un-mirrored with flip != 0 (the sample at x' is read from w - 1 - x'), resampled to (H, W) and
+ * merged into acc [B][C][H][W] and acc_depth [B][H][W]:
+ *   VMTL_TTA_PROB   acc (+)= weight * softmax_c(resampled logits)
+ *   VMTL_TTA_LOGIT  acc (+)= weight * resampled logits
+ *   both            acc_depth (+)= weight * depth_gain * bilinear(sigmoid(depth_logits)), the sigmoid of vmtl_eltwise
+ *                   mode 1 applied per tap
+ * first != 0 assigns (whatever the accumulators held), first == 0 adds.  depth_logits and acc_depth are null together.
+ * vmtl_tta_finish: acc (and acc_depth, nullable together with depth) resampled from (H, W) to (Ho, Wo) channel by
+ * channel, keeping a running best: segm int64 [B][Ho][Wo] = arg-max (the first maximum wins, as vmtl_argmax_channels),
+ * depth float [B][Ho][Wo] = inv_weight * bilinear(acc_depth), confidence (nullable) float [B][Ho][Wo] = the largest
+ * softmax probability of the merged map there: best / sum for VMTL_TTA_PROB, max softmax_c(inv_weight * resampled acc)
+ * by an online softmax in the same pass for VMTL_TTA_LOGIT.  mode: the one the accumulator was filled with. */
+#define VMTL_TTA_PROB 0
+#define VMTL_TTA_LOGIT 1
+int vmtl_tta_view(const float* img, int ld, float* out, int B, int H, int W, int Ho, int Wo, int flip, void* stream);
+int vmtl_tta_accumulate(const float* logits, const float* depth_logits, float* acc, float* acc_depth, int B, int C,
+                        int h, int w, int H, int W, int flip, float weight, float depth_gain, int mode, int first,
+                        void* stream);
+int vmtl_tta_finish(const float* acc, const float* acc_depth, float inv_weight, long long* segm, float* depth,
+                    float* confidence, int B, int C, int H, int W, int Ho, int Wo, int mode, void* stream);
 
 /* ---- losses ------------------------------------------------------------------------------
  * lit_module.py:31,123 (CrossEntropyLoss); losses.py:14-36 (SILogLoss); lit_module.py:68,112 (MAE). */

@@ -81,6 +81,10 @@ __device__ __forceinline__ float act_fwd(float v, int act) {
   }
 }
 
+// the sigmoid of the depth head's post-processing (vmtl_eltwise mode 1; csrc/tta.hip applies it per tap): libm's expf,
+// not the fast exponential of VMTL_ACT_SIGMOID above, and one definition so that both give the same bits
+__device__ __forceinline__ float sigmoid_exact(float v) { return 1.f / (1.f + expf(-v)); }
+
 // derivative of act at pre-activation v (torch conventions: relu'(0)=0,
 // hardswish' = 0 for v<-3, 1 for v>3, (2v+3)/6 between (torch uses < and >,
 // the boundary points take the middle formula), hardsigmoid' = 1/6 on (-3,3)).

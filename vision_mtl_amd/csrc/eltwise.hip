@@ -458,7 +458,7 @@ __global__ __launch_bounds__(256) void ew_kernel(const float* __restrict__ a, co
     const float av = a[i];
     float r;
     if (mode == 0) r = av + b[i];
-    else if (mode == 1) r = 1.f / (1.f + expf(-av));
+    else if (mode == 1) r = sigmoid_exact(av);
     else if (mode == 2) r = b[i] * av * (1.f - av);
     else r = av * b[0];
     y[i] = r;

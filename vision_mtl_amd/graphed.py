@@ -201,7 +201,10 @@ class GraphedEval(_StaticBatch):
     stage "val" / "test": shared_step; the call returns the loss and appends loss + metrics to
     module.step_outputs[stage] as the eager step does.  stage "predict": predict_step, with or without "mask" / "depth"
     in the batch; the call returns {"segm", "depth"} as fresh tensors (the reference keeps every batch's predictions)
-    and appends to step_outputs["predict"] when the targets are there.
+    and appends to step_outputs["predict"] when the targets are there.  `module.predict_augment`
+    (inference.PredictAugment) at construction is captured with it - every view's forward, the merge and the finish are
+    nodes of the one graph - and "confidence" is returned as well when the object asks for it; a call raises ValueError
+    when the attribute is another object than the one captured.
 
     When a BatchNorm of the model is in eval mode the step runs inside ops.eval_bn_table: the first node of the graph
     derives every eval-mode layer's statistics from the running buffers as they are at replay time.  Parameters are
@@ -223,6 +226,8 @@ class GraphedEval(_StaticBatch):
             raise ValueError(f"GraphedEval(stage={stage!r}): the batch needs 'mask' and 'depth'")
         self.module, self.stage = module, stage
         self._init_static(module, example_batch)
+        # an inference.PredictAugment, recorded like the transform: its views, merge and finish launches join the graph
+        self.predict_augment = getattr(module, "predict_augment", None) if stage == "predict" else None
         bns = [m for m in module.model.modules() if isinstance(m, torch.nn.BatchNorm2d)]
         self.training = module.training
         self._modes = tuple(m.training for m in bns)
@@ -282,6 +287,9 @@ class GraphedEval(_StaticBatch):
             raise ValueError(f"GraphedEval: captured with module.training={self.training}, called with "
                              f"module.training={self.module.training} (or a BatchNorm changed mode); capture one "
                              "GraphedEval per mode")
+        if self.stage == "predict" and getattr(self.module, "predict_augment", None) is not self.predict_augment:
+            raise ValueError(f"GraphedEval: captured with module.predict_augment={self.predict_augment!r}, called with "
+                             f"{getattr(self.module, 'predict_augment', None)!r}; capture one GraphedEval per predict_augment")
         self._fill(batch)
         self.graph.replay()
         self.replays += 1
@@ -292,7 +300,10 @@ class GraphedEval(_StaticBatch):
             for i, k in enumerate(self._keys):
                 so[k].append(stats[i])
         if self.stage == "predict":
-            return {"segm": self._out["segm"].clone(), "depth": self._out["depth"].clone()}
+            out = {"segm": self._out["segm"].clone(), "depth": self._out["depth"].clone()}
+            if "confidence" in self._out:  # inference.PredictAugment(return_confidence=True)
+                out["confidence"] = self._out["confidence"].clone()
+            return out
         return stats[self._keys.index("loss")] if "loss" in self._keys else self._out.clone()
 
 

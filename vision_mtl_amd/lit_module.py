@@ -112,6 +112,9 @@ class MTLModule(nn.Module):
         # a data.DeviceAugment: training_step applies it to the device batch (validation, test and predict never do;
         # GraphedStep(stage="train") records it at construction and captures it)
         self.train_augment = None
+        # an inference.PredictAugment: predict_step merges flipped / rescaled views and returns predictions at its output
+        # size (training, validation and test never look at it; GraphedEval(stage="predict") records it at construction)
+        self.predict_augment = None
         self._mining = False  # True inside a training step's calc_losses
 
     def forward(self, x: torch.Tensor) -> dict:
@@ -193,12 +196,37 @@ class MTLModule(nn.Module):
         return self.shared_step(batch=batch, stage="test")
 
     def predict_step(self, batch: dict, batch_idx: int = 0, dataloader_idx: int = 0):
+        if self.predict_augment is not None:
+            return self._predict_augmented(batch)
         out = self.postprocess_raw_out(self(batch["img"]))
         if "mask" in batch and "depth" in batch:
             gt_mask, gt_depth = batch["mask"], batch["depth"]
             self.update_step_stats("predict", self.calc_losses(gt_mask, gt_depth, out),
                                    self.calc_metrics(gt_mask, gt_depth, out))
         return {"segm": out["segm_predictions"], "depth": out["depth_predictions"]}
+
+    def _predict_augmented(self, batch: dict) -> dict:
+        """predict_step under `predict_augment`: the merged predictions at the object's output size.  With targets in the
+        batch (at that size) the four metrics go through calc_metrics as in the plain step; the "loss" entry is the NaN
+        placeholder - a merged prediction has no logits to put a criterion on."""
+        img = batch["img"]
+        has_targets = "mask" in batch and "depth" in batch
+        if has_targets:  # checked before any launch
+            B, _, H, W = img.shape
+            Ho, Wo = self.predict_augment.out_size(H, W)
+            gt_mask, gt_depth = batch["mask"], batch["depth"]
+            if tuple(gt_mask.shape) != (B, Ho, Wo) or tuple(gt_depth.shape) not in ((B, Ho, Wo, 1), (B, Ho, Wo)):
+                raise ValueError(f"MTLModule.predict_step: predict_augment returns predictions of size {(Ho, Wo)}: mask "
+                                 f"must be {(B, Ho, Wo)} and depth {(B, Ho, Wo, 1)}, got {tuple(gt_mask.shape)} and "
+                                 f"{tuple(gt_depth.shape)}")
+        res = self.predict_augment(self.model, img)
+        if has_targets:
+            out = {"segm_predictions": res["segm"], "depth_predictions": res["depth"].view(gt_depth.shape)}
+            nan = self._nan.get(img.device)
+            if nan is None:
+                nan = self._nan[img.device] = torch.full((), float("nan"), device=img.device)
+            self.update_step_stats("predict", {"loss": nan}, self.calc_metrics(gt_mask, gt_depth, out))
+        return res
 
     def shared_epoch_end(self, stage: Any):
         return summarize_epoch_metrics(self.step_outputs[stage], metric_name_prefix=stage)

@@ -2533,6 +2533,114 @@ def augment_apply(img, mask, depth, params, scales, crop_hw):
     return view, m, d
 
 
+TTA_MAX_CLASSES = 32  # csrc/tta.hip TTA_MAX_C
+TTA_MODES = {"prob": 0, "logit": 1}  # include/vmtl.h VMTL_TTA_PROB / VMTL_TTA_LOGIT
+
+
+def _tta_size(size, what):
+    if (not isinstance(size, (tuple, list)) or len(size) != 2
+            or any(isinstance(v, bool) or not isinstance(v, int) or v < 1 for v in size)):
+        raise ValueError(f"{what} must be two positive ints (H, W), got {size!r}")
+    return int(size[0]), int(size[1])
+
+
+def _tta_mode(mode, what):
+    if mode not in TTA_MODES:
+        raise ValueError(f"{what}: merge must be one of {tuple(TTA_MODES)}, got {mode!r}")
+    return TTA_MODES[mode]
+
+
+def _tta_classes(C, what):
+    if not 1 <= C <= TTA_MAX_CLASSES:
+        raise ValueError(f"{what}: 1 <= C <= {TTA_MAX_CLASSES} classes are supported, got {C}")
+
+
+def tta_view(img, size, flip=False):
+    """One view of an image batch for test-time augmentation, as one launch (csrc/tta.hip): bilinear resize to `size`
+    (F.interpolate, align_corners=False, no antialias), then mirrored in x when `flip` is set.
+
+    img: what augment_apply takes - a (B,3,H,W) view over the model's NHWC input storage, a (B,H,W,3) tensor in dataset
+    sample layout, or a plain (B,3,H,W) tensor (re-laid first).  Returns the (B,3,Ho,Wo) view of a NEW NHWC storage (pad
+    lane 0), which the model picks up without a relayout."""
+    Ho, Wo = _tta_size(size, "tta_view: size")
+    st = getattr(img, "_vmtl_nhwc", None)
+    if (st is not None and img.dim() == 4 and st.dim() == 4 and st.shape[-1] == 4 and st.shape[0] == img.shape[0]
+            and tuple(st.shape[1:3]) == tuple(img.shape[2:])):
+        src, ld = _req(st, "img"), 4
+    elif img.dim() == 4 and img.shape[-1] == 3 and img.shape[1] != 3:
+        src, ld = _req(img, "img"), 3
+    elif img.dim() == 4 and img.shape[1] == 3:
+        src, ld = to_nhwc(_req(img, "img")), 4
+    else:
+        raise ValueError(f"tta_view: img must be (B, 3, H, W) or (B, H, W, 3), got {tuple(img.shape)}")
+    B, H, W, _ = src.shape
+    out = _empty((B, Ho, Wo, 4), src)
+    _k("vmtl_tta_view", img=src, ld=ld, out=out, B=B, H=H, W=W, Ho=Ho, Wo=Wo, flip=int(bool(flip)))
+    view = out[..., :3].permute(0, 3, 1, 2)
+    view._vmtl_nhwc = out
+    return view
+
+
+def tta_accumulate(logits, depth_logits, acc, acc_depth, flip=False, weight=1.0, depth_gain=1.0, merge="prob",
+                   first=False):
+    """Merge one view into the accumulators, as one launch (csrc/tta.hip): logits (B,C,h,w) and depth_logits (B,1,h,w)
+    (or None, with acc_depth None) as the model returns them for the view are un-mirrored when `flip` is set, resampled
+    to the base size and added to acc (B,C,H,W) - weight * softmax ("prob") or weight * logits ("logit") - and to
+    acc_depth (B,H,W) - weight * depth_gain * bilinear(sigmoid(depth_logits)).  first=True assigns instead of adding
+    (the accumulators need no zeroing).  The accumulators are written in place and returned."""
+    mode = _tta_mode(merge, "tta_accumulate")
+    logits = _req(logits, "logits")
+    if _req(acc, "acc") is not acc:
+        raise ValueError("tta_accumulate: acc is written in place and must be contiguous")
+    if logits.dim() != 4 or acc.dim() != 4 or acc.shape[:2] != logits.shape[:2]:
+        raise ValueError(f"tta_accumulate: logits (B, C, h, w) and acc (B, C, H, W) expected, got {tuple(logits.shape)} "
+                         f"and {tuple(acc.shape)}")
+    B, C, h, w = logits.shape
+    H, W = acc.shape[2:]
+    _tta_classes(C, "tta_accumulate")
+    if (depth_logits is None) != (acc_depth is None):
+        raise ValueError("tta_accumulate: depth_logits and acc_depth are given together or not at all")
+    if depth_logits is not None:
+        depth_logits = _req(depth_logits, "depth_logits")
+        if _req(acc_depth, "acc_depth") is not acc_depth:
+            raise ValueError("tta_accumulate: acc_depth is written in place and must be contiguous")
+        if tuple(depth_logits.shape) != (B, 1, h, w) or acc_depth.numel() != B * H * W:
+            raise ValueError(f"tta_accumulate: depth_logits {(B, 1, h, w)} and acc_depth {(B, H, W)} expected, got "
+                             f"{tuple(depth_logits.shape)} and {tuple(acc_depth.shape)}")
+    _k("vmtl_tta_accumulate", logits=logits, depth_logits=depth_logits, acc=acc, acc_depth=acc_depth, B=B, C=C, h=h, w=w,
+       H=H, W=W, flip=int(bool(flip)), weight=float(weight), depth_gain=float(depth_gain), mode=mode, first=int(bool(first)))
+    return acc, acc_depth
+
+
+def tta_finish(acc, acc_depth, inv_weight, size=None, merge="prob", confidence=False):
+    """Predictions from the merged map at any output size, as one launch (csrc/tta.hip): acc (B,C,H,W) and acc_depth
+    (B,H,W) or None are resampled to `size` (default: their own) channel by channel and reduced on the fly, so the
+    (B,C,Ho,Wo) map never exists.  Returns (segm int64 (B,Ho,Wo), depth float32 (B,Ho,Wo) = inv_weight *
+    bilinear(acc_depth) or None, confidence float32 (B,Ho,Wo) - the largest softmax probability of the merged map - or
+    None).  merge: the mode the accumulator was filled with."""
+    mode = _tta_mode(merge, "tta_finish")
+    acc = _req(acc, "acc")
+    if acc.dim() != 4:
+        raise ValueError(f"tta_finish: acc must be (B, C, H, W), got {tuple(acc.shape)}")
+    B, C, H, W = acc.shape
+    _tta_classes(C, "tta_finish")
+    Ho, Wo = (H, W) if size is None else _tta_size(size, "tta_finish: size")
+    inv_weight = float(inv_weight)
+    if not (inv_weight > 0 and math.isfinite(inv_weight)):
+        raise ValueError(f"tta_finish: inv_weight must be a finite float > 0, got {inv_weight!r}")
+    depth = None
+    if acc_depth is not None:
+        acc_depth = _req(acc_depth, "acc_depth")
+        if acc_depth.numel() != B * H * W:
+            raise ValueError(f"tta_finish: acc_depth must be {(B, H, W)}, got {tuple(acc_depth.shape)}")
+        depth = _empty((B, Ho, Wo), acc)
+    segm = torch.empty((B, Ho, Wo), dtype=torch.int64, device=acc.device)
+    conf = _empty((B, Ho, Wo), acc) if confidence else None
+    _k("vmtl_tta_finish", acc=acc, acc_depth=acc_depth, inv_weight=inv_weight, segm=segm, depth=depth, confidence=conf,
+       B=B, C=C, H=H, W=W, Ho=Ho, Wo=Wo, mode=mode)
+    return segm, depth, conf
+
+
 class _ToNCHW(torch.autograd.Function):
     """internal [B,H,W,Cs] -> (B,C,H,W) contiguous, the reference's output layout."""
 

@@ -58,6 +58,16 @@ def init_model(args: argparse.Namespace, data_cfg: DataConfig) -> MTLModule:
                        # opt-in: SILog + weight * multi-scale gradient matching as the depth loss
                        depth_grad_weight=getattr(args, "depth_grad_weight", None),
                        depth_grad_scales=getattr(args, "depth_grad_scales", 4))
+    # opt-in: test-time augmentation / output-size predictions of the predict step; an
+    # attribute like train_augment, nothing goes into hparams
+    scales, flip = getattr(args, "predict_scales", None), getattr(args, "predict_flip", None)
+    out_size, merge = getattr(args, "predict_output_size", None), getattr(args, "predict_merge", None)
+    if any(v is not None for v in (scales, flip, out_size, merge)):
+        from ..inference import PredictAugment
+
+        module.predict_augment = PredictAugment(scales=(1.0,) if scales is None else scales, flip=bool(flip),
+                                                output_size=None if out_size is None else tuple(out_size),
+                                                merge="prob" if merge is None else merge)
     if getattr(args, "ckpt_dir", None):
         from .ckpt import load_ckpt_model
 
