@@ -68,24 +68,6 @@ __global__ __launch_bounds__(RED_THREADS) void bn_stats_kernel(const float* __re
   }
 }
 
-// fp64 sums of N values per thread over a 256-thread workgroup: out[i] (i < N) valid on every thread after the
-// call.  One barrier pair; fixed association order (run-to-run reproducible).
-template <int N>
-__device__ __forceinline__ void block_sum_n(double (&s)[N], double (*sh)[N] /* [4][N] */) {
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s[i] += __shfl_xor(s[i], o, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) sh[threadIdx.x >> 6][i] = s[i];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < N; ++i) s[i] = (sh[0][i] + sh[1][i]) + (sh[2][i] + sh[3][i]);
-}
-
 // mean / invstd from the (mean_b, M2_b) rows; block b covers rows [b*rows_per_blk, min(M, (b+1)*rows_per_blk)).
 // Optionally updates running stats the way torch does (momentum, unbiased variance).
 // This launch sits on the dependent chain of EVERY BatchNorm of the forward pass (56 per `basic` step), where its
@@ -885,11 +867,8 @@ __global__ __launch_bounds__(256) void sum_channels_kernel(const float* __restri
   __shared__ double sh[4];
   double a = 0.0;
   for (int c = threadIdx.x; c < C; c += 256) a += (double)v[c];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = a;
-  __syncthreads();
-  if (threadIdx.x == 0) out[0] = (float)(sh[0] + sh[1] + sh[2] + sh[3]);
+  a = block_sum_thread0(a, sh);
+  if (threadIdx.x == 0) out[0] = (float)a;
 }
 
 // out[c] = column sums of the partial rows; reduce_all: out[0] = their sum over channels, through the scratch row

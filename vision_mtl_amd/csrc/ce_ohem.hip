@@ -136,7 +136,7 @@ __global__ __launch_bounds__(OH_THREADS) void oh_pixel_kernel(const float* __res
   if (threadIdx.x < 2) lc[threadIdx.x] = 0u;
   __syncthreads();
   unsigned nv = 0, nt = 0;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long long)gridDim.x * blockDim.x) {
+  VMTL_GRID_STRIDE(i, P) {
     const long long b = i / HW, hw = i - b * HW;
     const float* r = z + b * sb + hw * sp;
     const long long t = tgt[i];
@@ -191,6 +191,7 @@ __global__ __launch_bounds__(OH_THREADS) void oh_pixel_kernel(const float* __res
     }
     nll[i] = v;
   }
+  // wave_sum's tree for the two counts together: two wave_sum calls put one tree behind the other
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     nv += __shfl_xor(nv, o, 64);
@@ -225,7 +226,7 @@ __global__ __launch_bounds__(OH_THREADS) void oh_round_kernel(const float* __res
   const unsigned prefix = R == 1 ? (unsigned)b0 : ((unsigned)b0 << 11) | (unsigned)b1;
   for (int j = threadIdx.x; j < NB; j += OH_THREADS) lh[j] = 0u;
   __syncthreads();
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long long)gridDim.x * blockDim.x) {
+  VMTL_GRID_STRIDE(i, P) {
     const float v = nll[i];
     if (v < 0.f) continue;  // the sentinel of an ignored pixel (a valid nll is >= +0.0f or NaN)
     const unsigned key = oh_key(v);
@@ -259,7 +260,7 @@ __global__ __launch_bounds__(OH_THREADS) void oh_sum_kernel(const float* __restr
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) ws->cut = cut;
   double num = 0.0, den = 0.0, cnt = 0.0;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long long)gridDim.x * blockDim.x) {
+  VMTL_GRID_STRIDE(i, P) {
     const float v = nll[i];
     if (v < 0.f || v < cut) continue;  // ignored, or easier than the cut; NaN stays in
     float w = 1.f;
@@ -333,7 +334,7 @@ __global__ __launch_bounds__(OH_THREADS) void oh_bwd_kernel(const float* __restr
                                                             long long sp, long long dsb, long long dsc, long long dsp,
                                                             OhBwd ex) {
   const float g = gout[0] / ex.stats[0], cut = ex.stats[2];
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long long)gridDim.x * blockDim.x) {
+  VMTL_GRID_STRIDE(i, P) {
     const long long b = i / HW, hw = i - b * HW;
     const long long off = b * sb + hw * sp, doff = b * dsb + hw * dsp;
     const long long t = tgt[i];
@@ -362,7 +363,7 @@ __global__ __launch_bounds__(OH_THREADS) void oh_bwd_nhwc_kernel(const float* __
   const float g = gout[0] / ex.stats[0], cut = ex.stats[2];
   const int Q = (C + 3) >> 2;
   const long long total = P * Q;
-  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+  VMTL_GRID_STRIDE(idx, total) {
     const long long i = idx / Q;
     const int q = (int)(idx - i * Q);
     const long long b = i / HW, hw = i - b * HW;

@@ -30,8 +30,11 @@ static inline bool valid_prec(int prec) { return prec == VMTL_PREC_FP32 || prec 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // Every launching entry point starts with VMTL_ENTER(): hipGetLastError() is per-thread state shared with
 // every other HIP user in the process (e.g. an ignored status inside the framework that hosts us), and
@@ -102,16 +105,51 @@ __device__ __forceinline__ float act_grad(float v, int act) {
   }
 }
 
-// 64-lane wavefront sum via DPP-free shuffles
-__device__ __forceinline__ float wave_sum(float v) {
+// 64-lane wavefront sum by the xor-shuffle tree 32, 16, .., 1 (float, double, unsigned, unsigned long long); every lane
+// gets the total.  The tree's order is part of the run-to-run reproducibility contract: reduce.h lists what is built on it.
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
 
-// XCD-aware bijective remap of a linear workgroup id: workgroups that end up
-// with consecutive remapped ids share an XCD (and therefore an L2).  Speed
-// only; any placement is correct.
+// The one grid-stride loop: element i of n for a 1-D grid of any size, 64-bit index.
+#define VMTL_GRID_STRIDE(i, n)                                                      \
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (n);     \
+       i += (long long)gridDim.x * blockDim.x)
+
+// fp32 -> bf16 operand rounding of the VMTL_PREC_BF16 contract: a plain cast, which is round-to-nearest-even with NaN
+// staying NaN, and compiles to v_cvt_pk_bf16_f32 (two values per instruction).  The results are the packed bf16 bits.
+__device__ __forceinline__ unsigned round_bf16x2(float lo, float hi) {
+  return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){lo, hi}, bf16x2));
+}
+__device__ __forceinline__ u32x2 round_bf16x4(f32x4 v) {
+  return __builtin_bit_cast(u32x2, __builtin_convertvector(v, bf16x4));
+}
+// a lane's eight k values of one v_mfma_f32_16x16x32_bf16 operand: two fp32 quads, rounded
+__device__ __forceinline__ bf16x8 round_bf16x8(f32x4 lo, f32x4 hi) {
+  const u32x2 l = round_bf16x4(lo), h = round_bf16x4(hi);
+  return __builtin_bit_cast(bf16x8, (u32x4){l[0], l[1], h[0], h[1]});
+}
+
+// Buffer-resource access: 32-bit byte offsets against a descriptor (base, stride 0, num_records = bytes, flag word).
+// 0x00020000 is word 3 of the descriptor with only DATA_FORMAT = 32-bit set (bits 15..18 = 4): a raw, unswizzled,
+// untyped buffer without stride or thread-id addressing.  With stride 0 the hardware checks every access's byte offset
+// against num_records: a load at an offset outside [0, bytes) returns zeros and a store there is dropped, so the
+// kernels pass 0xFFFFFFFF for "no element here" (and a zero-length descriptor for "no tensor") instead of branching.
+// Build descriptors from wave-uniform values only.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* base, int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, bytes, 0x00020000);
+}
+__device__ __forceinline__ f32x4 buf_load16(__amdgpu_buffer_rsrc_t r, unsigned byte_offset) {
+  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, byte_offset, 0, 0));
+}
+
+// LDS-only workgroup barrier: waits for this wave's LDS traffic, not for its global loads in flight (__syncthreads()
+// would also drain a prefetch)
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
 // Sum over the four lane quarters (lanes l, l+16, l+32, l+48 of a wave; every lane gets the total).
 // (Round 3 tried gfx950's v_permlane16_swap / v_permlane32_swap here - two VALU instructions instead of two ds_bpermute
 // round trips.  Every kernel test passed, but MTAN's end-to-end gradients came out up to 18 % wrong in builds where the
@@ -125,6 +163,9 @@ __device__ __forceinline__ float quarter_sum(float v) {
 // every lane gets the value its column's lane of quarter 0 holds (lane & 15)
 __device__ __forceinline__ float quarter0_bcast(float v) { return __shfl(v, threadIdx.x & 15, 64); }
 
+// XCD-aware bijective remap of a linear workgroup id: workgroups that end up
+// with consecutive remapped ids share an XCD (and therefore an L2).  Speed
+// only; any placement is correct.
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   const int q = nwg >> 3, r = nwg & 7;
   const int xcd = bid & 7, idx = bid >> 3;

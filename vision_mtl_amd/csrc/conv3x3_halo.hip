@@ -86,10 +86,6 @@ struct HaloCfg {
   static_assert(CS % 4 == 0 && FG >= 1, "channel quads");
 };
 
-__device__ __forceinline__ f32x4 ch_bload(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
-}
-
 template <int CS, int TN, bool TAIL>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void conv3x3_halo_kernel(HaloP p) {
   using C = HaloCfg<CS, TN, TAIL>;
@@ -116,8 +112,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
   const int ty = t % p.tiles_y, b = t / p.tiles_y;
   const int h0 = ty * CH_TM, w0 = tx * CH_TW;
 
-  const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.wp, 0, p.wp_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_x = buf_rsrc(p.x, p.x_bytes);
+  const __amdgpu_buffer_rsrc_t rs_w = buf_rsrc(p.wp, p.wp_bytes);
 
   // ---- per-channel parameters into LDS (vectors of logical length: element-wise, zeros past the end)
   const bool has_pro = p.pa != nullptr;
@@ -177,7 +173,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
       const int hy = pp / CH_HX, hx = pp - hy * CH_HX;
       const int gh = h0 - 1 + hy, gw = w0 - 1 + hx;
       const bool ok = f < C::NST && (unsigned)gh < (unsigned)p.H && (unsigned)gw < (unsigned)p.W;
-      r0[it] = ch_bload(rs_x, ok ? (unsigned)((b * p.H + gh) * p.W + gw) * (unsigned)(CS * 4) + 16u * s : OOB);
+      r0[it] = buf_load16(rs_x, ok ? (unsigned)((b * p.H + gh) * p.W + gw) * (unsigned)(CS * 4) + 16u * s : OOB);
     }
     if (has_pro) __syncthreads();  // the prologue coefficients are in LDS
 #pragma unroll
@@ -247,7 +243,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
     int ai;
     group(g, koff, ai);
 #pragma unroll
-    for (int j = 0; j < NB; ++j) bq[j] = ch_bload(rs_w, wrow[j] + koff);
+    for (int j = 0; j < NB; ++j) bq[j] = buf_load16(rs_w, wrow[j] + koff);
   };
   auto load_a = [&](int g, f32x4 (&aq)[RT]) {
     unsigned koff;

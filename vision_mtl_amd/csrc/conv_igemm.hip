@@ -101,10 +101,6 @@ __device__ __forceinline__ void glds16(const float* src, float* lds_dst) {
 // accumulation: a1b1 + a1b2 + a2b1 + a1b3 + a2b2 + a3b1, dropped terms < 2^-24 relative.  Measured error is
 // below the fp32-MFMA path's (tools/ubench/gemm_bf16x3_vs_f32.hip); see DESIGN.md section 7 for why it is
 // not switched on.
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ u32x2 round_bf16x4(f32x4 v) {
-  return __builtin_bit_cast(u32x2, __builtin_convertvector(v, bf16x4));
-}
 
 __device__ __forceinline__ void split3(f32x4 v, u32x2& p1, u32x2& p2, u32x2& p3) {
   unsigned x[4], r1[4], r2[4];
@@ -227,12 +223,13 @@ __global__ __launch_bounds__(256, (TM * TN >= 20 && WAVES_N == 2) ? 2 : 1) void 
   // an out-of-image tap / tile edge is an out-of-range offset, which the hardware answers with zeros - no
   // zero-fill moves, no divergent branch around the load (the narrow tiles were VALU-issue bound: 7 VALU
   // instructions per MFMA, measured with SQ_INSTS_VALU / SQ_INSTS_MFMA).
-  const __amdgpu_buffer_rsrc_t rs_x =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)((unsigned)p.B * p.H * p.W * p.Cs * 4u), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_x2 = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(UP2 && p.x2 != nullptr ? p.x2 : p.x), 0, UP2 ? (int)(16u * p.B * p.H * p.W * p.C2s) : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)wp, 0, (int)((unsigned)p.Nw * p.Ktot * 4u), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_x = buf_rsrc(p.x, (int)((unsigned)p.B * p.H * p.W * p.Cs * 4u));
+  const __amdgpu_buffer_rsrc_t rs_x2 =
+      buf_rsrc(UP2 && p.x2 != nullptr ? p.x2 : p.x, UP2 ? (int)(16u * p.B * p.H * p.W * p.C2s) : 0);
+  const __amdgpu_buffer_rsrc_t rs_w = buf_rsrc(wp, (int)((unsigned)p.Nw * p.Ktot * 4u));
   constexpr unsigned OOB = 0xFFFFFFFFu;
+  // common.h's buf_load16, kept as the local lambda: through the function the compiler swaps the operands of two address
+  // additions in every UP2 instantiation (profiles/shared_helpers/README.md)
   auto bload = [](__amdgpu_buffer_rsrc_t r, unsigned off) -> f32x4 {
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
   };
@@ -987,7 +984,7 @@ static int launch_conv_ns(ConvP& p, hipStream_t st) {
 __global__ __launch_bounds__(256) void sum_slabs_kernel(const float* __restrict__ slabs, float* __restrict__ y,
                                                         int nslabs, long long n4, const float* __restrict__ bias,
                                                         int ldy, int Cout) {
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+  VMTL_GRID_STRIDE(i, n4) {
     f32x4 s = reinterpret_cast<const f32x4*>(slabs)[i];
     for (int z = 1; z < nslabs; ++z) s += reinterpret_cast<const f32x4*>(slabs)[(size_t)z * n4 + i];
     if (bias != nullptr) {

@@ -25,17 +25,6 @@
 // very value.  Tile choice, persistent-program count and statistics geometry do not depend on the precision.
 #include "common.h"
 
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ u32x2 pw_round_bf16x4(f32x4 v) {
-  return __builtin_bit_cast(u32x2, __builtin_convertvector(v, bf16x4));
-}
-// a lane's eight k values of one v_mfma_f32_16x16x32_bf16 operand: two fp32 quads, rounded
-__device__ __forceinline__ bf16x8 pw_round_bf16x8(f32x4 lo, f32x4 hi) {
-  const u32x2 l = pw_round_bf16x4(lo), h = pw_round_bf16x4(hi);
-  return __builtin_bit_cast(bf16x8, (u32x4){l[0], l[1], h[0], h[1]});
-}
-
 struct PwP {
   const float* x;     // [M][Ks]
   const float* wp;    // [Nw][Ks]
@@ -134,20 +123,14 @@ __global__ __launch_bounds__(256) void pw_gemm_kernel(PwP p) {
 #pragma unroll
   for (int j = 0; j < TN; ++j) boff[j] = (unsigned)(bp[j] - p.wp) * 4u;
   constexpr unsigned OOB = 0xFFFFFFFFu;
-  const auto rsrc = [](const float* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-  };
-  const __amdgpu_buffer_rsrc_t rs_a = rsrc(p.x, (unsigned)p.M * (unsigned)lda * 4u);
-  const __amdgpu_buffer_rsrc_t rs_b = rsrc(p.wp, (unsigned)p.Nw * (unsigned)p.Ks * 4u);
-  const __amdgpu_buffer_rsrc_t rs_pa = rsrc(p.pa, (unsigned)p.Ks * 4u);
-  const __amdgpu_buffer_rsrc_t rs_pc = rsrc(p.pc, (unsigned)p.Ks * 4u);
+  const __amdgpu_buffer_rsrc_t rs_a = buf_rsrc(p.x, (unsigned)p.M * (unsigned)lda * 4u);
+  const __amdgpu_buffer_rsrc_t rs_b = buf_rsrc(p.wp, (unsigned)p.Nw * (unsigned)p.Ks * 4u);
+  const __amdgpu_buffer_rsrc_t rs_pa = buf_rsrc(p.pa, (unsigned)p.Ks * 4u);
+  const __amdgpu_buffer_rsrc_t rs_pc = buf_rsrc(p.pc, (unsigned)p.Ks * 4u);
   // no residual: a zero-length descriptor, every load returns zeros
-  const __amdgpu_buffer_rsrc_t rs_res = rsrc(p.res, p.res != nullptr ? (unsigned)p.M * (unsigned)p.Ks * 4u : 0u);
+  const __amdgpu_buffer_rsrc_t rs_res = buf_rsrc(p.res, p.res != nullptr ? (unsigned)p.M * (unsigned)p.Ks * 4u : 0u);
   const __amdgpu_buffer_rsrc_t rs_ao =
-      rsrc(p.a_out, (p.a_out != nullptr && tile_n == 0) ? (unsigned)p.M * (unsigned)p.Ks * 4u : 0u);
-  const auto bload = [](__amdgpu_buffer_rsrc_t r, unsigned off) -> f32x4 {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
-  };
+      buf_rsrc(p.a_out, (p.a_out != nullptr && tile_n == 0) ? (unsigned)p.M * (unsigned)p.Ks * 4u : 0u);
 
   struct Frag { f32x4 a[TM], b[TN], pa, pc, r[TM]; };
   auto load = [&](int g, Frag& f) {
@@ -157,8 +140,8 @@ __global__ __launch_bounds__(256) void pw_gemm_kernel(PwP p) {
       const unsigned kb = 64u * (unsigned)g;
       if (PRO) {
         const unsigned ko = kok ? kb + 16u * (unsigned)lq : OOB;
-        f.pa = bload(rs_pa, ko);
-        f.pc = bload(rs_pc, ko);
+        f.pa = buf_load16(rs_pa, ko);
+        f.pc = buf_load16(rs_pc, ko);
       }
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
@@ -167,12 +150,12 @@ __global__ __launch_bounds__(256) void pw_gemm_kernel(PwP p) {
           const float* src = 16 * g + 4 * lq >= p.K1 ? ap2[i] : ap[i];  // K1 % 4 == 0: a quad has one source
           f.a[i] = *reinterpret_cast<const f32x4*>(ok ? src + 16 * g : g_pw_zero_page);
         } else {
-          f.a[i] = bload(rs_a, ok ? aoff[i] + kb : OOB);
+          f.a[i] = buf_load16(rs_a, ok ? aoff[i] + kb : OOB);
         }
-        if (PRO) f.r[i] = bload(rs_res, ok ? aoff[i] + kb : OOB);  // lda == Ks: the residual's offsets are A's
+        if (PRO) f.r[i] = buf_load16(rs_res, ok ? aoff[i] + kb : OOB);  // lda == Ks: the residual's offsets are A's
       }
 #pragma unroll
-      for (int j = 0; j < TN; ++j) f.b[j] = bload(rs_b, (kok & bok[j]) ? boff[j] + kb : OOB);
+      for (int j = 0; j < TN; ++j) f.b[j] = buf_load16(rs_b, (kok & bok[j]) ? boff[j] + kb : OOB);
       return;
     }
     const bool kok = g < G && 16 * g + 4 * lq < p.Ks;
@@ -275,9 +258,9 @@ __global__ __launch_bounds__(256) void pw_gemm_kernel(PwP p) {
       prologue(f[1], g + KW);
       bf16x8 fa[TM], fb[TN];
 #pragma unroll
-      for (int i = 0; i < TM; ++i) fa[i] = pw_round_bf16x8(f[0].a[i], f[1].a[i]);
+      for (int i = 0; i < TM; ++i) fa[i] = round_bf16x8(f[0].a[i], f[1].a[i]);
 #pragma unroll
-      for (int j = 0; j < TN; ++j) fb[j] = pw_round_bf16x8(f[0].b[j], f[1].b[j]);
+      for (int j = 0; j < TN; ++j) fb[j] = round_bf16x8(f[0].b[j], f[1].b[j]);
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -449,7 +432,7 @@ __global__ __launch_bounds__(256) void pw_gemm_kernel(PwP p) {
 //     registers BEFORE the K loop of tile t and stores it to LDS after tile t's epilogue - one full tile (32-128 KB per
 //     CU) is in flight under the MFMAs, and the K loop itself has NO barrier and no global traffic (all of K is in LDS);
 //   * full-width tiles: N <= 128 is one column tile, A is read exactly once;
-//   * barriers are LDS-only (s_waitcnt lgkmcnt(0); s_barrier): __syncthreads() would also wait for the prefetch;
+//   * barriers are LDS-only (lds_barrier): __syncthreads() would also wait for the prefetch;
 //   * the pre-activation prologue act(pa*x + pc) runs when a tile is STAGED (once per element, not per fragment use) and
 //     the activated matrix goes back to HBM as the coalesced rows it was loaded in;
 //   * epilogue as above (bias, pad-channel zeros, per-tile BatchNorm (mean, M2), two-destination split store).
@@ -461,7 +444,6 @@ __global__ __launch_bounds__(256) void pw_gemm_kernel(PwP p) {
 // v_mfma_f32_16x16x32_bf16 per (i, j) and 32-deep chunk.  It reads whole chunks, so the zero fill of k >= Ks in the last
 // chunk (Ks = 40, 72, 136, ...) - B and A staging both write it - is what makes a half-full chunk exact.  Barriers,
 // prefetch and epilogue are the fp32 kernel's; the output tile may now be LARGER than the A image it aliases.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // wave tile (TM*16) x (TN*16), WM x WN waves; KC = K chunks of 32 the instantiation can hold (Ks <= 32 * KC)
 // EZ: BatchNorm-backward epilogue (see PwP::ez_x; no addend): dz = acc * act'(gamma * xhat + beta) and (sum dz, sum dz * xhat);
@@ -508,7 +490,7 @@ __global__ __launch_bounds__(WM* WN * 64) void pw_big_kernel(PwP p, int nprog) {
       if (BN % SR == 0 || row < BN) {
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         if (c < nkc && n < p.Nw && k < p.Ks) v = *reinterpret_cast<const f32x4*>(p.wp + (size_t)n * p.Ks + k);
-        if constexpr (BF16) *reinterpret_cast<u32x2*>(Bb + (c * BN + row) * 64 + ksb) = pw_round_bf16x4(v);
+        if constexpr (BF16) *reinterpret_cast<u32x2*>(Bb + (c * BN + row) * 64 + ksb) = round_bf16x4(v);
         else *reinterpret_cast<f32x4*>(Bs + (c * BN + row) * 32 + ks) = v;
       }
     }
@@ -561,7 +543,7 @@ __global__ __launch_bounds__(WM* WN * 64) void pw_big_kernel(PwP p, int nprog) {
               *reinterpret_cast<f32x4*>(p.a_out + (size_t)m * p.Ks + k) = v;
             if (m >= p.M) v = (f32x4){0.f, 0.f, 0.f, 0.f};  // rows past M: act(pc) need not be 0
           }
-          if constexpr (BF16) *reinterpret_cast<u32x2*>(Ab + (c * BM + r0 + SR * i) * 64 + ksb) = pw_round_bf16x4(v);
+          if constexpr (BF16) *reinterpret_cast<u32x2*>(Ab + (c * BM + r0 + SR * i) * 64 + ksb) = round_bf16x4(v);
           else *reinterpret_cast<f32x4*>(As + (c * BM + r0 + SR * i) * 32 + ks) = v;
         }
       }

@@ -77,12 +77,11 @@ struct SmallP {
   int dbg;  // tuning aid (VMTL_SMALL_DBG): 1 skip the output stores, 2 skip halo staging, 4 skip the MFMA loop, 8 no start skew
 };
 
-// Workgroup barrier for LDS hand-overs only.  __syncthreads() is also a global-memory fence: it drains vmcnt, i.e.
-// waits for every outstanding global STORE (the previous tile's output rows, the a_out rows) and prefetch load at
-// each of the five barriers of a tile - measured as 26 % of the wave cycles parked, matrix pipe 69 % busy at two
-// waves per SIMD.  Nothing another wave reads through global memory is produced inside the tile loop, so the
-// barrier only has to order LDS traffic: wait for this wave's LDS operations, then s_barrier.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// The tile loop's barriers are lds_barrier() (common.h), for LDS hand-overs only.  __syncthreads() is also a
+// global-memory fence: it drains vmcnt, i.e. waits for every outstanding global STORE (the previous tile's output
+// rows, the a_out rows) and prefetch load at each of the five barriers of a tile - measured as 26 % of the wave cycles
+// parked, matrix pipe 69 % busy at two waves per SIMD.  Nothing another wave reads through global memory is produced
+// inside the tile loop, so the barrier only has to order LDS traffic.
 
 // per-CU arrival tickets (index: XCC id << 8 | SE/SH/CU id), see the start-skew note in the kernel
 static __device__ int g_small_cu_ticket[4096];

@@ -70,10 +70,6 @@ struct UhCfg {
   static_assert(256 / SQ * SQ <= 256, "statistics lanes");
 };
 
-__device__ __forceinline__ f32x4 uh_bload(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
-}
-
 template <int C0S, int C1S, int TM, int TN, int NT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void conv_up2_halo_kernel(Up2HaloP p) {
   using C = UhCfg<C0S, C1S, TM, TN, NT>;
@@ -100,10 +96,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
   const int hl0 = ty * TM, wl0 = tx * UH_TW;  // low-res origin of the tile
   const int H = 2 * p.H2, W = 2 * p.W2;
 
-  const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.xl, 0, p.xl_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_x = buf_rsrc(p.xl, p.xl_bytes);
   const __amdgpu_buffer_rsrc_t rs_s =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(C1S > 0 ? p.skip : p.xl), 0, C1S > 0 ? p.skip_bytes : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.wp, 0, p.wp_bytes, 0x00020000);
+      buf_rsrc(C1S > 0 ? p.skip : p.xl, C1S > 0 ? p.skip_bytes : 0);
+  const __amdgpu_buffer_rsrc_t rs_w = buf_rsrc(p.wp, p.wp_bytes);
 
   // ---- weight rows of this wave's phase: byte offset of (row, k quad 0); rows >= Nw read zeros (out of range)
   unsigned wrow[NB];
@@ -140,7 +136,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
       const int hy = pp / HX0, hx = pp - hy * HX0;
       const int gh = hl0 - 1 + hy, gw = wl0 - 1 + hx;
       const bool ok = f < C::NST0 && (unsigned)gh < (unsigned)p.H2 && (unsigned)gw < (unsigned)p.W2;
-      r0[it] = uh_bload(rs_x, ok ? (unsigned)((b * p.H2 + gh) * p.W2 + gw) * (unsigned)(C0S * 4) + 16u * s : OOB);
+      r0[it] = buf_load16(rs_x, ok ? (unsigned)((b * p.H2 + gh) * p.W2 + gw) * (unsigned)(C0S * 4) + 16u * s : OOB);
     }
 #pragma unroll
     for (int it = 0; it < C::IT1; ++it) {
@@ -149,7 +145,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
       const int hy = pp / HX1, hx = pp - hy * HX1;
       const int gh = 2 * hl0 - 1 + hy, gw = 2 * wl0 - 1 + hx;
       const bool ok = f < C::NST1 && (unsigned)gh < (unsigned)H && (unsigned)gw < (unsigned)W;
-      r1[it] = uh_bload(rs_s, ok ? (unsigned)((b * H + gh) * W + gw) * (unsigned)(C1S * 4) + 16u * s : OOB);
+      r1[it] = buf_load16(rs_s, ok ? (unsigned)((b * H + gh) * W + gw) * (unsigned)(C1S * 4) + 16u * s : OOB);
     }
 #pragma unroll
     for (int it = 0; it < C::IT0; ++it) {
@@ -201,7 +197,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
     int ai, istep;
     group(g, koff, ai, istep);
 #pragma unroll
-    for (int j = 0; j < NB; ++j) bq[j] = uh_bload(rs_w, wrow[j] + koff);
+    for (int j = 0; j < NB; ++j) bq[j] = buf_load16(rs_w, wrow[j] + koff);
   };
   auto load_a = [&](int g, f32x4 (&aq)[TM]) {
     unsigned koff;

@@ -39,12 +39,6 @@ struct WgradP {
 
 #define BP 32
 
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-// (lo, hi) rounded to bf16 (round-to-nearest-even, NaN stays NaN: a plain cast, v_cvt_pk_bf16_f32), packed in one word
-__device__ __forceinline__ unsigned rne_bf16x2(float lo, float hi) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){lo, hi}, bf16x2));
-}
 #define WG_BNK 128  // kk columns per workgroup (4 waves x 2 tiles x 16)
 
 // smallest row stride >= w (floats, multiple of 4) that is == 16 (mod 64): the four pixel rows of one fragment read
@@ -165,13 +159,10 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradP p) {
   f32x4 ry[PD][YIT], rx[PD][XP];
   // buffer loads: 32-bit offsets, out-of-range (slice end, image border, tile edge) reads return zeros
   const __amdgpu_buffer_rsrc_t rs_dy =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.dy, 0, (int)((unsigned)p.M * p.ldy * 4u), 0x00020000);
+      buf_rsrc(p.dy, (int)((unsigned)p.M * p.ldy * 4u));
   const __amdgpu_buffer_rsrc_t rs_x =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)((unsigned)p.B * p.H * p.W * p.Cs * 4u), 0x00020000);
+      buf_rsrc(p.x, (int)((unsigned)p.B * p.H * p.W * p.Cs * 4u));
   constexpr unsigned OOB = 0xFFFFFFFFu;
-  auto bload = [](__amdgpu_buffer_rsrc_t r, unsigned off) -> f32x4 {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
-  };
   // slot: compile-time index after unrolling (register arrays must not be indexed at run time)
   // live (uniform): the chunk lies inside the slice; a dead chunk's loads are issued with the out-of-range offset
   auto load_tile = [&](int pp, f32x4* ry_s, f32x4* rx_s, bool live = true) {
@@ -180,7 +171,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradP p) {
       const unsigned ybase = (unsigned)pp * (unsigned)p.ldy * 4u;
 #pragma unroll
       for (int it = 0; it < YIT; ++it)
-        ry_s[it] = bload(rs_dy, ((tyoff[it] >= 0) & live) ? ybase + (unsigned)tyoff[it] : OOB);
+        ry_s[it] = buf_load16(rs_dy, ((tyoff[it] >= 0) & live) ? ybase + (unsigned)tyoff[it] : OOB);
       const int hin = s_ho * p.stride;  // uniform: first input row / column of the chunk (before the tap shift)
       const int win = s_wo * p.stride;
       const unsigned xbase = (unsigned)((s_b * p.H + hin) * p.W + win) * (unsigned)p.Cs * 4u;
@@ -189,7 +180,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradP p) {
 #pragma unroll
       for (int i = 0; i < XP; ++i) {
         const bool ok = hok & ((unsigned)(win + tw[i]) < (unsigned)p.W);
-        rx_s[i] = bload(rs_x, ok ? xbase + (unsigned)toff[i] : OOB);
+        rx_s[i] = buf_load16(rs_x, ok ? xbase + (unsigned)toff[i] : OOB);
       }
       s_wo += BP;
       if (s_wo >= p.Wo) {
@@ -207,7 +198,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradP p) {
       const int row = idx / YQ, q = idx - row * YQ;
       const int m = pp + row, co = co0 + q * 4;
       const bool ok = idx < BP * YQ && m < p_end && co < p.ldy;
-      ry_s[it] = bload(rs_dy, ok ? ((unsigned)m * (unsigned)p.ldy + (unsigned)co) * 4u : OOB);
+      ry_s[it] = buf_load16(rs_dy, ok ? ((unsigned)m * (unsigned)p.ldy + (unsigned)co) * 4u : OOB);
     }
 #pragma unroll
     for (int i = 0; i < XP; ++i) {
@@ -220,7 +211,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradP p) {
         v = (f32x4){0.f, 0.f, 0.f, 0.f};
         if (ok) v = *reinterpret_cast<const f32x4*>(xsrc + (size_t)((xb[i] * p.H + h) * p.W + w) * xstride);
       } else {
-        v = bload(rs_x, ok ? off : OOB);
+        v = buf_load16(rs_x, ok ? off : OOB);
       }
       rx_s[i] = v;
       // advance this row by BP pixels
@@ -281,10 +272,10 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradP p) {
       for (int w = 0; w < 4; ++w) {
 #pragma unroll
         for (int i = 0; i < TM; ++i)
-          fa[i][w] = rne_bf16x2(ys[8 * w * LDY + i * 16], ys[(8 * w + 4) * LDY + i * 16]);
+          fa[i][w] = round_bf16x2(ys[8 * w * LDY + i * 16], ys[(8 * w + 4) * LDY + i * 16]);
 #pragma unroll
         for (int j = 0; j < TN; ++j)
-          fb[j][w] = rne_bf16x2(xs[8 * w * LDX + j * 16], xs[(8 * w + 4) * LDX + j * 16]);
+          fb[j][w] = round_bf16x2(xs[8 * w * LDX + j * 16], xs[(8 * w + 4) * LDX + j * 16]);
       }
 #pragma unroll
       for (int j = 0; j < TN; ++j) {

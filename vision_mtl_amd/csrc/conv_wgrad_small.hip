@@ -71,24 +71,21 @@ __global__ __launch_bounds__(256) void wgrad_small_kernel(WsP p) {
     ylds[it] = ok ? px * WS_LDP + q * 4 : -1;
   }
   const __amdgpu_buffer_rsrc_t rs_x =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)((unsigned)p.B * p.H * p.W * p.Cs * 4u), 0x00020000);
+      buf_rsrc(p.x, (int)((unsigned)p.B * p.H * p.W * p.Cs * 4u));
   const __amdgpu_buffer_rsrc_t rs_dy =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.dy, 0, (int)((unsigned)p.B * p.H * p.W * p.ldy * 4u), 0x00020000);
-  auto bload = [](__amdgpu_buffer_rsrc_t r, unsigned off) -> f32x4 {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
-  };
+      buf_rsrc(p.dy, (int)((unsigned)p.B * p.H * p.W * p.ldy * 4u));
   // input row rr of image b (zeros outside the image): scalar row base + thread constant
   auto load_x = [&](int rr, f32x4* rx) {
     const bool rok = rr >= 0 && rr < p.H;
     const unsigned base = (unsigned)(b * p.H + rr) * (unsigned)p.W * (unsigned)p.Cs * 4u;
 #pragma unroll
-    for (int it = 0; it < 2; ++it) rx[it] = bload(rs_x, (rok & (xoff[it] >= 0)) ? base + (unsigned)xoff[it] : OOB);
+    for (int it = 0; it < 2; ++it) rx[it] = buf_load16(rs_x, (rok & (xoff[it] >= 0)) ? base + (unsigned)xoff[it] : OOB);
   };
   auto load_y = [&](int rr, f32x4* ry) {
     const bool rok = rr < r1;  // rows past the segment (or the image) contribute nothing
     const unsigned base = (unsigned)(b * p.H + rr) * (unsigned)p.W * (unsigned)p.ldy * 4u;
 #pragma unroll
-    for (int it = 0; it < 2; ++it) ry[it] = bload(rs_dy, (rok & (yoff[it] >= 0)) ? base + (unsigned)yoff[it] : OOB);
+    for (int it = 0; it < 2; ++it) ry[it] = buf_load16(rs_dy, (rok & (yoff[it] >= 0)) ? base + (unsigned)yoff[it] : OOB);
   };
   auto store_x = [&](int rr, const f32x4* rx) {  // row rr lives in slot (rr + 1) & 3
     float* xs = Xs + ((rr + 1) & 3) * WS_XROW;

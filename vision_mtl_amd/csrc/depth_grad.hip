@@ -50,12 +50,6 @@ __device__ __forceinline__ void dg_yx(I i, int H, int W, int& y, int& x) {
 // sign as torch's: 0 at 0 (and at NaN)
 __device__ __forceinline__ float dg_sgn(float d) { return (float)((d > 0.f) - (d < 0.f)); }
 
-__device__ __forceinline__ double dg_wave_sum(double s) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  return s;
-}
-
 // The loads of a pixel never depend on a loaded value (validity selects, it does not branch), so all of them are in
 // flight together: these sweeps are latency-bound, not bandwidth-bound, at a few pixels per thread.  Counts come from
 // ballots (wave-uniform integers), sums from fp64 shuffles; the block's waves are folded in a fixed order behind one
@@ -79,8 +73,8 @@ __global__ __launch_bounds__(256) void dg_resid_kernel(const float* __restrict__
     s2 += (double)g * (double)g;
     resid[i] = g;
   }
-  s1 = dg_wave_sum(s1);
-  s2 = dg_wave_sum(s2);
+  s1 = wave_sum(s1);
+  s2 = wave_sum(s2);
   const int w = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) {
     shd[w * 3 + 0] = (double)n;
@@ -132,7 +126,7 @@ __global__ __launch_bounds__(256) void dg_stencil_kernel(const float* __restrict
   const int w = threadIdx.x >> 6;
 #pragma unroll
   for (int k = 0; k < SCALES; ++k) {
-    const double sk = dg_wave_sum(S[k]);
+    const double sk = wave_sum(S[k]);
     if ((threadIdx.x & 63) == 0) {
       shd[w * 2 * SCALES + 2 * k] = sk;
       shd[w * 2 * SCALES + 2 * k + 1] = (double)N[k];  // a count: exact in fp64
@@ -157,7 +151,7 @@ __global__ __launch_bounds__(1024) void dg_finalize_kernel(const double* __restr
   double s = 0.0;
   if (j < 3 + 2 * scales)
     for (int i = lane; i < nblk; i += 64) s += partial[(long long)j * nblk + i];
-  s = dg_wave_sum(s);
+  s = wave_sum(s);
   if (lane == 0) tot[j] = s;
   __syncthreads();
   if (threadIdx.x == 0) {

@@ -17,8 +17,7 @@ __global__ __launch_bounds__(256) void dwconv_fwd_kernel(const float* __restrict
                                                          float* __restrict__ y, int B, int H, int W, int Cs, int Ho,
                                                          int Wo, int K, int stride, int pad, long long total4) {
   const int CQ = Cs >> 2;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total4;
-       i += (long long)gridDim.x * blockDim.x) {
+  VMTL_GRID_STRIDE(i, total4) {
     const int q = (int)(i % CQ);
     const long long pix = i / CQ;
     const int wo = (int)(pix % Wo), ho = (int)((pix / Wo) % Ho), b = (int)(pix / ((long long)Wo * Ho));
@@ -231,8 +230,7 @@ __global__ __launch_bounds__(256) void dwconv_bwd_data_kernel(const float* __res
                                                               int B, int H, int W, int Cs, int Ho, int Wo, int K,
                                                               int stride, int pad, long long total4) {
   const int CQ = Cs >> 2;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total4;
-       i += (long long)gridDim.x * blockDim.x) {
+  VMTL_GRID_STRIDE(i, total4) {
     const int q = (int)(i % CQ);
     const long long pix = i / CQ;
     const int w = (int)(pix % W), h = (int)((pix / W) % H), b = (int)(pix / ((long long)W * H));
@@ -271,8 +269,7 @@ __global__ __launch_bounds__(256) void dwconv_bwd_data_tpl_kernel(const float* _
   constexpr int PAD = (K - 1) / 2;
   const int CQ = Cs >> 2;
   const int H2 = S == 2 ? H >> 1 : H, W2 = W >> 1;  // thread grid: stride 1 -> (H, W/2) pairs, stride 2 -> 2x2 blocks
-  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-       idx += (long long)gridDim.x * blockDim.x) {
+  VMTL_GRID_STRIDE(idx, total) {
     const int q = (int)(idx % CQ);
     const long long pix = idx / CQ;
     const int j = (int)(pix % W2), i = (int)((pix / W2) % H2), b = (int)(pix / ((long long)W2 * H2));

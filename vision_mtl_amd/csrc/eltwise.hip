@@ -21,10 +21,6 @@ static inline int ew_grid(long long total, int per_block = 256) {
   return (int)nb;
 }
 
-#define GRID_STRIDE(i, total)                                                           \
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (total);     \
-       i += (long long)gridDim.x * blockDim.x)
-
 // (channel quad, column, row, image) of flat float4 index i over a [B][H][W][CQ] map.  The decode is the bulk of the VALU work of
 // these streaming kernels: with 64-bit operands each division is ~100 instructions (bilinear x2 ran at 2.8 TB/s); every map of
 // this library has fewer than 2^31 float4 elements, so the 32-bit form is the one that runs (uniform switch).
@@ -62,7 +58,7 @@ struct CatSrc {
 __global__ __launch_bounds__(256) void concat2_kernel(CatSrc s0, CatSrc s1, float* __restrict__ y, int B, int H,
                                                       int W, int Cd, long long total4) {
   const int CQ = Cd >> 2;
-  GRID_STRIDE(i, total4) {
+  VMTL_GRID_STRIDE(i, total4) {
     const int q = (int)(i % CQ);
     const unsigned pix = (unsigned)(i / CQ);
     const unsigned w = pix % (unsigned)W, hb = pix / (unsigned)W;
@@ -109,7 +105,7 @@ __global__ __launch_bounds__(256) void concat2_bwd_kernel(const float* __restric
                                                           int Cs, int up, int oh, int ow, long long total4) {
   const int CQ = Cs >> 2;
   const bool aligned = (c_off & 3) == 0;
-  GRID_STRIDE(i, total4) {
+  VMTL_GRID_STRIDE(i, total4) {
     const int q = (int)(i % CQ);
     const unsigned pix = (unsigned)(i / CQ);
     const unsigned ws = pix % (unsigned)Ws, hb = pix / (unsigned)Ws;
@@ -167,7 +163,7 @@ extern "C" int vmtl_concat2_bwd(const float* dy, float* dx, int B, int H, int W,
 __global__ __launch_bounds__(256) void maxpool2_kernel(const float* __restrict__ x, float* __restrict__ y, int B,
                                                        int H, int W, int Cs, long long total4) {
   const int CQ = Cs >> 2, Ho = H >> 1, Wo = W >> 1;
-  GRID_STRIDE(i, total4) {
+  VMTL_GRID_STRIDE(i, total4) {
     const Pix4 px = decode_pix(i, CQ, Wo, Ho, total4 < (1ll << 31));
     const int q = px.q, wo = px.w, ho = px.h, b = px.b;
     const float* base = x + ((size_t)(b * H + 2 * ho) * W + 2 * wo) * Cs + (size_t)q * 4;
@@ -190,7 +186,7 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_kernel(const float* __restri
                                                            long long total4) {
   // one thread per OUTPUT pixel quad: recompute the argmax, write all four input gradients
   const int CQ = Cs >> 2, Ho = H >> 1, Wo = W >> 1;
-  GRID_STRIDE(i, total4) {
+  VMTL_GRID_STRIDE(i, total4) {
     const Pix4 px = decode_pix(i, CQ, Wo, Ho, total4 < (1ll << 31));
     const int q = px.q, wo = px.w, ho = px.h, b = px.b;
     const size_t o00 = ((size_t)(b * H + 2 * ho) * W + 2 * wo) * Cs + (size_t)q * 4;
@@ -255,7 +251,7 @@ __global__ __launch_bounds__(256) void bilinear_up2_kernel(const float* __restri
                                                            long long total4) {
   const int CQ = Cs >> 2, Ho = 2 * H, Wo = 2 * W;
   const bool small = total4 < (1ll << 31);
-  GRID_STRIDE(i, total4) {
+  VMTL_GRID_STRIDE(i, total4) {
     const Pix4 px = decode_pix(i, CQ, Wo, Ho, small);
     const int q = px.q, wo = px.w, ho = px.h, b = px.b;
     int h0, h1, w0, w1;
@@ -282,7 +278,7 @@ __global__ __launch_bounds__(256) void bilinear_up2_bwd_kernel(const float* __re
   // reciprocal scales once per thread (the candidate ranges below carry a margin of one pixel on each side, which absorbs the
   // rounding difference to a true division; every candidate is re-tested exactly with bil_coord)
   const float ish = 1.f / fmaxf(sh, 1e-20f), isw = 1.f / fmaxf(sw, 1e-20f);
-  GRID_STRIDE(i, total4) {
+  VMTL_GRID_STRIDE(i, total4) {
     const Pix4 px = decode_pix(i, CQ, W, H, small);
     const int q = px.q, w = px.w, h = px.h, b = px.b;
     // candidate output rows: those with floor(sh*ho) in {h-1, h} (clamped in float: sh may be 0)
@@ -364,7 +360,7 @@ __global__ __launch_bounds__(256) void channel_bcast_kernel(const float* __restr
                                                             float* __restrict__ y, int HW, int Cs, int mode,
                                                             long long total4) {
   const int CQ = Cs >> 2;
-  GRID_STRIDE(i, total4) {
+  VMTL_GRID_STRIDE(i, total4) {
     const int q = (int)(i % CQ);
     const int b = (int)(i / ((long long)CQ * HW));
     const f32x4 sv = *reinterpret_cast<const f32x4*>(s + (size_t)b * Cs + (size_t)q * 4);
@@ -427,7 +423,7 @@ __global__ __launch_bounds__(256) void stitch_kernel(const float* __restrict__ x
                                                      float* __restrict__ y, int C, int Cs, int wstride,
                                                      long long total4) {
   const int CQ = Cs >> 2;
-  GRID_STRIDE(i, total4) {
+  VMTL_GRID_STRIDE(i, total4) {
     const int q = (int)(i % CQ);
     f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
 #pragma unroll
@@ -454,7 +450,7 @@ extern "C" int vmtl_stitch(const float* x, const float* w, float* y, long long M
 // mode 3: y = a * s (s = *scalar_ptr)
 __global__ __launch_bounds__(256) void ew_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                  float* __restrict__ y, int mode, long long total) {
-  GRID_STRIDE(i, total) {
+  VMTL_GRID_STRIDE(i, total) {
     const float av = a[i];
     float r;
     if (mode == 0) r = av + b[i];
@@ -467,7 +463,7 @@ __global__ __launch_bounds__(256) void ew_kernel(const float* __restrict__ a, co
 
 __global__ __launch_bounds__(256) void axpby_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                     float* __restrict__ y, float wa, float wb, long long total) {
-  GRID_STRIDE(i, total) y[i] = wa * a[i] + wb * b[i];
+  VMTL_GRID_STRIDE(i, total) y[i] = wa * a[i] + wb * b[i];
 }
 
 // y = wa * a + wb * b (the weighted sum of the two task losses, reference lit_module.py:127-129)
@@ -483,7 +479,7 @@ extern "C" int vmtl_axpby(const float* a, const float* b, float* y, float wa, fl
 __global__ __launch_bounds__(256) void add_n_kernel(const f32x4* __restrict__ a, const f32x4* __restrict__ b,
                                                     const f32x4* __restrict__ c, const f32x4* __restrict__ d,
                                                     f32x4* __restrict__ y, long long n4) {
-  GRID_STRIDE(i, n4) {
+  VMTL_GRID_STRIDE(i, n4) {
     f32x4 r = a[i] + b[i];
     if (c != nullptr) r += c[i];
     if (d != nullptr) r += d[i];
@@ -513,7 +509,7 @@ extern "C" int vmtl_eltwise(const float* a, const float* b, float* y, int mode, 
 // like torch.argmax on ties)
 __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ z, long long* __restrict__ out, int HW,
                                                      int C, long long sb, long long sc, long long sp, long long P) {
-  GRID_STRIDE(i, P) {
+  VMTL_GRID_STRIDE(i, P) {
     const long long b = i / HW, hw = i - b * HW;
     const float* r = z + b * sb + hw * sp;
     float m = r[0];
@@ -541,7 +537,7 @@ extern "C" int vmtl_argmax_channels(const float* z, long long* out, int B, int H
 // wider tensor (y may point at a channel offset inside the pixel).
 __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restrict__ x, float* __restrict__ y, int C,
                                                            int HW, int Cs, int Cw, long long total) {
-  GRID_STRIDE(i, total) {
+  VMTL_GRID_STRIDE(i, total) {
     const int c = (int)(i % Cw);
     const long long pix = i / Cw;
     const int hw = (int)(pix % HW);
@@ -552,7 +548,7 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restri
 
 __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const float* __restrict__ x, float* __restrict__ y, int C,
                                                            int HW, int Cs, long long total) {
-  GRID_STRIDE(i, total) {
+  VMTL_GRID_STRIDE(i, total) {
     const int hw = (int)(i % HW);
     const long long bc = i / HW;
     const int c = (int)(bc % C);
@@ -584,7 +580,7 @@ extern "C" int vmtl_nhwc_to_nchw(const float* x, float* y, int B, int C, int HW,
 // [P][Cs] with zero pad channels; y = x * scale (scale = 1/255 for 8-bit sources that were not rescaled on the host).
 __global__ __launch_bounds__(256) void hwc_pad_kernel(const float* __restrict__ x, float* __restrict__ y, int C, int Cs,
                                                       float scale, long long total) {
-  GRID_STRIDE(i, total) {
+  VMTL_GRID_STRIDE(i, total) {
     const int c = (int)(i % Cs);
     const long long pix = i / Cs;
     y[i] = c < C ? x[pix * C + c] * scale : 0.f;

@@ -47,18 +47,6 @@ __device__ __forceinline__ void ea_pixel(float pf, float tf, float min_depth, Ea
   a.d3 += r < 1.953125 ? 1u : 0u;
 }
 
-__device__ __forceinline__ unsigned wave_sum_u(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // Segmentation part (P > 0): the LDS histogram of metrics.hip's confusion_kernel<true>, flushed into the int64 matrix.
 // Depth part (Pd > 0): the first nblk_d workgroups sweep the pixels and leave one row of partials each.
 // VEC: dpred / dtgt are 16-byte aligned (valid 4-byte aligned): float4 loads over Pd / 4 quads, scalar tail.
@@ -77,7 +65,7 @@ __global__ __launch_bounds__(256) void ea_accum_kernel(const long long* __restri
   if (P > 0) {
     for (int i = threadIdx.x; i < C * C; i += blockDim.x) hist[i] = 0u;
     __syncthreads();
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long long)gridDim.x * blockDim.x) {
+    VMTL_GRID_STRIDE(i, P) {
       const long long t = tgt[i], p = pred[i];
       if (t != ignore && t >= 0 && t < C && p >= 0 && p < C) atomicAdd(&hist[(int)t * C + (int)p], 1u);
     }
@@ -116,8 +104,8 @@ __global__ __launch_bounds__(256) void ea_accum_kernel(const long long* __restri
   }
   // wavefront sums by a fixed shuffle tree, then the four wavefronts in order: one row of partials per workgroup
 #pragma unroll
-  for (int k = 0; k < EA_NSUM; ++k) a.s[k] = wave_sum_d(a.s[k]);
-  const unsigned c0 = wave_sum_u(a.n), c1 = wave_sum_u(a.d1), c2 = wave_sum_u(a.d2), c3 = wave_sum_u(a.d3);
+  for (int k = 0; k < EA_NSUM; ++k) a.s[k] = wave_sum(a.s[k]);
+  const unsigned c0 = wave_sum(a.n), c1 = wave_sum(a.d1), c2 = wave_sum(a.d2), c3 = wave_sum(a.d3);
   __syncthreads();  // A
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll
@@ -132,12 +120,6 @@ __global__ __launch_bounds__(256) void ea_accum_kernel(const long long* __restri
   double* slot = partial + (size_t)k * nblk_d + blockIdx.x;  // k < EA_WS below
   if (k < EA_NSUM) *slot = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
   else if (k < EA_NSUM + 4) *reinterpret_cast<unsigned long long*>(slot) = cnt[k - EA_NSUM];
-}
-
-__device__ __forceinline__ unsigned long long wave_sum_ull(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // One workgroup: the workspace rows into acc in a fixed order, and / or a ready int32 step matrix into cm.
@@ -171,14 +153,14 @@ __global__ __launch_bounds__(256) void ea_fold_kernel(const double* __restrict__
     s[k] = v[0][k];
 #pragma unroll
     for (int r = 1; r < EA_FOLD_ROWS; ++r) s[k] += v[r][k];
-    s[k] = wave_sum_d(s[k]);
+    s[k] = wave_sum(s[k]);
   }
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     c[k] = u[0][k];
 #pragma unroll
     for (int r = 1; r < EA_FOLD_ROWS; ++r) c[k] += u[r][k];
-    c[k] = wave_sum_ull(c[k]);
+    c[k] = wave_sum(c[k]);
   }
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll

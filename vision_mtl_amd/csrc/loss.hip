@@ -23,21 +23,9 @@
 // (numerator, denominator) pairs and leaves the denominator in a two-float `stats` buffer on the device
 // (stats[0] = sum of weights over valid pixels, stats[1] = the weighted nll sum); the backward reads stats[0], so the
 // step never waits for the host.
-#include "common.h"
+#include "reduce.h"
 
 #define CE_THREADS 256
-
-__device__ __forceinline__ double block_sum_d(double v, double* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  const int nw = blockDim.x >> 6;
-  for (int i = 0; i < nw; ++i) s += sh[i];
-  return s;
-}
 
 // ------------------------------------------------------------------ cross entropy: what the variants do differently
 // The operands only the weighted / ignoring variant has.  weight: C floats or null (all ones); ignore: VMTL_NO_IGNORE
@@ -88,9 +76,9 @@ __device__ __forceinline__ void ce_add(double& num, double& den, long long t, in
 // partial: one double per block, or (numerator, denominator) per block
 template <bool EX>
 __device__ __forceinline__ void ce_store_partials(double num, double den, double* __restrict__ partial, double* shd) {
-  const double bn = block_sum_d(num, shd);
+  const double bn = block_sum(num, shd);
   if constexpr (EX) {
-    const double bd = block_sum_d(den, shd);
+    const double bd = block_sum(den, shd);
     if (threadIdx.x == 0) {
       partial[2 * blockIdx.x] = bn;
       partial[2 * blockIdx.x + 1] = bd;
@@ -142,7 +130,7 @@ __global__ __launch_bounds__(CE_THREADS) void ce_fwd_kernel(const float* __restr
                                                             int C, long long sb, long long sc, long long sp) {
   __shared__ double shd[4];
   double num = 0.0, den = 0.0;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long long)gridDim.x * blockDim.x) {
+  VMTL_GRID_STRIDE(i, P) {
     const long long b = i / HW, hw = i - b * HW;
     const float* r = z + b * sb + hw * sp;
     float m = r[0];
@@ -171,7 +159,7 @@ __global__ __launch_bounds__(CE_THREADS) void ce_fwd_regs_kernel(const float* __
                                                                  int C, long long sb, long long sc, long long sp) {
   __shared__ double shd[4];
   double num = 0.0, den = 0.0;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long long)gridDim.x * blockDim.x) {
+  VMTL_GRID_STRIDE(i, P) {
     const long long b = i / HW, hw = i - b * HW;
     const float* r = z + b * sb + hw * sp;
     float v[4 * Q];
@@ -202,7 +190,7 @@ __global__ void sum_finalize_kernel(const double* __restrict__ partial, int n, d
   __shared__ double shd[4];
   double s = 0.0;
   for (int i = threadIdx.x; i < n; i += blockDim.x) s += partial[i];
-  const double t = block_sum_d(s, shd);
+  const double t = block_sum(s, shd);
   if (threadIdx.x == 0) out[0] = (err != nullptr && err[0] != 0) ? __int_as_float(0x7fc00000) : (float)(t * scale);
 }
 
@@ -215,8 +203,8 @@ __global__ void ce_ex_finalize_kernel(const double* __restrict__ partial, int n,
     num += partial[2 * i];
     den += partial[2 * i + 1];
   }
-  num = block_sum_d(num, shd);
-  den = block_sum_d(den, shd);
+  num = block_sum(num, shd);
+  den = block_sum(den, shd);
   if (threadIdx.x == 0) {
     loss[0] = (float)(num / den);
     stats[0] = (float)den;
@@ -234,7 +222,7 @@ __global__ __launch_bounds__(CE_THREADS) void ce_bwd_kernel(const float* __restr
                                                             long long sp, long long dsb, long long dsc, long long dsp,
                                                             CeEx<EX> ex) {
   const float g = ce_grad_unit<EX>(gout, P, ex);
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long long)gridDim.x * blockDim.x) {
+  VMTL_GRID_STRIDE(i, P) {
     const long long b = i / HW, hw = i - b * HW;
     const long long off = b * sb + hw * sp, doff = b * dsb + hw * dsp;
     float m = z[off];
@@ -264,7 +252,7 @@ __global__ __launch_bounds__(CE_THREADS) void ce_bwd_nhwc_kernel(const float* __
   const float g = ce_grad_unit<EX>(gout, P, ex);
   const int Q = (C + 3) >> 2;
   const long long total = P * Q;
-  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+  VMTL_GRID_STRIDE(idx, total) {
     const long long i = idx / Q;
     const int q = (int)(idx - i * Q);
     const long long b = i / HW, hw = i - b * HW;
@@ -530,7 +518,7 @@ __global__ __launch_bounds__(256) void silog_fwd_kernel(const float* __restrict_
                                                         double* __restrict__ partial) {
   __shared__ double shd[4];
   double n = 0.0, s1 = 0.0, s2 = 0.0;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long long)gridDim.x * blockDim.x) {
+  VMTL_GRID_STRIDE(i, P) {
     if (valid(tgt, i)) {
       const float g = logf(pred[i]) - logf(tgt[i]);
       n += 1.0;
@@ -538,9 +526,9 @@ __global__ __launch_bounds__(256) void silog_fwd_kernel(const float* __restrict_
       s2 += (double)g * (double)g;
     }
   }
-  const double bn = block_sum_d(n, shd);
-  const double b1 = block_sum_d(s1, shd);
-  const double b2 = block_sum_d(s2, shd);
+  const double bn = block_sum(n, shd);
+  const double b1 = block_sum(s1, shd);
+  const double b2 = block_sum(s2, shd);
   if (threadIdx.x == 0) {
     partial[blockIdx.x * 3 + 0] = bn;
     partial[blockIdx.x * 3 + 1] = b1;
@@ -557,9 +545,9 @@ __global__ void silog_finalize_kernel(const double* __restrict__ partial, int nb
     s1 += partial[i * 3 + 1];
     s2 += partial[i * 3 + 2];
   }
-  n = block_sum_d(n, shd);
-  s1 = block_sum_d(s1, shd);
-  s2 = block_sum_d(s2, shd);
+  n = block_sum(n, shd);
+  s1 = block_sum(s1, shd);
+  s2 = block_sum(s2, shd);
   if (threadIdx.x == 0) {
     const double mu = s1 / n;                          // n == 0 -> NaN, as torch.mean of an empty tensor
     const double var = (s2 - n * mu * mu) / (n - 1.0); // n == 1 -> NaN (unbiased variance), as torch.var
@@ -580,7 +568,7 @@ __global__ __launch_bounds__(256) void silog_bwd_kernel(const float* __restrict_
   const float n = stats[0], mu = stats[1], dg = stats[2];
   const float k = gout[0] * 5.f / sqrtf(dg);
   const float a = 2.f / (n - 1.f), b = 0.3f * mu / n;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long long)gridDim.x * blockDim.x) {
+  VMTL_GRID_STRIDE(i, P) {
     float r = 0.f;
     if (valid(tgt, i)) {
       const float p = pred[i];
@@ -651,9 +639,9 @@ __global__ __launch_bounds__(256) void l1_fwd_kernel(const float* __restrict__ p
                                                      long long P, double* __restrict__ partial) {
   __shared__ double shd[4];
   double s = 0.0;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long long)gridDim.x * blockDim.x)
+  VMTL_GRID_STRIDE(i, P)
     s += (double)fabsf(pred[i] - tgt[i]);
-  const double b = block_sum_d(s, shd);
+  const double b = block_sum(s, shd);
   if (threadIdx.x == 0) partial[blockIdx.x] = b;
 }
 
@@ -661,7 +649,7 @@ __global__ __launch_bounds__(256) void l1_bwd_kernel(const float* __restrict__ p
                                                      const float* __restrict__ gout, long long P,
                                                      float* __restrict__ dpred) {
   const float g = gout[0] / (float)P;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long long)gridDim.x * blockDim.x) {
+  VMTL_GRID_STRIDE(i, P) {
     const float d = pred[i] - tgt[i];
     dpred[i] = d > 0.f ? g : (d < 0.f ? -g : 0.f);
   }

@@ -22,7 +22,7 @@ __global__ __launch_bounds__(256) void confusion_kernel(const long long* __restr
   extern __shared__ int hist[];
   for (int i = threadIdx.x; i < C * C; i += blockDim.x) hist[i] = 0;
   __syncthreads();
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (long long)gridDim.x * blockDim.x) {
+  VMTL_GRID_STRIDE(i, P) {
     const long long t = tgt[i], p = pred[i];
     if ((!IGN || t != ignore) && t >= 0 && t < C && p >= 0 && p < C) atomicAdd(&hist[(int)t * C + (int)p], 1);
   }

@@ -13,7 +13,7 @@
 //   depthwise  : R1=1 R0=1    T=KK    C=C    st=1 sc=KK                   flip=0
 //
 // Adam follows torch.optim.Adam (reference vision_mtl/training_lit.py:51,87).
-#include "common.h"
+#include "reduce.h"
 
 // scale (nullable): a per-INPUT-channel factor folded into the operand - the cross-stitch scale of the tensor the conv
 // reads (reference models/cross_stitch_model.py:32-37: y[a] = w[a,a,(c)] * x[a], always followed by a dense conv in the
@@ -24,8 +24,7 @@ __global__ __launch_bounds__(256) void pack_kernel(const float* __restrict__ src
                                                    int R0, int T, int C, int Cs, long long sr1, long long sr0,
                                                    long long st, long long sc, int flip, long long total,
                                                    const float* __restrict__ scale, int sstride, int smode) {
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
+  VMTL_GRID_STRIDE(i, total) {
     const int c = (int)(i % Cs);
     long long rest = i / Cs;
     const int tp = (int)(rest % T);
@@ -63,8 +62,7 @@ __global__ __launch_bounds__(256) void pack_batch_kernel(const PackDesc* __restr
     for (int k = threadIdx.x; k < n; k += 256) starts[k] = descs[k].start;
     __syncthreads();
   }
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
+  VMTL_GRID_STRIDE(i, total) {
     int lo = 0, hi = n - 1;  // last descriptor with start <= i
     while (lo < hi) {
       const int mid = (lo + hi + 1) >> 1;
@@ -106,8 +104,7 @@ extern "C" int vmtl_pack_weights_batch(const void* descs, int n, long long total
 __global__ __launch_bounds__(256) void pack_slice_kernel(const float* __restrict__ src, float* __restrict__ dst, int R0,
                                                          int T, int C, int group, long long sr0, long long st,
                                                          long long sc, int flip, long long total) {
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
+  VMTL_GRID_STRIDE(i, total) {
     const int c = (int)(i % C);
     long long rest = i / C;
     const int tp = (int)(rest % T);
@@ -259,6 +256,8 @@ __global__ __launch_bounds__(256) void stitch_wsum_kernel(const float* __restric
     const int r0 = j / T, t = j - r0 * T;
     a += (double)prod[((size_t)r0 * C + c) * T + t];
   }
+  // reduce.h's block_sum_thread0, written out: behind the helper the compiler orders this kernel's last instructions
+  // differently (profiles/shared_helpers/README.md)
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = a;
@@ -270,11 +269,8 @@ __global__ __launch_bounds__(256) void sum_vec_kernel(const float* __restrict__ 
   __shared__ double sh[4];
   double a = 0.0;
   for (int j = threadIdx.x; j < n; j += 256) a += (double)v[j];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = a;
-  __syncthreads();
-  if (threadIdx.x == 0) out[0] = (float)(sh[0] + sh[1] + sh[2] + sh[3]);
+  a = block_sum_thread0(a, sh);
+  if (threadIdx.x == 0) out[0] = (float)a;
 }
 
 // packed: nslabs slabs [R0][T][Cs] (forward packing of a (R0 = Cout, C = Cin, T taps) conv weight); grad: dL/dW in the
@@ -313,8 +309,7 @@ __global__ __launch_bounds__(256) void pack_up2_fwd_kernel(const float* __restri
                                                            int Cout, int C0, int C0s, int C1, int C1s,
                                                            long long total) {
   const int Cin = C0 + C1, Ktot = 4 * C0s + 9 * C1s;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
+  VMTL_GRID_STRIDE(i, total) {
     const int kk = (int)(i % Ktot);
     const long long rest = i / Ktot;
     const int n = (int)(rest % Cout), phase = (int)(rest / Cout);
@@ -343,8 +338,7 @@ __global__ __launch_bounds__(256) void pack_up2_fwd_kernel(const float* __restri
 // (dh, dw) paired with (kh, kw); rows c < C0 (4x4 / stride 2 / pad 1 convolution over dY)
 __global__ __launch_bounds__(256) void pack_up2_dgrad_kernel(const float* __restrict__ w, float* __restrict__ dst,
                                                              int Cout, int Cos, int C0, int Cin, long long total) {
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
+  VMTL_GRID_STRIDE(i, total) {
     const int n = (int)(i % Cos);
     long long rest = i / Cos;
     const int pos = (int)(rest % 16), c = (int)(rest / 16);
@@ -443,7 +437,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   const float bc2 = 1.f - powf(b2, step);
   const float step_size = lr / bc1;
   const float inv_sqrt_bc2 = 1.f / sqrtf(bc2);
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+  VMTL_GRID_STRIDE(i, n) {
     float gi = g[i] * gscale;
     const float pi = p[i];
     if (wd != 0.f) gi += wd * pi;

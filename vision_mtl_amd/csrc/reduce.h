@@ -1,5 +1,20 @@
 // Deterministic two-stage per-channel (column) reduction skeleton shared by the
-// BatchNorm, bias-gradient, depthwise-weight-gradient and stitch-gradient kernels.
+// BatchNorm, bias-gradient, depthwise-weight-gradient and stitch-gradient kernels,
+// and the workgroup sums of the library.
+//
+// Every sum here and in the kernels is run-to-run reproducible because its association order is fixed - but the orders
+// are NOT all the same, and they give different bits.  All start with the 64-lane xor tree 32, 16, .., 1 per wave
+// (wave_sum in common.h; the forms below spell it in place, which keeps their callers' instruction order) and differ in
+// how the waves' totals w0..w3 are combined:
+//
+//   form                               who gets the total   order of the waves
+//   block_sum, block_rows_sum          every thread         (((0.0 + w0) + w1) + w2) + w3 [+ .. for more waves]
+//   block_sum_thread0                  thread 0             ((w0 + w1) + w2) + w3
+//   block_sum_n<N>                     every thread         (w0 + w1) + (w2 + w3)
+//   eval_accum.hip, depth_grad.hip     the storing threads  ((w0 + w1) + w2) + w3, written out in the kernels
+//                                                           (several values per wave behind one barrier)
+//
+// A kernel keeps the form it has: moving it to another changes the last bits of its results.
 #pragma once
 #include "common.h"
 
@@ -162,6 +177,35 @@ __device__ __forceinline__ double block_sum(double s, double* sh /* >= 4 doubles
   double t = 0.0;
   for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += sh[i];
   return t;
+}
+
+// fp64 sum over a 256-thread workgroup (four waves) behind ONE barrier, for a kernel that ends with thread 0 storing
+// the total: every thread that reads the return value gets the total, in the order ((w0 + w1) + w2) + w3.
+// sh must not be in use when the call is made (there is no barrier in front of the writes).
+__device__ __forceinline__ double block_sum_thread0(double s, double* sh /* >= 4 doubles */) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+  __syncthreads();
+  return sh[0] + sh[1] + sh[2] + sh[3];
+}
+
+// fp64 sums of N values per thread over a 256-thread workgroup: out[i] (i < N) valid on every thread after the
+// call.  One barrier pair; fixed association order (run-to-run reproducible).
+template <int N>
+__device__ __forceinline__ void block_sum_n(double (&s)[N], double (*sh)[N] /* [4][N] */) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s[i] += __shfl_xor(s[i], o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) sh[threadIdx.x >> 6][i] = s[i];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < N; ++i) s[i] = (sh[0][i] + sh[1][i]) + (sh[2][i] + sh[3][i]);
 }
 
 // Row sweep without a reduction: same thread -> (row offset, float4 column) mapping as

@@ -28,10 +28,6 @@ static inline int tta_grid(long long P) {
   return (int)nb;
 }
 
-#define TTA_PIXELS(i, P)                                                                \
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (P);         \
-       i += (long long)gridDim.x * blockDim.x)
-
 // pixel i of [B][H][W] -> (b, y, x); the 32-bit form is the one that runs (uniform switch: 64-bit divisions are ~100
 // instructions each), the 64-bit one takes over when B * H * W passes 2^31
 __device__ __forceinline__ void tta_byx(long long i, int H, int W, bool small, int& b, int& y, int& x) {
@@ -109,7 +105,7 @@ template <int LD, bool SAME>
 __global__ __launch_bounds__(256) void tta_view_kernel(const float* __restrict__ img, f32x4* __restrict__ out, int H,
                                                        int W, int Ho, int Wo, float sh, float sw, int flip,
                                                        long long P, bool small) {
-  TTA_PIXELS(i, P) {
+  VMTL_GRID_STRIDE(i, P) {
     int b, y, x;
     tta_byx(i, Ho, Wo, small, b, y, x);
     // resample first, mirror after: output column x shows column Wo - 1 - x of the resized image
@@ -154,7 +150,7 @@ __global__ __launch_bounds__(256) void tta_accumulate_kernel(const float* __rest
                                                              int flip, float weight, float depth_weight, int first,
                                                              long long P, bool small) {
   const size_t hw = (size_t)h * w, HW = (size_t)H * W;
-  TTA_PIXELS(i, P) {
+  VMTL_GRID_STRIDE(i, P) {
     int b, y, x;
     tta_byx(i, H, W, small, b, y, x);
     const TtaTaps t = tta_taps<SAME>(y, x, h, w, sh, sw, flip);
@@ -238,7 +234,7 @@ __global__ __launch_bounds__(256) void tta_finish_same_kernel(const float* __res
                                                               float* __restrict__ confidence, int C, long long HW,
                                                               long long P, bool small) {
   const bool conf = confidence != nullptr;
-  TTA_PIXELS(i, P) {
+  VMTL_GRID_STRIDE(i, P) {
     long long b, pix;
     if (small) {
       const unsigned u = (unsigned)i, q = u / (unsigned)HW;
@@ -274,7 +270,7 @@ __global__ __launch_bounds__(256) void tta_finish_rows_kernel(const float* __res
                                                               bool small) {
   const size_t HW = (size_t)H * W;
   const bool conf = confidence != nullptr;
-  TTA_PIXELS(i, PG) {
+  VMTL_GRID_STRIDE(i, PG) {
     int b, g, x;
     tta_byx(i, G, Wo, small, b, g, x);
     int x0, x1;
