@@ -394,7 +394,7 @@ def test_up2_conv(dev, case):
     _check_up2(dev, case)
 
 
-@pytest.mark.parametrize("tile", [0, 3, 5, 9, 12, 13, 14, 15])
+@pytest.mark.parametrize("tile", list(range(16)))  # the one tile dispatch instantiates the UP2 form for every id
 def test_up2_conv_forced_tile(dev, tile, vmtl_env):
     vmtl_env("VMTL_FORCE_TILE", str(tile))
     _check_up2(dev, (2, 24, 6, 10, 12, 35))

@@ -454,10 +454,7 @@ __global__ __launch_bounds__(256) void oh_bwd_nhwc_rows_kernel(const float* __re
 
 // ------------------------------------------------------------------ entry points
 static inline int oh_blocks(long long P) {
-  long long nb = cdivll(P, OH_THREADS);
-  if (nb > OH_BLOCKS_MAX) nb = OH_BLOCKS_MAX;
-  if (nb < 1) nb = 1;
-  return (int)nb;
+  return grid_1d(P, OH_THREADS, OH_BLOCKS_MAX);
 }
 
 // the cleared head (counters, three histograms) and (sum w nll, sum w, kept) per block of the sum pass
@@ -522,10 +519,9 @@ extern "C" int vmtl_ce_ohem_bwd(const float* logits, const long long* target, co
   const long long P = (long long)B * HW;
   const OhBwd ex = {weight, ignore_index, stats, nll};
   if (dsc == 1 && dsp == ((C + 3) & ~3) && dsp <= 32 && dsb == dsp * HW) {
-    long long nb = cdivll(P, 256);
-    if (nb > 8192) nb = 8192;
-#define CALL(QV)                                                                                              \
-  hipLaunchKernelGGL((oh_bwd_nhwc_rows_kernel<QV>), dim3((int)nb), dim3(256), 0, st, logits, target, grad_out, \
+    const int nb = grid_1d(P, 256, 8192);
+#define CALL(QV)                                                                                         \
+  hipLaunchKernelGGL((oh_bwd_nhwc_rows_kernel<QV>), dim3(nb), dim3(256), 0, st, logits, target, grad_out, \
                      dlogits, P, HW, C, sb, sc, sp, ex)
     switch ((int)dsp >> 2) {
       case 1: CALL(1); break;
@@ -539,9 +535,8 @@ extern "C" int vmtl_ce_ohem_bwd(const float* logits, const long long* target, co
     }
 #undef CALL
   } else if (dsc == 1 && (dsp & 3) == 0 && dsp >= ((C + 3) & ~3) && dsb == dsp * HW) {
-    long long nb = cdivll(P * ((C + 3) >> 2), OH_THREADS);
-    if (nb > 8192) nb = 8192;
-    hipLaunchKernelGGL(oh_bwd_nhwc_kernel, dim3((int)nb), dim3(OH_THREADS), 0, st, logits, target, grad_out, dlogits, P,
+    const int nb = grid_1d(P * ((C + 3) >> 2), OH_THREADS, 8192);
+    hipLaunchKernelGGL(oh_bwd_nhwc_kernel, dim3(nb), dim3(OH_THREADS), 0, st, logits, target, grad_out, dlogits, P,
                        HW, C, sb, sc, sp, (int)dsp, ex);
   } else {
     hipLaunchKernelGGL(oh_bwd_kernel, dim3(oh_blocks(P)), dim3(OH_THREADS), 0, st, logits, target, grad_out, dlogits, P,

@@ -71,6 +71,25 @@ static inline int env_int(EnvInt& e) {
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline long long cdivll(long long a, long long b) { return (a + b - 1) / b; }
 
+// Blocks of a 1-D grid whose kernel strides over n items (VMTL_GRID_STRIDE): one block per `per_block` items, at least
+// 1 and at most `cap`.  per_block and cap are each launch site's own (several were tuned).
+static inline int grid_1d(long long n, int per_block, int cap) {
+  const long long nb = cdivll(n, per_block);
+  return nb < 1 ? 1 : (nb > cap ? cap : (int)nb);
+}
+
+// Compute units of the current device, queried once per process (version.hip); 256 when the query fails.
+int vmtl_num_cus();
+
+// Opts `kernel` into `bytes` of dynamic LDS (a launch that asks for more than 64 KB fails without it).  Set on every
+// launch: a function attribute is per device, and a cached flag would be neither thread-safe nor right for a second
+// GPU of the process (the call is a cheap driver-side table update).
+static inline int allow_dynamic_lds(const void* kernel, size_t bytes) {
+  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e != hipSuccess) vmtl_last_hip_error = (int)e;
+  return e == hipSuccess ? VMTL_OK : VMTL_ERR_LAUNCH;
+}
+
 __device__ __forceinline__ float act_fwd(float v, int act) {
   switch (act) {
     case VMTL_ACT_RELU: return v > 0.f ? v : 0.f;

@@ -373,9 +373,8 @@ template <int CS, int TN, bool TAIL>
 static int launch_halo(HaloP& p, hipStream_t st) {
   using C = HaloCfg<CS, TN, TAIL>;
   static_assert(C::LDS_BYTES * 2 <= 160 * 1024, "two workgroups per CU");
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_halo_kernel<CS, TN, TAIL>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES) != hipSuccess)
-    return VMTL_ERR_LAUNCH;
+  const int rc = allow_dynamic_lds(reinterpret_cast<const void*>(&conv3x3_halo_kernel<CS, TN, TAIL>), C::LDS_BYTES);
+  if (rc) return rc;
   p.tiles_x = cdiv(p.W, CH_TW);
   p.tiles_y = cdiv(p.H, CH_TM);
   hipLaunchKernelGGL((conv3x3_halo_kernel<CS, TN, TAIL>), dim3(p.B * p.tiles_x * p.tiles_y), dim3(256), C::LDS_BYTES, st, p);

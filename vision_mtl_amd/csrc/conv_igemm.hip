@@ -36,37 +36,37 @@
 #define LDT BK  // un-padded 128-byte rows; the 16-byte slot index is XOR-swizzled with (row & 7)
 
 struct ConvP {
-  const float* x;     // [B][H][W][Cs]
-  const float* wp;    // [Nw][Ktot]
-  const float* bias;  // [Nw] or nullptr
-  float* y;           // [B][Ho][Wo][ldy]  (or pixel-shuffled, see shuffle)
-  float* stats;       // optional [tiles_m][2][ldy] per-row-block column (mean, M2) for BatchNorm
-  int B, H, W, Cs;
-  int Ho, Wo, ldy;
-  int Nw;             // valid weight rows (Cout, or 4*Cout for shuffle)
-  int Cout;           // logical channels written non-zero per output pixel
-  int KH, KW, stride, pad;
-  int Ktot, M;
-  int act;
-  int shuffle;        // 1: rows n=(u*2+v)*Cout+co are scattered to (2h+u, 2w+v, co)
-  int tiles_m, tiles_n;
+  const float* x = nullptr;     // [B][H][W][Cs]
+  const float* wp = nullptr;    // [Nw][Ktot]
+  const float* bias = nullptr;  // [Nw] or nullptr
+  float* y = nullptr;           // [B][Ho][Wo][ldy]  (or pixel-shuffled, see shuffle)
+  float* stats = nullptr;       // optional [tiles_m][2][ldy] per-row-block column (mean, M2) for BatchNorm
+  int B = 0, H = 0, W = 0, Cs = 0;
+  int Ho = 0, Wo = 0, ldy = 0;
+  int Nw = 0;         // valid weight rows (Cout, or 4*Cout for shuffle)
+  int Cout = 0;       // logical channels written non-zero per output pixel
+  int KH = 0, KW = 0, stride = 0, pad = 0;
+  int Ktot = 0, M = 0;
+  int act = 0;
+  int shuffle = 0;    // 1: rows n=(u*2+v)*Cout+co are scattered to (2h+u, 2w+v, co)
+  int tiles_m = 0, tiles_n = 0;  // set by the launcher from the tile it instantiates
   // UP2 mode (nearest-x2 upsample of x, concat with x2, 3x3 conv, evaluated as four 2x2 phase convs on
   // the low-res map): x is the LOW-res source [B][H][W][Cs]; x2 the full-res skip [B][2H][2W][C2s] (may
   // be null); wp holds 4 phase matrices [4][Nw][Ktot], Ktot = 4*Cs + 9*C2s; M = B*H*W rows per phase.
-  const float* x2;
-  int C2s;
+  const float* x2 = nullptr;
+  int C2s = 0;
   // split-K (launches without bias / activation / stats / shuffle only): blockIdx.y = K slice, every
   // slice writes its partial tile to ksl_out + slice * M * ldy; vmtl_sum_slabs adds them into y.
-  int ksplit, ksteps_per_split;
+  int ksplit = 1, ksteps_per_split = 0;
   // BatchNorm + activation BACKWARD of the layer that produced the tensor whose gradient this launch computes
   // (data-gradient launches only; ez_x = null: off): y = acc * act'(gamma*xhat + beta), xhat = (ez_x - mean)*invstd,
   // and stats[tile_m][2][ldy] = per-row-block column sums (sum y, sum y*xhat) instead of (mean, M2).
-  const float* ez_x;  // [M][ldy], the producer's pre-BatchNorm activation
-  const float* ez_mean;
-  const float* ez_invstd;
-  const float* ez_gamma;
-  const float* ez_beta;
-  int ez_act;
+  const float* ez_x = nullptr;  // [M][ldy], the producer's pre-BatchNorm activation
+  const float* ez_mean = nullptr;
+  const float* ez_invstd = nullptr;
+  const float* ez_gamma = nullptr;
+  const float* ez_beta = nullptr;
+  int ez_act = 0;
 };
 
 // NT > 0: the last NT output columns of the tile ("tail") are not given an MFMA tile of their own; every
@@ -859,25 +859,107 @@ __global__ __launch_bounds__(256, (TM * TN >= 20 && WAVES_N == 2) ? 2 : 1) void 
 }
 
 // ---------------------------------------------------------------------------
-// host-side tile selection + launchers
+// host side: launchers, tile selection, entry points
 // ---------------------------------------------------------------------------
-struct TileCfg { int bm, bn; float eff; };
-// id -> <TM, TN, WAVES_M, WAVES_N[, tail]>
-//  0 <2,2,4,1> 128x32    1 <2,3,4,1> 128x48    2 <2,4,4,1> 128x64    3 <2,5,4,1> 128x80
-//  4 <4,3,2,2> 128x96    5 <4,4,2,2> 128x128   6 <2,9,4,1> 128x144   7 <4,5,2,2> 128x160
-//  8 <1,2,4,1> 64x32     9 <1,4,4,1> 64x64    10 <2,4,2,2> 64x128   11 <1,9,4,1> 64x144
-// 12 <2,2,4,1,+4> 128x(32+4)   13 <2,1,4,1,+4> 128x(16+4)   14 <2,4,4,1,+4> 128x(64+4)   (VALU tail columns)
-// 15 <2,1,4,1> 128x16
-// eff = measured MFMA-rate of the tile relative to the 144-wide one on MI355X (tools/bench_conv.py):
-// narrow tiles re-stage the A operand more often per MFMA.
-static const TileCfg kTiles[] = {{128, 32, 0.62f}, {128, 48, 0.72f}, {128, 64, 0.80f}, {128, 80, 0.88f},
-                                 {128, 96, 0.92f}, {128, 128, 0.95f}, {128, 144, 1.0f}, {128, 160, 1.0f},
-                                 {64, 32, 0.50f},  {64, 64, 0.85f},  {64, 128, 0.75f},  {64, 144, 1.0f},
-                                 {128, 36, 0.62f}, {128, 20, 0.43f}, {128, 68, 0.85f}, {128, 16, 0.38f}};
+// opt-in bf16x3 operand split for the wide tiles (VMTL_BF16X3=1); see the kernel comment
+static bool conv_bf16x3() {
+  static EnvInt e{"VMTL_BF16X3", 0};  // cached; the parity tests toggle it through vmtl_reload_env()
+  return env_int(e) == 1;
+}
+
+// LDS-DMA staging depth: 0 = register staging.  VMTL_GLDS overrides (tuning aid).
+static int conv_glds_stages() {
+  static EnvInt e{"VMTL_GLDS", 0};
+  const int v = env_int(e);
+  return (v == 2 || v == 3) ? v : 0;
+}
+
+template <int TM, int TN, int WMV, int WNV, bool UP2, int NT, int NS, int PL = 0>
+static int launch_conv_ns(ConvP& p, hipStream_t st) {
+  constexpr int BM = WMV * TM * 16, BN = WNV * TN * 16 + NT;
+  p.tiles_m = cdiv(p.M, BM) * (UP2 ? 4 : 1);
+  p.tiles_n = cdiv(p.shuffle ? p.Nw : p.ldy, BN);
+  // buffer addressing: every operand is reached through a 32-bit byte offset
+  if ((long long)p.B * p.H * p.W * p.Cs * 4 >= (1ll << 32) || (long long)p.Nw * p.Ktot * 4 >= (1ll << 32) ||
+      (UP2 && (long long)16 * p.B * p.H * p.W * p.C2s >= (1ll << 32)))
+    return VMTL_ERR_UNSUPPORTED;
+  constexpr int NBUF = NS >= 2 ? NS : 2;
+  constexpr int BNR = NS >= 2 ? (BN + 31) / 32 * 32 : BN;
+  const size_t lds = PL ? (size_t)2 * PL * (BM + BN) * 64 : (size_t)NBUF * (BM + BNR) * LDT * sizeof(float);
+  const int rc = allow_dynamic_lds(reinterpret_cast<const void*>(&conv_igemm_kernel<TM, TN, WMV, WNV, UP2, NT, NS, PL>), lds);
+  if (rc) return rc;
+  hipLaunchKernelGGL((conv_igemm_kernel<TM, TN, WMV, WNV, UP2, NT, NS, PL>),
+                     dim3(p.tiles_m * p.tiles_n, p.ksplit > 1 ? p.ksplit : 1), dim3(256), lds, st, p);
+  return vmtl_check_launch();
+}
+
+template <int TM, int TN, int WMV, int WNV, bool UP2, int NT>
+static int launch_conv(ConvP& p, hipStream_t st, int prec) {
+  // bf16 precision: one plane, register staging; the tuning switches below (VMTL_BF16X3, VMTL_GLDS) are fp32-only
+  if (prec == VMTL_PREC_BF16) return launch_conv_ns<TM, TN, WMV, WNV, UP2, NT, 0, 1>(p, st);
+  if constexpr (NT == 0 && WNV * TN >= 5) {
+    // long K loops only: the three planes need 1.5x the LDS (one workgroup per CU for the 128-row tiles), which a
+    // 4-6 step loop cannot amortise (MTAN's full-resolution 1x1 convs ran 40 % slower with it)
+    if (conv_bf16x3() && cdiv(p.Ktot, BK) >= 24) return launch_conv_ns<TM, TN, WMV, WNV, UP2, NT, 0, 3>(p, st);
+  }
+  if constexpr (!UP2 && (WMV * TM) % 2 == 0) {
+    const int ns = conv_glds_stages();
+    if (ns == 2) return launch_conv_ns<TM, TN, WMV, WNV, UP2, NT, 2>(p, st);
+    if (ns == 3) return launch_conv_ns<TM, TN, WMV, WNV, UP2, NT, 3>(p, st);
+  }
+  return launch_conv_ns<TM, TN, WMV, WNV, UP2, NT, 0>(p, st);
+}
+
+// The tile configurations, stated once: X(id, TM, TN, WAVES_M, WAVES_N, NT, eff).  A tile covers
+// WAVES_M*TM*16 output rows and WAVES_N*TN*16 MFMA columns plus NT VALU tail columns (NT above the kernel).
+// eff = measured MFMA rate of the tile relative to the 144-wide one on MI355X (tools/bench_conv.py): narrow tiles
+// re-stage the A operand more often per MFMA.  kTiles[] (what the geometry queries size buffers from) and
+// launch_tile() (the kernel that runs) are both generated from this list.
+#define VMTL_CONV_TILES(X)                      \
+  X(0, 2, 2, 4, 1, 0, 0.62f)  /* 128 x 32   */  \
+  X(1, 2, 3, 4, 1, 0, 0.72f)  /* 128 x 48   */  \
+  X(2, 2, 4, 4, 1, 0, 0.80f)  /* 128 x 64   */  \
+  X(3, 2, 5, 4, 1, 0, 0.88f)  /* 128 x 80   */  \
+  X(4, 4, 3, 2, 2, 0, 0.92f)  /* 128 x 96   */  \
+  X(5, 4, 4, 2, 2, 0, 0.95f)  /* 128 x 128  */  \
+  X(6, 2, 9, 4, 1, 0, 1.0f)   /* 128 x 144  */  \
+  X(7, 4, 5, 2, 2, 0, 1.0f)   /* 128 x 160  */  \
+  X(8, 1, 2, 4, 1, 0, 0.50f)  /*  64 x 32   */  \
+  X(9, 1, 4, 4, 1, 0, 0.85f)  /*  64 x 64   */  \
+  X(10, 2, 4, 2, 2, 0, 0.75f) /*  64 x 128  */  \
+  X(11, 1, 9, 4, 1, 0, 1.0f)  /*  64 x 144  */  \
+  X(12, 2, 2, 4, 1, 4, 0.62f) /* 128 x 32+4 */  \
+  X(13, 2, 1, 4, 1, 4, 0.43f) /* 128 x 16+4 */  \
+  X(14, 2, 4, 4, 1, 4, 0.85f) /* 128 x 64+4 */  \
+  X(15, 2, 1, 4, 1, 0, 0.38f) /* 128 x 16   */
+
+struct TileCfg { int id, bm, bn; float eff; };
+#define VMTL_TILE_CFG(id, TM, TN, WMV, WNV, NT, eff) {id, WMV * TM * 16, WNV * TN * 16 + NT, eff},
+static constexpr TileCfg kTiles[] = {VMTL_CONV_TILES(VMTL_TILE_CFG)};
+#undef VMTL_TILE_CFG
 #define VMTL_NTILES 16
 #define VMTL_NBIG 12
 static const int kBigIds[] = {0, 1, 2, 3, 4, 5, 6, 7, 12, 13, 14, 15};
 static const int kSmallIds[] = {8, 9, 10, 11};
+
+static constexpr bool tiles_in_id_order() {
+  for (int i = 0; i < VMTL_NTILES; ++i)
+    if (kTiles[i].id != i) return false;
+  return true;
+}
+static_assert(sizeof(kTiles) / sizeof(kTiles[0]) == VMTL_NTILES && tiles_in_id_order(), "kTiles[] is indexed by tile id");
+
+// the kernel of tile `id`; an id outside the list runs the last configuration
+template <bool UP2>
+static int launch_tile(int id, ConvP& p, hipStream_t st, int prec) {
+  switch (id) {
+#define VMTL_TILE_CASE(id, TM, TN, WMV, WNV, NT, eff) \
+  case id: return launch_conv<TM, TN, WMV, WNV, UP2, NT>(p, st, prec);
+    VMTL_CONV_TILES(VMTL_TILE_CASE)
+#undef VMTL_TILE_CASE
+    default: return launch_tile<UP2>(VMTL_NTILES - 1, p, st, prec);
+  }
+}
 
 static int pick_from(const int* ids, int n, int ncols) {
   // minimise issued MFMA work / tile efficiency = (padded columns) / eff
@@ -893,8 +975,6 @@ static int pick_from(const int* ids, int n, int ncols) {
   }
   return best;
 }
-
-static bool conv_bf16x3();
 
 // VMTL_FORCE_TILE=id: every launch uses that tile configuration (cached, see env_int)
 static int forced_tile() {
@@ -924,62 +1004,7 @@ extern "C" int vmtl_conv2d_stats_block(int B, int Ho, int Wo, int ldy) {
   return kTiles[conv_pick_tile(B * Ho * Wo, ldy)].bm;
 }
 
-template <int TM, int TN, int WMV, int WNV, bool UP2, int NT, int NS, int PL = 0>
-static int launch_conv_ns(ConvP& p, hipStream_t st);
-
-// opt-in bf16x3 operand split for the wide tiles (VMTL_BF16X3=1); see the kernel comment
-static bool conv_bf16x3() {
-  static EnvInt e{"VMTL_BF16X3", 0};  // cached; the parity tests toggle it through vmtl_reload_env()
-  return env_int(e) == 1;
-}
-
-// LDS-DMA staging depth: 0 = register staging.  VMTL_GLDS overrides (tuning aid).
-static int conv_glds_stages() {
-  static EnvInt e{"VMTL_GLDS", 0};
-  const int v = env_int(e);
-  return (v == 2 || v == 3) ? v : 0;
-}
-
-template <int TM, int TN, int WMV, int WNV, bool UP2 = false, int NT = 0>
-static int launch_conv(ConvP& p, hipStream_t st, int prec) {
-  // bf16 precision: one plane, register staging; the tuning switches below (VMTL_BF16X3, VMTL_GLDS) are fp32-only
-  if (prec == VMTL_PREC_BF16) return launch_conv_ns<TM, TN, WMV, WNV, UP2, NT, 0, 1>(p, st);
-  if constexpr (NT == 0 && WNV * TN >= 5) {
-    // long K loops only: the three planes need 1.5x the LDS (one workgroup per CU for the 128-row tiles), which a
-    // 4-6 step loop cannot amortise (MTAN's full-resolution 1x1 convs ran 40 % slower with it)
-    if (conv_bf16x3() && cdiv(p.Ktot, BK) >= 24) return launch_conv_ns<TM, TN, WMV, WNV, UP2, NT, 0, 3>(p, st);
-  }
-  if constexpr (!UP2 && (WMV * TM) % 2 == 0) {
-    const int ns = conv_glds_stages();
-    if (ns == 2) return launch_conv_ns<TM, TN, WMV, WNV, UP2, NT, 2>(p, st);
-    if (ns == 3) return launch_conv_ns<TM, TN, WMV, WNV, UP2, NT, 3>(p, st);
-  }
-  return launch_conv_ns<TM, TN, WMV, WNV, UP2, NT, 0>(p, st);
-}
-
-template <int TM, int TN, int WMV, int WNV, bool UP2, int NT, int NS, int PL>
-static int launch_conv_ns(ConvP& p, hipStream_t st) {
-  constexpr int BM = WMV * TM * 16, BN = WNV * TN * 16 + NT;
-  p.tiles_m = cdiv(p.M, BM) * (UP2 ? 4 : 1);
-  p.tiles_n = cdiv(p.shuffle ? p.Nw : p.ldy, BN);
-  // buffer addressing: every operand is reached through a 32-bit byte offset
-  if ((long long)p.B * p.H * p.W * p.Cs * 4 >= (1ll << 32) || (long long)p.Nw * p.Ktot * 4 >= (1ll << 32) ||
-      (UP2 && (long long)16 * p.B * p.H * p.W * p.C2s >= (1ll << 32)))
-    return VMTL_ERR_UNSUPPORTED;
-  constexpr int NBUF = NS >= 2 ? NS : 2;
-  constexpr int BNR = NS >= 2 ? (BN + 31) / 32 * 32 : BN;
-  const size_t lds = PL ? (size_t)2 * PL * (BM + BN) * 64 : (size_t)NBUF * (BM + BNR) * LDT * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<TM, TN, WMV, WNV, UP2, NT, NS, PL>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((conv_igemm_kernel<TM, TN, WMV, WNV, UP2, NT, NS, PL>),
-                     dim3(p.tiles_m * p.tiles_n, p.ksplit > 1 ? p.ksplit : 1), dim3(256), lds, st, p);
-  return vmtl_check_launch();
-}
-
+// ---- split-K: K slices into slabs, then their sum -------------------------------------------------
 // y = sum of the K-slice slabs (+ bias[n], n = column of a [rows][ldy] matrix; pad columns n >= Cout stay 0)
 __global__ __launch_bounds__(256) void sum_slabs_kernel(const float* __restrict__ slabs, float* __restrict__ y,
                                                         int nslabs, long long n4, const float* __restrict__ bias,
@@ -997,26 +1022,67 @@ __global__ __launch_bounds__(256) void sum_slabs_kernel(const float* __restrict_
   }
 }
 
-// K slices a forward/dgrad launch of this shape would use (1 = none).  Only launches without
-// bias/activation/stats/shuffle are split; the caller then passes a workspace of
-// splits * B*Ho*Wo * ldy floats (vmtl_conv2d_fwd_ws) and the partial tiles are summed in slice order.
 // K slices for a tile grid of `blocks` workgroups and nk K steps: split while the grid alone leaves the chip under-filled
 // (fewer than VMTL_KSPLIT_BLOCKS workgroups, default 512 = two per CU: one 4-wave workgroup per CU is one wave per SIMD
 // and hides no latency - decoder block 0 at bs 32 ran at 82 TF on 256 workgroups), at least 16 K steps per slice
 static int ksplit_for(long long blocks, int nk, int ldy) {
   static EnvInt e_blocks{"VMTL_KSPLIT_BLOCKS", 512};  // tuning aid
   const int target = env_int(e_blocks);
-  if (blocks >= target || nk < 32 || (ldy & 3)) return 1;
+  if (blocks <= 0 || blocks >= target || nk < 32 || (ldy & 3)) return 1;
   long long s = cdivll(target, blocks);
   if (s > 8) s = 8;
   if (s > nk / 16) s = nk / 16;
   return s < 2 ? 1 : (int)s;
 }
 
+// The split-K launch of tile `id`: `splits` K slices write their partial tiles to the slabs `ws` ([splits] x the
+// layout of y, full-resolution for UP2), which are then summed in slice order into y (+ bias).
+template <bool UP2>
+static int launch_split(int id, ConvP& p, int splits, float* ws, float* y, const float* bias, hipStream_t st, int prec) {
+  p.y = ws;
+  p.ksplit = splits;
+  p.ksteps_per_split = cdiv(cdiv(p.Ktot, BK), splits);
+  const int rc = launch_tile<UP2>(id, p, st, prec);
+  if (rc) return rc;
+  const long long n4 = (long long)(UP2 ? 4 : 1) * p.M * p.ldy / 4;
+  hipLaunchKernelGGL(sum_slabs_kernel, dim3(grid_1d(n4, 256, 4096)), dim3(256), 0, st, ws, y, splits, n4, bias, p.ldy,
+                     p.Cout);
+  return vmtl_check_launch();
+}
+
+// ---- plain convolution ----------------------------------------------------------------------------
+// K slices a forward/dgrad launch of this shape would use (1 = none, also for an empty shape).  Only launches without
+// bias/activation/stats/shuffle are split; the caller then passes a workspace of
+// splits * B*Ho*Wo * ldy floats (vmtl_conv2d_fwd_ws) and the partial tiles are summed in slice order.
 extern "C" int vmtl_conv2d_ksplit(int B, int Ho, int Wo, int ldy, int Ktot) {
+  if (B <= 0 || Ho <= 0 || Wo <= 0 || ldy <= 0 || Ktot <= 0) return 1;
   const int M = B * Ho * Wo;
   const int id = conv_pick_tile(M, ldy);
   return ksplit_for((long long)cdiv(M, kTiles[id].bm) * cdiv(ldy, kTiles[id].bn), cdiv(Ktot, BK), ldy);
+}
+
+// the argument check of every plain entry point (direct and split-K), after the precision
+static int conv2d_check(const float* x, const float* wp, const float* y, const float* stats, int B, int H, int W, int Cs,
+                        int Ho, int Wo, int ldy, int Nw, int Cout, int KH, int KW, int stride, int pad, int shuffle) {
+  if (!x || !wp || !y) return VMTL_ERR_ARG;
+  if (Cs <= 0 || (Cs & 3) || B <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0) return VMTL_ERR_ARG;
+  if (KH <= 0 || KW <= 0 || stride <= 0 || pad < 0 || Nw <= 0 || Cout <= 0 || ldy <= 0) return VMTL_ERR_ARG;
+  if (!shuffle && (Cout > ldy || Nw > ldy)) return VMTL_ERR_ARG;
+  if (shuffle && (Nw != 4 * Cout || Cout > ldy || stats)) return VMTL_ERR_ARG;
+  // output extent must match the conv arithmetic
+  if ((H + 2 * pad - KH) / stride + 1 != Ho || (W + 2 * pad - KW) / stride + 1 != Wo) return VMTL_ERR_ARG;
+  if ((long long)B * Ho * Wo > 0x7fffffffLL || (long long)B * H * W > 0x7fffffffLL) return VMTL_ERR_ARG;
+  return VMTL_OK;
+}
+
+// the parameter block of a plain conv without bias / activation / statistics / shuffle / split: the caller adds its own
+static ConvP conv2d_params(const float* x, const float* wp, float* y, int B, int H, int W, int Cs, int Ho, int Wo,
+                           int ldy, int Nw, int Cout, int KH, int KW, int stride, int pad) {
+  ConvP p;
+  p.x = x; p.wp = wp; p.y = y;
+  p.B = B; p.H = H; p.W = W; p.Cs = Cs; p.Ho = Ho; p.Wo = Wo; p.ldy = ldy; p.Nw = Nw; p.Cout = Cout;
+  p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.Ktot = KH * KW * Cs; p.M = B * Ho * Wo;
+  return p;
 }
 
 static int conv2d_fwd_impl(const float* x, const float* wp, const float* bias, float* y, float* stats,
@@ -1025,42 +1091,16 @@ static int conv2d_fwd_impl(const float* x, const float* wp, const float* bias, f
                            const float* ez_mean, const float* ez_invstd, const float* ez_gamma, const float* ez_beta,
                            int ez_act, int prec, void* stream) {
   VMTL_ENTER();
-  if (!valid_prec(prec) || !x || !wp || !y) return VMTL_ERR_ARG;
-  if (Cs <= 0 || (Cs & 3) || B <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0) return VMTL_ERR_ARG;
-  if (KH <= 0 || KW <= 0 || stride <= 0 || pad < 0 || Nw <= 0 || Cout <= 0 || ldy <= 0) return VMTL_ERR_ARG;
-  if (!shuffle && (Cout > ldy || Nw > ldy)) return VMTL_ERR_ARG;
-  if (shuffle && (Nw != 4 * Cout || Cout > ldy || stats)) return VMTL_ERR_ARG;
-  // output extent must match the conv arithmetic
-  if ((H + 2 * pad - KH) / stride + 1 != Ho || (W + 2 * pad - KW) / stride + 1 != Wo) return VMTL_ERR_ARG;
-  if ((long long)B * Ho * Wo > 0x7fffffffLL || (long long)B * H * W > 0x7fffffffLL) return VMTL_ERR_ARG;
-  ConvP p;
-  p.x = x; p.wp = wp; p.bias = bias; p.y = y; p.stats = stats;
-  p.B = B; p.H = H; p.W = W; p.Cs = Cs; p.Ho = Ho; p.Wo = Wo; p.ldy = ldy; p.Nw = Nw; p.Cout = Cout;
-  p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.Ktot = KH * KW * Cs; p.M = B * Ho * Wo;
-  p.act = act; p.shuffle = shuffle; p.x2 = nullptr; p.C2s = 0; p.ksplit = 1; p.ksteps_per_split = 0;
+  if (!valid_prec(prec)) return VMTL_ERR_ARG;
+  if (conv2d_check(x, wp, y, stats, B, H, W, Cs, Ho, Wo, ldy, Nw, Cout, KH, KW, stride, pad, shuffle)) return VMTL_ERR_ARG;
+  ConvP p = conv2d_params(x, wp, y, B, H, W, Cs, Ho, Wo, ldy, Nw, Cout, KH, KW, stride, pad);
+  p.bias = bias; p.stats = stats; p.act = act; p.shuffle = shuffle;
   p.ez_x = ez_x; p.ez_mean = ez_mean; p.ez_invstd = ez_invstd; p.ez_gamma = ez_gamma; p.ez_beta = ez_beta; p.ez_act = ez_act;
   hipStream_t st = (hipStream_t)stream;
   if (shuffle && ldy > Cout &&  // the scatter only writes co < Cout: keep the pad-channel invariant
       hipMemsetAsync(y, 0, (size_t)B * 4 * Ho * Wo * ldy * sizeof(float), st) != hipSuccess)
     return VMTL_ERR_LAUNCH;
-  switch (conv_pick_tile(p.M, shuffle ? Nw : ldy)) {
-    case 0: return launch_conv<2, 2, 4, 1>(p, st, prec);
-    case 1: return launch_conv<2, 3, 4, 1>(p, st, prec);
-    case 2: return launch_conv<2, 4, 4, 1>(p, st, prec);
-    case 3: return launch_conv<2, 5, 4, 1>(p, st, prec);
-    case 4: return launch_conv<4, 3, 2, 2>(p, st, prec);
-    case 5: return launch_conv<4, 4, 2, 2>(p, st, prec);
-    case 6: return launch_conv<2, 9, 4, 1>(p, st, prec);
-    case 7: return launch_conv<4, 5, 2, 2>(p, st, prec);
-    case 8: return launch_conv<1, 2, 4, 1>(p, st, prec);
-    case 9: return launch_conv<1, 4, 4, 1>(p, st, prec);
-    case 10: return launch_conv<2, 4, 2, 2>(p, st, prec);
-    case 11: return launch_conv<1, 9, 4, 1>(p, st, prec);
-    case 12: return launch_conv<2, 2, 4, 1, false, 4>(p, st, prec);
-    case 13: return launch_conv<2, 1, 4, 1, false, 4>(p, st, prec);
-    case 14: return launch_conv<2, 4, 4, 1, false, 4>(p, st, prec);
-    default: return launch_conv<2, 1, 4, 1>(p, st, prec);
-  }
+  return launch_tile<false>(conv_pick_tile(p.M, shuffle ? Nw : ldy), p, st, prec);
 }
 
 extern "C" int vmtl_conv2d_fwd_p(const float* x, const float* wp, const float* bias, float* y, float* stats,
@@ -1104,46 +1144,13 @@ extern "C" int vmtl_conv2d_fwd_ws_p(const float* x, const float* wp, const float
                                     int pad, int precision, void* stream) {
   VMTL_ENTER();
   if (!valid_prec(precision)) return VMTL_ERR_ARG;
-  const int prec = precision;
+  if (conv2d_check(x, wp, y, nullptr, B, H, W, Cs, Ho, Wo, ldy, Nw, Cout, KH, KW, stride, pad, 0)) return VMTL_ERR_ARG;
   const int splits = vmtl_conv2d_ksplit(B, Ho, Wo, ldy, KH * KW * Cs);
   if (splits <= 1 || ws == nullptr)
-    return vmtl_conv2d_fwd_p(x, wp, bias, y, nullptr, B, H, W, Cs, Ho, Wo, ldy, Nw, Cout, KH, KW, stride, pad, 0, 0, prec,
-                             stream);
-  if (!x || !wp || !y || Cs <= 0 || (Cs & 3) || Nw > ldy || Cout > ldy) return VMTL_ERR_ARG;
-  if ((H + 2 * pad - KH) / stride + 1 != Ho || (W + 2 * pad - KW) / stride + 1 != Wo) return VMTL_ERR_ARG;
-  ConvP p;
-  p.x = x; p.wp = wp; p.bias = nullptr; p.y = ws; p.stats = nullptr; p.x2 = nullptr; p.C2s = 0;
-  p.B = B; p.H = H; p.W = W; p.Cs = Cs; p.Ho = Ho; p.Wo = Wo; p.ldy = ldy; p.Nw = Nw; p.Cout = Cout;
-  p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.Ktot = KH * KW * Cs; p.M = B * Ho * Wo;
-  p.act = 0; p.shuffle = 0; p.ez_x = nullptr; p.ez_mean = p.ez_invstd = p.ez_gamma = p.ez_beta = nullptr; p.ez_act = 0;
-  p.ksplit = splits;
-  p.ksteps_per_split = cdiv(cdiv(p.Ktot, BK), splits);
-  hipStream_t st = (hipStream_t)stream;
-  int rc;
-  switch (conv_pick_tile(p.M, ldy)) {
-    case 0: rc = launch_conv<2, 2, 4, 1>(p, st, prec); break;
-    case 1: rc = launch_conv<2, 3, 4, 1>(p, st, prec); break;
-    case 2: rc = launch_conv<2, 4, 4, 1>(p, st, prec); break;
-    case 3: rc = launch_conv<2, 5, 4, 1>(p, st, prec); break;
-    case 4: rc = launch_conv<4, 3, 2, 2>(p, st, prec); break;
-    case 5: rc = launch_conv<4, 4, 2, 2>(p, st, prec); break;
-    case 6: rc = launch_conv<2, 9, 4, 1>(p, st, prec); break;
-    case 7: rc = launch_conv<4, 5, 2, 2>(p, st, prec); break;
-    case 8: rc = launch_conv<1, 2, 4, 1>(p, st, prec); break;
-    case 9: rc = launch_conv<1, 4, 4, 1>(p, st, prec); break;
-    case 10: rc = launch_conv<2, 4, 2, 2>(p, st, prec); break;
-    case 11: rc = launch_conv<1, 9, 4, 1>(p, st, prec); break;
-    case 12: rc = launch_conv<2, 2, 4, 1, false, 4>(p, st, prec); break;
-    case 13: rc = launch_conv<2, 1, 4, 1, false, 4>(p, st, prec); break;
-    case 14: rc = launch_conv<2, 4, 4, 1, false, 4>(p, st, prec); break;
-    default: rc = launch_conv<2, 1, 4, 1>(p, st, prec); break;
-  }
-  if (rc) return rc;
-  const long long n4 = (long long)p.M * ldy / 4;
-  long long nb = cdivll(n4, 256);
-  if (nb > 4096) nb = 4096;
-  hipLaunchKernelGGL(sum_slabs_kernel, dim3((int)nb), dim3(256), 0, st, ws, y, splits, n4, bias, ldy, Cout);
-  return vmtl_check_launch();
+    return vmtl_conv2d_fwd_p(x, wp, bias, y, nullptr, B, H, W, Cs, Ho, Wo, ldy, Nw, Cout, KH, KW, stride, pad, 0, 0,
+                             precision, stream);
+  ConvP p = conv2d_params(x, wp, y, B, H, W, Cs, Ho, Wo, ldy, Nw, Cout, KH, KW, stride, pad);
+  return launch_split<false>(conv_pick_tile(p.M, ldy), p, splits, ws, y, bias, (hipStream_t)stream, precision);
 }
 
 extern "C" int vmtl_conv2d_fwd_ws(const float* x, const float* wp, const float* bias, float* y, float* ws, int B, int H,
@@ -1176,15 +1183,34 @@ extern "C" int vmtl_conv2d_up2_stats_block(int B, int H2, int W2, int ldy) {
   return kTiles[up2_pick_tile(B * H2 * W2, ldy)].bm;
 }
 
-// K slices of the phase-decomposed conv for this shape (1 = none): the deep decoder blocks at small batch are a few dozen
-// workgroups with a K loop of 80-150 steps (decoder block 0 at bs 8: 64 workgroups, 21 TF before)
+// K slices of the phase-decomposed conv for this shape (1 = none, also for an empty shape): the deep decoder blocks at
+// small batch are a few dozen workgroups with a K loop of 80-150 steps (decoder block 0 at bs 8: 64 workgroups, 21 TF before)
 extern "C" int vmtl_conv2d_up2_ksplit(int B, int H2, int W2, int ldy, int Ktot) {
+  if (B <= 0 || H2 <= 0 || W2 <= 0 || ldy <= 0 || Ktot <= 0) return 1;
   const int Mq = B * H2 * W2;
   const int id = up2_pick_tile(Mq, ldy);
   return ksplit_for((long long)cdiv(Mq, kTiles[id].bm) * 4 * cdiv(ldy, kTiles[id].bn), cdiv(Ktot, BK), ldy);
 }
 
-static int up2_launch(ConvP& p, int id, hipStream_t st, int prec);
+// the argument check of every UP2 entry point (direct and split-K), after the precision
+static int up2_check(const float* xl, const float* skip, const float* wp_eff, const float* y, int B, int H2, int W2,
+                     int C0s, int C1s, int ldy, int Cout) {
+  if (!xl || !wp_eff || !y || B <= 0 || H2 <= 0 || W2 <= 0 || C0s <= 0 || (C0s & 3) || (C1s & 3) || C1s < 0)
+    return VMTL_ERR_ARG;
+  if ((skip == nullptr) != (C1s == 0) || Cout <= 0 || Cout > ldy || (ldy & 3)) return VMTL_ERR_ARG;
+  if ((long long)B * H2 * W2 * 4 > 0x7fffffffLL) return VMTL_ERR_ARG;
+  return VMTL_OK;
+}
+
+// the parameter block of an UP2 conv without statistics / split
+static ConvP up2_params(const float* xl, const float* skip, const float* wp_eff, float* y, int B, int H2, int W2, int C0s,
+                        int C1s, int ldy, int Cout) {
+  ConvP p;
+  p.x = xl; p.x2 = skip; p.wp = wp_eff; p.y = y;
+  p.B = B; p.H = H2; p.W = W2; p.Cs = C0s; p.C2s = C1s; p.Ho = H2; p.Wo = W2; p.ldy = ldy; p.Nw = Cout;
+  p.Cout = Cout; p.KH = 2; p.KW = 2; p.stride = 1; p.pad = 0; p.Ktot = 4 * C0s + 9 * C1s; p.M = B * H2 * W2;
+  return p;
+}
 
 // stats (optional): [4 * ceil(B*H2*W2 / block)][2][ldy]; only valid when block divides B*H2*W2
 extern "C" int vmtl_conv2d_up2_fwd_p(const float* xl, const float* skip, const float* wp_eff, float* y, float* stats,
@@ -1192,19 +1218,12 @@ extern "C" int vmtl_conv2d_up2_fwd_p(const float* xl, const float* skip, const f
                                      void* stream) {
   VMTL_ENTER();
   if (!valid_prec(precision)) return VMTL_ERR_ARG;
-  if (!xl || !wp_eff || !y || B <= 0 || H2 <= 0 || W2 <= 0 || C0s <= 0 || (C0s & 3) || (C1s & 3) || C1s < 0)
-    return VMTL_ERR_ARG;
-  if ((skip == nullptr) != (C1s == 0) || Cout <= 0 || Cout > ldy) return VMTL_ERR_ARG;
-  if ((long long)B * H2 * W2 * 4 > 0x7fffffffLL) return VMTL_ERR_ARG;
-  ConvP p;
-  p.x = xl; p.x2 = skip; p.wp = wp_eff; p.bias = nullptr; p.y = y; p.stats = stats;
-  p.B = B; p.H = H2; p.W = W2; p.Cs = C0s; p.C2s = C1s; p.Ho = H2; p.Wo = W2; p.ldy = ldy; p.Nw = Cout;
-  p.Cout = Cout; p.KH = 2; p.KW = 2; p.stride = 1; p.pad = 0; p.Ktot = 4 * C0s + 9 * C1s; p.M = B * H2 * W2;
-  p.act = 0; p.shuffle = 0; p.ksplit = 1; p.ksteps_per_split = 0;
-  p.ez_x = nullptr; p.ez_mean = p.ez_invstd = p.ez_gamma = p.ez_beta = nullptr; p.ez_act = 0;
+  if (up2_check(xl, skip, wp_eff, y, B, H2, W2, C0s, C1s, ldy, Cout)) return VMTL_ERR_ARG;
+  ConvP p = up2_params(xl, skip, wp_eff, y, B, H2, W2, C0s, C1s, ldy, Cout);
+  p.stats = stats;
   const int id = up2_pick_tile(p.M, ldy);
   if (stats && (p.M % kTiles[id].bm)) return VMTL_ERR_ARG;
-  return up2_launch(p, id, (hipStream_t)stream, precision);
+  return launch_tile<true>(id, p, (hipStream_t)stream, precision);
 }
 
 extern "C" int vmtl_conv2d_up2_fwd(const float* xl, const float* skip, const float* wp_eff, float* y, float* stats,
@@ -1219,51 +1238,15 @@ extern "C" int vmtl_conv2d_up2_fwd_ws_p(const float* xl, const float* skip, cons
                                         void* stream) {
   VMTL_ENTER();
   if (!valid_prec(precision)) return VMTL_ERR_ARG;
+  if (up2_check(xl, skip, wp_eff, y, B, H2, W2, C0s, C1s, ldy, Cout)) return VMTL_ERR_ARG;
   const int splits = vmtl_conv2d_up2_ksplit(B, H2, W2, ldy, 4 * C0s + 9 * C1s);
   if (splits <= 1 || ws == nullptr)
     return vmtl_conv2d_up2_fwd_p(xl, skip, wp_eff, y, nullptr, B, H2, W2, C0s, C1s, ldy, Cout, precision, stream);
-  if (!xl || !wp_eff || !y || B <= 0 || H2 <= 0 || W2 <= 0 || C0s <= 0 || (C0s & 3) || (C1s & 3) || C1s < 0)
-    return VMTL_ERR_ARG;
-  if ((skip == nullptr) != (C1s == 0) || Cout <= 0 || Cout > ldy || (ldy & 3)) return VMTL_ERR_ARG;
-  if ((long long)B * H2 * W2 * 4 > 0x7fffffffLL) return VMTL_ERR_ARG;
-  ConvP p;
-  p.x = xl; p.x2 = skip; p.wp = wp_eff; p.bias = nullptr; p.y = ws; p.stats = nullptr;
-  p.B = B; p.H = H2; p.W = W2; p.Cs = C0s; p.C2s = C1s; p.Ho = H2; p.Wo = W2; p.ldy = ldy; p.Nw = Cout;
-  p.Cout = Cout; p.KH = 2; p.KW = 2; p.stride = 1; p.pad = 0; p.Ktot = 4 * C0s + 9 * C1s; p.M = B * H2 * W2;
-  p.act = 0; p.shuffle = 0; p.ksplit = splits; p.ksteps_per_split = cdiv(cdiv(p.Ktot, BK), splits);
-  p.ez_x = nullptr; p.ez_mean = p.ez_invstd = p.ez_gamma = p.ez_beta = nullptr; p.ez_act = 0;
-  hipStream_t st = (hipStream_t)stream;
-  const int rc = up2_launch(p, up2_pick_tile(p.M, ldy), st, precision);
-  if (rc) return rc;
-  const long long n4 = (long long)4 * p.M * ldy / 4;
-  long long nb = cdivll(n4, 256);
-  if (nb > 4096) nb = 4096;
-  hipLaunchKernelGGL(sum_slabs_kernel, dim3((int)nb), dim3(256), 0, st, ws, y, splits, n4, (const float*)nullptr, ldy, Cout);
-  return vmtl_check_launch();
+  ConvP p = up2_params(xl, skip, wp_eff, y, B, H2, W2, C0s, C1s, ldy, Cout);
+  return launch_split<true>(up2_pick_tile(p.M, ldy), p, splits, ws, y, nullptr, (hipStream_t)stream, precision);
 }
 
 extern "C" int vmtl_conv2d_up2_fwd_ws(const float* xl, const float* skip, const float* wp_eff, float* y, float* ws, int B,
                                       int H2, int W2, int C0s, int C1s, int ldy, int Cout, void* stream) {
   return vmtl_conv2d_up2_fwd_ws_p(xl, skip, wp_eff, y, ws, B, H2, W2, C0s, C1s, ldy, Cout, VMTL_PREC_FP32, stream);
-}
-
-static int up2_launch(ConvP& p, int id, hipStream_t st, int prec) {
-  switch (id) {
-    case 0: return launch_conv<2, 2, 4, 1, true>(p, st, prec);
-    case 1: return launch_conv<2, 3, 4, 1, true>(p, st, prec);
-    case 2: return launch_conv<2, 4, 4, 1, true>(p, st, prec);
-    case 3: return launch_conv<2, 5, 4, 1, true>(p, st, prec);
-    case 4: return launch_conv<4, 3, 2, 2, true>(p, st, prec);
-    case 5: return launch_conv<4, 4, 2, 2, true>(p, st, prec);
-    case 6: return launch_conv<2, 9, 4, 1, true>(p, st, prec);
-    case 7: return launch_conv<4, 5, 2, 2, true>(p, st, prec);
-    case 8: return launch_conv<1, 2, 4, 1, true>(p, st, prec);
-    case 9: return launch_conv<1, 4, 4, 1, true>(p, st, prec);
-    case 10: return launch_conv<2, 4, 2, 2, true>(p, st, prec);
-    case 11: return launch_conv<1, 9, 4, 1, true>(p, st, prec);
-    case 12: return launch_conv<2, 2, 4, 1, true, 4>(p, st, prec);
-    case 13: return launch_conv<2, 1, 4, 1, true, 4>(p, st, prec);
-    case 14: return launch_conv<2, 4, 4, 1, true, 4>(p, st, prec);
-    default: return launch_conv<2, 1, 4, 1, true>(p, st, prec);
-  }
 }

@@ -26,37 +26,37 @@
 #include "common.h"
 
 struct PwP {
-  const float* x;     // [M][Ks]
-  const float* wp;    // [Nw][Ks]
-  const float* bias;  // [Nw] or null
-  float* y;           // [M][ldy]
-  float* stats;       // optional [tiles_m][2][ldy]: per-row-block column (mean, M2)
-  int M, Ks, ldy, Nw, Cout;
-  int tiles_m, tiles_n;
+  const float* x = nullptr;     // [M][Ks]
+  const float* wp = nullptr;    // [Nw][Ks]
+  const float* bias = nullptr;  // [Nw] or null
+  float* y = nullptr;           // [M][ldy]
+  float* stats = nullptr;       // optional [tiles_m][2][ldy]: per-row-block column (mean, M2)
+  int M = 0, Ks = 0, ldy = 0, Nw = 0, Cout = 0;
+  int tiles_m = 0, tiles_n = 0;  // set by the launcher from the tile it instantiates
   // virtual concat (MTAN attention, reference models/mtan_model.py:57-59,139-141): the K axis is [x | x2] - columns
   // [0, K1) of a row come from x (row stride K1), [K1, Ks) from x2 (row stride Ks - K1); and its mirror for the data
   // gradient: output columns [0, N1) go to y (row stride N1), [N1, ldy) to y2 (row stride ldy - N1)
-  const float* x2;  // null: single source
-  float* y2;        // null: single destination
-  int K1, N1;
+  const float* x2 = nullptr;  // null: single source
+  float* y2 = nullptr;        // null: single destination
+  int K1 = 0, N1 = 0;
   // pre-activation node (PRO): the A operand is act(pa[k] * x + pc[k]) - BatchNorm + activation of the layer that
   // produced x, applied to the fragments on their way into the MFMAs; a_out (nullable) receives the activated matrix
   // once (workgroups of column tile 0), for the weight-gradient kernel
-  const float* pa;
-  const float* pc;
-  const float* res;  // nullable [M][Ks]: added after the activation (a block's residual branch: a = act(pa*x + pc) + res)
-  float* a_out;
-  int act_in;
+  const float* pa = nullptr;  // null: no prologue
+  const float* pc = nullptr;
+  const float* res = nullptr;  // nullable [M][Ks]: added after the activation (a block's residual branch: a = act(pa*x + pc) + res)
+  float* a_out = nullptr;
+  int act_in = 0;
   // BatchNorm-backward epilogue (ez_x != null): the launch is the data gradient of a conv whose input was
   // act(BN(ez_x)); it stores dz = acc * act'(gamma * xhat + beta) instead of acc and per-row-block (sum dz,
   // sum dz * xhat) in `stats` - the BatchNorm backward then needs no reduction pass of its own
-  const float* ez_x;
-  const float* ez_mean;
-  const float* ez_invstd;
-  const float* ez_gamma;
-  const float* ez_beta;
-  const float* ez_add;  // nullable [M][ldy]: a second gradient of the differentiated tensor, added to acc first
-  int ez_act;
+  const float* ez_x = nullptr;
+  const float* ez_mean = nullptr;
+  const float* ez_invstd = nullptr;
+  const float* ez_gamma = nullptr;
+  const float* ez_beta = nullptr;
+  const float* ez_add = nullptr;  // nullable [M][ldy]: a second gradient of the differentiated tensor, added to acc first
+  int ez_act = 0;
 };
 
 // wave tile 32 rows x (16*TN) columns; KW waves of the workgroup split K, the other 4/KW stack along M
@@ -849,10 +849,6 @@ static bool pw_big_cfg(int M, int ldy, int Ks, BigCfg* out) {
   return true;
 }
 
-// variant 0: launches that may run on the large-M kernel (vmtl_conv1x1_fwd / _cat_fwd / _bn_fwd / _cat_dgrad / _bnbwd);
-// 1: launches that always run on pw_gemm_kernel (residual operand, BatchNorm-backward epilogue with an addend)
-static int pw_num_cus();
-
 // programs (persistent workgroups per column tile) of the large-M kernel for this problem: one per CU, two where the LDS
 // images of two workgroups fit a CU (their staging / epilogue phases then overlap the other's K loop).
 // The occupancy is computed from the FP32 image sizes in BOTH precisions: the one-row-per-workgroup statistics layout
@@ -863,11 +859,13 @@ static int pw_big_nprog(int M, int ldy, const BigCfg& c) {
   const long long lds = ((long long)c.kc * c.bn * 32 + (a_floats > o_floats ? a_floats : o_floats)) * 4 + 2 * 512 * 16;
   static EnvInt e_occ{"VMTL_PW_BIG_OCC", 2};  // tuning aid
   const int occ = (2 * lds <= 160 * 1024 && env_int(e_occ) >= 2) ? 2 : 1;
-  int nprog = occ * pw_num_cus() / tiles_n;
+  int nprog = occ * vmtl_num_cus() / tiles_n;
   if (nprog < 1) nprog = 1;
   return nprog > tiles_m ? tiles_m : nprog;
 }
 
+// variant 0: launches that may run on the large-M kernel (vmtl_conv1x1_fwd / _cat_fwd / _bn_fwd / _cat_dgrad / _bnbwd);
+// 1: launches that always run on pw_gemm_kernel (residual operand, BatchNorm-backward epilogue with an addend)
 extern "C" int vmtl_conv1x1_stats_block(int M, int ldy, int Ks, int variant) {
   BigCfg c;
   if (variant == 0 && pw_big_cfg(M, ldy, Ks, &c)) {
@@ -883,18 +881,6 @@ extern "C" int vmtl_conv1x1_stats_rows(int M, int ldy, int Ks, int variant) {
   return cdiv(M, vmtl_conv1x1_stats_block(M, ldy, Ks, variant));
 }
 
-static int pw_num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-            ? prop.multiProcessorCount
-            : 256;
-  }
-  return n;
-}
-
 template <int TM, int TN, int WM, int WN, int KC, bool BF16>
 static int launch_pw_big_t(PwP& p, hipStream_t st) {
   constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
@@ -908,15 +894,12 @@ static int launch_pw_big_t(PwP& p, hipStream_t st) {
   const BigCfg cfg = {0, BM, BN, KC};  // (LDS bytes in pw_big_nprog assume the 8-wave reduction scratch: an upper bound for 4 waves)
   const int nprog = pw_big_nprog(p.M, p.ldy, cfg);
   const dim3 grid(nprog, p.tiles_n);
-#define VMTL_PW_BIG_LAUNCH(SRC2, PRO, EZ)                                                                               \
-  {                                                                                                                     \
-    static bool attr_set = false;                                                                                       \
-    if (!attr_set) {                                                                                                    \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_big_kernel<TM, TN, WM, WN, KC, SRC2, PRO, EZ, BF16>), \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                 \
-      attr_set = true;                                                                                                  \
-    }                                                                                                                   \
-    hipLaunchKernelGGL((pw_big_kernel<TM, TN, WM, WN, KC, SRC2, PRO, EZ, BF16>), grid, dim3(NTHR), lds, st, p, nprog);  \
+#define VMTL_PW_BIG_LAUNCH(SRC2, PRO, EZ)                                                                              \
+  {                                                                                                                    \
+    constexpr auto kernel = &pw_big_kernel<TM, TN, WM, WN, KC, SRC2, PRO, EZ, BF16>;                                   \
+    const int rc = allow_dynamic_lds(reinterpret_cast<const void*>(kernel), lds);                                      \
+    if (rc) return rc;                                                                                                 \
+    hipLaunchKernelGGL(kernel, grid, dim3(NTHR), lds, st, p, nprog);                                                   \
   }
   if (p.ez_x != nullptr) VMTL_PW_BIG_LAUNCH(false, false, true)
   else if (p.x2 != nullptr) VMTL_PW_BIG_LAUNCH(true, false, false)
@@ -983,11 +966,6 @@ static int launch_pw(PwP& p, int prec, hipStream_t st) {
   return prec == VMTL_PREC_BF16 ? launch_pw_t<TN, KW, true, false>(p, st) : launch_pw_t<TN, KW, false, false>(p, st);
 }
 
-static void pw_plain(PwP& p) {  // no prologue, ordinary epilogue
-  p.pa = p.pc = p.res = nullptr; p.a_out = nullptr; p.act_in = 0;
-  p.ez_x = p.ez_mean = p.ez_invstd = p.ez_gamma = p.ez_beta = p.ez_add = nullptr; p.ez_act = 0;
-}
-
 // kernel and tile choice do not look at the precision: the statistics geometry is the same in both
 static int pw_dispatch(PwP& p, int prec, hipStream_t st) {
   BigCfg c;
@@ -1008,8 +986,6 @@ extern "C" int vmtl_conv1x1_fwd_p(const float* x, const float* wp, const float* 
   if (Nw <= 0 || Nw > ldy || Cout <= 0 || Cout > Nw) return VMTL_ERR_ARG;
   PwP p;
   p.x = x; p.wp = wp; p.bias = bias; p.y = y; p.stats = stats; p.M = M; p.Ks = Ks; p.ldy = ldy; p.Nw = Nw; p.Cout = Cout;
-  p.x2 = nullptr; p.y2 = nullptr; p.K1 = 0; p.N1 = 0;
-  pw_plain(p);
   return pw_dispatch(p, precision, (hipStream_t)stream);
 }
 
@@ -1031,8 +1007,7 @@ extern "C" int vmtl_conv1x1_cat_fwd_p(const float* x, int K1, const float* x2, i
   if (Nw <= 0 || Nw > ldy || Cout <= 0 || Cout > Nw) return VMTL_ERR_ARG;
   PwP p;
   p.x = x; p.wp = wp; p.bias = bias; p.y = y; p.stats = stats; p.M = M; p.Ks = K1 + K2s; p.ldy = ldy; p.Nw = Nw;
-  p.Cout = Cout; p.x2 = x2; p.y2 = nullptr; p.K1 = K1; p.N1 = 0;
-  pw_plain(p);
+  p.Cout = Cout; p.x2 = x2; p.K1 = K1;
   return pw_dispatch(p, precision, (hipStream_t)stream);
 }
 
@@ -1051,9 +1026,8 @@ extern "C" int vmtl_conv1x1_cat_dgrad_p(const float* dy, const float* wp, float*
       N2 <= 0 || N2 > N2s)
     return VMTL_ERR_ARG;
   PwP p;
-  p.x = dy; p.wp = wp; p.bias = nullptr; p.y = dx; p.stats = nullptr; p.M = M; p.Ks = Ks; p.ldy = N1 + N2s;
-  p.Nw = N1 + N2; p.Cout = N1 + N2; p.x2 = nullptr; p.y2 = dx2; p.K1 = 0; p.N1 = N1;
-  pw_plain(p);
+  p.x = dy; p.wp = wp; p.y = dx; p.M = M; p.Ks = Ks; p.ldy = N1 + N2s;
+  p.Nw = N1 + N2; p.Cout = N1 + N2; p.y2 = dx2; p.N1 = N1;
   return pw_dispatch(p, precision, (hipStream_t)stream);
 }
 
@@ -1073,8 +1047,6 @@ static int conv1x1_bn_fwd_impl(const float* x, const float* coef_a, const float*
   if (act_in != VMTL_ACT_NONE && act_in != VMTL_ACT_RELU && act_in != VMTL_ACT_HSWISH) return VMTL_ERR_ARG;
   PwP p;
   p.x = x; p.wp = wp; p.bias = bias; p.y = y; p.stats = stats; p.M = M; p.Ks = Ks; p.ldy = ldy; p.Nw = Nw; p.Cout = Cout;
-  p.x2 = nullptr; p.y2 = nullptr; p.K1 = 0; p.N1 = 0;
-  pw_plain(p);
   p.pa = coef_a; p.pc = coef_c; p.res = res; p.a_out = a_out; p.act_in = act_in;
   return pw_dispatch(p, prec, (hipStream_t)stream);
 }
@@ -1127,9 +1099,7 @@ static int conv1x1_bnbwd_impl(const float* dy, const float* wp, const float* add
     return VMTL_ERR_ARG;
   if (Nw <= 0 || Nw > ldy || Cout <= 0 || Cout > Nw) return VMTL_ERR_ARG;
   PwP p;
-  p.x = dy; p.wp = wp; p.bias = nullptr; p.y = dz; p.stats = stats; p.M = M; p.Ks = Ks; p.ldy = ldy; p.Nw = Nw;
-  p.Cout = Cout; p.x2 = nullptr; p.y2 = nullptr; p.K1 = 0; p.N1 = 0;
-  pw_plain(p);
+  p.x = dy; p.wp = wp; p.y = dz; p.stats = stats; p.M = M; p.Ks = Ks; p.ldy = ldy; p.Nw = Nw; p.Cout = Cout;
   p.ez_x = ez_x; p.ez_mean = ez_mean; p.ez_invstd = ez_invstd; p.ez_gamma = ez_gamma; p.ez_beta = ez_beta; p.ez_act = ez_act;
   p.ez_add = addend;
   return pw_dispatch(p, prec, (hipStream_t)stream);

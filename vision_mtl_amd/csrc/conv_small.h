@@ -584,20 +584,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 }
 
 // ---------------------------------------------------------------------------------------------- launch
-int small_cus();
 int small_grid(int ntiles, int* acc_rows);
 
 template <int CS, int TN, int NT, bool X2>
 static int launch_small_x(SmallP& p, hipStream_t st) {
   using C = SmallCfg<CS, TN, NT>;
-  // set on every launch: a function attribute is per device, and a cached flag would be neither thread-safe nor
-  // right for a second GPU of the process (the call is a cheap driver-side table update)
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_small_kernel<CS, TN, NT, X2>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES) != hipSuccess)
-    return VMTL_ERR_LAUNCH;
+  const int rc = allow_dynamic_lds(reinterpret_cast<const void*>(&conv3x3_small_kernel<CS, TN, NT, X2>), C::LDS_BYTES);
+  if (rc) return rc;
   static_assert(C::LDS_BYTES * 2 <= 160 * 1024, "two workgroups per CU (small_grid() assumes it)");
   int grid = p.grid;
-  if (CSM_DBG(p) & 64) grid = small_cus() < p.ntiles ? small_cus() : p.ntiles;  // tuning aid: one workgroup per CU
+  if (CSM_DBG(p) & 64) grid = vmtl_num_cus() < p.ntiles ? vmtl_num_cus() : p.ntiles;  // tuning aid: one workgroup per CU
   hipLaunchKernelGGL((conv3x3_small_kernel<CS, TN, NT, X2>), dim3(grid), dim3(256), C::LDS_BYTES, st, p);
   return vmtl_check_launch();
 }

@@ -7,25 +7,13 @@ int vmtl_small_launch_cs32(SmallP& p, hipStream_t st);
 int vmtl_small_launch_cs36(SmallP& p, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------------- host side
-int small_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        v <= 0)
-      v = 256;
-    n = v;
-  }
-  return n;
-}
-
 // Persistent grid: two workgroups per CU.  With a statistics epilogue every workgroup must see the same number of
 // tiles (the BatchNorm finalize weights all rows equally), so the grid is the largest divisor of the tile count that
 // still fills at least half the slots; a workgroup then ACCUMULATES its tiles into one statistics row (512 rows
 // instead of 8192 for 32 x 128 x 256: the one-workgroup-per-channel finalize kernels took 33 us on 8192 rows).
 // Shapes without such a divisor keep one row per tile.
 int small_grid(int ntiles, int* acc_rows) {
-  const int slots = 2 * small_cus();
+  const int slots = 2 * vmtl_num_cus();
   int best = 0;
   for (int g = slots < ntiles ? slots : ntiles; g >= 1; --g)
     if (ntiles % g == 0) { best = g; break; }

@@ -319,9 +319,8 @@ template <int C0S, int C1S, int TM, int TN, int NT>
 static int launch_up2_halo(Up2HaloP& p, hipStream_t st) {
   using C = UhCfg<C0S, C1S, TM, TN, NT>;
   static_assert(C::LDS_BYTES <= 64 * 1024, "at least two workgroups per CU");
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up2_halo_kernel<C0S, C1S, TM, TN, NT>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES) != hipSuccess)
-    return VMTL_ERR_LAUNCH;
+  const int rc = allow_dynamic_lds(reinterpret_cast<const void*>(&conv_up2_halo_kernel<C0S, C1S, TM, TN, NT>), C::LDS_BYTES);
+  if (rc) return rc;
   p.tiles_x = cdiv(p.W2, UH_TW);
   p.tiles_y = cdiv(p.H2, TM);
   hipLaunchKernelGGL((conv_up2_halo_kernel<C0S, C1S, TM, TN, NT>), dim3(p.B * p.tiles_x * p.tiles_y), dim3(256),

@@ -21,20 +21,20 @@
 // order (deterministic, no float atomics) while converting to the torch layout.
 // ---------------------------------------------------------------------------
 struct WgradP {
-  const float* x;   // [B][H][W][Cs]
-  const float* dy;  // [B][Ho][Wo][ldy]
-  float* slabs;     // [splits][Nw][Ktot]
-  int B, H, W, Cs;
-  int Ho, Wo, ldy;
-  int Nw;
-  int KH, KW, stride, pad;
-  int Ktot, M;
-  int chunk;        // pixels per z-slice (multiple of BP)
-  int tiles_kk, tiles_co, splits;
+  const float* x = nullptr;   // [B][H][W][Cs]
+  const float* dy = nullptr;  // [B][Ho][Wo][ldy]
+  float* slabs = nullptr;     // [splits][Nw][Ktot]
+  int B = 0, H = 0, W = 0, Cs = 0;
+  int Ho = 0, Wo = 0, ldy = 0;
+  int Nw = 0;
+  int KH = 0, KW = 0, stride = 0, pad = 0;
+  int Ktot = 0, M = 0;
+  int chunk = 0;  // pixels per z-slice (multiple of BP)
+  int tiles_kk = 0, tiles_co = 0, splits = 0;  // chunk and these: set by the dispatch and the launcher
   // virtual concat (1x1 only): channels [0, K1) of a pixel come from x (row stride K1), [K1, Cs) from x2 (row stride
   // Cs - K1); null = single source
-  const float* x2;
-  int K1;
+  const float* x2 = nullptr;
+  int K1 = 0;
 };
 
 #define BP 32
@@ -425,28 +425,6 @@ static int wgrad_lds_bytes(int rows) {
   return lds(0);
 }
 
-static int wgrad_splits_uncached(int M, int Nw, int Ktot);
-
-// number of pixel slices (= slabs the caller must provide: splits * Nw * Ktot floats); memoised: the search below walks
-// up to a few thousand candidates, and this is called twice per weight-gradient launch on the (eager) launch path
-extern "C" int vmtl_conv2d_wgrad_splits(int M, int Nw, int Ktot) {
-  if (M <= 0 || Nw <= 0 || Ktot <= 0) return 0;
-  static std::mutex mu;
-  static std::unordered_map<unsigned long long, int> memo;
-  static int memo_epoch = 0;
-  const unsigned long long key = ((unsigned long long)M << 32) ^ ((unsigned long long)Nw << 20) ^ (unsigned long long)Ktot;
-  std::lock_guard<std::mutex> lk(mu);
-  if (memo_epoch != vmtl_env_epoch) {  // the tuning overrides may have changed
-    memo.clear();
-    memo_epoch = vmtl_env_epoch;
-  }
-  auto it = memo.find(key);
-  if (it != memo.end()) return it->second;
-  const int v = wgrad_splits_uncached(M, Nw, Ktot);
-  memo.emplace(key, v);
-  return v;
-}
-
 static int wgrad_splits_uncached(int M, int Nw, int Ktot) {
   const long long tiles = (long long)cdiv(Ktot, WG_BNK) * cdiv(Nw, wgrad_rows(Nw));
   // Pixels per slice: at least 16 K-steps (512) - except for SMALL problems (<= 16384 pixels: the deep encoder layers,
@@ -493,8 +471,25 @@ static int wgrad_splits_uncached(int M, int Nw, int Ktot) {
   return (int)best;
 }
 
-template <int TM, int NTR, int PM, bool FAST, bool BF16 = false>
-static int launch_wgrad_pm(WgradP& p, int splits, hipStream_t st);
+// number of pixel slices (= slabs the caller must provide: splits * Nw * Ktot floats); memoised: the search below walks
+// up to a few thousand candidates, and this is called twice per weight-gradient launch on the (eager) launch path
+extern "C" int vmtl_conv2d_wgrad_splits(int M, int Nw, int Ktot) {
+  if (M <= 0 || Nw <= 0 || Ktot <= 0) return 0;
+  static std::mutex mu;
+  static std::unordered_map<unsigned long long, int> memo;
+  static int memo_epoch = 0;
+  const unsigned long long key = ((unsigned long long)M << 32) ^ ((unsigned long long)Nw << 20) ^ (unsigned long long)Ktot;
+  std::lock_guard<std::mutex> lk(mu);
+  if (memo_epoch != vmtl_env_epoch) {  // the tuning overrides may have changed
+    memo.clear();
+    memo_epoch = vmtl_env_epoch;
+  }
+  auto it = memo.find(key);
+  if (it != memo.end()) return it->second;
+  const int v = wgrad_splits_uncached(M, Nw, Ktot);
+  memo.emplace(key, v);
+  return v;
+}
 
 // Stride rule per tile height.  Measured on MI355X (tools/bench_conv.py, VMTL_WG_PAD A/B, round 3): the conflict-free
 // strides remove ALL bank-conflict cycles (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE 0.425 -> 0.000 on the 144-row tile)
@@ -516,6 +511,36 @@ static_assert(wg_pm<144>() == 1 && wg_pm<80>() == 1 && wg_pm<36>() == 2 && wg_pm
 static bool wgrad_fast_ok(const WgradP& p) {
   static EnvInt e{"VMTL_WG_FAST", 1};  // tuning aid: 0 = the general loader everywhere
   return env_int(e) != 0 && p.x2 == nullptr && p.Wo % BP == 0 && p.chunk % BP == 0;
+}
+
+template <int TM, int NTR, int PM, bool FAST, bool BF16, bool PIPE>
+static int launch_wgrad_pipe(WgradP& p, int splits, hipStream_t st) {
+  constexpr int BMC = TM * 16 + NTR;
+  constexpr int PD = (TM <= 2 ? 3 : (TM <= 4 && NTR == 0) ? 2 : 1);
+  const size_t lds = (size_t)2 * BP * (wg_ld(BMC, PM) + wg_ld(WG_BNK, PM)) * sizeof(float);
+  const int rc = allow_dynamic_lds(reinterpret_cast<const void*>(&conv_wgrad_kernel<TM, NTR, PM, PD, FAST, BF16, PIPE>), lds);
+  if (rc) return rc;
+  if ((long long)p.M * p.ldy * 4 >= (1ll << 32) || (long long)p.B * p.H * p.W * p.Cs * 4 >= (1ll << 32))
+    return VMTL_ERR_UNSUPPORTED;  // buffer addressing: 32-bit byte offsets
+  p.tiles_kk = cdiv(p.Ktot, WG_BNK);
+  p.tiles_co = cdiv(p.Nw, BMC);
+  p.splits = splits;
+  hipLaunchKernelGGL((conv_wgrad_kernel<TM, NTR, PM, PD, FAST, BF16, PIPE>), dim3(p.tiles_kk * p.tiles_co * splits), dim3(256), lds, st,
+                     p);
+  return vmtl_check_launch();
+}
+
+template <int TM, int NTR, int PM, bool FAST, bool BF16 = false>
+static int launch_wgrad_pm(WgradP& p, int splits, hipStream_t st) {
+  constexpr int PD = (TM <= 2 ? 3 : (TM <= 4 && NTR == 0) ? 2 : 1);
+  // PD == 3 only (tile heights 16 / 20 / 32 / 36): at PD = 2 (48 / 64 rows) the peeled loop measured 4-5 % SLOWER in
+  // the step (9.9 -> 10.4 us, 15.3 -> 15.9 us per launch, 66 launches each: its slices are four chunks, all prologue and
+  // tail, and the code is twice as long); the general loaders keep the guarded loop too
+  if constexpr (PD >= 3 && FAST) {
+    static EnvInt e{"VMTL_WG_PIPE", 1};  // 0 = the guarded loop (same-build comparisons)
+    if (env_int(e)) return launch_wgrad_pipe<TM, NTR, PM, FAST, BF16, true>(p, splits, st);
+  }
+  return launch_wgrad_pipe<TM, NTR, PM, FAST, BF16, false>(p, splits, st);
 }
 
 template <int TM, int NTR = 0>
@@ -542,44 +567,24 @@ static int launch_wgrad(WgradP& p, int splits, hipStream_t st, int prec) {
   return launch_wgrad_pm<TM, NTR, PMD, false>(p, splits, st);
 }
 
-template <int TM, int NTR, int PM, bool FAST, bool BF16, bool PIPE>
-static int launch_wgrad_pipe(WgradP& p, int splits, hipStream_t st);
-
-template <int TM, int NTR, int PM, bool FAST, bool BF16>
-static int launch_wgrad_pm(WgradP& p, int splits, hipStream_t st) {
-  constexpr int PD = (TM <= 2 ? 3 : (TM <= 4 && NTR == 0) ? 2 : 1);
-  // PD == 3 only (tile heights 16 / 20 / 32 / 36): at PD = 2 (48 / 64 rows) the peeled loop measured 4-5 % SLOWER in
-  // the step (9.9 -> 10.4 us, 15.3 -> 15.9 us per launch, 66 launches each: its slices are four chunks, all prologue and
-  // tail, and the code is twice as long); the general loaders keep the guarded loop too
-  if constexpr (PD >= 3 && FAST) {
-    static EnvInt e{"VMTL_WG_PIPE", 1};  // 0 = the guarded loop (same-build comparisons)
-    if (env_int(e)) return launch_wgrad_pipe<TM, NTR, PM, FAST, BF16, true>(p, splits, st);
+static int wgrad_dispatch(WgradP& p, int splits, void* stream, int prec) {
+  const int Nw = p.Nw;
+  if (splits != vmtl_conv2d_wgrad_splits(p.M, Nw, p.Ktot)) return VMTL_ERR_ARG;
+  p.chunk = cdiv(cdiv(p.M, splits), BP) * BP;
+  hipStream_t st = (hipStream_t)stream;
+  switch (wgrad_rows(Nw)) {
+    case 16: return launch_wgrad<1>(p, splits, st, prec);
+    case 32: return launch_wgrad<2>(p, splits, st, prec);
+    case 48: return launch_wgrad<3>(p, splits, st, prec);
+    case 64: return launch_wgrad<4>(p, splits, st, prec);
+    case 80: return launch_wgrad<5>(p, splits, st, prec);
+    case 20: return launch_wgrad<1, 4>(p, splits, st, prec);
+    case 36: return launch_wgrad<2, 4>(p, splits, st, prec);
+    case 68: return launch_wgrad<4, 4>(p, splits, st, prec);
+    case 128: return launch_wgrad<8>(p, splits, st, prec);
+    default: return launch_wgrad<9>(p, splits, st, prec);
   }
-  return launch_wgrad_pipe<TM, NTR, PM, FAST, BF16, false>(p, splits, st);
 }
-
-template <int TM, int NTR, int PM, bool FAST, bool BF16, bool PIPE>
-static int launch_wgrad_pipe(WgradP& p, int splits, hipStream_t st) {
-  constexpr int BMC = TM * 16 + NTR;
-  constexpr int PD = (TM <= 2 ? 3 : (TM <= 4 && NTR == 0) ? 2 : 1);
-  const size_t lds = (size_t)2 * BP * (wg_ld(BMC, PM) + wg_ld(WG_BNK, PM)) * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<TM, NTR, PM, PD, FAST, BF16, PIPE>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  if ((long long)p.M * p.ldy * 4 >= (1ll << 32) || (long long)p.B * p.H * p.W * p.Cs * 4 >= (1ll << 32))
-    return VMTL_ERR_UNSUPPORTED;  // buffer addressing: 32-bit byte offsets
-  p.tiles_kk = cdiv(p.Ktot, WG_BNK);
-  p.tiles_co = cdiv(p.Nw, BMC);
-  p.splits = splits;
-  hipLaunchKernelGGL((conv_wgrad_kernel<TM, NTR, PM, PD, FAST, BF16, PIPE>), dim3(p.tiles_kk * p.tiles_co * splits), dim3(256), lds, st,
-                     p);
-  return vmtl_check_launch();
-}
-
-static int wgrad_dispatch(WgradP& p, int splits, void* stream, int prec);
 
 extern "C" int vmtl_conv2d_wgrad_p(const float* x, const float* dy, float* slabs, int splits, int B, int H, int W,
                                    int Cs, int Ho, int Wo, int ldy, int Nw, int KH, int KW, int stride, int pad,
@@ -592,7 +597,6 @@ extern "C" int vmtl_conv2d_wgrad_p(const float* x, const float* dy, float* slabs
   WgradP p;
   p.x = x; p.dy = dy; p.slabs = slabs; p.B = B; p.H = H; p.W = W; p.Cs = Cs; p.Ho = Ho; p.Wo = Wo; p.ldy = ldy;
   p.Nw = Nw; p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.Ktot = KH * KW * Cs; p.M = B * Ho * Wo;
-  p.x2 = nullptr; p.K1 = 0;
   return wgrad_dispatch(p, splits, stream, precision);
 }
 
@@ -622,23 +626,4 @@ extern "C" int vmtl_conv1x1_cat_wgrad_p(const float* x, int K1, const float* x2,
 extern "C" int vmtl_conv1x1_cat_wgrad(const float* x, int K1, const float* x2, int K2s, const float* dy, float* slabs,
                                       int splits, int M, int ldy, int Nw, void* stream) {
   return vmtl_conv1x1_cat_wgrad_p(x, K1, x2, K2s, dy, slabs, splits, M, ldy, Nw, VMTL_PREC_FP32, stream);
-}
-
-static int wgrad_dispatch(WgradP& p, int splits, void* stream, int prec) {
-  const int Nw = p.Nw;
-  if (splits != vmtl_conv2d_wgrad_splits(p.M, Nw, p.Ktot)) return VMTL_ERR_ARG;
-  p.chunk = cdiv(cdiv(p.M, splits), BP) * BP;
-  hipStream_t st = (hipStream_t)stream;
-  switch (wgrad_rows(Nw)) {
-    case 16: return launch_wgrad<1>(p, splits, st, prec);
-    case 32: return launch_wgrad<2>(p, splits, st, prec);
-    case 48: return launch_wgrad<3>(p, splits, st, prec);
-    case 64: return launch_wgrad<4>(p, splits, st, prec);
-    case 80: return launch_wgrad<5>(p, splits, st, prec);
-    case 20: return launch_wgrad<1, 4>(p, splits, st, prec);
-    case 36: return launch_wgrad<2, 4>(p, splits, st, prec);
-    case 68: return launch_wgrad<4, 4>(p, splits, st, prec);
-    case 128: return launch_wgrad<8>(p, splits, st, prec);
-    default: return launch_wgrad<9>(p, splits, st, prec);
-  }
 }

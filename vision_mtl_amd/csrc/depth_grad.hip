@@ -233,17 +233,12 @@ __global__ __launch_bounds__(256) void dg_bwd_kernel(const float* __restrict__ p
 
 // forward sweeps: a block per 1024 pixels, at most 1024 blocks (their partials are what the finalize reads)
 static inline int dg_blocks(long long P) {
-  long long nb = cdivll(P, DG_PIX_PER_BLOCK);
-  if (nb > DG_BLOCKS_MAX) nb = DG_BLOCKS_MAX;
-  if (nb < 1) nb = 1;
-  return (int)nb;
+  return grid_1d(P, DG_PIX_PER_BLOCK, DG_BLOCKS_MAX);
 }
 
 // backward sweep: no reduction, a pixel per thread while the grid allows it
 static inline int dg_bwd_blocks(long long P) {
-  long long nb = cdivll(P, 256);
-  if (nb > DG_BWD_BLOCKS_MAX) nb = DG_BWD_BLOCKS_MAX;
-  return (int)nb;
+  return grid_1d(P, 256, DG_BWD_BLOCKS_MAX);
 }
 
 // int pixel indices: i + grid stride, 4 * i (a byte offset) and 32 * W (the farthest neighbour's offset) all fit

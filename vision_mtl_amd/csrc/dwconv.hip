@@ -501,13 +501,6 @@ __global__ __launch_bounds__(256) void dwconv_bwd_w_finalize_kernel(const float*
   }
 }
 
-static inline int dw_grid(long long total4) {
-  long long nb = cdivll(total4, 256);
-  if (nb > 8192) nb = 8192;
-  if (nb < 1) nb = 1;
-  return (int)nb;
-}
-
 static int dw_check(int B, int H, int W, int Cs, int Ho, int Wo, int K, int stride, int pad) {
   if (B <= 0 || H <= 0 || W <= 0 || (Cs & 3) || Cs <= 0) return VMTL_ERR_ARG;
   if ((K != 3 && K != 5) || (stride != 1 && stride != 2) || pad < 0) return VMTL_ERR_ARG;
@@ -522,7 +515,7 @@ extern "C" int vmtl_dwconv_fwd(const float* x, const float* wp, float* y, int B,
   if (!x || !wp || !y) return VMTL_ERR_ARG;
   if (int e = dw_check(B, H, W, Cs, Ho, Wo, K, stride, pad)) return e;
   const long long total4 = (long long)B * Ho * Wo * (Cs >> 2);
-  hipLaunchKernelGGL(dwconv_fwd_kernel, dim3(dw_grid(total4)), dim3(256), 0, (hipStream_t)stream, x, wp, y, B, H, W,
+  hipLaunchKernelGGL(dwconv_fwd_kernel, dim3(grid_1d(total4, 256, 8192)), dim3(256), 0, (hipStream_t)stream, x, wp, y, B, H, W,
                      Cs, Ho, Wo, K, stride, pad, total4);
   return vmtl_check_launch();
 }
@@ -609,9 +602,9 @@ static int dw_bwd_data_impl(const float* dy, const float* wp, const float* adden
   if (!generic_only && pad == (K - 1) / 2 && (K == 3 || K == 5) && (W & 1) == 0 &&
       (stride == 1 || (stride == 2 && (H & 1) == 0 && Ho == H / 2 && Wo == W / 2))) {
     const long long total = stride == 1 ? total4 / 2 : total4 / 4;
-#define CALLD(KV, SV)                                                                                              \
-  hipLaunchKernelGGL((dwconv_bwd_data_tpl_kernel<KV, SV>), dim3(dw_grid(total)), dim3(256), 0, (hipStream_t)stream, dy, \
-                     wp, addend, dx, B, H, W, Cs, Ho, Wo, total)
+#define CALLD(KV, SV)                                                                                    \
+  hipLaunchKernelGGL((dwconv_bwd_data_tpl_kernel<KV, SV>), dim3(grid_1d(total, 256, 8192)), dim3(256), 0, \
+                     (hipStream_t)stream, dy, wp, addend, dx, B, H, W, Cs, Ho, Wo, total)
     if (K == 3 && stride == 1) CALLD(3, 1);
     else if (K == 3) CALLD(3, 2);
     else if (stride == 1) CALLD(5, 1);
@@ -619,7 +612,7 @@ static int dw_bwd_data_impl(const float* dy, const float* wp, const float* adden
 #undef CALLD
     return vmtl_check_launch();
   }
-  hipLaunchKernelGGL(dwconv_bwd_data_kernel, dim3(dw_grid(total4)), dim3(256), 0, (hipStream_t)stream, dy, wp, addend, dx,
+  hipLaunchKernelGGL(dwconv_bwd_data_kernel, dim3(grid_1d(total4, 256, 8192)), dim3(256), 0, (hipStream_t)stream, dy, wp, addend, dx,
                      B, H, W, Cs, Ho, Wo, K, stride, pad, total4);
   return vmtl_check_launch();
 }

@@ -14,13 +14,6 @@
 //   nchw<->nhwc  : boundary layout change (reference tensors are NCHW)
 #include "common.h"
 
-static inline int ew_grid(long long total, int per_block = 256) {
-  long long nb = cdivll(total, per_block);
-  if (nb > 8192) nb = 8192;
-  if (nb < 1) nb = 1;
-  return (int)nb;
-}
-
 // (channel quad, column, row, image) of flat float4 index i over a [B][H][W][CQ] map.  The decode is the bulk of the VALU work of
 // these streaming kernels: with 64-bit operands each division is ~100 instructions (bilinear x2 ran at 2.8 TB/s); every map of
 // this library has fewer than 2^31 float4 elements, so the 32-bit form is the one that runs (uniform switch).
@@ -142,7 +135,7 @@ extern "C" int vmtl_concat2(const float* a, int Ha, int Wa, int Ca, int Csa, int
   CatSrc s0{a, Ha, Wa, Ca, Csa, upa, oha, owa};
   CatSrc s1{b, Hb, Wb, Cb, Csb, Cb ? upb : 1, ohb, owb};
   const long long total4 = (long long)B * H * W * (Cd >> 2);
-  hipLaunchKernelGGL(concat2_kernel, dim3(ew_grid(total4)), dim3(256), 0, (hipStream_t)stream, s0, s1, y, B, H, W, Cd,
+  hipLaunchKernelGGL(concat2_kernel, dim3(grid_1d(total4, 256, 8192)), dim3(256), 0, (hipStream_t)stream, s0, s1, y, B, H, W, Cd,
                      total4);
   return vmtl_check_launch();
 }
@@ -153,7 +146,7 @@ extern "C" int vmtl_concat2_bwd(const float* dy, float* dx, int B, int H, int W,
   if (!dy || !dx || c_off < 0 || c_off + C > Cd || (Cs & 3) || (Cd & 3) || (up != 1 && up != 2)) return VMTL_ERR_ARG;
   if ((long long)B * Hs * Ws > 0x7fffffffLL) return VMTL_ERR_ARG;
   const long long total4 = (long long)B * Hs * Ws * (Cs >> 2);
-  hipLaunchKernelGGL(concat2_bwd_kernel, dim3(ew_grid(total4)), dim3(256), 0, (hipStream_t)stream, dy, dx, B, H, W, Cd,
+  hipLaunchKernelGGL(concat2_bwd_kernel, dim3(grid_1d(total4, 256, 8192)), dim3(256), 0, (hipStream_t)stream, dy, dx, B, H, W, Cd,
                      c_off, Hs, Ws, C, Cs, up, oh, ow, total4);
   return vmtl_check_launch();
 }
@@ -220,7 +213,7 @@ extern "C" int vmtl_maxpool2_fwd(const float* x, float* y, int B, int H, int W, 
   VMTL_ENTER();
   if (!x || !y || (Cs & 3) || (H & 1) || (W & 1) || H < 2 || W < 2) return VMTL_ERR_ARG;
   const long long total4 = (long long)B * (H / 2) * (W / 2) * (Cs >> 2);
-  hipLaunchKernelGGL(maxpool2_kernel, dim3(ew_grid(total4)), dim3(256), 0, (hipStream_t)stream, x, y, B, H, W, Cs,
+  hipLaunchKernelGGL(maxpool2_kernel, dim3(grid_1d(total4, 256, 8192)), dim3(256), 0, (hipStream_t)stream, x, y, B, H, W, Cs,
                      total4);
   return vmtl_check_launch();
 }
@@ -230,7 +223,7 @@ extern "C" int vmtl_maxpool2_bwd(const float* x, const float* dy, float* dx, int
   VMTL_ENTER();
   if (!x || !dy || !dx || (Cs & 3) || (H & 1) || (W & 1) || H < 2 || W < 2) return VMTL_ERR_ARG;
   const long long total4 = (long long)B * (H / 2) * (W / 2) * (Cs >> 2);
-  hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(ew_grid(total4)), dim3(256), 0, (hipStream_t)stream, x, dy, dx, B, H,
+  hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(grid_1d(total4, 256, 8192)), dim3(256), 0, (hipStream_t)stream, x, dy, dx, B, H,
                      W, Cs, total4);
   return vmtl_check_launch();
 }
@@ -320,7 +313,7 @@ extern "C" int vmtl_bilinear_up2_fwd(const float* x, float* y, int B, int H, int
   VMTL_ENTER();
   if (!x || !y || (Cs & 3) || B <= 0 || H <= 0 || W <= 0) return VMTL_ERR_ARG;
   const long long total4 = (long long)B * 4 * H * W * (Cs >> 2);
-  hipLaunchKernelGGL(bilinear_up2_kernel, dim3(ew_grid(total4)), dim3(256), 0, (hipStream_t)stream, x, y, B, H, W, Cs,
+  hipLaunchKernelGGL(bilinear_up2_kernel, dim3(grid_1d(total4, 256, 8192)), dim3(256), 0, (hipStream_t)stream, x, y, B, H, W, Cs,
                      bil_scale(H), bil_scale(W), total4);
   return vmtl_check_launch();
 }
@@ -329,7 +322,7 @@ extern "C" int vmtl_bilinear_up2_bwd(const float* dy, float* dx, int B, int H, i
   VMTL_ENTER();
   if (!dy || !dx || (Cs & 3) || B <= 0 || H <= 0 || W <= 0) return VMTL_ERR_ARG;
   const long long total4 = (long long)B * H * W * (Cs >> 2);
-  hipLaunchKernelGGL(bilinear_up2_bwd_kernel, dim3(ew_grid(total4)), dim3(256), 0, (hipStream_t)stream, dy, dx, B, H,
+  hipLaunchKernelGGL(bilinear_up2_bwd_kernel, dim3(grid_1d(total4, 256, 8192)), dim3(256), 0, (hipStream_t)stream, dy, dx, B, H,
                      W, Cs, bil_scale(H), bil_scale(W), total4);
   return vmtl_check_launch();
 }
@@ -403,7 +396,7 @@ extern "C" int vmtl_channel_bcast(const float* x, const float* s, float* y, int 
   VMTL_ENTER();
   if (!s || !y || (mode == 0 && !x) || (Cs & 3) || B <= 0 || HW <= 0) return VMTL_ERR_ARG;
   const long long total4 = (long long)B * HW * (Cs >> 2);
-  hipLaunchKernelGGL(channel_bcast_kernel, dim3(ew_grid(total4)), dim3(256), 0, (hipStream_t)stream, x, s, y, HW, Cs,
+  hipLaunchKernelGGL(channel_bcast_kernel, dim3(grid_1d(total4, 256, 8192)), dim3(256), 0, (hipStream_t)stream, x, s, y, HW, Cs,
                      mode, total4);
   return vmtl_check_launch();
 }
@@ -440,7 +433,7 @@ extern "C" int vmtl_stitch(const float* x, const float* w, float* y, long long M
   VMTL_ENTER();
   if (!x || !w || !y || (Cs & 3) || M <= 0 || C > Cs) return VMTL_ERR_ARG;
   const long long total4 = M * (Cs >> 2);
-  hipLaunchKernelGGL(stitch_kernel, dim3(ew_grid(total4)), dim3(256), 0, (hipStream_t)stream, x, w, y, C, Cs, wstride,
+  hipLaunchKernelGGL(stitch_kernel, dim3(grid_1d(total4, 256, 8192)), dim3(256), 0, (hipStream_t)stream, x, w, y, C, Cs, wstride,
                      total4);
   return vmtl_check_launch();
 }
@@ -470,7 +463,7 @@ __global__ __launch_bounds__(256) void axpby_kernel(const float* __restrict__ a,
 extern "C" int vmtl_axpby(const float* a, const float* b, float* y, float wa, float wb, long long total, void* stream) {
   VMTL_ENTER();
   if (!a || !b || !y || total <= 0) return VMTL_ERR_ARG;
-  hipLaunchKernelGGL(axpby_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, a, b, y, wa, wb, total);
+  hipLaunchKernelGGL(axpby_kernel, dim3(grid_1d(total, 256, 8192)), dim3(256), 0, (hipStream_t)stream, a, b, y, wa, wb, total);
   return vmtl_check_launch();
 }
 
@@ -493,7 +486,7 @@ extern "C" int vmtl_add_n(const float* a, const float* b, const float* c, const 
   VMTL_ENTER();
   if (!a || !b || !y || total <= 0 || (total & 3) || (d && !c)) return VMTL_ERR_ARG;
   if ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d | (uintptr_t)y) & 15) != 0) return VMTL_ERR_ARG;
-  hipLaunchKernelGGL(add_n_kernel, dim3(ew_grid(total / 4)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)a,
+  hipLaunchKernelGGL(add_n_kernel, dim3(grid_1d(total / 4, 256, 8192)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)a,
                      (const f32x4*)b, (const f32x4*)c, (const f32x4*)d, (f32x4*)y, total / 4);
   return vmtl_check_launch();
 }
@@ -501,7 +494,7 @@ extern "C" int vmtl_add_n(const float* a, const float* b, const float* c, const 
 extern "C" int vmtl_eltwise(const float* a, const float* b, float* y, int mode, long long total, void* stream) {
   VMTL_ENTER();
   if (!a || !y || total <= 0 || mode < 0 || mode > 3 || (mode != 1 && !b)) return VMTL_ERR_ARG;
-  hipLaunchKernelGGL(ew_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, a, b, y, mode, total);
+  hipLaunchKernelGGL(ew_kernel, dim3(grid_1d(total, 256, 8192)), dim3(256), 0, (hipStream_t)stream, a, b, y, mode, total);
   return vmtl_check_launch();
 }
 
@@ -527,7 +520,7 @@ extern "C" int vmtl_argmax_channels(const float* z, long long* out, int B, int H
   VMTL_ENTER();
   if (!z || !out || B <= 0 || HW <= 0 || C <= 0) return VMTL_ERR_ARG;
   const long long P = (long long)B * HW;
-  hipLaunchKernelGGL(argmax_kernel, dim3(ew_grid(P)), dim3(256), 0, (hipStream_t)stream, z, out, HW, C, sb, sc, sp, P);
+  hipLaunchKernelGGL(argmax_kernel, dim3(grid_1d(P, 256, 8192)), dim3(256), 0, (hipStream_t)stream, z, out, HW, C, sb, sc, sp, P);
   return vmtl_check_launch();
 }
 
@@ -561,7 +554,7 @@ extern "C" int vmtl_nchw_to_nhwc(const float* x, float* y, int B, int C, int HW,
   VMTL_ENTER();
   if (!x || !y || C > Cw || Cw > Cs || B <= 0) return VMTL_ERR_ARG;
   const long long total = (long long)B * HW * Cw;
-  hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, x, y, C, HW, Cs,
+  hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(grid_1d(total, 256, 8192)), dim3(256), 0, (hipStream_t)stream, x, y, C, HW, Cs,
                      Cw, total);
   return vmtl_check_launch();
 }
@@ -570,7 +563,7 @@ extern "C" int vmtl_nhwc_to_nchw(const float* x, float* y, int B, int C, int HW,
   VMTL_ENTER();
   if (!x || !y || C > Cs || B <= 0) return VMTL_ERR_ARG;
   const long long total = (long long)B * C * HW;
-  hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, x, y, C, HW, Cs,
+  hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(grid_1d(total, 256, 8192)), dim3(256), 0, (hipStream_t)stream, x, y, C, HW, Cs,
                      total);
   return vmtl_check_launch();
 }
@@ -591,7 +584,7 @@ extern "C" int vmtl_hwc_to_nhwc_pad(const float* x, float* y, long long P, int C
   VMTL_ENTER();
   if (!x || !y || P <= 0 || C <= 0 || C > Cs || (Cs & 3)) return VMTL_ERR_ARG;
   const long long total = P * Cs;
-  hipLaunchKernelGGL(hwc_pad_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, x, y, C, Cs, scale, total);
+  hipLaunchKernelGGL(hwc_pad_kernel, dim3(grid_1d(total, 256, 8192)), dim3(256), 0, (hipStream_t)stream, x, y, C, Cs, scale, total);
   return vmtl_check_launch();
 }
 

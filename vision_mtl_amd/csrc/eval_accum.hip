@@ -247,10 +247,7 @@ __global__ __launch_bounds__(64) void ea_finalize_kernel(const long long* __rest
 }
 
 static inline int ea_depth_blocks(long long Pd) {
-  long long nb = cdivll(Pd, 1024);
-  if (nb > EA_BLOCKS_MAX) nb = EA_BLOCKS_MAX;
-  if (nb < 1) nb = 1;
-  return (int)nb;
+  return grid_1d(Pd, 1024, EA_BLOCKS_MAX);
 }
 
 extern "C" long long vmtl_eval_accum_workspace_bytes(long long P) {

@@ -306,10 +306,8 @@ extern "C" int vmtl_channel_scale_add(const float* x, const float* s, const floa
   VMTL_ENTER();
   if (!x || !s || !y || (Cs & 3) || B <= 0 || HW <= 0) return VMTL_ERR_ARG;
   const long long total4 = (long long)B * HW * (Cs >> 2);
-  long long blocks = (total4 + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(channel_scale_add_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, s, t, t_scale,
-                     y, HW, Cs, total4);
+  hipLaunchKernelGGL(channel_scale_add_kernel, dim3(grid_1d(total4, 256, 4096)), dim3(256), 0, (hipStream_t)stream, x, s,
+                     t, t_scale, y, HW, Cs, total4);
   return vmtl_check_launch();
 }
 

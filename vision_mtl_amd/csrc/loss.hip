@@ -339,10 +339,7 @@ __global__ __launch_bounds__(256) void ce_bwd_nhwc_rows_kernel(const float* __re
 
 // ------------------------------------------------------------------ cross entropy: launchers and entry points
 static inline int ce_blocks(long long P) {
-  long long nb = cdivll(P, CE_THREADS);
-  if (nb > 2048) nb = 2048;
-  if (nb < 1) nb = 1;
-  return (int)nb;
+  return grid_1d(P, CE_THREADS, 2048);
 }
 
 // The per-block partials of the loss into `partial` (ce_blocks(P) entries): logits in registers for C <= 32.
@@ -386,10 +383,9 @@ static void ce_bwd_launch(const float* logits, const long long* target, const fl
                           CeEx<EX> ex, long long P, int HW, int C, long long sb, long long sc, long long sp,
                           long long dsb, long long dsc, long long dsp, hipStream_t st) {
   if (dsc == 1 && dsp == ((C + 3) & ~3) && dsp <= 32 && dsb == dsp * HW) {
-    long long nb = cdivll(P, 256);
-    if (nb > 8192) nb = 8192;
-#define CALL(QV)                                                                                                 \
-  hipLaunchKernelGGL((ce_bwd_nhwc_rows_kernel<QV, EX>), dim3((int)nb), dim3(256), 0, st, logits, target, grad_out, \
+    const int nb = grid_1d(P, 256, 8192);
+#define CALL(QV)                                                                                            \
+  hipLaunchKernelGGL((ce_bwd_nhwc_rows_kernel<QV, EX>), dim3(nb), dim3(256), 0, st, logits, target, grad_out, \
                      dlogits, P, HW, C, sb, sc, sp, ex)
     switch ((int)dsp >> 2) {
       case 1: CALL(1); break;
@@ -403,9 +399,8 @@ static void ce_bwd_launch(const float* logits, const long long* target, const fl
     }
 #undef CALL
   } else if (dsc == 1 && (dsp & 3) == 0 && dsp >= ((C + 3) & ~3) && dsb == dsp * HW) {
-    long long nb = cdivll(P * ((C + 3) >> 2), CE_THREADS);
-    if (nb > 8192) nb = 8192;
-    hipLaunchKernelGGL(ce_bwd_nhwc_kernel<EX>, dim3((int)nb), dim3(CE_THREADS), 0, st, logits, target, grad_out, dlogits,
+    const int nb = grid_1d(P * ((C + 3) >> 2), CE_THREADS, 8192);
+    hipLaunchKernelGGL(ce_bwd_nhwc_kernel<EX>, dim3(nb), dim3(CE_THREADS), 0, st, logits, target, grad_out, dlogits,
                        P, HW, C, sb, sc, sp, (int)dsp, ex);
   } else {
     ce_bwd_launch_strided<EX>(logits, target, grad_out, dlogits, ex, P, HW, C, sb, sc, sp, dsb, dsc, dsp, st);
@@ -580,10 +575,7 @@ __global__ __launch_bounds__(256) void silog_bwd_kernel(const float* __restrict_
 }
 
 static inline int sl_blocks(long long P) {
-  long long nb = cdivll(P, 1024);
-  if (nb > SL_BLOCKS_MAX) nb = SL_BLOCKS_MAX;
-  if (nb < 1) nb = 1;
-  return (int)nb;
+  return grid_1d(P, 1024, SL_BLOCKS_MAX);
 }
 
 extern "C" long long vmtl_silog_workspace_bytes(long long P) { return (long long)sl_blocks(P) * 3 * sizeof(double); }

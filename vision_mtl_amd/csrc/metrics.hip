@@ -64,11 +64,8 @@ static int confusion_launch(const long long* pred, const long long* target, int*
   if (!pred || !target || !cm || P <= 0 || C <= 0 || C > CM_MAX_C) return VMTL_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(cm, 0, (size_t)C * C * sizeof(int), st) != hipSuccess) return VMTL_ERR_LAUNCH;
-  long long nb = cdivll(P, 256 * 8);
-  if (nb > 1024) nb = 1024;
-  if (nb < 1) nb = 1;
-  hipLaunchKernelGGL(confusion_kernel<IGN>, dim3((int)nb), dim3(256), (size_t)C * C * sizeof(int), st, pred, target, cm,
-                     P, C, ignore);
+  hipLaunchKernelGGL(confusion_kernel<IGN>, dim3(grid_1d(P, 256 * 8, 1024)), dim3(256), (size_t)C * C * sizeof(int), st, pred,
+                     target, cm, P, C, ignore);
   return vmtl_check_launch();
 }
 

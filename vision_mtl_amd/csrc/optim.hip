@@ -29,10 +29,7 @@
 #define VMTL_OPTIM_CTL_FLOATS 16
 
 static inline int opt_blocks(long long n) {  // float4 per thread and trip; a function of n alone (see Determinism)
-  long long nb = cdivll(n, 4 * OPT_THREADS);
-  if (nb > OPT_MAX_BLOCKS) nb = OPT_MAX_BLOCKS;
-  if (nb < 1) nb = 1;
-  return (int)nb;
+  return grid_1d(n, 4 * OPT_THREADS, OPT_MAX_BLOCKS);
 }
 
 // elements in front of the first 16-byte boundary of a 4-byte-aligned pointer, at most n
@@ -242,9 +239,8 @@ extern "C" int vmtl_adam_step_ex(float* p, const float* g, float* m, float* v, c
     hipLaunchKernelGGL(adam_ex_kernel<true>, dim3(opt_blocks(n)), dim3(OPT_THREADS), 0, (hipStream_t)stream, p, g, m,
                        v, ctl, lr, lr_ptr, eps, weight_decay, decoupled, grad_scale, n);
   } else {
-    long long nb = cdivll(n, OPT_THREADS);
-    if (nb > 4 * OPT_MAX_BLOCKS) nb = 4 * OPT_MAX_BLOCKS;
-    hipLaunchKernelGGL(adam_ex_kernel<false>, dim3((int)nb), dim3(OPT_THREADS), 0, (hipStream_t)stream, p, g, m, v,
+    const int nb = grid_1d(n, OPT_THREADS, 4 * OPT_MAX_BLOCKS);
+    hipLaunchKernelGGL(adam_ex_kernel<false>, dim3(nb), dim3(OPT_THREADS), 0, (hipStream_t)stream, p, g, m, v,
                        ctl, lr, lr_ptr, eps, weight_decay, decoupled, grad_scale, n);
   }
   return vmtl_check_launch();

@@ -92,9 +92,7 @@ extern "C" int vmtl_pack_desc_bytes(void) { return (int)sizeof(PackDesc); }
 extern "C" int vmtl_pack_weights_batch(const void* descs, int n, long long total, void* stream) {
   VMTL_ENTER();
   if (!descs || n <= 0 || total <= 0) return VMTL_ERR_ARG;
-  long long nb = cdivll(total, 256);
-  if (nb > 8192) nb = 8192;
-  hipLaunchKernelGGL(pack_batch_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(pack_batch_kernel, dim3(grid_1d(total, 256, 8192)), dim3(256), 0, (hipStream_t)stream,
                      (const PackDesc*)descs, n, total);
   return vmtl_check_launch();
 }
@@ -157,19 +155,12 @@ __global__ __launch_bounds__(256) void unpack_kernel(const float* __restrict__ p
   }
 }
 
-static inline int pk_grid(long long total) {
-  long long nb = cdivll(total, 256);
-  if (nb > 4096) nb = 4096;
-  if (nb < 1) nb = 1;
-  return (int)nb;
-}
-
 extern "C" int vmtl_pack_weights(const float* src, float* dst, int R1, int R0, int T, int C, int Cs, long long sr1,
                                  long long sr0, long long st, long long sc, int flip, void* stream) {
   VMTL_ENTER();
   if (!src || !dst || R1 <= 0 || R0 <= 0 || T <= 0 || C <= 0 || C > Cs) return VMTL_ERR_ARG;
   const long long total = (long long)R1 * R0 * T * Cs;
-  hipLaunchKernelGGL(pack_kernel, dim3(pk_grid(total)), dim3(256), 0, (hipStream_t)stream, src, dst, R1, R0, T, C, Cs,
+  hipLaunchKernelGGL(pack_kernel, dim3(grid_1d(total, 256, 4096)), dim3(256), 0, (hipStream_t)stream, src, dst, R1, R0, T, C, Cs,
                      sr1, sr0, st, sc, flip, total, (const float*)nullptr, 0, 0);
   return vmtl_check_launch();
 }
@@ -182,7 +173,7 @@ extern "C" int vmtl_pack_weights_scaled(const float* src, float* dst, int R1, in
   if (!src || !dst || !scale || R1 <= 0 || R0 <= 0 || T <= 0 || C <= 0 || C > Cs || (smode != 1 && smode != 2) || sstride < 0)
     return VMTL_ERR_ARG;
   const long long total = (long long)R1 * R0 * T * Cs;
-  hipLaunchKernelGGL(pack_kernel, dim3(pk_grid(total)), dim3(256), 0, (hipStream_t)stream, src, dst, R1, R0, T, C, Cs,
+  hipLaunchKernelGGL(pack_kernel, dim3(grid_1d(total, 256, 4096)), dim3(256), 0, (hipStream_t)stream, src, dst, R1, R0, T, C, Cs,
                      sr1, sr0, st, sc, flip, total, scale, sstride, smode);
   return vmtl_check_launch();
 }
@@ -192,7 +183,7 @@ extern "C" int vmtl_pack_weights_slice(const float* src, float* dst, int R0, int
   VMTL_ENTER();
   if (!src || !dst || R0 <= 0 || T <= 0 || C <= 0 || C > group) return VMTL_ERR_ARG;
   const long long total = (long long)R0 * T * C;
-  hipLaunchKernelGGL(pack_slice_kernel, dim3(pk_grid(total)), dim3(256), 0, (hipStream_t)stream, src, dst, R0, T, C,
+  hipLaunchKernelGGL(pack_slice_kernel, dim3(grid_1d(total, 256, 4096)), dim3(256), 0, (hipStream_t)stream, src, dst, R0, T, C,
                      group, sr0, st, sc, flip, total);
   return vmtl_check_launch();
 }
@@ -204,9 +195,7 @@ extern "C" int vmtl_unpack_weights(const float* packed, float* grad, int R1, int
   if (!packed || !grad || R1 <= 0 || R0 <= 0 || T <= 0 || C <= 0 || C > Cs || nslabs <= 0) return VMTL_ERR_ARG;
   if (slab_stride <= 0) slab_stride = (long long)R1 * R0 * T * Cs;  // slabs hold exactly these rows
   const long long total = (long long)R1 * R0 * T * C;
-  long long nb = cdivll(total, 64);
-  if (nb > 8192) nb = 8192;
-  hipLaunchKernelGGL(unpack_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, packed, grad, R1, R0, T, C, Cs,
+  hipLaunchKernelGGL(unpack_kernel, dim3(grid_1d(total, 64, 8192)), dim3(256), 0, (hipStream_t)stream, packed, grad, R1, R0, T, C, Cs,
                      sr1, sr0, st, sc, flip, nslabs, slab_stride, total);
   return vmtl_check_launch();
 }
@@ -284,10 +273,8 @@ extern "C" int vmtl_unpack_weights_stitch(const float* packed, float* grad, cons
     return VMTL_ERR_ARG;
   if (slab_stride <= 0) slab_stride = (long long)R0 * T * Cs;
   const long long total = (long long)R0 * C * T;
-  long long nb = cdivll(total, 64);
-  if (nb > 8192) nb = 8192;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(unpack_stitch_kernel, dim3((int)nb), dim3(256), 0, st, packed, grad, work, w, scale, sstride, R0, T, C,
+  hipLaunchKernelGGL(unpack_stitch_kernel, dim3(grid_1d(total, 64, 8192)), dim3(256), 0, st, packed, grad, work, w, scale, sstride, R0, T, C,
                      Cs, nslabs, slab_stride, total);
   float* per_c = reduce_all ? work + total : ds;
   hipLaunchKernelGGL(stitch_wsum_kernel, dim3(C), dim3(256), 0, st, work, per_c, R0, C, T);
@@ -400,7 +387,7 @@ extern "C" int vmtl_pack_up2_fwd(const float* w, float* dst, int Cout, int C0, i
   VMTL_ENTER();
   if (!w || !dst || Cout <= 0 || C0 <= 0 || C0 > C0s || C1 < 0 || C1 > C1s) return VMTL_ERR_ARG;
   const long long total = 4ll * Cout * (4 * C0s + 9 * C1s);
-  hipLaunchKernelGGL(pack_up2_fwd_kernel, dim3(pk_grid(total)), dim3(256), 0, (hipStream_t)stream, w, dst, Cout, C0,
+  hipLaunchKernelGGL(pack_up2_fwd_kernel, dim3(grid_1d(total, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, dst, Cout, C0,
                      C0s, C1, C1s, total);
   return vmtl_check_launch();
 }
@@ -409,7 +396,7 @@ extern "C" int vmtl_pack_up2_dgrad(const float* w, float* dst, int Cout, int Cos
   VMTL_ENTER();
   if (!w || !dst || Cout <= 0 || Cout > Cos || C0 <= 0 || C0 > Cin) return VMTL_ERR_ARG;
   const long long total = (long long)C0 * 16 * Cos;
-  hipLaunchKernelGGL(pack_up2_dgrad_kernel, dim3(pk_grid(total)), dim3(256), 0, (hipStream_t)stream, w, dst, Cout, Cos,
+  hipLaunchKernelGGL(pack_up2_dgrad_kernel, dim3(grid_1d(total, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, dst, Cout, Cos,
                      C0, Cin, total);
   return vmtl_check_launch();
 }
@@ -419,9 +406,7 @@ extern "C" int vmtl_unpack_up2(const float* slabs, float* grad, int Cout, int Co
   VMTL_ENTER();
   if (!slabs || !grad || Cout <= 0 || Cout > Cos || C0 <= 0 || C0 > Cin || nslabs <= 0) return VMTL_ERR_ARG;
   const long long total = (long long)C0 * 9 * Cout;
-  long long nb = cdivll(total, 64);
-  if (nb > 8192) nb = 8192;
-  hipLaunchKernelGGL(unpack_up2_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, slabs, grad, Cout,
+  hipLaunchKernelGGL(unpack_up2_kernel, dim3(grid_1d(total, 64, 8192)), dim3(256), 0, (hipStream_t)stream, slabs, grad, Cout,
                      Cos, C0, Cin, nslabs, (long long)C0 * 16 * Cos, total);
   return vmtl_check_launch();
 }
@@ -454,7 +439,7 @@ extern "C" int vmtl_adam_step(float* p, const float* g, float* m, float* v, cons
                               float b2, float eps, float weight_decay, float grad_scale, long long n, void* stream) {
   VMTL_ENTER();
   if (!p || !g || !m || !v || !step_ptr || n <= 0) return VMTL_ERR_ARG;
-  hipLaunchKernelGGL(adam_kernel, dim3(pk_grid(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, step_ptr, lr, b1,
+  hipLaunchKernelGGL(adam_kernel, dim3(grid_1d(n, 256, 4096)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, step_ptr, lr, b1,
                      b2, eps, weight_decay, grad_scale, n);
   return vmtl_check_launch();
 }

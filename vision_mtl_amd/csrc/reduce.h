@@ -262,10 +262,7 @@ static inline int sweep_blocks(long long M, int Cs) {
   // ~16 float4 per thread per block keeps enough loads in flight without starving the grid
   long long per_blk = (long long)RED_THREADS * 16 / (Cs >> 2 > 0 ? (Cs >> 2) : 1);
   if (per_blk < 1) per_blk = 1;
-  long long nb = (M + per_blk - 1) / per_blk;
-  if (nb > 8192) nb = 8192;
-  if (nb < 1) nb = 1;
-  return (int)nb;
+  return grid_1d(M, (int)per_blk, 8192);
 }
 
 // Chan's parallel merge of (count, mean, M2) per channel quad: (n, mean, m2) <- merged with (nb, mb, m2b)

@@ -21,13 +21,6 @@
 
 #define TTA_MAX_C 32
 
-static inline int tta_grid(long long P) {
-  long long nb = cdivll(P, 256);
-  if (nb > 8192) nb = 8192;
-  if (nb < 1) nb = 1;
-  return (int)nb;
-}
-
 // pixel i of [B][H][W] -> (b, y, x); the 32-bit form is the one that runs (uniform switch: 64-bit divisions are ~100
 // instructions each), the 64-bit one takes over when B * H * W passes 2^31
 __device__ __forceinline__ void tta_byx(long long i, int H, int W, bool small, int& b, int& y, int& x) {
@@ -336,7 +329,7 @@ extern "C" int vmtl_tta_view(const float* img, int ld, float* out, int B, int H,
   const bool same = H == Ho && W == Wo, small = tta_small(P);
   const float sh = tta_scale(H, Ho), sw = tta_scale(W, Wo);
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid(tta_grid(P)), block(256);
+  const dim3 grid(grid_1d(P, 256, 8192)), block(256);
 #define TTA_VIEW(LD, SAME) \
   hipLaunchKernelGGL((tta_view_kernel<LD, SAME>), grid, block, 0, st, img, (f32x4*)out, H, W, Ho, Wo, sh, sw, flip, P, small)
   if (ld == 4) {
@@ -362,7 +355,7 @@ extern "C" int vmtl_tta_accumulate(const float* logits, const float* depth_logit
   const bool same = h == H && w == W, small = tta_small(P);
   const float sh = tta_scale(h, H), sw = tta_scale(w, W), dw = weight * depth_gain;
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid(tta_grid(P)), block(256);
+  const dim3 grid(grid_1d(P, 256, 8192)), block(256);
 #define TTA_ACC(MODE, SAME)                                                                                          \
   hipLaunchKernelGGL((tta_accumulate_kernel<MODE, SAME>), grid, block, 0, st, logits, depth_logits, acc, acc_depth, C, \
                      h, w, H, W, sh, sw, flip, weight, dw, first, P, small)
@@ -387,9 +380,9 @@ extern "C" int vmtl_tta_finish(const float* acc, const float* acc_depth, float i
   const dim3 block(256);
   if (H == Ho && W == Wo) {
     const long long HW = (long long)H * W;
-#define TTA_FIN(MODE)                                                                                               \
-  hipLaunchKernelGGL((tta_finish_same_kernel<MODE>), dim3(tta_grid(P)), block, 0, st, acc, acc_depth, inv_weight, segm, \
-                     depth, confidence, C, HW, P, tta_small(P))
+#define TTA_FIN(MODE)                                                                                            \
+  hipLaunchKernelGGL((tta_finish_same_kernel<MODE>), dim3(grid_1d(P, 256, 8192)), block, 0, st, acc, acc_depth, \
+                     inv_weight, segm, depth, confidence, C, HW, P, tta_small(P))
     if (mode == VMTL_TTA_PROB) TTA_FIN(VMTL_TTA_PROB); else TTA_FIN(VMTL_TTA_LOGIT);
 #undef TTA_FIN
     return vmtl_check_launch();
@@ -397,9 +390,9 @@ extern "C" int vmtl_tta_finish(const float* acc, const float* acc_depth, float i
   const int G = cdiv(Ho, TTA_ROWS);
   const long long PG = (long long)B * G * Wo;
   const float sh = tta_scale(H, Ho), sw = tta_scale(W, Wo);
-#define TTA_FIN(MODE)                                                                                               \
-  hipLaunchKernelGGL((tta_finish_rows_kernel<MODE>), dim3(tta_grid(PG)), block, 0, st, acc, acc_depth, inv_weight, segm, \
-                     depth, confidence, C, H, W, Ho, Wo, G, sh, sw, PG, tta_small(PG))
+#define TTA_FIN(MODE)                                                                                             \
+  hipLaunchKernelGGL((tta_finish_rows_kernel<MODE>), dim3(grid_1d(PG, 256, 8192)), block, 0, st, acc, acc_depth, \
+                     inv_weight, segm, depth, confidence, C, H, W, Ho, Wo, G, sh, sw, PG, tta_small(PG))
   if (mode == VMTL_TTA_PROB) TTA_FIN(VMTL_TTA_PROB); else TTA_FIN(VMTL_TTA_LOGIT);
 #undef TTA_FIN
   return vmtl_check_launch();

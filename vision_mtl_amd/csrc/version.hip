@@ -11,6 +11,19 @@ int vmtl_env_epoch = 1;
 // re-read the VMTL_* tuning overrides on their next use (they are cached after the first read)
 extern "C" int vmtl_reload_env(void) { return ++vmtl_env_epoch; }
 
+// the persistent grids (conv_small, pw_big) size themselves by the CU count of the device current at first use
+int vmtl_num_cus() {
+  static int n = 0;
+  if (n == 0) {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        v <= 0)
+      v = 256;
+    n = v;
+  }
+  return n;
+}
+
 // HIP's description of the last launch failure seen on this thread (status -2), for error messages
 extern "C" const char* vmtl_last_error_string(void) { return hipGetErrorString((hipError_t)vmtl_last_hip_error); }
 
