@@ -267,6 +267,38 @@ int vmtl_dwconv_bwd_data_add(const float* dy, const float* wp, const float* adde
 int vmtl_dwconv_bwd_weight_rows(int M, int Cs);
 int vmtl_dwconv_bwd_weight(const float* x, const float* dy, float* partial, float* dw, int B, int H, int W,
                            int C, int Cs, int Ho, int Wo, int K, int stride, int pad, void* stream);
+/* The three row queries above (vmtl_dwconv_bn_stats_rows, vmtl_dwconv_bn_stats_block, vmtl_dwconv_bwd_weight_rows) never
+ * trap: for M <= 0 or Cs <= 0 the two row counts are 1 and the block is some positive even number.  Every launcher above
+ * answers Ho <= 0, Wo <= 0 or a padded map smaller than the kernel (H + 2*pad < K, W + 2*pad < K) with -1.
+ *
+ * Which kernel a depthwise launcher starts: host-only queries over the launcher's own integer arguments.  The launchers
+ * switch on these results, so the answer is the dispatch.  < 0: the status the launcher returns for these arguments.
+ * Otherwise a bit field:
+ *   VMTL_DW_ROUTE_ACT_MASK  fused forward: the VMTL_ACT_* code the kernel is instantiated for (none / relu / hswish)
+ *   VMTL_DW_ROUTE_SPEC      the compile-time specialisation (fused forward: the pair kernel, needs an even Wo; data
+ *                           gradient: even W, for stride 2 also even H; weight gradient: the pair kernel, even Wo; the
+ *                           gradients also need pad == (K-1)/2); clear = the run-time-K "generic" kernel.  VMTL_DWBN_GENERIC
+ *                           (non-zero, read with the other VMTL_* overrides) clears it everywhere
+ *   VMTL_DW_ROUTE_K5        K == 5.  Set on specialised routes and on the generic weight gradient (its <25> instantiation;
+ *                           clear = <9>); always clear on the generic forward and data gradient, which take K at run time
+ *   VMTL_DW_ROUTE_S2        stride == 2, specialised routes only
+ *   VMTL_DW_ROUTE_WLDS      fused forward, 5x5 pair kernel: the packed weights go through LDS - when a statistics block has
+ *                           at least 12 output pixels and the 25*Cs floats fit into a workgroup's 160 KB next to the
+ *                           kernel's 9216 static bytes (Cs <= 1544)
+ *   VMTL_DW_ROUTE_FIN32     weight gradient: the finalize with 32 elements per workgroup (C*K*K >= 4096), clear = 8
+ *   VMTL_DW_ROUTE_QL(r)     weight gradient: quad lanes of the first stage, 1, 2, 4, 8 or 16
+ * The fused forward has 3 generic + 18 specialised routes, the data gradient 1 + 4, the weight gradient 2 + 4 first stages
+ * x 2 finalizes x 5 lane counts. */
+#define VMTL_DW_ROUTE_ACT_MASK 3
+#define VMTL_DW_ROUTE_SPEC 4
+#define VMTL_DW_ROUTE_K5 8
+#define VMTL_DW_ROUTE_S2 16
+#define VMTL_DW_ROUTE_WLDS 32
+#define VMTL_DW_ROUTE_FIN32 64
+#define VMTL_DW_ROUTE_QL(r) (1 << (((r) >> 8) & 7))
+int vmtl_dwconv_bn_fwd_route(int B, int H, int W, int Cs, int Ho, int Wo, int K, int stride, int pad, int act);
+int vmtl_dwconv_bwd_data_route(int B, int H, int W, int Cs, int Ho, int Wo, int K, int stride, int pad);
+int vmtl_dwconv_bwd_weight_route(int B, int H, int W, int C, int Cs, int Ho, int Wo, int K, int stride, int pad);
 
 /* torch parameter layout <-> packed GEMM operand (formula in csrc/pack.hip). */
 int vmtl_pack_weights(const float* src, float* dst, int R1, int R0, int T, int C, int Cs, long long sr1,

@@ -25,7 +25,7 @@ pytestmark = pytest.mark.gpu
 
 # every test of these modules is swept
 SWEPT_MODULES = ("test_kernels_gpu", "test_conv_small_gpu", "test_resnet_kernels_gpu", "test_se_gate_gpu",
-                 "test_stitch_mix_gpu")
+                 "test_stitch_mix_gpu", "test_dwconv_kernels_gpu")
 
 # of these modules, the functions that call ops nodes directly and build no model (the bf16 instantiations are
 # different kernels from the fp32 ones the modules above reach)
@@ -73,6 +73,10 @@ EXCLUDED_LAUNCH = [
      "2 Mi pixels, there for the stride loop past the grid cap: allocation-heavy under a copy per launch"),
     ("tests/test_loss_ignore_gpu.py::test_silog_with_mask[4194307]",
      "4 Mi pixels, there for the block cap of sl_blocks: allocation-heavy under a copy per launch"),
+    ("tests/test_dwconv_kernels_gpu.py::test_past_the_grid_cap[past-the-grid-cap-fwd-and-generic-dgrad]",
+     "2 Mi work items, there for the stride loop past the grid cap: allocation-heavy under a copy per launch"),
+    ("tests/test_dwconv_kernels_gpu.py::test_past_the_grid_cap[past-the-grid-cap-tpl-k3s1-dgrad]",
+     "2 Mi work items, there for the stride loop past the grid cap: allocation-heavy under a copy per launch"),
 ]
 
 LEFT_IN_PLACE_CAP = 0.05  # of the tensor arguments of test_launch_guarded (see the tally test): a condition, not a measurement

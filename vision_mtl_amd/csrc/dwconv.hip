@@ -105,9 +105,15 @@ __global__ __launch_bounds__(RED_THREADS) void dwconv_bn_fwd_kernel(
     red_n[t] = t < T ? n : 0.f;
     __syncthreads();
     if (t < cq) {
+      // the row lanes are merged as DEVIATIONS from the first lane's mean: a running mean near a large |mean| would be
+      // rounded to that magnitude's grid at every merge, and over 256 lanes those roundings add up (1.5e-4 of the
+      // variance at mean / std = 6000); differences of nearby means are exact
+      const f32x4 base = red_mean[t];
       float nt = red_n[t];
-      f32x4 mt = red_mean[t], m2t = red_m2[t];
-      for (int j = 1; j < rpt; ++j) chan_merge(nt, mt, m2t, red_n[t + j * cq], red_mean[t + j * cq], red_m2[t + j * cq]);
+      f32x4 mt = {0.f, 0.f, 0.f, 0.f}, m2t = red_m2[t];
+      for (int j = 1; j < rpt; ++j)
+        chan_merge(nt, mt, m2t, red_n[t + j * cq], red_mean[t + j * cq] - base, red_m2[t + j * cq]);
+      mt += base;
       *reinterpret_cast<f32x4*>(partial + ((size_t)blockIdx.x * 2 + 0) * Cs + (size_t)(q0 + t) * 4) = mt;
       *reinterpret_cast<f32x4*>(partial + ((size_t)blockIdx.x * 2 + 1) * Cs + (size_t)(q0 + t) * 4) = m2t;
     }
@@ -215,9 +221,15 @@ __global__ __launch_bounds__(RED_THREADS) void dwconv_bn_fwd_pair_kernel(
     red_n[t] = t < T ? n : 0.f;
     __syncthreads();
     if (t < cq) {
+      // the row lanes are merged as DEVIATIONS from the first lane's mean: a running mean near a large |mean| would be
+      // rounded to that magnitude's grid at every merge, and over 256 lanes those roundings add up (1.5e-4 of the
+      // variance at mean / std = 6000); differences of nearby means are exact
+      const f32x4 base = red_mean[t];
       float nt = red_n[t];
-      f32x4 mt = red_mean[t], m2t = red_m2[t];
-      for (int j = 1; j < rpt; ++j) chan_merge(nt, mt, m2t, red_n[t + j * cq], red_mean[t + j * cq], red_m2[t + j * cq]);
+      f32x4 mt = {0.f, 0.f, 0.f, 0.f}, m2t = red_m2[t];
+      for (int j = 1; j < rpt; ++j)
+        chan_merge(nt, mt, m2t, red_n[t + j * cq], red_mean[t + j * cq] - base, red_m2[t + j * cq]);
+      mt += base;
       *reinterpret_cast<f32x4*>(partial + ((size_t)blockIdx.x * 2 + 0) * Cs + (size_t)(q0 + t) * 4) = mt;
       *reinterpret_cast<f32x4*>(partial + ((size_t)blockIdx.x * 2 + 1) * Cs + (size_t)(q0 + t) * 4) = m2t;
     }
@@ -504,9 +516,27 @@ __global__ __launch_bounds__(256) void dwconv_bwd_w_finalize_kernel(const float*
 static int dw_check(int B, int H, int W, int Cs, int Ho, int Wo, int K, int stride, int pad) {
   if (B <= 0 || H <= 0 || W <= 0 || (Cs & 3) || Cs <= 0) return VMTL_ERR_ARG;
   if ((K != 3 && K != 5) || (stride != 1 && stride != 2) || pad < 0) return VMTL_ERR_ARG;
+  // a map smaller than the unpadded kernel: C's division truncates towards zero, so (H + 2*pad - K) / stride + 1 is 0
+  // there (not negative), or 1 where it should be 0 (stride 2), and would pass the comparison below
+  if (Ho <= 0 || Wo <= 0 || H + 2 * pad < K || W + 2 * pad < K) return VMTL_ERR_ARG;
   if ((H + 2 * pad - K) / stride + 1 != Ho || (W + 2 * pad - K) / stride + 1 != Wo) return VMTL_ERR_ARG;
   if ((long long)B * H * W > 0x7fffffffLL) return VMTL_ERR_ARG;
   return VMTL_OK;
+}
+
+// Route codes of the three *_route queries (include/vmtl.h documents them): which kernel a launcher starts.  Every
+// launcher switches on its own query's result, so the answer a test gets is the dispatch.
+#define DW_ROUTE_SPEC 4    // the compile-time specialisation (pair / tpl kernels), else the run-time-K kernel
+#define DW_ROUTE_K5 8      // K == 5 (specialised routes, and the generic weight gradient's <25> instantiation)
+#define DW_ROUTE_S2 16     // stride == 2 (specialised routes only)
+#define DW_ROUTE_WLDS 32   // fused forward: the 5x5 weights through LDS
+#define DW_ROUTE_FIN32 64  // weight gradient: finalize<32>, else <8>
+#define DW_ROUTE_QL_SHIFT 8
+
+// tuning aid: non-zero = the run-time-K kernels everywhere (same-build comparisons of the two routes)
+static bool dw_generic_only() {
+  static EnvInt e{"VMTL_DWBN_GENERIC", 0};
+  return env_int(e) != 0;
 }
 
 extern "C" int vmtl_dwconv_fwd(const float* x, const float* wp, float* y, int B, int H, int W, int Cs, int Ho, int Wo,
@@ -527,53 +557,73 @@ extern "C" int vmtl_dwconv_fwd(const float* x, const float* wp, float* y, int B,
 // red_blocks() - the row blocks must stay SHORT for the deep layers (M = 1024 pixels x 240 quads left 64 workgroups
 // of 16 serial pixels each: slower than the three launches it replaces): two pixels per thread, at most 1024 rows.
 static int dwbn_rows(int M, int Cs) {
-  const int cq = Cs >> 2;
+  const int cq = Cs >= 4 ? Cs >> 2 : 1;  // a query with Cs <= 0 gets an answer, not a division by zero
   const int rpt = cq >= RED_THREADS ? 1 : RED_THREADS / cq;
-  static int per_thread = -1;
-  if (per_thread < 0) {
-    const char* e = getenv("VMTL_DWBN_ROWS");  // tuning aid: output pixels per thread
-    per_thread = e ? atoi(e) : 2;
-    if (per_thread < 1) per_thread = 1;
-  }
+  static EnvInt e_rows{"VMTL_DWBN_ROWS", 2};  // tuning aid: output pixels per thread
+  const int per_thread = env_int(e_rows) < 1 ? 1 : env_int(e_rows);
   int rows = per_thread * rpt;
-  if (rows < cdiv(M, 1024)) rows = cdiv(M, 1024);
+  if (M > 0 && rows < cdiv(M, 1024)) rows = cdiv(M, 1024);
   return (rows + 1) & ~1;  // even: the pair kernel's blocks start on an even output pixel
 }
-extern "C" int vmtl_dwconv_bn_stats_rows(int M, int Cs) { return cdiv(M, dwbn_rows(M, Cs)); }
+// an empty shape (M <= 0 or Cs <= 0) has one row, as the k-split queries answer 1
+extern "C" int vmtl_dwconv_bn_stats_rows(int M, int Cs) { return M <= 0 || Cs <= 0 ? 1 : cdiv(M, dwbn_rows(M, Cs)); }
 extern "C" int vmtl_dwconv_bn_stats_block(int M, int Cs) { return dwbn_rows(M, Cs); }
+
+// The 5x5 pair kernel's static LDS (red_mean, red_m2, red_n) and what a workgroup of gfx950 may hold in all
+#define DWBN_STATIC_LDS (RED_THREADS * (16 + 16 + 4))
+#define DW_LDS_LIMIT (160 * 1024)
+
+extern "C" int vmtl_dwconv_bn_fwd_route(int B, int H, int W, int Cs, int Ho, int Wo, int K, int stride, int pad, int act) {
+  if (int e = dw_check(B, H, W, Cs, Ho, Wo, K, stride, pad)) return e;
+  if (pad != (K - 1) / 2) return VMTL_ERR_ARG;  // the a_out ownership rule assumes "same"-style padding
+  if (act != VMTL_ACT_NONE && act != VMTL_ACT_RELU && act != VMTL_ACT_HSWISH) return VMTL_ERR_ARG;
+  if (dw_generic_only() || (Wo & 1)) return act;
+  int route = DW_ROUTE_SPEC | act | (K == 5 ? DW_ROUTE_K5 : 0) | (stride == 2 ? DW_ROUTE_S2 : 0);
+  // 5x5 weights through LDS when the workgroup's pixels (rows x its share of the channel quads) outnumber the
+  // K*K*Cs floats it would copy - and the copy fits next to the reduction scratch
+  if (K == 5 && dwbn_rows(B * Ho * Wo, Cs) >= 12 && DWBN_STATIC_LDS + (size_t)25 * Cs * sizeof(float) <= DW_LDS_LIMIT)
+    route |= DW_ROUTE_WLDS;
+  return route;
+}
 
 extern "C" int vmtl_dwconv_bn_fwd(const float* x, const float* coef_a, const float* coef_c, int act, const float* wp,
                                   float* y, float* a_out, float* partial, int B, int H, int W, int Cs, int Ho, int Wo, int K,
                                   int stride, int pad, void* stream) {
   VMTL_ENTER();
   if (!x || !coef_a || !coef_c || !wp || !y) return VMTL_ERR_ARG;
-  if (int e = dw_check(B, H, W, Cs, Ho, Wo, K, stride, pad)) return e;
-  if (pad != (K - 1) / 2) return VMTL_ERR_ARG;  // the a_out ownership rule assumes "same"-style padding
+  const int route = vmtl_dwconv_bn_fwd_route(B, H, W, Cs, Ho, Wo, K, stride, pad, act);
+  if (route < 0) return route;
   const int M = B * Ho * Wo;
   const int rows = dwbn_rows(M, Cs);
   const int nblk = cdiv(M, rows);
-  static const bool generic_only = getenv("VMTL_DWBN_GENERIC") != nullptr;  // tuning aid: the run-time-K kernel
-  if (!generic_only && (Wo & 1) == 0 && (K == 3 || K == 5) && (stride == 1 || stride == 2) &&
-      (act == VMTL_ACT_NONE || act == VMTL_ACT_RELU || act == VMTL_ACT_HSWISH)) {
-    // 5x5 weights through LDS when the workgroup's pixels (rows x its share of the channel quads) outnumber the
-    // K*K*Cs floats it would copy
-    const bool wlds = K == 5 && rows >= 12;
+  if (route & DW_ROUTE_SPEC) {
+    // a WLDS launch asks for K*K*Cs floats of dynamic LDS: more than 64 KB from Cs = 564 on, hence allow_dynamic_lds
 #define CALLP(A, KV, SV, WL)                                                                                           \
-  hipLaunchKernelGGL((dwconv_bn_fwd_pair_kernel<A, KV, SV, WL>), dim3(nblk), dim3(RED_THREADS),                        \
-                     WL ? (size_t)KV * KV * Cs * sizeof(float) : 0, (hipStream_t)stream, x, coef_a, coef_c, wp, y,     \
-                     a_out, partial, H, W, Cs, Ho, Wo, M, rows)
-#define CALLKS(A)                                              \
-  do {                                                         \
-    if (K == 3 && stride == 1) CALLP(A, 3, 1, false);          \
-    else if (K == 3) CALLP(A, 3, 2, false);                    \
-    else if (stride == 1 && wlds) CALLP(A, 5, 1, true);        \
-    else if (stride == 1) CALLP(A, 5, 1, false);               \
-    else if (wlds) CALLP(A, 5, 2, true);                       \
-    else CALLP(A, 5, 2, false);                                \
+  do {                                                                                                                 \
+    constexpr auto kernel = &dwconv_bn_fwd_pair_kernel<A, KV, SV, WL>;                                                 \
+    const size_t lds = WL ? (size_t)KV * KV * Cs * sizeof(float) : 0;                                                  \
+    if (WL) {                                                                                                          \
+      const int rc = allow_dynamic_lds(reinterpret_cast<const void*>(kernel), lds);                                    \
+      if (rc) return rc;                                                                                               \
+    }                                                                                                                  \
+    hipLaunchKernelGGL(kernel, dim3(nblk), dim3(RED_THREADS), lds, (hipStream_t)stream, x, coef_a, coef_c, wp, y,      \
+                       a_out, partial, H, W, Cs, Ho, Wo, M, rows);                                                     \
   } while (0)
-    if (act == VMTL_ACT_NONE) CALLKS(VMTL_ACT_NONE);
-    else if (act == VMTL_ACT_RELU) CALLKS(VMTL_ACT_RELU);
-    else CALLKS(VMTL_ACT_HSWISH);
+#define CALLKS(A)                                                              \
+  switch (route & (DW_ROUTE_K5 | DW_ROUTE_S2 | DW_ROUTE_WLDS)) {               \
+    case 0: CALLP(A, 3, 1, false); break;                                      \
+    case DW_ROUTE_S2: CALLP(A, 3, 2, false); break;                            \
+    case DW_ROUTE_K5 | DW_ROUTE_WLDS: CALLP(A, 5, 1, true); break;             \
+    case DW_ROUTE_K5: CALLP(A, 5, 1, false); break;                            \
+    case DW_ROUTE_K5 | DW_ROUTE_S2 | DW_ROUTE_WLDS: CALLP(A, 5, 2, true); break; \
+    case DW_ROUTE_K5 | DW_ROUTE_S2: CALLP(A, 5, 2, false); break;              \
+    default: return VMTL_ERR_ARG;                                              \
+  }
+    switch (route & 3) {
+      case VMTL_ACT_NONE: CALLKS(VMTL_ACT_NONE); break;
+      case VMTL_ACT_RELU: CALLKS(VMTL_ACT_RELU); break;
+      default: CALLKS(VMTL_ACT_HSWISH); break;
+    }
 #undef CALLKS
 #undef CALLP
     return vmtl_check_launch();
@@ -581,7 +631,7 @@ extern "C" int vmtl_dwconv_bn_fwd(const float* x, const float* coef_a, const flo
 #define CALL(A)                                                                                                       \
   hipLaunchKernelGGL((dwconv_bn_fwd_kernel<A>), dim3(nblk), dim3(RED_THREADS), 0, (hipStream_t)stream, x, coef_a, coef_c, \
                      wp, y, a_out, partial, H, W, Cs, Ho, Wo, K, stride, pad, M, rows)
-  switch (act) {
+  switch (route) {
     case VMTL_ACT_NONE: CALL(VMTL_ACT_NONE); break;
     case VMTL_ACT_RELU: CALL(VMTL_ACT_RELU); break;
     case VMTL_ACT_HSWISH: CALL(VMTL_ACT_HSWISH); break;
@@ -593,22 +643,31 @@ extern "C" int vmtl_dwconv_bn_fwd(const float* x, const float* coef_a, const flo
 
 // dx = dwconv^T(dy) [+ addend]: addend (nullable, dx's shape) is a second gradient of the same tensor - the residual
 // branch of a block whose input also feeds the depthwise conv - added on the way out instead of in its own pass
+extern "C" int vmtl_dwconv_bwd_data_route(int B, int H, int W, int Cs, int Ho, int Wo, int K, int stride, int pad) {
+  if (int e = dw_check(B, H, W, Cs, Ho, Wo, K, stride, pad)) return e;
+  if (!dw_generic_only() && pad == (K - 1) / 2 && (W & 1) == 0 &&
+      (stride == 1 || ((H & 1) == 0 && Ho == H / 2 && Wo == W / 2)))
+    return DW_ROUTE_SPEC | (K == 5 ? DW_ROUTE_K5 : 0) | (stride == 2 ? DW_ROUTE_S2 : 0);
+  return 0;
+}
+
 static int dw_bwd_data_impl(const float* dy, const float* wp, const float* addend, float* dx, int B, int H, int W, int Cs,
                             int Ho, int Wo, int K, int stride, int pad, void* stream) {
   if (!dy || !wp || !dx) return VMTL_ERR_ARG;
-  if (int e = dw_check(B, H, W, Cs, Ho, Wo, K, stride, pad)) return e;
+  const int route = vmtl_dwconv_bwd_data_route(B, H, W, Cs, Ho, Wo, K, stride, pad);
+  if (route < 0) return route;
   const long long total4 = (long long)B * H * W * (Cs >> 2);
-  static const bool generic_only = getenv("VMTL_DWBN_GENERIC") != nullptr;  // tuning aid: the run-time-K kernel
-  if (!generic_only && pad == (K - 1) / 2 && (K == 3 || K == 5) && (W & 1) == 0 &&
-      (stride == 1 || (stride == 2 && (H & 1) == 0 && Ho == H / 2 && Wo == W / 2))) {
-    const long long total = stride == 1 ? total4 / 2 : total4 / 4;
+  if (route & DW_ROUTE_SPEC) {
+    const long long total = route & DW_ROUTE_S2 ? total4 / 4 : total4 / 2;
 #define CALLD(KV, SV)                                                                                    \
   hipLaunchKernelGGL((dwconv_bwd_data_tpl_kernel<KV, SV>), dim3(grid_1d(total, 256, 8192)), dim3(256), 0, \
                      (hipStream_t)stream, dy, wp, addend, dx, B, H, W, Cs, Ho, Wo, total)
-    if (K == 3 && stride == 1) CALLD(3, 1);
-    else if (K == 3) CALLD(3, 2);
-    else if (stride == 1) CALLD(5, 1);
-    else CALLD(5, 2);
+    switch (route & (DW_ROUTE_K5 | DW_ROUTE_S2)) {
+      case 0: CALLD(3, 1); break;
+      case DW_ROUTE_S2: CALLD(3, 2); break;
+      case DW_ROUTE_K5: CALLD(5, 1); break;
+      default: CALLD(5, 2); break;
+    }
 #undef CALLD
     return vmtl_check_launch();
   }
@@ -633,7 +692,7 @@ extern "C" int vmtl_dwconv_bwd_data_add(const float* dy, const float* wp, const 
 // row blocks of the weight gradient's first stage: ~2048 workgroups in total (the 64x128 maps ran 256 workgroups = one
 // wave per SIMD at 0.5 TB/s), at least two passes per row lane, at most DWW_MAX_RB partial rows for the finalize
 static void dww_geometry(int M, int Cs, int* QLo, int* panels_o, int* rows_o, int* nblk_o) {
-  const int CQ = Cs >> 2;
+  const int CQ = Cs >= 4 ? Cs >> 2 : 1;  // a query with Cs <= 0 gets an answer, not a division by zero
   int QL = 16;
   while (QL > 1 && (QL >> 1) >= CQ) QL >>= 1;  // smallest power of two >= CQ, at most 16
   const int panels = cdiv(CQ, QL);
@@ -644,44 +703,60 @@ static void dww_geometry(int M, int Cs, int* QLo, int* panels_o, int* rows_o, in
   if (nblk < 1) nblk = 1;
   int rows = cdiv(M, nblk);
   rows = (rows + 1) & ~1;  // even: the pair kernel's blocks start on an even output pixel
-  *QLo = QL; *panels_o = panels; *rows_o = rows; *nblk_o = cdiv(M, rows);
+  if (rows < 2) rows = 2;  // M <= 0
+  *QLo = QL; *panels_o = panels; *rows_o = rows; *nblk_o = M <= 0 ? 1 : cdiv(M, rows);
 }
 
+// an empty shape (M <= 0 or Cs <= 0) has one row, as the k-split queries answer 1
 extern "C" int vmtl_dwconv_bwd_weight_rows(int M, int Cs) {
   int QL, panels, rows, nblk;
   dww_geometry(M, Cs, &QL, &panels, &rows, &nblk);
   return nblk;
 }
 
+extern "C" int vmtl_dwconv_bwd_weight_route(int B, int H, int W, int C, int Cs, int Ho, int Wo, int K, int stride, int pad) {
+  if (C <= 0 || C > Cs) return VMTL_ERR_ARG;
+  if (int e = dw_check(B, H, W, Cs, Ho, Wo, K, stride, pad)) return e;
+  int QL, panels, rows, nblk;
+  dww_geometry(B * Ho * Wo, Cs, &QL, &panels, &rows, &nblk);
+  int route = K == 5 ? DW_ROUTE_K5 : 0;  // generic: dwconv_bwd_w_kernel<9> / <25>
+  if (!dw_generic_only() && (Wo & 1) == 0 && pad == (K - 1) / 2) route |= DW_ROUTE_SPEC | (stride == 2 ? DW_ROUTE_S2 : 0);
+  // few elements (narrow early layers, which also have the most partial rows): more row groups per element
+  if (C * K * K >= 4096) route |= DW_ROUTE_FIN32;
+  return route | (__builtin_ctz(QL) << DW_ROUTE_QL_SHIFT);
+}
+
 // partial: vmtl_dwconv_bwd_weight_rows(B*Ho*Wo, Cs) * K*K * Cs floats.  dw: torch (C,1,K,K) layout.
 extern "C" int vmtl_dwconv_bwd_weight(const float* x, const float* dy, float* partial, float* dw, int B, int H, int W,
                                       int C, int Cs, int Ho, int Wo, int K, int stride, int pad, void* stream) {
   VMTL_ENTER();
-  if (!x || !dy || !partial || !dw || C <= 0 || C > Cs) return VMTL_ERR_ARG;
-  if (int e = dw_check(B, H, W, Cs, Ho, Wo, K, stride, pad)) return e;
+  if (!x || !dy || !partial || !dw) return VMTL_ERR_ARG;
+  const int route = vmtl_dwconv_bwd_weight_route(B, H, W, C, Cs, Ho, Wo, K, stride, pad);
+  if (route < 0) return route;
   hipStream_t st = (hipStream_t)stream;
   const int M = B * Ho * Wo;
   int QL, panels, rows, nblk;
   dww_geometry(M, Cs, &QL, &panels, &rows, &nblk);
-  static const bool generic_only = getenv("VMTL_DWBN_GENERIC") != nullptr;  // tuning aid: the run-time-K kernel
-  if (!generic_only && (Wo & 1) == 0 && pad == (K - 1) / 2 && (K == 3 || K == 5) && (stride == 1 || stride == 2)) {
 #define CALLW(KV, SV)                                                                                              \
   hipLaunchKernelGGL((dwconv_bwd_w_pair_kernel<KV, SV>), dim3(panels, nblk), dim3(256), 0, st, x, dy, H, W, Cs, Ho, Wo, \
                      M, QL, rows, partial)
-    if (K == 3 && stride == 1) CALLW(3, 1);
-    else if (K == 3) CALLW(3, 2);
-    else if (stride == 1) CALLW(5, 1);
-    else CALLW(5, 2);
-#undef CALLW
-  } else if (K == 3) {
-    hipLaunchKernelGGL((dwconv_bwd_w_kernel<9>), dim3(panels, nblk), dim3(256), 0, st, x, dy, H, W, Cs, Ho, Wo, K,
-                       stride, pad, M, QL, partial);
-  } else {
-    hipLaunchKernelGGL((dwconv_bwd_w_kernel<25>), dim3(panels, nblk), dim3(256), 0, st, x, dy, H, W, Cs, Ho, Wo, K,
-                       stride, pad, M, QL, partial);
+  switch (route & (DW_ROUTE_SPEC | DW_ROUTE_K5 | DW_ROUTE_S2)) {
+    case DW_ROUTE_SPEC: CALLW(3, 1); break;
+    case DW_ROUTE_SPEC | DW_ROUTE_S2: CALLW(3, 2); break;
+    case DW_ROUTE_SPEC | DW_ROUTE_K5: CALLW(5, 1); break;
+    case DW_ROUTE_SPEC | DW_ROUTE_K5 | DW_ROUTE_S2: CALLW(5, 2); break;
+    case 0:
+      hipLaunchKernelGGL((dwconv_bwd_w_kernel<9>), dim3(panels, nblk), dim3(256), 0, st, x, dy, H, W, Cs, Ho, Wo, K,
+                         stride, pad, M, QL, partial);
+      break;
+    case DW_ROUTE_K5:
+      hipLaunchKernelGGL((dwconv_bwd_w_kernel<25>), dim3(panels, nblk), dim3(256), 0, st, x, dy, H, W, Cs, Ho, Wo, K,
+                         stride, pad, M, QL, partial);
+      break;
+    default: return VMTL_ERR_ARG;
   }
-  // few elements (narrow early layers, which also have the most partial rows): more row groups per element
-  if (C * K * K >= 4096)
+#undef CALLW
+  if (route & DW_ROUTE_FIN32)
     hipLaunchKernelGGL(dwconv_bwd_w_finalize_kernel<32>, dim3(cdiv(C * K * K, 32)), dim3(256), 0, st, partial, nblk,
                        K * K, C, Cs, dw);
   else
