@@ -640,6 +640,36 @@ int vmtl_ce_ohem_bwd(const float* logits, const long long* target, const float* 
                      const float* stats, const float* nll, const float* grad_out, float* dlogits, int B, int HW, int C,
                      long long sb, long long sc, long long sp, long long dsb, long long dsc, long long dsp,
                      void* stream);
+/* Cross entropy plus a Dice / Jaccard / Tversky region-overlap term (ce_region.hip).  No reference call site: the
+ * multiclass DiceLoss / JaccardLoss / TverskyLoss of segmentation_models_pytorch, the library behind the reference's
+ * models (vision_mtl/utils/model_utils.py:3), next to the CrossEntropyLoss of lit_module.py:31,123.  With p = softmax(z) and every
+ * sum over the valid pixels (t_i != ignore_index) of the whole batch:
+ *   TP_c = sum p_ic 1[t_i = c], S_c = sum p_ic, N_c = #{i valid: t_i = c},
+ *   D_c = TP_c + alpha (S_c - TP_c) + beta (N_c - TP_c) + smooth,  T_c = (TP_c + smooth) / D_c,
+ *   L_region = (1/C) sum_{c: N_c > 0} (1 - T_c)   (alpha = beta = 0.5: Dice; alpha = beta = 1: Jaccard),
+ *   loss = ce_weight * CE + region_weight * L_region, CE as vmtl_ce_fwd_ex (weight applies to CE only).
+ * alpha, beta finite > 0; smooth, ce_weight finite >= 0; region_weight finite > 0.  ce_weight == 0: CE is neither
+ * evaluated nor differentiated (terms[0] = 0, stats = {0, 0}).  2 <= C <= VMTL_CE_REGION_MAX_CLASSES, else
+ * VMTL_ERR_UNSUPPORTED without a launch (and 0 workspace bytes).  The forward writes loss, terms (2 device floats: CE,
+ * L_region, unweighted), stats (2 floats as vmtl_ce_fwd_ex), coef (2*C floats: a_c, then b_c, with
+ * dL_region/dp_ic = b_c + a_c 1[t_i = c]; exactly 0 for an absent class) and counts (C+1 int64: N_c, then the number of
+ * valid pixels).  Every pixel ignored: L_region = 0 exactly, CE = NaN.  A valid label outside [0, C): loss, terms and
+ * the whole of coef are NaN.  workspace: vmtl_ce_region_workspace_bytes(P, C) bytes, 8-byte aligned; weight,
+ * ignore_index, argmax as vmtl_ce_fwd_ex.  Sums are fp64 per-block partials added in a fixed order (no floating-point
+ * atomics): results are bit-identical run to run.
+ * Backward: dz_c = grad_out [ce_weight w[t] (p_c - 1[c == t]) / stats[0] + region_weight p_c (g_c - sum_k p_k g_k)],
+ * g_c = b_c + a_c 1[c == t]; exactly 0.0f in every written lane of an ignored pixel; layouts and written lanes as
+ * vmtl_ce_bwd_ex. */
+#define VMTL_CE_REGION_MAX_CLASSES 32
+long long vmtl_ce_region_workspace_bytes(long long P, int C);
+int vmtl_ce_region_fwd(const float* logits, const long long* target, const float* weight, long long ignore_index,
+                       float alpha, float beta, float smooth, float ce_weight, float region_weight, float* loss,
+                       float* terms, float* stats, float* coef, long long* counts, void* workspace, long long* argmax,
+                       int B, int HW, int C, long long sb, long long sc, long long sp, void* stream);
+int vmtl_ce_region_bwd(const float* logits, const long long* target, const float* weight, long long ignore_index,
+                       const float* stats, const float* coef, const float* grad_out, float ce_weight,
+                       float region_weight, float* dlogits, int B, int HW, int C, long long sb, long long sc,
+                       long long sp, long long dsb, long long dsc, long long dsp, void* stream);
 long long vmtl_silog_workspace_bytes(long long P);
 int vmtl_silog_fwd(const float* pred, const float* target, float min_depth, float* loss, float* stats,
                    void* workspace, long long P, void* stream);

@@ -28,7 +28,9 @@ class MTLModule(nn.Module):
                  segm_class_weights: t.Optional[t.Sequence[float]] = None,
                  loss_balancing: t.Union[None, str, TaskBalancer] = None, dwa_temperature: float = 2.0,
                  segm_ohem_min_kept: t.Optional[int] = None, segm_ohem_thresh: t.Optional[float] = None,
-                 depth_grad_weight: t.Optional[float] = None, depth_grad_scales: int = 4):
+                 depth_grad_weight: t.Optional[float] = None, depth_grad_scales: int = 4,
+                 segm_region_weight: t.Optional[float] = None, segm_region_alpha: float = 0.5,
+                 segm_region_beta: float = 0.5, segm_region_smooth: float = 0.0):
         """segm_ignore_index / segm_class_weights (opt-in, INTEGRATION.md): the `ignore_index` and per-class `weight`
         of the segmentation criterion; the ignore index also keeps those pixels out of the segmentation metrics.
         loss_balancing (opt-in): "uncertainty" | "dwa" | "geometric" or a balancing.TaskBalancer
@@ -39,8 +41,24 @@ class MTLModule(nn.Module):
         predict keep reporting the un-mined loss of `segm_criterion` with the same weights and ignore index.
         depth_grad_weight / depth_grad_scales (opt-in): `depth_criterion` becomes
         SILog + depth_grad_weight * the multi-scale gradient-matching term (losses.SILogGradLoss), in every stage: it is
-        part of the loss definition, like the class weights."""
+        part of the loss definition, like the class weights.
+        segm_region_weight / segm_region_alpha / _beta / _smooth (opt-in): `segm_criterion`
+        becomes cross entropy + segm_region_weight * the Dice / Tversky region term (losses.CrossEntropyLoss with
+        region_weight), in every stage, like depth_grad_weight; it does not combine with segm_ohem_min_kept."""
         super().__init__()
+        region = {}
+        if segm_region_weight is not None:  # checked before anything is built
+            if segm_ohem_min_kept is not None or segm_ohem_thresh is not None:
+                raise ValueError("MTLModule: segm_region_weight does not combine with segm_ohem_min_kept / "
+                                 "segm_ohem_thresh (mining the region term is not supported)")
+            if not 2 <= num_classes <= ops.CE_REGION_MAX_CLASSES:
+                raise ValueError(f"MTLModule: segm_region_weight takes 2 to {ops.CE_REGION_MAX_CLASSES} classes, got "
+                                 f"num_classes = {num_classes}")
+            region = dict(
+                region_weight=ops.region_loss_number(segm_region_weight, "segm_region_weight", "MTLModule", positive=True),
+                region_alpha=ops.region_loss_number(segm_region_alpha, "segm_region_alpha", "MTLModule", positive=True),
+                region_beta=ops.region_loss_number(segm_region_beta, "segm_region_beta", "MTLModule", positive=True),
+                region_smooth=ops.region_loss_number(segm_region_smooth, "segm_region_smooth", "MTLModule"))
         if loss_balancing is not None:
             if loss_segm_weight != 1.0 or loss_depth_weight != 1.0:
                 raise ValueError("MTLModule: loss_balancing replaces the static loss weights: leave loss_segm_weight and "
@@ -65,7 +83,9 @@ class MTLModule(nn.Module):
             self.hparams.update(loss_balancing=loss_balancing.method, dwa_temperature=loss_balancing.temperature)
         self.num_classes = num_classes
         self.model = model
-        self.segm_criterion = CrossEntropyLoss(weight=segm_class_weights, ignore_index=segm_ignore_index)
+        if region:  # the default module keeps the hparams and the criterion it always had
+            self.hparams.update({"segm_" + k: v for k, v in region.items()})
+        self.segm_criterion = CrossEntropyLoss(weight=segm_class_weights, ignore_index=segm_ignore_index, **region)
         if segm_class_weights is not None:  # the model usually arrives on its device: the weights join it there
             p = next(model.parameters(), None)
             if p is not None:

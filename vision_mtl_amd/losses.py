@@ -91,11 +91,27 @@ class CrossEntropyLoss(nn.Module):
 
     ohem_min_kept (opt-in): online hard example mining - the mean runs over the valid pixels whose true-class probability
     is below ohem_thresh (in (0, 1]; None: pure top-K), and never over fewer than ohem_min_kept pixels per image
-    (ops.cross_entropy_ohem).  Mining is on iff ohem_min_kept is given."""
+    (ops.cross_entropy_ohem).  Mining is on iff ohem_min_kept is given.
+
+    region_weight (opt-in): the loss becomes this cross entropy + region_weight * the Tversky region term with
+    (region_alpha, region_beta, region_smooth) - Dice by default - from one node (ops.segm_region_loss).  `weight`
+    keeps applying to the cross entropy only.  It does not combine with mining."""
 
     def __init__(self, weight: t.Optional[torch.Tensor] = None, ignore_index: t.Optional[int] = None,
-                 ohem_min_kept: t.Optional[int] = None, ohem_thresh: t.Optional[float] = None):
+                 ohem_min_kept: t.Optional[int] = None, ohem_thresh: t.Optional[float] = None,
+                 region_weight: t.Optional[float] = None, region_alpha: float = 0.5, region_beta: float = 0.5,
+                 region_smooth: float = 0.0):
         super().__init__()
+        if region_weight is not None:
+            if ohem_min_kept is not None or ohem_thresh is not None:
+                raise ValueError("CrossEntropyLoss: region_weight does not combine with ohem_min_kept / ohem_thresh "
+                                 "(mining the region term is not supported)")
+            region_weight = ops.region_loss_number(region_weight, "region_weight", "CrossEntropyLoss", positive=True)
+            region_alpha = ops.region_loss_number(region_alpha, "region_alpha", "CrossEntropyLoss", positive=True)
+            region_beta = ops.region_loss_number(region_beta, "region_beta", "CrossEntropyLoss", positive=True)
+            region_smooth = ops.region_loss_number(region_smooth, "region_smooth", "CrossEntropyLoss")
+        self.region_weight = region_weight
+        self.region = (region_alpha, region_beta, region_smooth)
         if ohem_min_kept is None:
             if ohem_thresh is not None:
                 raise ValueError("CrossEntropyLoss: ohem_thresh needs ohem_min_kept (mining is on iff ohem_min_kept is set)")
@@ -118,6 +134,9 @@ class CrossEntropyLoss(nn.Module):
         self.register_buffer("weight", weight, persistent=False)
 
     def forward(self, logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        if self.region_weight is not None:
+            return ops.segm_region_loss(logits, target, self.region_weight, *self.region, weight=self.weight,
+                                        ignore_index=self.ignore_index)
         if self.ohem_min_kept is not None:
             return ops.cross_entropy_ohem(logits, target, self.ohem_min_kept, self.ohem_thresh, weight=self.weight,
                                           ignore_index=self.ignore_index)
@@ -125,10 +144,52 @@ class CrossEntropyLoss(nn.Module):
 
     def forward_with_predictions(self, logits: torch.Tensor, target: torch.Tensor):
         """(loss, argmax_c logits): the loss pass finds each pixel's maximum anyway (one launch instead of two)."""
+        if self.region_weight is not None:
+            return ops.segm_region_loss_with_argmax(logits, target, self.region_weight, *self.region, weight=self.weight,
+                                                    ignore_index=self.ignore_index)
         if self.ohem_min_kept is not None:
             return ops.cross_entropy_ohem_with_argmax(logits, target, self.ohem_min_kept, self.ohem_thresh,
                                                       weight=self.weight, ignore_index=self.ignore_index)
         return ops.cross_entropy_with_argmax(logits, target, weight=self.weight, ignore_index=self.ignore_index)
+
+
+class TverskyLoss(nn.Module):
+    """The region term alone (ops.segm_region_loss with ce_weight = 0): the multiclass TverskyLoss of
+    segmentation_models_pytorch on logits (B,C,H,W) and an int64 target (B,H,W),
+    (1/C) sum_{c present} (1 - (TP_c + smooth) / (TP_c + alpha FP_c + beta FN_c + smooth)) over the pixels whose target
+    is not ignore_index.  Every pixel ignored: exactly 0.  No parameters or buffers."""
+
+    def __init__(self, alpha: float = 0.5, beta: float = 0.5, smooth: float = 0.0, ignore_index: t.Optional[int] = None):
+        super().__init__()
+        who = type(self).__name__
+        self.alpha = ops.region_loss_number(alpha, "alpha", who, positive=True)
+        self.beta = ops.region_loss_number(beta, "beta", who, positive=True)
+        self.smooth = ops.region_loss_number(smooth, "smooth", who)
+        if ignore_index is not None and (isinstance(ignore_index, bool) or not isinstance(ignore_index, int)):
+            raise TypeError(f"{who}: ignore_index must be an int or None, got {ignore_index!r}")
+        self.ignore_index = ignore_index
+
+    def forward(self, logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        return ops.segm_region_loss(logits, target, 1.0, self.alpha, self.beta, self.smooth,
+                                    ignore_index=self.ignore_index, ce_weight=0.0)
+
+    def forward_with_predictions(self, logits: torch.Tensor, target: torch.Tensor):
+        return ops.segm_region_loss_with_argmax(logits, target, 1.0, self.alpha, self.beta, self.smooth,
+                                                ignore_index=self.ignore_index, ce_weight=0.0)
+
+
+class DiceLoss(TverskyLoss):
+    """TverskyLoss with alpha = beta = 0.5: 1 - 2 TP / (S + N) per present class."""
+
+    def __init__(self, smooth: float = 0.0, ignore_index: t.Optional[int] = None):
+        super().__init__(0.5, 0.5, smooth, ignore_index)
+
+
+class JaccardLoss(TverskyLoss):
+    """TverskyLoss with alpha = beta = 1: 1 - TP / (S + N - TP) per present class."""
+
+    def __init__(self, smooth: float = 0.0, ignore_index: t.Optional[int] = None):
+        super().__init__(1.0, 1.0, smooth, ignore_index)
 
 
 class L1Loss(nn.Module):

@@ -3305,6 +3305,103 @@ def cross_entropy_ohem_with_argmax(logits, target, min_kept, thresh=None, weight
     return _CrossEntropyOHEM.apply(logits, target, weight, ign, tau, total, True)
 
 
+CE_REGION_MAX_CLASSES = 32  # include/vmtl.h VMTL_CE_REGION_MAX_CLASSES: the register form of csrc/ce_region.hip
+
+
+class _CrossEntropyRegion(torch.autograd.Function):
+    """ce_weight * (weighted / ignoring cross entropy) + region_weight * the Dice / Jaccard / Tversky region term
+    (csrc/ce_region.hip) from one pass over the logits per direction.  The forward leaves the
+    cross entropy's denominator (stats) and the 2C coefficients of the term's gradient (coef) on the device; the backward
+    reads them there, so the node never waits for the host and captures like _CrossEntropy.  The gradient is handed off
+    in the same NHWC storage.  weight (cross entropy only) gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight, ignore_index, alpha, beta, smooth, ce_weight, region_weight, want_argmax):
+        logits = _req(logits, "logits")
+        if target.dtype != torch.int64:
+            raise TypeError("segm_region_loss: target must be int64 class indices")
+        target = target.contiguous()
+        B, C, H, W = logits.shape
+        if tuple(target.shape) != (B, H, W):
+            raise ValueError(f"segm_region_loss: target shape {tuple(target.shape)} does not match logits {(B, H, W)}")
+        if not 2 <= C <= CE_REGION_MAX_CLASSES:
+            raise ValueError(f"segm_region_loss: the region term takes 2 to {CE_REGION_MAX_CLASSES} classes, got {C}")
+        weight = _ce_weight(weight, logits)
+        P = B * H * W
+        loss, terms, stats, coef = (_empty(s, logits) for s in ((), (2,), (2,), (2 * C,)))
+        counts = torch.empty((C + 1,), dtype=torch.int64, device=logits.device)
+        ws = torch.empty((lib().raw("vmtl_ce_region_workspace_bytes")(P, C) // 8,), dtype=torch.float64,
+                         device=logits.device)
+        pred = torch.empty((B, H, W), dtype=torch.int64, device=logits.device) if want_argmax else None
+        _k("vmtl_ce_region_fwd", logits=logits, target=target, weight=weight, ignore_index=ignore_index, alpha=alpha,
+           beta=beta, smooth=smooth, ce_weight=ce_weight, region_weight=region_weight, loss=loss, terms=terms,
+           stats=stats, coef=coef, counts=counts, workspace=ws, argmax=pred, B=B, HW=H * W, C=C, sb=C * H * W, sc=H * W,
+           sp=1)
+        ctx.save_for_backward(logits, target, stats, coef, *(() if weight is None else (weight,)))
+        ctx.ignore_index, ctx.ce_weight, ctx.region_weight = ignore_index, ce_weight, region_weight
+        if want_argmax:
+            ctx.mark_non_differentiable(pred)
+            return loss, pred
+        return loss
+
+    @staticmethod
+    def backward(ctx, g, _gpred=None):
+        logits, target, stats, coef, *w = ctx.saved_tensors
+        B, C, H, W = logits.shape
+        g = _req(g, "grad_output")
+        ld = ceil4(C + 1)  # the NHWC storage with room for one more head, as _CrossEntropy.backward lays it out
+        st = _empty((B, H, W, ld), logits)
+        _k("vmtl_ce_region_bwd", logits=logits, target=target, weight=w[0] if w else None, ignore_index=ctx.ignore_index,
+           stats=stats, coef=coef, grad_out=g, ce_weight=ctx.ce_weight, region_weight=ctx.region_weight, dlogits=st,
+           B=B, HW=H * W, C=C, sb=C * H * W, sc=H * W, sp=1, dsb=H * W * ld, dsc=1, dsp=ld)
+        dl = st[..., :C].permute(0, 3, 1, 2)
+        dl._vmtl_nhwc = st
+        return (dl,) + (None,) * 9
+
+
+def region_loss_number(v, name, who="segm_region_loss", positive=False) -> float:
+    """A finite float >= 0 (> 0 with `positive`) among the region term's scalars; TypeError / ValueError otherwise."""
+    if isinstance(v, bool) or not isinstance(v, (int, float)):
+        raise TypeError(f"{who}: {name} must be a float, got {v!r}")
+    if not math.isfinite(v) or v < 0 or (positive and v == 0):
+        raise ValueError(f"{who}: {name} must be finite and {'> 0' if positive else '>= 0'}, got {v!r}")
+    return float(v)
+
+
+def _region_args(logits, region_weight, alpha, beta, smooth, weight, ignore_index, ce_weight):
+    """Everything that can be wrong with the call, before any launch."""
+    args = (region_loss_number(alpha, "alpha", positive=True), region_loss_number(beta, "beta", positive=True),
+            region_loss_number(smooth, "smooth"), region_loss_number(ce_weight, "ce_weight"),
+            region_loss_number(region_weight, "region_weight", positive=True))
+    ign = _ce_ignore(weight, ignore_index)
+    if logits.dim() != 4:
+        raise ValueError(f"segm_region_loss: logits must be (B,C,H,W), got shape {tuple(logits.shape)}")
+    if not 2 <= logits.shape[1] <= CE_REGION_MAX_CLASSES:
+        raise ValueError(f"segm_region_loss: the region term takes 2 to {CE_REGION_MAX_CLASSES} classes, got "
+                         f"{logits.shape[1]}")
+    return (NO_IGNORE if ign is None else ign,) + args
+
+
+def segm_region_loss(logits, target, region_weight=1.0, alpha=0.5, beta=0.5, smooth=0.0, weight=None, ignore_index=None,
+                     ce_weight=1.0):
+    """ce_weight * ops.cross_entropy(logits, target, weight, ignore_index) + region_weight * the Tversky region term
+    L = (1/C) sum_{c present} (1 - (TP_c + smooth) / (TP_c + alpha FP_c + beta FN_c + smooth)) on the softmax
+    probabilities over the valid pixels of the batch (alpha = beta = 0.5: Dice, alpha = beta = 1: Jaccard; the
+    multiclass form of segmentation_models_pytorch: a class absent from the labels adds 0).  `weight` applies to the
+    cross entropy only; ce_weight = 0 is the term alone.  At most 32 classes."""
+    return _CrossEntropyRegion.apply(logits, target, weight,
+                                     *_region_args(logits, region_weight, alpha, beta, smooth, weight, ignore_index,
+                                                   ce_weight), False)
+
+
+def segm_region_loss_with_argmax(logits, target, region_weight=1.0, alpha=0.5, beta=0.5, smooth=0.0, weight=None,
+                                 ignore_index=None, ce_weight=1.0):
+    """(loss, argmax over the class axis) from the one pass over the logits; the prediction is written for every pixel."""
+    return _CrossEntropyRegion.apply(logits, target, weight,
+                                     *_region_args(logits, region_weight, alpha, beta, smooth, weight, ignore_index,
+                                                   ce_weight), True)
+
+
 class _SILog(torch.autograd.Function):
     """reference losses.py:29-36 on predictions in (0,1); pred and target hold the same number of elements.  The valid
     pixels are those with target > min_depth, or those of an explicit uint8 mask (losses.py:29-31 with `mask` given)."""

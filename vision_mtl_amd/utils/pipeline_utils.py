@@ -57,7 +57,13 @@ def init_model(args: argparse.Namespace, data_cfg: DataConfig) -> MTLModule:
                        segm_ohem_thresh=getattr(args, "segm_ohem_thresh", None),
                        # opt-in: SILog + weight * multi-scale gradient matching as the depth loss
                        depth_grad_weight=getattr(args, "depth_grad_weight", None),
-                       depth_grad_scales=getattr(args, "depth_grad_scales", 4))
+                       depth_grad_scales=getattr(args, "depth_grad_scales", 4),
+                       # opt-in: cross entropy + weight * Dice / Tversky region term as the
+                       # segmentation loss
+                       segm_region_weight=getattr(args, "segm_region_weight", None),
+                       segm_region_alpha=getattr(args, "segm_region_alpha", 0.5),
+                       segm_region_beta=getattr(args, "segm_region_beta", 0.5),
+                       segm_region_smooth=getattr(args, "segm_region_smooth", 0.0))
     # opt-in: test-time augmentation / output-size predictions of the predict step; an
     # attribute like train_augment, nothing goes into hparams
     scales, flip = getattr(args, "predict_scales", None), getattr(args, "predict_flip", None)
