@@ -21,9 +21,10 @@ GOUT = 1.7  # the loss is scaled before backward: grad_output is not 1
 IGN = 255
 # name: (C, B, H, W).  a: ragged last wave, P = 130; c: the production class count; d: the wide-ld gradient layout;
 # e: past the 32 logits the register forms hold; f: P = 526 683 > 2048 * 256 - the grid-stride loops, the block cap and
-# many blocks feeding one global histogram
-CASES = {"a": (3, 2, 5, 13), "c": (19, 2, 5, 13), "d": (20, 2, 5, 13), "e": (33, 2, 5, 13), "f": (3, 3, 419, 419)}
-SMALL = ("a", "c", "d", "e")
+# many blocks feeding one global histogram; g .. k: the remaining register forms (Q = ceil(C / 4) = 3, 4, 6, 7, 8)
+CASES = {"a": (3, 2, 5, 13), "c": (19, 2, 5, 13), "d": (20, 2, 5, 13), "e": (33, 2, 5, 13), "f": (3, 3, 419, 419),
+         "g": (9, 2, 5, 13), "h": (14, 2, 5, 13), "i": (22, 2, 5, 13), "j": (26, 2, 5, 13), "k": (30, 2, 5, 13)}
+SMALL = ("a", "c", "d", "e", "g", "h", "i", "j", "k")
 THRESHOLDS = (None, 1.0, 0.7, 1e-6)
 
 

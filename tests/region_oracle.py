@@ -17,8 +17,10 @@ GOUT = 1.7  # the loss is scaled before backward: grad_output is not 1
 IGN = 255
 # name: (C, B, H, W).  a: ragged last wave, P = 130; c: the production class count; d: ld = 24 (the wide-ld gradient
 # layout); g: the class limit, ld = 36; f: P = 526 683 > 2048 * 256 - the grid-stride loop and every per-block partial row
-CASES = {"a": (3, 2, 5, 13), "c": (19, 2, 5, 13), "d": (20, 2, 5, 13), "g": (32, 2, 5, 13), "f": (3, 3, 419, 419)}
-SMALL = ("a", "c", "d", "g")
+# h .. l: the remaining register forms (Q = ceil(C / 4) = 3, 4, 6, 7, 8 below the limit)
+CASES = {"a": (3, 2, 5, 13), "c": (19, 2, 5, 13), "d": (20, 2, 5, 13), "g": (32, 2, 5, 13), "f": (3, 3, 419, 419),
+         "h": (9, 2, 5, 13), "i": (14, 2, 5, 13), "j": (22, 2, 5, 13), "k": (26, 2, 5, 13), "l": (30, 2, 5, 13)}
+SMALL = ("a", "c", "d", "g", "h", "i", "j", "k", "l")
 VARIANTS = ("c_absent", "c_void_only")  # of case c: one class removed from the labels / present only under void pixels
 SETTINGS = ((0.5, 0.5, 0.0), (1.0, 1.0, 0.0), (0.3, 0.7, 1.0))  # (alpha, beta, smooth): Dice, Jaccard, a Tversky
 

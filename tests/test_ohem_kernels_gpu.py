@@ -343,7 +343,7 @@ def test_node_matches_the_c_abi_and_hands_off_nhwc(dev, name):
     assert torch.equal(pred.cpu(), c["z"].argmax(dim=1))
 
 
-@pytest.mark.parametrize("name", ["a", "c", "d", "e"])
+@pytest.mark.parametrize("name", O.SMALL)
 def test_c_abi_layouts_write_the_lanes_the_ex_kernels_write(dev, name):
     """vmtl_ce_ohem_bwd in the three layouts - NHWC rows of exactly ceil4(C) floats, NHWC with a wider ld, NCHW - on
     sentinel-filled buffers: the same values in each, and the written elements are those vmtl_ce_bwd_ex writes."""

@@ -29,16 +29,16 @@
 //   3. sum pass   : resolves the cut the same way, accumulates (sum w nll, sum w, count) over the kept pixels as fp64
 //                   per-block partials; one finalize block sums them in a fixed order and writes loss, stats, counts.
 // The backward reads the SAVED nll and stats[2] = cut to decide membership - a recomputed nll need not reproduce the
-// forward's bits at the cut - and is otherwise vmtl_ce_bwd_ex: the same three layouts, the same written lanes.
+// forward's bits at the cut - and is otherwise vmtl_ce_bwd_ex: the three gradient kernels of ce_pixel.h under OHEM's
+// policy, so the same three layouts and the same written lanes.
 //
 // No allocation, no sync, everything on the caller's stream (the counters and histograms are cleared in-stream by a
 // memset node), so the node captures into a graph: K and tau are host constants, V, the cut and the denominator never
 // leave the device.
-#include "common.h"
+#include "ce_pixel.h"
 #include "reduce.h"
 
-#define OH_THREADS 256
-#define OH_BLOCKS_MAX 2048
+#define OH_THREADS CE_THREADS
 #define OH_BINS0 2048  // key >> 21
 #define OH_BINS1 2048  // (key >> 10) & 0x7ff
 #define OH_BINS2 1024  // key & 0x3ff
@@ -53,8 +53,6 @@ struct OhemWs {
   unsigned hist[OH_BINS0 + OH_BINS1 + OH_BINS2];
 };
 static_assert(sizeof(OhemWs) % 8 == 0, "the partials behind the head are doubles");
-
-#define OH_NAN __int_as_float(0x7fc00000)
 
 __device__ __forceinline__ unsigned oh_key(float nll) { return nll != nll ? 0xFFFFFFFFu : __float_as_uint(nll); }
 
@@ -120,9 +118,8 @@ __device__ __forceinline__ void oh_flush(const unsigned* lh, unsigned* __restric
 }
 
 // ------------------------------------------------------------------ forward: pixel pass
-// Element (b, c, hw) of the logits sits at z[b*sb + c*sc + hw*sp], as in loss.hip.  One thread per pixel; Q > 0 holds
-// the pixel's 4*Q >= C logits in registers (C <= 32), Q = 0 sweeps the channel planes three times.  The log-softmax
-// subtracts the max first (see loss.hip); the argmax is written for ignored pixels too.
+// One thread per pixel, the pixel pass of ce_pixel.h: Q > 0 holds the pixel's 4*Q >= C logits in registers (C <= 32),
+// Q = 0 sweeps the channel planes.  The argmax is written for ignored pixels too.
 template <int Q>
 __global__ __launch_bounds__(OH_THREADS) void oh_pixel_kernel(const float* __restrict__ z,
                                                               const long long* __restrict__ tgt, long long ignore,
@@ -137,50 +134,35 @@ __global__ __launch_bounds__(OH_THREADS) void oh_pixel_kernel(const float* __res
   __syncthreads();
   unsigned nv = 0, nt = 0;
   VMTL_GRID_STRIDE(i, P) {
-    const long long b = i / HW, hw = i - b * HW;
-    const float* r = z + b * sb + hw * sp;
+    const float* r = ce_pixel(z, i, HW, sb, sp);
     const long long t = tgt[i];
-    const bool valid = t != ignore, inside = t >= 0 && t < C;
-    float m, s = 0.f, zt = 0.f;
-    int am = 0;
+    const bool valid = t != ignore, inside = ce_label_inside(t, C);
+    CeMax mx;
+    float s = 0.f, zt = 0.f;
     bool fin = true;
     if constexpr (Q > 0) {
       float v[4 * Q];
-#pragma unroll
-      for (int c = 0; c < 4 * Q; ++c) v[c] = c < C ? r[c * sc] : 0.f;
-      m = v[0];
-#pragma unroll
-      for (int c = 1; c < 4 * Q; ++c)
-        if (c < C && v[c] > m) { m = v[c]; am = c; }  // first maximum wins, like torch.argmax on ties
+      ce_load<Q>(v, r, C, sc);
+      mx = ce_max_argmax<Q>(v, C);
       if (valid) {
+        s = ce_sum_exp<Q>(v, C, mx.m);
 #pragma unroll
-        for (int c = 0; c < 4 * Q; ++c) {
-          if (c < C) {
-            s += expf(v[c] - m);
-            fin = fin && fabsf(v[c]) < HUGE_VALF;
-          }
-          if (c == t) zt = v[c];
-        }
+        for (int c = 0; c < 4 * Q; ++c)
+          if (c < C) fin = fin && fabsf(v[c]) < HUGE_VALF;
+        zt = ce_pick<Q>(v, t);
       }
     } else {
-      m = r[0];
-      for (int c = 1; c < C; ++c) {
-        const float v = r[c * sc];
-        if (v > m) { m = v; am = c; }
-      }
+      mx = ce_sweep_max_argmax(r, C, sc);
       if (valid) {
-        for (int c = 0; c < C; ++c) {
-          const float v = r[c * sc];
-          s += expf(v - m);
-          fin = fin && fabsf(v) < HUGE_VALF;
-        }
+        s = ce_sweep_sum_exp(r, C, sc, mx.m, [&](float v) { fin = fin && fabsf(v) < HUGE_VALF; });
         if (inside) zt = r[t * sc];
       }
     }
-    if (amax != nullptr) amax[i] = am;
+    const float m = mx.m;
+    if (amax != nullptr) amax[i] = mx.am;
     float v = -1.f;  // ignored: below every cut
     if (valid) {
-      v = OH_NAN;
+      v = ce_nan();  // the rule for labels (ce_pixel.h); non-finite logits rank the same way
       if (inside && fin) {
         v = (m - zt) + logf(s);
         v = v > 0.f ? v : 0.f;  // finite logits: never NaN here; -0.0f and any rounding below zero become +0.0f
@@ -266,7 +248,7 @@ __global__ __launch_bounds__(OH_THREADS) void oh_sum_kernel(const float* __restr
     float w = 1.f;
     if (weight != nullptr) {
       const long long t = tgt[i];
-      if (t >= 0 && t < C) w = weight[t];  // a label outside [0, C) never indexes w (its nll is NaN)
+      if (ce_label_inside(t, C)) w = weight[t];  // a label outside [0, C) never indexes w (its nll is NaN)
     }
     num += (double)w * (double)v;
     den += (double)w;
@@ -307,155 +289,32 @@ __global__ void oh_finalize_kernel(const double* __restrict__ partial, int n, co
 }
 
 // ------------------------------------------------------------------ backward
-// The operands of the backward beside the logits: stats as the forward left it ({den, num, cut, 0}), nll as it saved it.
-struct OhBwd {
+// A linear policy of ce_pixel.h: dz_c = (softmax_c - 1[c == t]) * k + bad with k = w[t] * g, g = gout / stats[0].  Its
+// operands beside the logits: stats as the forward left it ({den, num, cut, 0}) and nll as it saved it.  A pixel is
+// zeroed when it is ignored or below the cut; most are, so the kernels skip a zeroed pixel's softmax with a branch.
+struct OhGrad {
   const float* __restrict__ weight;
   long long ignore;
   const float* __restrict__ stats;
   const float* __restrict__ nll;
+
+  struct Wg : CeLinearWg {
+    const float* __restrict__ weight;
+    long long ignore;
+    const float* __restrict__ nll;
+    float g, cut;
+    __device__ __forceinline__ CeLinearPx pixel(long long i, long long t, int C) const {
+      return ce_linear_px(t, C, g, weight, t == ignore || nll[i] < cut);
+    }
+  };
+  template <int>
+  __device__ __forceinline__ Wg begin(const float* __restrict__ gout, long long, int) const {
+    return {{}, weight, ignore, nll, gout[0] / stats[0], stats[2]};
+  }
 };
 
-// dz_c = (softmax_c - 1[c == t]) * k + bad with k = w[t] * g, g = gout / stats[0].  `zero`: the pixel is ignored or
-// below the cut, and the kernels store 0.0f in every lane they own (a select, never a product with g, which is inf when
-// nothing is kept).  bad: NaN for a kept pixel whose label is outside [0, C), which never indexes w.
-__device__ __forceinline__ float oh_scale(long long i, long long t, int C, float g, float cut, OhBwd ex, float& bad,
-                                          bool& zero) {
-  zero = t == ex.ignore || ex.nll[i] < cut;
-  const bool oob = t < 0 || t >= C;
-  bad = (oob && !zero) ? OH_NAN : 0.f;
-  return (!oob && ex.weight != nullptr) ? ex.weight[t] * g : g;
-}
-
-// generic strides, C lanes per pixel
-__global__ __launch_bounds__(OH_THREADS) void oh_bwd_kernel(const float* __restrict__ z,
-                                                            const long long* __restrict__ tgt,
-                                                            const float* __restrict__ gout, float* __restrict__ dz,
-                                                            long long P, int HW, int C, long long sb, long long sc,
-                                                            long long sp, long long dsb, long long dsc, long long dsp,
-                                                            OhBwd ex) {
-  const float g = gout[0] / ex.stats[0], cut = ex.stats[2];
-  VMTL_GRID_STRIDE(i, P) {
-    const long long b = i / HW, hw = i - b * HW;
-    const long long off = b * sb + hw * sp, doff = b * dsb + hw * dsp;
-    const long long t = tgt[i];
-    float bad;
-    bool zero;
-    const float k = oh_scale(i, t, C, g, cut, ex, bad, zero);
-    if (zero) {
-      for (int c = 0; c < C; ++c) dz[doff + c * dsc] = 0.f;
-      continue;
-    }
-    float m = z[off];
-    for (int c = 1; c < C; ++c) m = fmaxf(m, z[off + c * sc]);
-    float s = 0.f;
-    for (int c = 0; c < C; ++c) s += expf(z[off + c * sc] - m);
-    const float inv = 1.f / s;
-    for (int c = 0; c < C; ++c) dz[doff + c * dsc] = (expf(z[off + c * sc] - m) * inv - (c == t ? 1.f : 0.f)) * k + bad;
-  }
-}
-
-// NHWC rows of ld >= ceil4(C) floats, of which the first ceil4(C) are written: one thread per (pixel, channel quad)
-__global__ __launch_bounds__(OH_THREADS) void oh_bwd_nhwc_kernel(const float* __restrict__ z,
-                                                                 const long long* __restrict__ tgt,
-                                                                 const float* __restrict__ gout, float* __restrict__ dz,
-                                                                 long long P, int HW, int C, long long sb, long long sc,
-                                                                 long long sp, int ld, OhBwd ex) {
-  const float g = gout[0] / ex.stats[0], cut = ex.stats[2];
-  const int Q = (C + 3) >> 2;
-  const long long total = P * Q;
-  VMTL_GRID_STRIDE(idx, total) {
-    const long long i = idx / Q;
-    const int q = (int)(idx - i * Q);
-    const long long b = i / HW, hw = i - b * HW;
-    const long long off = b * sb + hw * sp;
-    const long long t = tgt[i];
-    float bad;
-    bool zero;
-    const float k = oh_scale(i, t, C, g, cut, ex, bad, zero);
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (!zero) {
-      float m = z[off];
-      for (int c = 1; c < C; ++c) m = fmaxf(m, z[off + c * sc]);
-      float s = 0.f;
-      for (int c = 0; c < C; ++c) s += expf(z[off + c * sc] - m);
-      const float inv = 1.f / s;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int c = 4 * q + e;
-        v[e] = c < C ? (expf(z[off + c * sc] - m) * inv - (c == t ? 1.f : 0.f)) * k + bad : 0.f;
-      }
-    }
-    *reinterpret_cast<f32x4*>(dz + i * ld + 4 * q) = v;
-  }
-}
-
-// NHWC rows of exactly Q = ceil(C/4) quads (ld == 4*Q): one thread per pixel, the wave's 64 finished rows turned
-// through LDS so that every store instruction writes 1 KB of consecutive gradient (loss.hip ce_bwd_nhwc_rows_kernel).
-template <int Q>
-__global__ __launch_bounds__(256) void oh_bwd_nhwc_rows_kernel(const float* __restrict__ z,
-                                                               const long long* __restrict__ tgt,
-                                                               const float* __restrict__ gout, float* __restrict__ dz,
-                                                               long long P, int HW, int C, long long sb, long long sc,
-                                                               long long sp, OhBwd ex) {
-  __shared__ f32x4 sm[4][64 * Q];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const float g = gout[0] / ex.stats[0], cut = ex.stats[2];
-  for (long long wg0 = (long long)blockIdx.x * 256; wg0 < P; wg0 += (long long)gridDim.x * 256) {  // uniform trip count
-    const long long base = wg0 + wave * 64, i = base + lane;
-    if (i < P) {
-      const long long t = tgt[i];
-      float bad;
-      bool zero;
-      const float k = oh_scale(i, t, C, g, cut, ex, bad, zero);
-      if (zero) {
-#pragma unroll
-        for (int q = 0; q < Q; ++q) sm[wave][lane * Q + q] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      } else {
-        const long long b = i / HW, hw = i - b * HW;
-        const float* r = z + b * sb + hw * sp;
-        float v[4 * Q];
-#pragma unroll
-        for (int c = 0; c < 4 * Q; ++c) v[c] = c < C ? r[c * sc] : 0.f;
-        float m = v[0];
-#pragma unroll
-        for (int c = 1; c < 4 * Q; ++c) m = c < C ? fmaxf(m, v[c]) : m;
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < 4 * Q; ++c) {
-          v[c] = c < C ? expf(v[c] - m) : 0.f;
-          s += v[c];
-        }
-        const float inv = 1.f / s;
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-          f32x4 o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int c = 4 * q + e;
-            o[e] = c < C ? (v[c] * inv - (c == t ? 1.f : 0.f)) * k + bad : 0.f;
-          }
-          sm[wave][lane * Q + q] = o;
-        }
-      }
-    }
-    __syncthreads();
-    if (base < P) {
-      const int nf4 = (int)(P - base < 64 ? P - base : 64) * Q;
-      f32x4* out = reinterpret_cast<f32x4*>(dz + base * (4 * Q));
-#pragma unroll
-      for (int j = 0; j < Q; ++j) {
-        const int idx = j * 64 + lane;
-        if (idx < nf4) out[idx] = sm[wave][idx];
-      }
-    }
-    __syncthreads();
-  }
-}
-
 // ------------------------------------------------------------------ entry points
-static inline int oh_blocks(long long P) {
-  return grid_1d(P, OH_THREADS, OH_BLOCKS_MAX);
-}
+static inline int oh_blocks(long long P) { return ce_blocks(P); }
 
 // the cleared head (counters, three histograms) and (sum w nll, sum w, kept) per block of the sum pass
 extern "C" long long vmtl_ce_ohem_workspace_bytes(long long P) {
@@ -482,21 +341,11 @@ extern "C" int vmtl_ce_ohem_fwd(const float* logits, const long long* target, co
   const int nblk = oh_blocks(P);
   const float tau = nll_thresh + 0.f;  // -0.0f -> +0.0f
   if (hipMemsetAsync(ws, 0, sizeof(OhemWs), st) != hipSuccess) return VMTL_ERR_LAUNCH;
-#define OHP(QV)                                                                                                      \
-  hipLaunchKernelGGL((oh_pixel_kernel<QV>), dim3(nblk), dim3(OH_THREADS), 0, st, logits, target, ignore_index, tau, nll, \
-                     argmax, ws, P, HW, C, sb, sc, sp)
-  switch (C <= 32 ? (C + 3) >> 2 : 0) {
-    case 1: OHP(1); break;
-    case 2: OHP(2); break;
-    case 3: OHP(3); break;
-    case 4: OHP(4); break;
-    case 5: OHP(5); break;
-    case 6: OHP(6); break;
-    case 7: OHP(7); break;
-    case 8: OHP(8); break;
-    default: OHP(0);
-  }
-#undef OHP
+  auto pixel = [&](auto q) {
+    hipLaunchKernelGGL((oh_pixel_kernel<decltype(q)::value>), dim3(nblk), dim3(OH_THREADS), 0, st, logits, target,
+                       ignore_index, tau, nll, argmax, ws, P, HW, C, sb, sc, sp);
+  };
+  ce_dispatch_q(C <= 32 ? (C + 3) >> 2 : 0, pixel, [&] { pixel(std::integral_constant<int, 0>{}); });
   hipLaunchKernelGGL(oh_round_kernel<1>, dim3(nblk), dim3(OH_THREADS), 0, st, (const float*)nll, ws, min_kept_total, P);
   hipLaunchKernelGGL(oh_round_kernel<2>, dim3(nblk), dim3(OH_THREADS), 0, st, (const float*)nll, ws, min_kept_total, P);
   hipLaunchKernelGGL(oh_sum_kernel, dim3(nblk), dim3(OH_THREADS), 0, st, (const float*)nll, target, weight, ws,
@@ -507,40 +356,16 @@ extern "C" int vmtl_ce_ohem_fwd(const float* logits, const long long* target, co
 }
 
 // dz_c = w[t] (softmax_c - 1[c == t]) grad_out / stats[0] on the pixels the forward kept (valid and not nll < stats[2]),
-// 0.0f in every written lane of every other pixel.  stats and nll as vmtl_ce_ohem_fwd left them.  The three layouts of
-// vmtl_ce_bwd_strided, chosen by the same tests, writing the same lanes.
+// 0.0f in every written lane of every other pixel.  stats and nll as vmtl_ce_ohem_fwd left them.  The layout is
+// ce_grad_layout's (ce_pixel.h), as for vmtl_ce_bwd_strided.
 extern "C" int vmtl_ce_ohem_bwd(const float* logits, const long long* target, const float* weight, long long ignore_index,
                                 const float* stats, const float* nll, const float* grad_out, float* dlogits, int B,
                                 int HW, int C, long long sb, long long sc, long long sp, long long dsb, long long dsc,
                                 long long dsp, void* stream) {
   VMTL_ENTER();
   if (!logits || !target || !stats || !nll || !grad_out || !dlogits || B <= 0 || HW <= 0 || C <= 0) return VMTL_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const long long P = (long long)B * HW;
-  const OhBwd ex = {weight, ignore_index, stats, nll};
-  if (dsc == 1 && dsp == ((C + 3) & ~3) && dsp <= 32 && dsb == dsp * HW) {
-    const int nb = grid_1d(P, 256, 8192);
-#define CALL(QV)                                                                                         \
-  hipLaunchKernelGGL((oh_bwd_nhwc_rows_kernel<QV>), dim3(nb), dim3(256), 0, st, logits, target, grad_out, \
-                     dlogits, P, HW, C, sb, sc, sp, ex)
-    switch ((int)dsp >> 2) {
-      case 1: CALL(1); break;
-      case 2: CALL(2); break;
-      case 3: CALL(3); break;
-      case 4: CALL(4); break;
-      case 5: CALL(5); break;
-      case 6: CALL(6); break;
-      case 7: CALL(7); break;
-      default: CALL(8); break;
-    }
-#undef CALL
-  } else if (dsc == 1 && (dsp & 3) == 0 && dsp >= ((C + 3) & ~3) && dsb == dsp * HW) {
-    const int nb = grid_1d(P * ((C + 3) >> 2), OH_THREADS, 8192);
-    hipLaunchKernelGGL(oh_bwd_nhwc_kernel, dim3(nb), dim3(OH_THREADS), 0, st, logits, target, grad_out, dlogits, P,
-                       HW, C, sb, sc, sp, (int)dsp, ex);
-  } else {
-    hipLaunchKernelGGL(oh_bwd_kernel, dim3(oh_blocks(P)), dim3(OH_THREADS), 0, st, logits, target, grad_out, dlogits, P,
-                       HW, C, sb, sc, sp, dsb, dsc, dsp, ex);
-  }
+  ce_grad_launch(ce_grad_layout(C, HW, dsb, dsc, dsp), logits, target, grad_out, dlogits,
+                 OhGrad{weight, ignore_index, stats, nll}, (long long)B * HW, HW, C, sb, sc, sp, dsb, dsc, dsp,
+                 (hipStream_t)stream);
   return vmtl_check_launch();
 }

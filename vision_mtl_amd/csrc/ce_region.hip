@@ -1,6 +1,7 @@
 // Cross entropy plus a Dice / Jaccard / Tversky region-overlap term for the segmentation criterion, forward and backward
 // (DESIGN.md section 24).  No reference call site: segmentation_models_pytorch's DiceLoss / JaccardLoss / TverskyLoss
-// in their multiclass form, fused with the weighted / ignoring cross entropy of loss.hip.
+// in their multiclass form, fused with the weighted / ignoring cross entropy (loss.hip's, restated here on the shared
+// pixel pass of ce_pixel.h).
 //
 // Semantics.  Logits z (B,C,H,W), int64 target t, optional class weights w (cross entropy only), optional ignore index:
 //   valid    : t_i != ignore_index; every sum runs over the valid pixels of the whole batch.  p_ic = softmax(z_i)_c.
@@ -25,10 +26,12 @@
 // The finalize workgroup sums the rows column by column in a fixed order, forms T_c, a_c, b_c,
 // the terms, stats and the loss in fp64 and rounds each to fp32 once.  No atomics on global memory at all (so nothing
 // to clear), no allocation, no sync; the grid depends on the shape only: bit-identical run to run, and it captures.
-// The backward recomputes the softmax as vmtl_ce_bwd_ex does and writes, in its three layouts and exactly its lanes,
+// The backward recomputes the softmax as every criterion of ce_pixel.h does and writes, in the three layouts of
+// ce_grad_layout and exactly their lanes,
 //   dz_c = grad_out [ce_weight w[t] (p_c - 1[c = t]) / stats[0] + region_weight p_c (g_c - sum_k p_k g_k)],
 // +0.0f in every written lane of an ignored pixel.
 #include "../../include/vmtl.h"
+#include "ce_pixel.h"
 #include "reduce.h"
 
 // Forward: 512 blocks of 512 threads at most.  Measured at 32x19x128x256 / 16x14x256x256 (us per forward): 1024 x 256
@@ -40,7 +43,6 @@
 #define CR_BWD_THREADS 256
 #define CR_FIN_THREADS 1024
 #define CR_MAXC VMTL_CE_REGION_MAX_CLASSES
-#define CR_NAN __int_as_float(0x7fc00000)
 static_assert(CR_MAXC == 32, "the register forms hold 4 * Q <= 32 logits");
 
 // One row of the workspace per block of the pixel pass, 8 bytes per column:
@@ -80,8 +82,7 @@ __device__ __forceinline__ double cr_wave_spread_sum(const float (&f)[NP], int l
 }
 
 // ------------------------------------------------------------------ forward: pixel pass
-// Element (b, c, hw) of the logits sits at z[b*sb + c*sc + hw*sp], as in loss.hip.  One thread per pixel, the pixel's
-// 4*Q >= C logits in registers.  The log-softmax subtracts the max first (see loss.hip); the argmax is written for
+// One thread per pixel, the pixel pass of ce_pixel.h in its register form (4*Q >= C logits).  The argmax is written for
 // ignored pixels too.  ce_on == 0: no nll, no weight read.
 template <int Q>
 __global__ __launch_bounds__(CR_THREADS) void cr_pixel_kernel(const float* __restrict__ z,
@@ -100,27 +101,15 @@ __global__ __launch_bounds__(CR_THREADS) void cr_pixel_kernel(const float* __res
   double num = 0.0, den = 0.0;
   unsigned nv = 0;
   VMTL_GRID_STRIDE(i, P) {
-    const long long b = i / HW, hw = i - b * HW;
-    const float* r = z + b * sb + hw * sp;
     float v[4 * Q];
-#pragma unroll
-    for (int c = 0; c < 4 * Q; ++c) v[c] = c < C ? r[c * sc] : 0.f;
+    ce_load<Q>(v, ce_pixel(z, i, HW, sb, sp), C, sc);
     const long long t = tgt[i];
-    float m = v[0];
-    int am = 0;
-#pragma unroll
-    for (int c = 1; c < 4 * Q; ++c)
-      if (c < C && v[c] > m) { m = v[c]; am = c; }  // first maximum wins, like torch.argmax on ties
-    if (amax != nullptr) amax[i] = am;
+    const CeMax mx = ce_max_argmax<Q>(v, C);
+    const float m = mx.m;
+    if (amax != nullptr) amax[i] = mx.am;
     if (t == ignore) continue;
-    const bool inside = t >= 0 && t < C;
-    float s = 0.f, zt = 0.f;
-#pragma unroll
-    for (int c = 0; c < 4 * Q; ++c) {
-      if (c == t) zt = v[c];
-      v[c] = c < C ? expf(v[c] - m) : 0.f;
-      s += v[c];
-    }
+    const bool inside = ce_label_inside(t, C);
+    const float zt = ce_pick<Q>(v, t), s = ce_exp_sum<Q>(v, C, m);
     const float inv = 1.f / s;
 #pragma unroll
     for (int c = 0; c < 4 * Q; ++c) {
@@ -136,7 +125,7 @@ __global__ __launch_bounds__(CR_THREADS) void cr_pixel_kernel(const float* __res
         num += (double)wt * (double)(logf(s) - (zt - m));
         den += (double)wt;
       } else {
-        num += (double)CR_NAN;  // as ce_counts in loss.hip: never a silent 0, never an index into w
+        num += (double)ce_nan();  // the rule for labels (ce_pixel.h)
       }
     }
   }
@@ -219,7 +208,7 @@ __global__ __launch_bounds__(CR_FIN_THREADS) void cr_finalize_kernel(const doubl
   }
   __syncthreads();
   const bool bad = tot[3 + 3 * C] != 0ull;
-  const double nan = (double)CR_NAN;
+  const double nan = (double)ce_nan();
   if (threadIdx.x < C) {
     const int c = threadIdx.x;
     const double Sc = __longlong_as_double((long long)tot[2 + c]), TPc = __longlong_as_double((long long)tot[2 + C + c]);
@@ -253,103 +242,96 @@ __global__ __launch_bounds__(CR_FIN_THREADS) void cr_finalize_kernel(const doubl
 }
 
 // ------------------------------------------------------------------ backward
-// One thread per pixel, logits in registers, b_c in registers, a_t from LDS.  MODE 0: NHWC rows of exactly Q quads
-// (ld == 4*Q), the wave's 64 finished rows turned through LDS so that every store instruction writes 1 KB of
-// consecutive gradient (loss.hip ce_bwd_nhwc_rows_kernel).  MODE 1: NHWC rows of ld > 4*Q floats, of which the first
-// ceil4(C) are written (Q quad stores per pixel).  MODE 2: generic strides, C lanes per pixel.
-struct CrBwd {
+// The gradient policy (ce_pixel.h): b_c in registers, a_t from LDS, and the cross entropy's k as a linear policy forms
+// it.  The term needs the pixel's whole softmax (the dot), so it has no per-lane form: the rows layout is the shared
+// ce_grad_rows_kernel, and the two other layouts are the one-thread-per-pixel kernel below instead of the sweep kernels.
+// An ignored pixel is skipped with a branch.
+// One lane: the cross entropy's product and the region term's, each rounded, then their sum, then bad.  Stated with
+// contraction off: fused, the compiler would pick the product a multiply-add swallows, and with it the last bit.
+__device__ __forceinline__ float cr_lane(float p, float hit, float k, float grg, float g, float dot, float bad) {
+#pragma clang fp contract(off)
+  const float ce = (p - hit) * k, rg = (grg * p) * (g - dot);
+  return (ce + rg) + bad;
+}
+
+struct CrGrad {
   const float* __restrict__ weight;
   long long ignore;
   const float* __restrict__ stats;
   const float* __restrict__ coef;
   float ce_weight, region_weight;
+
+  struct Px {
+    bool zero, inside;
+  };
+  template <int Q>
+  struct Wg {
+    const float* __restrict__ weight;
+    long long ignore;
+    const float* sa;  // a_c, in LDS
+    float cb[4 * Q];  // b_c
+    float gce, grg;
+    __device__ __forceinline__ Px pixel(long long, long long t, int C) const { return {t == ignore, ce_label_inside(t, C)}; }
+    template <int, class Put>
+    __device__ __forceinline__ void lanes(const Px& px, float (&v)[4 * Q], float inv, long long t, int C, Put put) const {
+      const float bad = px.inside ? 0.f : ce_nan();  // the rule for labels: such a label never indexes w or the table
+      const float at = px.inside ? sa[t] : 0.f;
+      const float k = (px.inside && weight != nullptr) ? weight[t] * gce : gce;
+      float dot = 0.f;
+#pragma unroll
+      for (int c = 0; c < 4 * Q; ++c) {
+        v[c] *= inv;
+        dot += v[c] * (cb[c] + (c == t ? at : 0.f));
+      }
+      float o[4 * Q];
+#pragma unroll
+      for (int c = 0; c < 4 * Q; ++c) {
+        const float hit = c == t ? 1.f : 0.f;
+        o[c] = c < C ? cr_lane(v[c], hit, k, grg, cb[c] + hit * at, dot, bad) : 0.f;
+      }
+#pragma unroll
+      for (int q = 0; q < Q; ++q) put(q, (f32x4){o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]});
+    }
+  };
+  template <int Q>
+  __device__ __forceinline__ Wg<Q> begin(const float* __restrict__ gout, long long, int C) const {
+    __shared__ float sa[4 * Q];
+    Wg<Q> wg;
+    wg.weight = weight;
+    wg.ignore = ignore;
+    wg.sa = sa;
+    if (threadIdx.x < 4 * Q) sa[threadIdx.x] = threadIdx.x < C ? coef[threadIdx.x] : 0.f;
+#pragma unroll
+    for (int c = 0; c < 4 * Q; ++c) wg.cb[c] = c < C ? coef[C + c] : 0.f;
+    // the cross entropy's unit as the weighted / ignoring policy's; a select when it is off (stats[0] is then 0)
+    wg.gce = ce_weight != 0.f ? gout[0] * ce_weight / stats[0] : 0.f;
+    wg.grg = gout[0] * region_weight;
+    __syncthreads();
+    return wg;
+  }
 };
 
-template <int Q, int MODE>
+// One thread per pixel, logits in registers.  WIDE: NHWC rows of ld > 4*Q floats, of which the first ceil4(C) are
+// written (Q quad stores per pixel); otherwise generic strides, C lanes per pixel.
+template <int Q, bool WIDE>
 __global__ __launch_bounds__(CR_BWD_THREADS) void cr_bwd_kernel(const float* __restrict__ z,
-                                                            const long long* __restrict__ tgt,
-                                                            const float* __restrict__ gout, float* __restrict__ dz,
-                                                            long long P, int HW, int C, long long sb, long long sc,
-                                                            long long sp, long long dsb, long long dsc, long long dsp,
-                                                            CrBwd ex) {
-  __shared__ f32x4 sm[MODE == 0 ? 4 : 1][MODE == 0 ? 64 * Q : 1];
-  __shared__ float sa[4 * Q];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (threadIdx.x < 4 * Q) sa[threadIdx.x] = threadIdx.x < C ? ex.coef[threadIdx.x] : 0.f;
-  float cb[4 * Q];
-#pragma unroll
-  for (int c = 0; c < 4 * Q; ++c) cb[c] = c < C ? ex.coef[C + c] : 0.f;
-  // the cross entropy's unit as ce_grad_unit<true>; a select when it is off (stats[0] is then 0)
-  const float gce = ex.ce_weight != 0.f ? gout[0] * ex.ce_weight / ex.stats[0] : 0.f;
-  const float grg = gout[0] * ex.region_weight;
-  __syncthreads();
-  for (long long wg0 = (long long)blockIdx.x * CR_BWD_THREADS; wg0 < P; wg0 += (long long)gridDim.x * CR_BWD_THREADS) {  // uniform trip count
-    const long long base = wg0 + wave * 64, i = base + lane;
-    if (i < P) {
-      const long long b = i / HW, hw = i - b * HW;
-      const long long t = tgt[i];
-      const bool zero = t == ex.ignore, inside = t >= 0 && t < C;
-      float o[4 * Q];
-      if (zero) {
-#pragma unroll
-        for (int c = 0; c < 4 * Q; ++c) o[c] = 0.f;
+                                                                const long long* __restrict__ tgt,
+                                                                const float* __restrict__ gout, float* __restrict__ dz,
+                                                                long long P, int HW, int C, long long sb, long long sc,
+                                                                long long sp, long long dsb, long long dsc, long long dsp,
+                                                                CrGrad pol) {
+  const auto wg = pol.template begin<Q>(gout, P, C);
+  VMTL_GRID_STRIDE(i, P) {
+    ce_grad_pixel<Q>(wg, z, tgt, i, HW, C, sb, sc, sp, [&](int q, f32x4 o) {
+      if constexpr (WIDE) {
+        reinterpret_cast<f32x4*>(dz + i * dsp)[q] = o;
       } else {
-        const float* r = z + b * sb + hw * sp;
-        float v[4 * Q];
+        float* out = ce_pixel(dz, i, HW, dsb, dsp);
 #pragma unroll
-        for (int c = 0; c < 4 * Q; ++c) v[c] = c < C ? r[c * sc] : 0.f;
-        float m = v[0];
-#pragma unroll
-        for (int c = 1; c < 4 * Q; ++c) m = c < C ? fmaxf(m, v[c]) : m;
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < 4 * Q; ++c) {
-          v[c] = c < C ? expf(v[c] - m) : 0.f;
-          s += v[c];
-        }
-        const float inv = 1.f / s;
-        const float bad = inside ? 0.f : CR_NAN;  // a label outside [0, C) never indexes w or the table
-        const float at = inside ? sa[t] : 0.f;
-        const float k = (inside && ex.weight != nullptr) ? ex.weight[t] * gce : gce;
-        float dot = 0.f;
-#pragma unroll
-        for (int c = 0; c < 4 * Q; ++c) {
-          v[c] *= inv;
-          dot += v[c] * (cb[c] + (c == t ? at : 0.f));
-        }
-#pragma unroll
-        for (int c = 0; c < 4 * Q; ++c) {
-          const float hit = c == t ? 1.f : 0.f;
-          o[c] = c < C ? (v[c] - hit) * k + grg * v[c] * ((cb[c] + hit * at) - dot) + bad : 0.f;
-        }
+        for (int j = 0; j < 4; ++j)
+          if (4 * q + j < C) out[(4 * q + j) * dsc] = o[j];
       }
-      if constexpr (MODE == 0) {
-#pragma unroll
-        for (int q = 0; q < Q; ++q) sm[wave][lane * Q + q] = (f32x4){o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]};
-      } else if constexpr (MODE == 1) {
-        f32x4* out = reinterpret_cast<f32x4*>(dz + i * dsp);
-#pragma unroll
-        for (int q = 0; q < Q; ++q) out[q] = (f32x4){o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]};
-      } else {
-        float* out = dz + b * dsb + hw * dsp;
-#pragma unroll
-        for (int c = 0; c < 4 * Q; ++c)
-          if (c < C) out[c * dsc] = o[c];
-      }
-    }
-    if constexpr (MODE == 0) {
-      __syncthreads();
-      if (base < P) {
-        const int nf4 = (int)(P - base < 64 ? P - base : 64) * Q;
-        f32x4* out = reinterpret_cast<f32x4*>(dz + base * (4 * Q));
-#pragma unroll
-        for (int j = 0; j < Q; ++j) {
-          const int idx = j * 64 + lane;
-          if (idx < nf4) out[idx] = sm[wave][idx];
-        }
-      }
-      __syncthreads();
-    }
+    });
   }
 }
 
@@ -379,20 +361,11 @@ extern "C" int vmtl_ce_region_fwd(const float* logits, const long long* target, 
   hipStream_t st = (hipStream_t)stream;
   const int nblk = cr_blocks(P);
   double* ws = (double*)workspace;
-#define CRP(QV)                                                                                                     \
-  hipLaunchKernelGGL((cr_pixel_kernel<QV>), dim3(nblk), dim3(CR_THREADS), 0, st, logits, target, weight, ignore_index, \
-                     ce_weight != 0.f ? 1 : 0, ws, argmax, P, HW, C, sb, sc, sp)
-  switch ((C + 3) >> 2) {
-    case 1: CRP(1); break;
-    case 2: CRP(2); break;
-    case 3: CRP(3); break;
-    case 4: CRP(4); break;
-    case 5: CRP(5); break;
-    case 6: CRP(6); break;
-    case 7: CRP(7); break;
-    default: CRP(8); break;
-  }
-#undef CRP
+  auto pixel = [&](auto q) {
+    hipLaunchKernelGGL((cr_pixel_kernel<decltype(q)::value>), dim3(nblk), dim3(CR_THREADS), 0, st, logits, target, weight,
+                       ignore_index, ce_weight != 0.f ? 1 : 0, ws, argmax, P, HW, C, sb, sc, sp);
+  };
+  ce_dispatch_q((C + 3) >> 2, pixel, [&] { pixel(std::integral_constant<int, 8>{}); });
   hipLaunchKernelGGL(cr_finalize_kernel, dim3(1), dim3(CR_FIN_THREADS), 0, st, (const double*)ws, nblk, C, alpha, beta,
                      smooth, ce_weight, region_weight, loss, terms, stats, coef, counts);
   return vmtl_check_launch();
@@ -410,32 +383,23 @@ extern "C" int vmtl_ce_region_bwd(const float* logits, const long long* target, 
   if (!cr_classes_ok(C)) return VMTL_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   const long long P = (long long)B * HW;
-  const CrBwd ex = {weight, ignore_index, stats, coef, ce_weight, region_weight};
-  const int nb = grid_1d(P, CR_BWD_THREADS, 8192);
-  // the three layouts of ce_bwd_launch (loss.hip), chosen by the same tests
-  const int c4 = (C + 3) & ~3;
-  const int mode = (dsc == 1 && dsp == c4 && dsb == dsp * HW) ? 0
-                   : (dsc == 1 && (dsp & 3) == 0 && dsp >= c4 && dsb == dsp * HW) ? 1 : 2;
-#define CRB(QV, MV)                                                                                              \
-  hipLaunchKernelGGL((cr_bwd_kernel<QV, MV>), dim3(nb), dim3(CR_BWD_THREADS), 0, st, logits, target, grad_out, dlogits, P, \
-                     HW, C, sb, sc, sp, dsb, dsc, dsp, ex)
-#define CRQ(QV)                   \
-  case QV:                        \
-    if (mode == 0) CRB(QV, 0);    \
-    else if (mode == 1) CRB(QV, 1); \
-    else CRB(QV, 2);              \
-    break
-  switch (c4 >> 2) {
-    CRQ(1);
-    CRQ(2);
-    CRQ(3);
-    CRQ(4);
-    CRQ(5);
-    CRQ(6);
-    CRQ(7);
-    CRQ(8);
+  const CrGrad pol = {weight, ignore_index, stats, coef, ce_weight, region_weight};
+  const CeGradLayout layout = ce_grad_layout(C, HW, dsb, dsc, dsp);
+  if (layout == CE_GRAD_ROWS) {
+    ce_grad_rows_launch(logits, target, grad_out, dlogits, pol, P, HW, C, sb, sc, sp, st);
+  } else {
+    const int nb = grid_1d(P, CR_BWD_THREADS, 8192);
+    ce_dispatch_q((C + 3) >> 2,
+                  [&](auto q) {
+                    constexpr int Q = decltype(q)::value;
+                    if (layout == CE_GRAD_WIDE)
+                      hipLaunchKernelGGL((cr_bwd_kernel<Q, true>), dim3(nb), dim3(CR_BWD_THREADS), 0, st, logits, target,
+                                         grad_out, dlogits, P, HW, C, sb, sc, sp, dsb, dsc, dsp, pol);
+                    else
+                      hipLaunchKernelGGL((cr_bwd_kernel<Q, false>), dim3(nb), dim3(CR_BWD_THREADS), 0, st, logits, target,
+                                         grad_out, dlogits, P, HW, C, sb, sc, sp, dsb, dsc, dsp, pol);
+                  },
+                  [] {});
   }
-#undef CRQ
-#undef CRB
   return vmtl_check_launch();
 }

@@ -19,13 +19,19 @@
 // compiles to, so the default step pays nothing for the variant.  The SILog kernels take their
 // validity test (target > min_depth, or the caller's mask) as a functor in the same way.
 //
+// These kernels spell the pixel pass and the three gradient layouts themselves instead of taking them from ce_pixel.h,
+// as the OHEM and region criteria do: built from the header's inlined pieces, the plain instantiations hold the same
+// operations but come out in another block and scheduling order, 1 - 2 % slower on the default step's path (DESIGN.md
+// section 16d).  What is shared with the header is what does not touch their code: the NaN constant, the rule for
+// labels, the layout decision, the Q dispatch and the block count.  A change to the rows kernel's tail or to the
+// label rule is made here and in ce_pixel.h.
+//
 // The weighted / ignoring cross entropy divides by a sum that depends on the targets.  Its forward reduces
 // (numerator, denominator) pairs and leaves the denominator in a two-float `stats` buffer on the device
 // (stats[0] = sum of weights over valid pixels, stats[1] = the weighted nll sum); the backward reads stats[0], so the
 // step never waits for the host.
+#include "ce_pixel.h"
 #include "reduce.h"
-
-#define CE_THREADS 256
 
 // ------------------------------------------------------------------ cross entropy: what the variants do differently
 // The operands only the weighted / ignoring variant has.  weight: C floats or null (all ones); ignore: VMTL_NO_IGNORE
@@ -42,17 +48,14 @@ struct CeEx<true> {
   const float* __restrict__ stats;
 };
 
-// Forward, before the pixel's sum of exponentials: false when the pixel adds no nll.  EX: its target is the ignore index
-// (adds nothing), or any other target outside [0, C), which adds NaN to the numerator and never indexes w.
-// torch raises on an out-of-range class index; raising here would need a host sync on the step path, so such a pixel
-// contributes NaN: the loss (and, in the backward, the gradient) fails the step VISIBLY instead of silently adding 0.
-// The plain variant skips nothing and applies the same rule in ce_add.
+// Forward, before the pixel's sum of exponentials: false when the pixel adds no nll (the rule for labels, ce_pixel.h).
+// The plain variant skips nothing and applies the rule in ce_add.
 template <bool EX>
 __device__ __forceinline__ bool ce_counts(long long t, int C, CeEx<EX> ex, double& num) {
   if constexpr (EX) {
     if (t == ex.ignore) return false;
-    if (t < 0 || t >= C) {
-      num += (double)__int_as_float(0x7fc00000);
+    if (!ce_label_inside(t, C)) {
+      num += (double)ce_nan();
       return false;
     }
   }
@@ -68,7 +71,7 @@ __device__ __forceinline__ void ce_add(double& num, double& den, long long t, in
     num += (double)wt * (double)nll();
     den += (double)wt;
   } else {
-    if (t < 0 || t >= C) num += (double)__int_as_float(0x7fc00000);  // see ce_counts
+    if (!ce_label_inside(t, C)) num += (double)ce_nan();  // see ce_counts
     else num += (double)nll();
   }
 }
@@ -103,24 +106,19 @@ template <bool EX>
 __device__ __forceinline__ float ce_scale(long long t, int C, float g, CeEx<EX> ex, float& bad, bool& zero) {
   if constexpr (EX) {
     zero = t == ex.ignore;
-    const bool oob = t < 0 || t >= C;
-    bad = (oob && !zero) ? __int_as_float(0x7fc00000) : 0.f;
+    const bool oob = !ce_label_inside(t, C);
+    bad = (oob && !zero) ? ce_nan() : 0.f;
     return (!oob && ex.weight != nullptr) ? ex.weight[t] * g : g;
   } else {
     zero = false;
-    bad = (t < 0 || t >= C) ? __int_as_float(0x7fc00000) : 0.f;
+    bad = (!ce_label_inside(t, C)) ? ce_nan() : 0.f;
     return g;
   }
 }
 
 // ------------------------------------------------------------------ cross entropy: kernels
-// Element (b, c, hw) of the logits sits at z[b*sb + c*sc + hw*sp]:
-//   NCHW (the reference's layout at the boundary): sb = C*HW, sc = HW, sp = 1  -> every channel
-//   read of a wave is 256 contiguous bytes;  NHWC: sb = HW*ld, sc = 1, sp = ld.
-// One thread per pixel; the (few) channels are reduced in registers.
-// Numerics: log-softmax is evaluated as (z - max) - log(sum exp(z - max)), subtracting the max FIRST
-// (exact for nearby floats).  Forming lse = max + log(sum) and then z - lse would lose ~ulp(max)
-// per pixel when the logits are large, a systematic error the backward pass of a deep net amplifies.
+// Element (b, c, hw) of the logits sits at z[b*sb + c*sc + hw*sp] (layouts: ce_pixel.h).  One thread per pixel; the
+// (few) channels are reduced in registers.  The log-softmax subtracts the max first (the numerics note of ce_pixel.h).
 // The argmax is written for ignored pixels too (the prediction does not depend on the target).
 template <bool EX>
 __global__ __launch_bounds__(CE_THREADS) void ce_fwd_kernel(const float* __restrict__ z,
@@ -191,7 +189,7 @@ __global__ void sum_finalize_kernel(const double* __restrict__ partial, int n, d
   double s = 0.0;
   for (int i = threadIdx.x; i < n; i += blockDim.x) s += partial[i];
   const double t = block_sum(s, shd);
-  if (threadIdx.x == 0) out[0] = (err != nullptr && err[0] != 0) ? __int_as_float(0x7fc00000) : (float)(t * scale);
+  if (threadIdx.x == 0) out[0] = (err != nullptr && err[0] != 0) ? ce_nan() : (float)(t * scale);
 }
 
 // The (numerator, denominator) pairs summed in the fixed order of sum_finalize_kernel.
@@ -338,72 +336,43 @@ __global__ __launch_bounds__(256) void ce_bwd_nhwc_rows_kernel(const float* __re
 }
 
 // ------------------------------------------------------------------ cross entropy: launchers and entry points
-static inline int ce_blocks(long long P) {
-  return grid_1d(P, CE_THREADS, 2048);
-}
-
 // The per-block partials of the loss into `partial` (ce_blocks(P) entries): logits in registers for C <= 32.
 template <bool EX>
 static void ce_fwd_launch(const float* logits, const long long* target, CeEx<EX> ex, double* partial, long long* amax,
                           long long P, int HW, int C, long long sb, long long sc, long long sp, hipStream_t st) {
   const int nblk = ce_blocks(P);
-#define CEF(QV)                                                                                                    \
-  hipLaunchKernelGGL((ce_fwd_regs_kernel<QV, EX>), dim3(nblk), dim3(CE_THREADS), 0, st, logits, target, ex, partial, \
-                     amax, P, HW, C, sb, sc, sp)
-  switch (C <= 32 ? (C + 3) >> 2 : 0) {
-    case 1: CEF(1); break;
-    case 2: CEF(2); break;
-    case 3: CEF(3); break;
-    case 4: CEF(4); break;
-    case 5: CEF(5); break;
-    case 6: CEF(6); break;
-    case 7: CEF(7); break;
-    case 8: CEF(8); break;
-    default:
-      hipLaunchKernelGGL(ce_fwd_kernel<EX>, dim3(nblk), dim3(CE_THREADS), 0, st, logits, target, ex, partial, amax, P, HW,
-                         C, sb, sc, sp);
-  }
-#undef CEF
+  ce_dispatch_q(
+      C <= 32 ? (C + 3) >> 2 : 0,
+      [&](auto q) {
+        hipLaunchKernelGGL((ce_fwd_regs_kernel<decltype(q)::value, EX>), dim3(nblk), dim3(CE_THREADS), 0, st, logits,
+                           target, ex, partial, amax, P, HW, C, sb, sc, sp);
+      },
+      [&] {
+        hipLaunchKernelGGL(ce_fwd_kernel<EX>, dim3(nblk), dim3(CE_THREADS), 0, st, logits, target, ex, partial, amax, P,
+                           HW, C, sb, sc, sp);
+      });
 }
 
+// The gradient in `layout`: ce_grad_layout's answer (ce_pixel.h, which also says what the three layouts are), or
+// CE_GRAD_STRIDED for any strides.
 template <bool EX>
-static void ce_bwd_launch_strided(const float* logits, const long long* target, const float* grad_out, float* dlogits,
-                                  CeEx<EX> ex, long long P, int HW, int C, long long sb, long long sc, long long sp,
-                                  long long dsb, long long dsc, long long dsp, hipStream_t st) {
-  hipLaunchKernelGGL(ce_bwd_kernel<EX>, dim3(ce_blocks(P)), dim3(CE_THREADS), 0, st, logits, target, grad_out, dlogits, P,
-                     HW, C, sb, sc, sp, dsb, dsc, dsp, ex);
-}
-
-// Element (b, c, hw) of the gradient goes to dlogits[b*dsb + c*dsc + hw*dsp].  With (HW*ld, 1, ld) the gradient lands
-// in the NHWC storage the head's data-gradient conv reads (one 76-byte run per pixel) and the NCHW -> NHWC relayout of
-// an 80 MB tensor disappears from the step.  Three layouts: rows of exactly ceil4(C) floats (turned through LDS), NHWC
-// with a wider ld (only the first ceil4(C) lanes are written), generic strides (C lanes).
-template <bool EX>
-static void ce_bwd_launch(const float* logits, const long long* target, const float* grad_out, float* dlogits,
-                          CeEx<EX> ex, long long P, int HW, int C, long long sb, long long sc, long long sp,
-                          long long dsb, long long dsc, long long dsp, hipStream_t st) {
-  if (dsc == 1 && dsp == ((C + 3) & ~3) && dsp <= 32 && dsb == dsp * HW) {
+static void ce_bwd_launch(CeGradLayout layout, const float* logits, const long long* target, const float* grad_out,
+                          float* dlogits, CeEx<EX> ex, long long P, int HW, int C, long long sb, long long sc,
+                          long long sp, long long dsb, long long dsc, long long dsp, hipStream_t st) {
+  if (layout == CE_GRAD_ROWS) {
     const int nb = grid_1d(P, 256, 8192);
-#define CALL(QV)                                                                                            \
-  hipLaunchKernelGGL((ce_bwd_nhwc_rows_kernel<QV, EX>), dim3(nb), dim3(256), 0, st, logits, target, grad_out, \
-                     dlogits, P, HW, C, sb, sc, sp, ex)
-    switch ((int)dsp >> 2) {
-      case 1: CALL(1); break;
-      case 2: CALL(2); break;
-      case 3: CALL(3); break;
-      case 4: CALL(4); break;
-      case 5: CALL(5); break;
-      case 6: CALL(6); break;
-      case 7: CALL(7); break;
-      default: CALL(8); break;
-    }
-#undef CALL
-  } else if (dsc == 1 && (dsp & 3) == 0 && dsp >= ((C + 3) & ~3) && dsb == dsp * HW) {
+    auto launch = [&](auto q) {
+      hipLaunchKernelGGL((ce_bwd_nhwc_rows_kernel<decltype(q)::value, EX>), dim3(nb), dim3(256), 0, st, logits, target,
+                         grad_out, dlogits, P, HW, C, sb, sc, sp, ex);
+    };
+    ce_dispatch_q((int)dsp >> 2, launch, [&] { launch(std::integral_constant<int, 8>{}); });
+  } else if (layout == CE_GRAD_WIDE) {
     const int nb = grid_1d(P * ((C + 3) >> 2), CE_THREADS, 8192);
     hipLaunchKernelGGL(ce_bwd_nhwc_kernel<EX>, dim3(nb), dim3(CE_THREADS), 0, st, logits, target, grad_out, dlogits,
                        P, HW, C, sb, sc, sp, (int)dsp, ex);
   } else {
-    ce_bwd_launch_strided<EX>(logits, target, grad_out, dlogits, ex, P, HW, C, sb, sc, sp, dsb, dsc, dsp, st);
+    hipLaunchKernelGGL(ce_bwd_kernel<EX>, dim3(ce_blocks(P)), dim3(CE_THREADS), 0, st, logits, target, grad_out, dlogits,
+                       P, HW, C, sb, sc, sp, dsb, dsc, dsp, ex);
   }
 }
 
@@ -463,19 +432,19 @@ extern "C" int vmtl_ce_bwd(const float* logits, const long long* target, const f
                            int HW, int C, long long sb, long long sc, long long sp, void* stream) {
   VMTL_ENTER();
   if (!logits || !target || !grad_out || !dlogits || B <= 0 || HW <= 0 || C <= 0) return VMTL_ERR_ARG;
-  ce_bwd_launch_strided<false>(logits, target, grad_out, dlogits, {}, (long long)B * HW, HW, C, sb, sc, sp, sb, sc, sp,
-                               (hipStream_t)stream);
+  ce_bwd_launch<false>(CE_GRAD_STRIDED, logits, target, grad_out, dlogits, {}, (long long)B * HW, HW, C, sb, sc, sp, sb,
+                       sc, sp, (hipStream_t)stream);
   return vmtl_check_launch();
 }
 
-// vmtl_ce_bwd with its own strides for dlogits (see ce_bwd_launch)
+// vmtl_ce_bwd with its own strides for dlogits, in the layout ce_grad_layout (ce_pixel.h) finds for them
 extern "C" int vmtl_ce_bwd_strided(const float* logits, const long long* target, const float* grad_out, float* dlogits,
                                    int B, int HW, int C, long long sb, long long sc, long long sp, long long dsb,
                                    long long dsc, long long dsp, void* stream) {
   VMTL_ENTER();
   if (!logits || !target || !grad_out || !dlogits || B <= 0 || HW <= 0 || C <= 0) return VMTL_ERR_ARG;
-  ce_bwd_launch<false>(logits, target, grad_out, dlogits, {}, (long long)B * HW, HW, C, sb, sc, sp, dsb, dsc, dsp,
-                       (hipStream_t)stream);
+  ce_bwd_launch<false>(ce_grad_layout(C, HW, dsb, dsc, dsp), logits, target, grad_out, dlogits, {}, (long long)B * HW,
+                       HW, C, sb, sc, sp, dsb, dsc, dsp, (hipStream_t)stream);
   return vmtl_check_launch();
 }
 
@@ -487,8 +456,9 @@ extern "C" int vmtl_ce_bwd_ex(const float* logits, const long long* target, cons
                               void* stream) {
   VMTL_ENTER();
   if (!logits || !target || !stats || !grad_out || !dlogits || B <= 0 || HW <= 0 || C <= 0) return VMTL_ERR_ARG;
-  ce_bwd_launch<true>(logits, target, grad_out, dlogits, {weight, ignore_index, stats}, (long long)B * HW, HW, C, sb, sc,
-                      sp, dsb, dsc, dsp, (hipStream_t)stream);
+  ce_bwd_launch<true>(ce_grad_layout(C, HW, dsb, dsc, dsp), logits, target, grad_out, dlogits,
+                      {weight, ignore_index, stats}, (long long)B * HW, HW, C, sb, sc, sp, dsb, dsc, dsp,
+                      (hipStream_t)stream);
   return vmtl_check_launch();
 }
 

@@ -3137,6 +3137,53 @@ def _ce_weight(weight, logits):
     return weight
 
 
+def _ce_dims(logits):
+    """The geometry operands of the loss kernels for NCHW-contiguous logits."""
+    B, C, H, W = logits.shape
+    return dict(B=B, HW=H * W, C=C, sb=C * H * W, sc=H * W, sp=1)
+
+
+def _ce_front(who, logits, target, weight, want_argmax, max_classes=None):
+    """What the segmentation criteria's nodes check and allocate before their forward kernel:
+    (logits, target, weight, geometry operands, the (B,H,W) int64 prediction buffer or None)."""
+    logits = _req(logits, "logits")
+    if target.dtype != torch.int64:
+        raise TypeError(f"{who}: target must be int64 class indices")
+    target = target.contiguous()
+    B, C, H, W = logits.shape
+    if tuple(target.shape) != (B, H, W):
+        raise ValueError(f"{who}: target shape {tuple(target.shape)} does not match logits {(B, H, W)}")
+    if max_classes is not None and not 2 <= C <= max_classes:
+        raise ValueError(f"{who}: the region term takes 2 to {max_classes} classes, got {C}")
+    weight = _ce_weight(weight, logits)
+    pred = torch.empty((B, H, W), dtype=torch.int64, device=logits.device) if want_argmax else None
+    return logits, target, weight, _ce_dims(logits), pred
+
+
+def _ce_result(ctx, loss, pred):
+    """loss, or (loss, prediction) when the node was asked for the argmax."""
+    if pred is None:
+        return loss
+    ctx.mark_non_differentiable(pred)
+    return loss, pred
+
+
+def _ce_grad_storage(logits):
+    """Where a criterion's backward kernel writes dlogits, and the stride operands that say so.  The gradient is laid out
+    NHWC with room for one more head ([B][H][W][ceil4(C+1)]) and returned as its (B,C,H,W) view (_ce_grad_view): a head
+    conv that consumes it (ops.decoder_tail) takes the storage as its dY operand without the NCHW -> NHWC relayout of
+    this 80 MB tensor; any other consumer sees an ordinary strided tensor."""
+    B, C, H, W = logits.shape
+    ld = ceil4(C + 1)
+    return _empty((B, H, W, ld), logits), dict(dsb=H * W * ld, dsc=1, dsp=ld)
+
+
+def _ce_grad_view(st, C):
+    dl = st[..., :C].permute(0, 3, 1, 2)
+    dl._vmtl_nhwc = st
+    return dl
+
+
 class _CrossEntropy(torch.autograd.Function):
     """mean_{b,h,w} -log_softmax(logits)[target]; logits (B,C,H,W) NCHW-contiguous.
 
@@ -3147,20 +3194,11 @@ class _CrossEntropy(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, target, weight, ignore_index, want_argmax):
-        logits = _req(logits, "logits")
-        if target.dtype != torch.int64:
-            raise TypeError("cross_entropy: target must be int64 class indices")
-        target = target.contiguous()
-        B, C, H, W = logits.shape
-        if tuple(target.shape) != (B, H, W):
-            raise ValueError(f"cross_entropy: target shape {tuple(target.shape)} does not match logits {(B, H, W)}")
-        weight = _ce_weight(weight, logits)
-        P = B * H * W
-        dims = dict(B=B, HW=H * W, C=C, sb=C * H * W, sc=H * W, sp=1)
+        logits, target, weight, dims, pred = _ce_front("cross_entropy", logits, target, weight, want_argmax)
+        P = target.numel()
         loss = _empty((), logits)
         ws_bytes = lib().raw("vmtl_ce_workspace_bytes" if ignore_index is None else "vmtl_ce_ex_workspace_bytes")(P)
         ws = torch.empty((ws_bytes // 8,), dtype=torch.float64, device=logits.device)
-        pred = torch.empty((B, H, W), dtype=torch.int64, device=logits.device) if want_argmax else None
         if ignore_index is not None:
             stats = _empty((2,), logits)
             _k("vmtl_ce_fwd_ex", logits=logits, target=target, weight=weight, ignore_index=ignore_index, loss=loss,
@@ -3173,30 +3211,19 @@ class _CrossEntropy(torch.autograd.Function):
                 _k("vmtl_ce_fwd", logits=logits, target=target, loss=loss, workspace=ws, **dims)
             ctx.save_for_backward(logits, target)
         ctx.ignore_index = ignore_index
-        if want_argmax:
-            ctx.mark_non_differentiable(pred)
-            return loss, pred
-        return loss
+        return _ce_result(ctx, loss, pred)
 
     @staticmethod
     def backward(ctx, g, _gpred=None):
         logits, target, *ex = ctx.saved_tensors  # ex: (stats[, weight]) of the weighted / ignoring form
-        B, C, H, W = logits.shape
         g = _req(g, "grad_output")
-        # the gradient is laid out NHWC with room for one more head ([B][H][W][ceil4(C+1)]) and returned as its
-        # (B,C,H,W) view: a head conv that consumes it (ops.decoder_tail) takes the storage as its dY operand without
-        # the NCHW -> NHWC relayout of this 80 MB tensor; any other consumer sees an ordinary strided tensor
-        ld = ceil4(C + 1)
-        st = _empty((B, H, W, ld), logits)
-        dims = dict(B=B, HW=H * W, C=C, sb=C * H * W, sc=H * W, sp=1, dsb=H * W * ld, dsc=1, dsp=ld)
+        st, dstrides = _ce_grad_storage(logits)
         if ctx.ignore_index is None:
-            _k("vmtl_ce_bwd_strided", logits=logits, target=target, grad_out=g, dlogits=st, **dims)
+            _k("vmtl_ce_bwd_strided", logits=logits, target=target, grad_out=g, dlogits=st, **_ce_dims(logits), **dstrides)
         else:
             _k("vmtl_ce_bwd_ex", logits=logits, target=target, weight=ex[1] if len(ex) > 1 else None,
-               ignore_index=ctx.ignore_index, stats=ex[0], grad_out=g, dlogits=st, **dims)
-        dl = st[..., :C].permute(0, 3, 1, 2)
-        dl._vmtl_nhwc = st
-        return dl, None, None, None, None
+               ignore_index=ctx.ignore_index, stats=ex[0], grad_out=g, dlogits=st, **_ce_dims(logits), **dstrides)
+        return _ce_grad_view(st, logits.shape[1]), None, None, None, None
 
 
 def _ce_ignore(weight, ignore_index):
@@ -3229,42 +3256,26 @@ class _CrossEntropyOHEM(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, target, weight, ignore_index, tau, min_kept_total, want_argmax):
-        logits = _req(logits, "logits")
-        if target.dtype != torch.int64:
-            raise TypeError("cross_entropy_ohem: target must be int64 class indices")
-        target = target.contiguous()
-        B, C, H, W = logits.shape
-        if tuple(target.shape) != (B, H, W):
-            raise ValueError(f"cross_entropy_ohem: target shape {tuple(target.shape)} does not match logits {(B, H, W)}")
-        weight = _ce_weight(weight, logits)
-        P = B * H * W
-        loss, stats, nll = _empty((), logits), _empty((4,), logits), _empty((B, H, W), logits)
+        logits, target, weight, dims, pred = _ce_front("cross_entropy_ohem", logits, target, weight, want_argmax)
+        P = target.numel()
+        loss, stats, nll = _empty((), logits), _empty((4,), logits), _empty(tuple(target.shape), logits)
         counts = torch.empty((2,), dtype=torch.int64, device=logits.device)
         ws = torch.empty((lib().raw("vmtl_ce_ohem_workspace_bytes")(P) // 8,), dtype=torch.float64, device=logits.device)
-        pred = torch.empty((B, H, W), dtype=torch.int64, device=logits.device) if want_argmax else None
         _k("vmtl_ce_ohem_fwd", logits=logits, target=target, weight=weight, ignore_index=ignore_index, nll_thresh=tau,
            min_kept_total=min_kept_total, loss=loss, stats=stats, counts=counts, nll=nll, workspace=ws, argmax=pred,
-           B=B, HW=H * W, C=C, sb=C * H * W, sc=H * W, sp=1)
+           **dims)
         ctx.save_for_backward(logits, target, stats, nll, *(() if weight is None else (weight,)))
         ctx.ignore_index = ignore_index
-        if want_argmax:
-            ctx.mark_non_differentiable(pred)
-            return loss, pred
-        return loss
+        return _ce_result(ctx, loss, pred)
 
     @staticmethod
     def backward(ctx, g, _gpred=None):
         logits, target, stats, nll, *w = ctx.saved_tensors
-        B, C, H, W = logits.shape
         g = _req(g, "grad_output")
-        ld = ceil4(C + 1)  # the NHWC storage with room for one more head, as _CrossEntropy.backward lays it out
-        st = _empty((B, H, W, ld), logits)
+        st, dstrides = _ce_grad_storage(logits)
         _k("vmtl_ce_ohem_bwd", logits=logits, target=target, weight=w[0] if w else None, ignore_index=ctx.ignore_index,
-           stats=stats, nll=nll, grad_out=g, dlogits=st, B=B, HW=H * W, C=C, sb=C * H * W, sc=H * W, sp=1,
-           dsb=H * W * ld, dsc=1, dsp=ld)
-        dl = st[..., :C].permute(0, 3, 1, 2)
-        dl._vmtl_nhwc = st
-        return dl, None, None, None, None, None, None
+           stats=stats, nll=nll, grad_out=g, dlogits=st, **_ce_dims(logits), **dstrides)
+        return (_ce_grad_view(st, logits.shape[1]),) + (None,) * 6
 
 
 def ohem_tau(thresh) -> float:
@@ -3317,46 +3328,29 @@ class _CrossEntropyRegion(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, target, weight, ignore_index, alpha, beta, smooth, ce_weight, region_weight, want_argmax):
-        logits = _req(logits, "logits")
-        if target.dtype != torch.int64:
-            raise TypeError("segm_region_loss: target must be int64 class indices")
-        target = target.contiguous()
-        B, C, H, W = logits.shape
-        if tuple(target.shape) != (B, H, W):
-            raise ValueError(f"segm_region_loss: target shape {tuple(target.shape)} does not match logits {(B, H, W)}")
-        if not 2 <= C <= CE_REGION_MAX_CLASSES:
-            raise ValueError(f"segm_region_loss: the region term takes 2 to {CE_REGION_MAX_CLASSES} classes, got {C}")
-        weight = _ce_weight(weight, logits)
-        P = B * H * W
+        logits, target, weight, dims, pred = _ce_front("segm_region_loss", logits, target, weight, want_argmax,
+                                                       max_classes=CE_REGION_MAX_CLASSES)
+        P, C = target.numel(), logits.shape[1]
         loss, terms, stats, coef = (_empty(s, logits) for s in ((), (2,), (2,), (2 * C,)))
         counts = torch.empty((C + 1,), dtype=torch.int64, device=logits.device)
         ws = torch.empty((lib().raw("vmtl_ce_region_workspace_bytes")(P, C) // 8,), dtype=torch.float64,
                          device=logits.device)
-        pred = torch.empty((B, H, W), dtype=torch.int64, device=logits.device) if want_argmax else None
         _k("vmtl_ce_region_fwd", logits=logits, target=target, weight=weight, ignore_index=ignore_index, alpha=alpha,
            beta=beta, smooth=smooth, ce_weight=ce_weight, region_weight=region_weight, loss=loss, terms=terms,
-           stats=stats, coef=coef, counts=counts, workspace=ws, argmax=pred, B=B, HW=H * W, C=C, sb=C * H * W, sc=H * W,
-           sp=1)
+           stats=stats, coef=coef, counts=counts, workspace=ws, argmax=pred, **dims)
         ctx.save_for_backward(logits, target, stats, coef, *(() if weight is None else (weight,)))
         ctx.ignore_index, ctx.ce_weight, ctx.region_weight = ignore_index, ce_weight, region_weight
-        if want_argmax:
-            ctx.mark_non_differentiable(pred)
-            return loss, pred
-        return loss
+        return _ce_result(ctx, loss, pred)
 
     @staticmethod
     def backward(ctx, g, _gpred=None):
         logits, target, stats, coef, *w = ctx.saved_tensors
-        B, C, H, W = logits.shape
         g = _req(g, "grad_output")
-        ld = ceil4(C + 1)  # the NHWC storage with room for one more head, as _CrossEntropy.backward lays it out
-        st = _empty((B, H, W, ld), logits)
+        st, dstrides = _ce_grad_storage(logits)
         _k("vmtl_ce_region_bwd", logits=logits, target=target, weight=w[0] if w else None, ignore_index=ctx.ignore_index,
            stats=stats, coef=coef, grad_out=g, ce_weight=ctx.ce_weight, region_weight=ctx.region_weight, dlogits=st,
-           B=B, HW=H * W, C=C, sb=C * H * W, sc=H * W, sp=1, dsb=H * W * ld, dsc=1, dsp=ld)
-        dl = st[..., :C].permute(0, 3, 1, 2)
-        dl._vmtl_nhwc = st
-        return (dl,) + (None,) * 9
+           **_ce_dims(logits), **dstrides)
+        return (_ce_grad_view(st, logits.shape[1]),) + (None,) * 9
 
 
 def region_loss_number(v, name, who="segm_region_loss", positive=False) -> float:
