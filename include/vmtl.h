@@ -831,6 +831,36 @@ int vmtl_adam_step_ex(float* p, const float* g, float* m, float* v, const float*
 int vmtl_grad_clip_(float* g, const void* workspace, float grad_scale, float max_norm, float* ctl, long long n,
                     void* stream);
 
+/* ---- averaged weights: EMA / SWA over flat fp32 buffers (csrc/weight_avg.hip) -------------
+ * `state`: the state block, 8 four-byte words, 8-byte aligned, zeroed once by the caller:
+ *   [0..1] n_averaged (one 64-bit integer)  [2] the weight w of this update  [3] this update copies
+ *   [4] this update is skipped  [5] running count of skipped updates  [6..7] unused
+ * Other pointers need 4-byte alignment only. */
+#define VMTL_WAVG_EMA 0
+#define VMTL_WAVG_SWA 1
+/* One workgroup.  ctl (nullable): an optimizer control block; when ctl[3] (its step was skipped) is set, this update is
+ * skipped too: state[4] = 1, the counter stays.  Otherwise state[2] = w, state[3] = (n_averaged == 0), state[4] = 0 and
+ * n_averaged += 1, with w computed in fp64 from n = n_averaged before the increment and rounded once:
+ *   n == 0: 1 (and the copy flag)   VMTL_WAVG_SWA: 1 / (n + 1)
+ *   VMTL_WAVG_EMA: 1 - d, d = decay + decay_lo (the fp32 pair of a double in [0, 1]); with warmup != 0
+ *   d = min(d, (1 + n) / (10 + n)) */
+int vmtl_wavg_control(float* state, const float* ctl, int mode, float decay, float decay_lo, int warmup,
+                      void* stream);
+/* e[i] = fma(w, p[i] - e[i], e[i]), or e[i] = p[i] on the copy flag; nothing is written on the skip flag; p is only read */
+int vmtl_wavg_update(float* e, const float* p, const float* state, long long n, void* stream);
+/* vmtl_adam_step_ex, then vmtl_wavg_update of the new p into e, in one pass and with the same bits as the two launches */
+int vmtl_adam_step_wavg(float* p, const float* g, float* m, float* v, float* e, const float* ctl,
+                        const float* state, float lr, const float* lr_ptr, float eps, float weight_decay,
+                        int decoupled, float grad_scale, long long n, void* stream);
+/* descs: device array of n records {float* src; float* avg; long long count} (vmtl_wavg_desc_bytes() each, 8-byte
+ * aligned, 1 <= n <= 65535), count <= max_n, written and validated by the host; one launch for all records.
+ * vmtl_wavg_buffers: avg <- the update above with src as p.  vmtl_swap_table_: src <-> avg, bit for bit. */
+int vmtl_wavg_desc_bytes(void);
+int vmtl_wavg_buffers(const void* descs, int n, long long max_n, const float* state, void* stream);
+int vmtl_swap_table_(const void* descs, int n, long long max_n, void* stream);
+/* a <-> b in place, moved as integers (NaN payloads survive); overlapping ranges are refused with VMTL_ERR_ARG */
+int vmtl_swap_(float* a, float* b, long long n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

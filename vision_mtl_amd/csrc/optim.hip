@@ -22,21 +22,8 @@
 //   [6] 1 / sqrt(1 - b2^step)   [7] b1   [8] 1 - b1   [9] b2   [10] 1 - b2   [11..15] unused
 // The betas arrive as a float pair (hi + lo): the C ABI carries no double, and 1 - b2 taken from the fp32 0.999 alone is off
 // by 3e-5 of its value - that much of every second-moment increment.
+#include "optim.h"
 #include "reduce.h"
-
-#define OPT_THREADS 256
-#define OPT_MAX_BLOCKS 1024  // 4 workgroups per CU: 64 KiB of 16-byte loads in flight per CU in the four-stream update
-#define VMTL_OPTIM_CTL_FLOATS 16
-
-static inline int opt_blocks(long long n) {  // float4 per thread and trip; a function of n alone (see Determinism)
-  return grid_1d(n, 4 * OPT_THREADS, OPT_MAX_BLOCKS);
-}
-
-// elements in front of the first 16-byte boundary of a 4-byte-aligned pointer, at most n
-__host__ __device__ static inline int opt_head(const void* ptr, long long n) {
-  const int h = (int)((16 - ((uintptr_t)ptr & 15)) & 15) >> 2;
-  return (long long)h < n ? h : (int)n;
-}
 
 // fixed-order fp64 sum of the nparts partials; every thread of the 256-thread workgroup returns the total
 __device__ __forceinline__ double partials_sum(const double* __restrict__ partials, int nparts, double* sh) {
@@ -143,24 +130,7 @@ extern "C" int vmtl_optim_control(const void* workspace, long long n, float max_
 }
 
 // ------------------------------------------------------------------ fused update
-struct AdamConsts {
-  float gscale, coef, b1, omb1, b2, omb2, step_size, inv_sqrt_bc2, eps, wd, decay;
-  int decoupled;
-};
-
-// torch/optim/adam.py _single_tensor_adam, element by element
-__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, const AdamConsts& c) {
-  float gi = g * c.gscale * c.coef;
-  if (c.decoupled)
-    p *= c.decay;
-  else if (c.wd != 0.f)
-    gi += c.wd * p;
-  m = c.b1 * m + c.omb1 * gi;
-  v = c.b2 * v + c.omb2 * gi * gi;
-  const float denom = sqrtf(v) * c.inv_sqrt_bc2 + c.eps;
-  p -= c.step_size * (m / denom);
-}
-
+// AdamConsts / adam_consts / adam_elem: optim.h (weight_avg.hip runs the same element update)
 template <bool VEC>
 __global__ __launch_bounds__(OPT_THREADS) void adam_ex_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                               float* __restrict__ m, float* __restrict__ v,
@@ -169,19 +139,7 @@ __global__ __launch_bounds__(OPT_THREADS) void adam_ex_kernel(float* __restrict_
                                                               int decoupled, float gscale, long long n) {
   if (ctl[3] != 0.f) return;  // skipped step: p, m and v keep their bits
   if (lr_ptr) lr = lr_ptr[0];
-  AdamConsts c;
-  c.gscale = gscale;
-  c.coef = ctl[1];
-  c.b1 = ctl[7];
-  c.omb1 = ctl[8];
-  c.b2 = ctl[9];
-  c.omb2 = ctl[10];
-  c.step_size = lr * ctl[5];
-  c.inv_sqrt_bc2 = ctl[6];
-  c.eps = eps;
-  c.wd = wd;
-  c.decoupled = decoupled;
-  c.decay = (float)(1.0 - (double)lr * (double)wd);
+  const AdamConsts c = adam_consts(ctl, lr, eps, wd, decoupled, gscale);
   if (VEC) {
     const int head = opt_head(p, n);  // the host checked that g, m and v share p's offset in a 16-byte line
     const long long nvec = (n - head) >> 2;
@@ -239,7 +197,7 @@ extern "C" int vmtl_adam_step_ex(float* p, const float* g, float* m, float* v, c
     hipLaunchKernelGGL(adam_ex_kernel<true>, dim3(opt_blocks(n)), dim3(OPT_THREADS), 0, (hipStream_t)stream, p, g, m,
                        v, ctl, lr, lr_ptr, eps, weight_decay, decoupled, grad_scale, n);
   } else {
-    const int nb = grid_1d(n, OPT_THREADS, 4 * OPT_MAX_BLOCKS);
+    const int nb = opt_blocks_scalar(n);
     hipLaunchKernelGGL(adam_ex_kernel<false>, dim3(nb), dim3(OPT_THREADS), 0, (hipStream_t)stream, p, g, m, v,
                        ctl, lr, lr_ptr, eps, weight_decay, decoupled, grad_scale, n);
   }

@@ -10,6 +10,7 @@ shape for this fabric).
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import weakref
@@ -88,6 +89,7 @@ class FlatArena:
         self._adam = None
         self._optim = None  # (workspace, control block) of the clipping / extended-update launches
         self.pending_scale = 1.0  # 1/world still to be applied to flat_grad (see all_reduce_mean / ArenaAdam)
+        self._applied_average = None  # the ArenaAverage whose weights stand in flat_param right now (ArenaAverage.applied)
         if broadcast:
             self.broadcast_parameters()
 
@@ -239,13 +241,22 @@ class FlatArena:
         return ops.scale_by_clip(self.flat_grad, float(max_norm), scale, ws, ctl)
 
     def adam_step(self, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0, *, max_grad_norm=None,
-                  decoupled_weight_decay=False, skip_nonfinite=False):
+                  decoupled_weight_decay=False, skip_nonfinite=False, average=None):
         """torch.optim.Adam semantics (reference training_lit.py:51,87) as ONE fused launch over the arena.
 
         max_grad_norm (clip the global norm of the true gradient first), decoupled_weight_decay (AdamW),
         skip_nonfinite (leave everything untouched when the gradient norm is inf / NaN) or a 0-dim device tensor as lr
         select the extended path instead (ops.adam_step_ex: norm pass when clipping or skipping, control launch, update):
-        the step counter is then incremented on the device, in the same tensor."""
+        the step counter is then incremented on the device, in the same tensor.
+
+        average (an ArenaAverage over this arena) selects the extended path too, ending in ops.adam_step_wavg: the new
+        parameters go into the average in the same pass, so the caller calls no average.update()."""
+        if self._applied_average is not None:
+            raise RuntimeError("FlatArena.adam_step: the averaged weights are applied (ArenaAverage.applied / swap): a step "
+                               "now would train the average instead of the live parameters")
+        if average is not None:
+            return self._adam_step_averaged(average, lr, betas, eps, weight_decay, grad_scale, max_grad_norm,
+                                            decoupled_weight_decay, skip_nonfinite)
         extended = (max_grad_norm is not None or decoupled_weight_decay or skip_nonfinite
                     or isinstance(lr, torch.Tensor))
         st = self._adam_state()
@@ -265,6 +276,25 @@ class FlatArena:
                           grad_scale)
         self._kernel_written.clear()
         ops.packs.invalidate()  # parameters changed through raw pointers: packed operands are stale
+
+    def _adam_step_averaged(self, average, lr, betas, eps, weight_decay, grad_scale, max_grad_norm, decoupled_weight_decay,
+                            skip_nonfinite):
+        """adam_step(average=...): the extended update with the average in the same pass (+ the buffers launch)."""
+        if not isinstance(average, ArenaAverage) or average.arena is not self:
+            raise ValueError("FlatArena.adam_step: average must be an ArenaAverage over this arena")
+        st = self._adam_state()
+        ops.side.join()
+        grad_scale, self.pending_scale = grad_scale * self.pending_scale, 1.0
+        ws, ctl = self._optim_buffers()
+        ops.adam_step_wavg(self.flat_param, self.flat_grad, st["m"], st["v"], average.flat_avg, average.state, st["step"],
+                           lr, betas, eps, weight_decay, grad_scale, mode=average.mode, decay=average.decay,
+                           warmup=average.warmup, max_grad_norm=max_grad_norm,
+                           decoupled_weight_decay=decoupled_weight_decay, skip_nonfinite=skip_nonfinite, workspace=ws,
+                           ctl=ctl)
+        if average._table is not None:
+            ops.wavg_buffers(average._table, average.state)
+        self._kernel_written.clear()
+        ops.packs.invalidate()
 
 
 class ArenaAdam(torch.optim.Optimizer):
@@ -290,17 +320,25 @@ class ArenaAdam(torch.optim.Optimizer):
     float.  Moments, workspace and control block are allocated here, and step() issues nothing but the vmtl launches, so
     it can be captured into a hipGraph on its own.  ops.packs.invalidate() stays host-side bookkeeping that a replay
     does not repeat: whoever REPLAYS a captured step() must call ops.packs.invalidate() after it - or use GraphedStep,
-    whose graph re-packs the operands every step."""
+    whose graph re-packs the operands every step.
+
+    average: an ArenaAverage over the same arena (opt-in; a plain attribute like max_grad_norm, not optimizer state).
+    step() then takes the extended path and its update launch also folds the new parameters into the average
+    (ops.adam_step_wavg), honouring skip_nonfinite: the caller calls no average.update().  Without it step() issues the
+    launches it always issued."""
 
     def __init__(self, arena: "FlatArena", lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, *,
-                 decoupled_weight_decay=False, max_grad_norm=None, skip_nonfinite=False, capturable=False):
+                 decoupled_weight_decay=False, max_grad_norm=None, skip_nonfinite=False, capturable=False, average=None):
         if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
             raise ValueError(f"ArenaAdam: max_grad_norm must be >= 0 or None, got {max_grad_norm}")
         if isinstance(lr, torch.Tensor):
             if not capturable:
                 raise ValueError("ArenaAdam: a tensor lr needs capturable=True (as torch.optim.Adam has it)")
             lr = float(lr)
+        if average is not None and (not isinstance(average, ArenaAverage) or average.arena is not arena):
+            raise ValueError("ArenaAdam: average must be an ArenaAverage over the same arena")
         self.arena = arena
+        self.average = average
         self.max_grad_norm = max_grad_norm
         self.skip_nonfinite = bool(skip_nonfinite)
         self.capturable = bool(capturable)
@@ -328,9 +366,10 @@ class ArenaAdam(torch.optim.Optimizer):
     def step(self, closure=None):
         loss = closure() if closure is not None else None
         g = self.param_groups[0]
+        kw = {} if self.average is None else {"average": self.average}  # absent by default: the call it always made
         self.arena.adam_step(lr=g["lr"], betas=tuple(g["betas"]), eps=g["eps"], weight_decay=g["weight_decay"],
                              max_grad_norm=self.max_grad_norm, skip_nonfinite=self.skip_nonfinite,
-                             decoupled_weight_decay=bool(g["decoupled_weight_decay"]))
+                             decoupled_weight_decay=bool(g["decoupled_weight_decay"]), **kw)
         return loss
 
     def zero_grad(self, set_to_none: bool = False):
@@ -397,6 +436,199 @@ class ArenaAdamW(ArenaAdam):
 
     def __init__(self, arena: "FlatArena", lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, **kw):
         super().__init__(arena, lr, betas, eps, weight_decay, decoupled_weight_decay=True, **kw)
+
+
+class ArenaAverage:
+    """An averaged copy of the arena's parameters, kept on the device as ONE flat buffer next to `flat_param`, and
+    evaluation under it.  mode "ema": e += (1 - decay) * (p - e) per update (timm's ModelEmaV2, torch's
+    AveragedModel(multi_avg_fn=get_ema_multi_avg_fn(decay))); warmup=True uses min(decay, (1 + n) / (10 + n)) with n the
+    updates so far (timm's warm-up rule).  mode "swa": the equal average e += (p - e) / (n + 1) (AveragedModel's
+    default).  The first update is an exact copy, as in torch; the average starts as a copy of the parameters, so it is
+    valid before the first update and after a run whose first steps were all skipped.
+
+    update(optimizer=None): control launch + one streaming pass (+ one launch for the buffers), no host sync and no
+    allocation, so it can be captured on its own or after a capturable ArenaAdam.step().  With the ArenaAdam passed, an
+    update after a step that skip_nonfinite skipped is skipped too (counter and average keep their bits).
+    ArenaAdam(arena, ..., average=avg) folds the update into the optimizer's own pass instead: call no update() then.
+
+    use_buffers=False (torch's default): the averaged model uses the live model's buffers (BatchNorm running
+    statistics); nothing is stored or exchanged for them.  use_buffers=True: the floating-point buffers of arena.model are
+    averaged with the same weight by one launch over a descriptor table and exchanged by applied(); integer buffers
+    (num_batches_tracked) stay the live model's.
+
+    applied(): a context manager under which the model computes with the averaged weights: `flat_param` and the average
+    (and the averaged buffers) are exchanged in place by ops.swap_ on entry and again on exit.  No address changes, so
+    parameter views, .grad bindings, BatchNorm-table signatures and captured graphs (GraphedEval) stay valid; the packed
+    operands are invalidated both ways.  It refuses to nest, and update() / FlatArena.adam_step() raise inside it.
+    swap() is the bare exchange.  MTLModule.weight_average = avg makes validation_step, test_step, predict_step and
+    GraphedEval run inside applied().
+
+    n_averaged: a 0-dim int64 device tensor, a view of the state block (ops.wavg_state); reading it is the caller's
+    choice of when to sync.
+
+    Checkpoints: state_dict() / load_state_dict() use the wire format of
+    torch.optim.swa_utils.AveragedModel(arena.model).state_dict(): "n_averaged" plus "module.<key>" for every key of
+    arena.model.state_dict(), in the torch layout, so a checkpoint moves between this object and torch's in both
+    directions.  Entries this object does not average (buffers without use_buffers, integer buffers, parameters
+    outside the arena) carry the live model's values on the way out - what AveragedModel holds for them - and are checked
+    for shape but not stored on the way in.  The arena's extra_params (a TaskBalancer's log-variances) travel as
+    "arena_extra.<i>", i counting them in arena order; an arena without extra parameters emits none, and torch's
+    AveragedModel does not know them (drop them before handing the dict to it).  Anything that does not match raises.
+    averaged_state_dict(module) is module.state_dict() with the averaged values in place of the live ones: hand it to
+    save_ckpt to write the model_{epoch}.pt of the averaged model.
+
+    Data-parallel runs: parameters are replicated and every rank applies the same update to the same values, so every
+    rank holds the same average without a collective (averaged buffers follow each rank's own BatchNorm statistics, as
+    the live ones do; FlatArena.broadcast_buffers aligns the live ones only).  This has NOT run on more than one GPU."""
+
+    EXTRA_KEY = "arena_extra."
+
+    def __init__(self, arena: "FlatArena", decay=0.999, mode="ema", warmup=False, use_buffers=False):
+        if not isinstance(arena, FlatArena):
+            raise ValueError(f"ArenaAverage: arena must be a FlatArena, got {type(arena).__name__}")
+        if mode not in ops.WAVG_MODES:
+            raise ValueError(f"ArenaAverage: mode must be one of {sorted(ops.WAVG_MODES)}, got {mode!r}")
+        if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 <= float(decay) <= 1.0:
+            raise ValueError(f"ArenaAverage: decay must be a float in [0, 1], got {decay!r}")
+        if warmup and mode != "ema":
+            raise ValueError("ArenaAverage: warmup is the EMA decay warm-up; it does not combine with mode='swa'")
+        self.arena = arena
+        self.decay, self.mode, self.warmup, self.use_buffers = float(decay), mode, bool(warmup), bool(use_buffers)
+        self.flat_avg = arena.flat_param.detach().clone()
+        self.state = ops.wavg_state(arena.flat_param)
+        self._n_model = sum(1 for p in arena.model.parameters() if p.requires_grad)  # arena.params[_n_model:]: extras
+        self._buffers, self._buf_avg, self._table = [], [], None
+        if self.use_buffers:
+            self._buffers = [b for b in arena.model.buffers() if b.is_floating_point()]
+            if any(b.dtype != torch.float32 or not b.is_contiguous() for b in self._buffers):
+                raise ValueError("ArenaAverage: use_buffers=True takes contiguous float32 buffers")
+            flat = torch.cat([b.detach().reshape(-1) for b in self._buffers]) if self._buffers else None
+            off = 0
+            for b in self._buffers:
+                self._buf_avg.append(flat[off:off + b.numel()].view(b.shape))
+                off += b.numel()
+            if self._buffers and arena.flat_param.is_cuda:
+                self._table = ops.wavg_buffer_table([(b.view(-1), a.view(-1)) for b, a in zip(self._buffers, self._buf_avg)])
+
+    @property
+    def n_averaged(self) -> torch.Tensor:
+        return ops.wavg_n_averaged(self.state)
+
+    @property
+    def is_applied(self) -> bool:
+        return self.arena._applied_average is self
+
+    def _not_applied(self, what):
+        if self.arena._applied_average is not None:
+            raise RuntimeError(f"ArenaAverage.{what}: the averaged weights are applied (inside applied()): flat_param "
+                               "holds the average, not the live parameters")
+
+    # ---- the update
+    @torch.no_grad()
+    def update(self, optimizer=None) -> None:
+        self._not_applied("update")
+        ctl = None
+        if optimizer is not None:
+            if getattr(optimizer, "arena", None) is not self.arena:
+                raise ValueError("ArenaAverage.update: optimizer must be the ArenaAdam of the same arena")
+            if getattr(optimizer, "average", None) is self:
+                raise ValueError("ArenaAverage.update: this optimizer already averages in its step() (average=): "
+                                 "calling update() as well would average every step twice")
+            o = self.arena._optim  # None: no extended step has run, so none was skipped
+            ctl = None if o is None else o[1]
+        ops.wavg_control(self.state, self.mode, self.decay, self.warmup, ctl=ctl)
+        ops.wavg_update(self.flat_avg, self.arena.flat_param, self.state)
+        if self._table is not None:
+            ops.wavg_buffers(self._table, self.state)
+        elif self._buffers:
+            ops._flat(self._buffers[0], "buffer")  # a CPU model: the no-CPU-fallback error
+
+    # ---- evaluation under the average
+    @torch.no_grad()
+    def swap(self) -> None:
+        """Exchange flat_param with the average (and the averaged buffers with the live ones), bit for bit, in place."""
+        ops.side.join()
+        ops.packs.join()  # a side-stream packing pass still reading the parameters is ordered before the exchange
+        ops.swap_(self.arena.flat_param, self.flat_avg)
+        if self._table is not None:
+            ops.swap_table_(self._table)
+        elif self._buffers:
+            ops._flat(self._buffers[0], "buffer")
+        ops.packs.invalidate()  # parameters changed through raw pointers: packed operands are stale
+
+    @contextlib.contextmanager
+    def applied(self):
+        if self.arena._applied_average is not None:
+            raise RuntimeError("ArenaAverage.applied: averaged weights are already applied to this arena (no nesting)")
+        self.swap()
+        self.arena._applied_average = self
+        try:
+            yield self
+        finally:
+            self.arena._applied_average = None
+            self.swap()
+
+    # ---- checkpoints
+    def _slices(self):
+        """id(parameter) -> its slice of the average, shaped like the parameter."""
+        a = self.arena
+        return {id(p): self.flat_avg[off:off + p.numel()].view(p.shape) for p, off in zip(a.params, a.offsets)}
+
+    def _averaged_of(self):
+        """id(tensor) -> averaged tensor, for every parameter of the arena and every averaged buffer."""
+        m = self._slices()
+        m.update({id(b): avg for b, avg in zip(self._buffers, self._buf_avg)})
+        return m
+
+    def _extras(self):
+        a = self.arena
+        return list(zip(a.params[self._n_model:], a.offsets[self._n_model:]))
+
+    @torch.no_grad()
+    def state_dict(self) -> dict:
+        self._not_applied("state_dict")
+        avg = self._averaged_of()
+        out = {"n_averaged": self.n_averaged.detach().clone()}
+        for k, t in self.arena.model.state_dict(keep_vars=True).items():
+            out["module." + k] = avg.get(id(t), t).detach().clone()
+        for i, (p, off) in enumerate(self._extras()):
+            out[f"{self.EXTRA_KEY}{i}"] = self.flat_avg[off:off + p.numel()].view(p.shape).clone()
+        return out
+
+    @torch.no_grad()
+    def load_state_dict(self, sd) -> None:
+        self._not_applied("load_state_dict")
+        if not isinstance(sd, dict) or "n_averaged" not in sd:
+            raise ValueError("ArenaAverage.load_state_dict: expected an AveragedModel state_dict ('n_averaged' + 'module.*')")
+        live = self.arena.model.state_dict(keep_vars=True)
+        expect = {"n_averaged": None}
+        expect.update({"module." + k: t for k, t in live.items()})
+        expect.update({f"{self.EXTRA_KEY}{i}": p for i, (p, _) in enumerate(self._extras())})
+        missing, extra = sorted(set(expect) - set(sd)), sorted(set(sd) - set(expect))
+        if missing or extra:
+            raise ValueError(f"ArenaAverage.load_state_dict: missing keys {missing}, unexpected keys {extra}")
+        n = torch.as_tensor(sd["n_averaged"])
+        if n.numel() != 1 or n.is_floating_point() or n.is_complex() or int(n) < 0:
+            raise ValueError(f"ArenaAverage.load_state_dict: n_averaged must be one non-negative integer, got {n!r}")
+        for k, t in expect.items():
+            if t is not None and tuple(sd[k].shape) != tuple(t.shape):
+                raise ValueError(f"ArenaAverage.load_state_dict: {k} has shape {tuple(sd[k].shape)}, the model "
+                                 f"{tuple(t.shape)}")
+        avg = self._averaged_of()
+        for k, t in expect.items():  # everything was checked: nothing is written before the whole dict matched
+            dst = None if t is None else avg.get(id(t))
+            if dst is not None:
+                dst.copy_(sd[k])
+        self.n_averaged.fill_(int(n))
+
+    @torch.no_grad()
+    def averaged_state_dict(self, module: torch.nn.Module) -> dict:
+        """module.state_dict() (an MTLModule around arena.model, or the model itself) with the averaged values in place
+        of the live ones: same keys, same order, fresh tensors."""
+        self._not_applied("averaged_state_dict")
+        avg = self._averaged_of()
+        return type(module.state_dict())((k, avg.get(id(t), t).detach().clone())
+                                         for k, t in module.state_dict(keep_vars=True).items())
 
 
 class _SyncGrads(torch.autograd.Function):

@@ -213,7 +213,15 @@ class GraphedEval(_StaticBatch):
     warm-up / rehearsal steps, step_outputs is left as it was and no gradient is written.  Like GraphedStep, the step
     keeps the convolution precision, module.device_transform and batch shapes in force at construction; a call raises
     ValueError on another batch shape or when module.training (or a BatchNorm's mode) differs from the capture.
-    bn_table=False keeps the per-layer eval-statistics launches (A/B measurement)."""
+    bn_table=False keeps the per-layer eval-statistics launches (A/B measurement).
+
+    `module.weight_average` (a dp.ArenaAverage): a call exchanges the averaged weights in before the replay and out after
+    it, as the eager evaluation steps do (ArenaAverage.applied).  The exchanges are ordinary launches outside the graph and
+    move no address, so the graph is the one captured without an average - also one captured before the average existed.
+    Construction never applies the average; it records whether the attribute was set, and a call raises ValueError when
+    that has changed since.  The record is the attribute `weight_average` of this object: a caller who sets
+    module.weight_average later and wants an existing capture to follow it assigns the same object here as well -
+    nothing is recaptured."""
 
     STAGES = ("val", "test", "predict")
 
@@ -228,6 +236,7 @@ class GraphedEval(_StaticBatch):
         self._init_static(module, example_batch)
         # an inference.PredictAugment, recorded like the transform: its views, merge and finish launches join the graph
         self.predict_augment = getattr(module, "predict_augment", None) if stage == "predict" else None
+        self.weight_average = getattr(module, "weight_average", None)
         bns = [m for m in module.model.modules() if isinstance(m, torch.nn.BatchNorm2d)]
         self.training = module.training
         self._modes = tuple(m.training for m in bns)
@@ -279,7 +288,7 @@ class GraphedEval(_StaticBatch):
                 self._table = table
             batch = self._model_batch()
             if self.stage == "predict":
-                return self.module.predict_step(batch)
+                return self.module._predict_step(batch)  # on the weights as they stand: see __call__
             return self.module.shared_step(batch, self.stage)
 
     def __call__(self, batch: dict):
@@ -290,8 +299,16 @@ class GraphedEval(_StaticBatch):
         if self.stage == "predict" and getattr(self.module, "predict_augment", None) is not self.predict_augment:
             raise ValueError(f"GraphedEval: captured with module.predict_augment={self.predict_augment!r}, called with "
                              f"{getattr(self.module, 'predict_augment', None)!r}; capture one GraphedEval per predict_augment")
+        average = getattr(self.module, "weight_average", None)
+        if average is not self.weight_average:
+            raise ValueError(f"GraphedEval: built with module.weight_average={self.weight_average!r}, called with "
+                             f"{average!r}; build one GraphedEval per weight_average")
         self._fill(batch)
-        self.graph.replay()
+        if average is None:
+            self.graph.replay()
+        else:
+            with average.applied():
+                self.graph.replay()
         self.replays += 1
         stats = None
         if self._stats is not None:

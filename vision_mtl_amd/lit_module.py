@@ -135,6 +135,10 @@ class MTLModule(nn.Module):
         # an inference.PredictAugment: predict_step merges flipped / rescaled views and returns predictions at its output
         # size (training, validation and test never look at it; GraphedEval(stage="predict") records it at construction)
         self.predict_augment = None
+        # a dp.ArenaAverage (EMA / SWA of the arena's parameters): validation_step, test_step and predict_step run with the
+        # averaged weights exchanged in (ArenaAverage.applied), training_step never does; GraphedEval records at
+        # construction whether it was set.  An attribute like train_augment: hparams and state_dict() keys do not change
+        self.weight_average = None
         self._mining = False  # True inside a training step's calc_losses
 
     def forward(self, x: torch.Tensor) -> dict:
@@ -210,12 +214,25 @@ class MTLModule(nn.Module):
         return self.shared_step(batch=batch, stage="train")
 
     def validation_step(self, batch: dict, batch_idx: Any = 0):
-        return self.shared_step(batch=batch, stage="val")
+        if self.weight_average is None:  # the default step makes the call it always made
+            return self.shared_step(batch=batch, stage="val")
+        with self.weight_average.applied():
+            return self.shared_step(batch=batch, stage="val")
 
     def test_step(self, batch: dict, batch_idx: Any = 0):
-        return self.shared_step(batch=batch, stage="test")
+        if self.weight_average is None:
+            return self.shared_step(batch=batch, stage="test")
+        with self.weight_average.applied():
+            return self.shared_step(batch=batch, stage="test")
 
     def predict_step(self, batch: dict, batch_idx: int = 0, dataloader_idx: int = 0):
+        if self.weight_average is None:
+            return self._predict_step(batch)
+        with self.weight_average.applied():
+            return self._predict_step(batch)
+
+    def _predict_step(self, batch: dict) -> dict:
+        """predict_step on the weights as they stand (GraphedEval captures this: the exchange is not part of its graph)."""
         if self.predict_augment is not None:
             return self._predict_augmented(batch)
         out = self.postprocess_raw_out(self(batch["img"]))

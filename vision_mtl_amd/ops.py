@@ -3677,3 +3677,107 @@ def adam_step_ex(p, g, m, v, step_t, lr, betas=(0.9, 0.999), eps=1e-8, weight_de
     _k("vmtl_adam_step_ex", p=p, g=g, m=m, v=v, ctl=ctl, lr=lr, lr_ptr=lr_ptr, eps=eps, weight_decay=weight_decay,
        decoupled=int(bool(decoupled_weight_decay)), grad_scale=grad_scale, n=n)
     return ctl
+
+
+# ----------------------------------------------------------------------------- averaged weights (csrc/weight_avg.hip)
+# EMA / SWA of flat fp32 buffers.  Plain launches like the optimizer's: under no_grad, in place, no host sync.
+WAVG_STATE_FLOATS = 8  # state block (include/vmtl.h): [0..1] n_averaged (int64) [2] weight [3] copy [4] skip [5] skipped count
+WAVG_N, WAVG_WEIGHT, WAVG_COPY, WAVG_SKIP, WAVG_SKIPPED = 0, 2, 3, 4, 5
+WAVG_MODES = {"ema": 0, "swa": 1}
+
+
+def wavg_state(like):
+    """A zeroed state block (n_averaged = 0: the first update copies)."""
+    return _empty((WAVG_STATE_FLOATS,), like).zero_()
+
+
+def wavg_n_averaged(state):
+    """n_averaged as a 0-dim int64 view of the state block (what torch's AveragedModel keeps as a long)."""
+    return state.view(torch.int64)[0]
+
+
+def _wavg_mode(mode, decay):
+    if mode not in WAVG_MODES:
+        raise ValueError(f"weight averaging: mode must be one of {sorted(WAVG_MODES)}, got {mode!r}")
+    d = float(decay)
+    if mode == "ema" and not 0.0 <= d <= 1.0:
+        raise ValueError(f"weight averaging: decay must lie in [0, 1], got {decay!r}")
+    return WAVG_MODES[mode], _hi_lo(d)
+
+
+def wavg_control(state, mode="ema", decay=0.999, warmup=False, ctl=None):
+    """The weight of the next update into `state`, n_averaged += 1 ON THE DEVICE; with an optimizer control block `ctl`
+    whose step was skipped, the update is skipped instead.  One launch of one workgroup."""
+    code, (d, d_lo) = _wavg_mode(mode, decay)
+    _k("vmtl_wavg_control", state=_flat(state, "state"), ctl=None if ctl is None else _flat(ctl, "ctl"), mode=code,
+       decay=d, decay_lo=d_lo, warmup=int(bool(warmup)))
+
+
+def wavg_update(e, p, state):
+    """e += w * (p - e) (a copy on the first update, nothing on a skipped one) with w and the flags read from `state`;
+    p is only read."""
+    e, p = _flat(e, "e"), _flat(p, "p")
+    if e.numel() != p.numel():
+        raise ValueError("wavg_update: e and p must hold the same number of elements")
+    _k("vmtl_wavg_update", e=e, p=p, state=_flat(state, "state"), n=e.numel())
+
+
+def adam_step_wavg(p, g, m, v, e, state, step_t, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0, *,
+                   mode="ema", decay=0.999, warmup=False, max_grad_norm=None, decoupled_weight_decay=False,
+                   skip_nonfinite=False, workspace=None, ctl=None):
+    """adam_step_ex with the averaged weights `e` updated in the same pass over the new p: the bits of adam_step_ex
+    followed by wavg_control(ctl=ctl) + wavg_update, one launch and one read of p fewer.
+    Launches: [sum of squares] + optimizer control + averaging control + update.  Returns the control block."""
+    p, g, m, v, e = _flat(p, "p"), _flat(g, "g"), _flat(m, "m"), _flat(v, "v"), _flat(e, "e")
+    n = p.numel()
+    if not (g.numel() == m.numel() == v.numel() == e.numel() == n):
+        raise ValueError("adam_step_wavg: p, g, m, v and e must hold the same number of elements")
+    max_norm = _max_norm(max_grad_norm)
+    need_norm = max_norm > 0.0 or bool(skip_nonfinite)
+    ctl = optim_control_block(p) if ctl is None else ctl
+    if need_norm:
+        workspace = grad_sumsq(g, workspace, grad_scale)
+    optim_control(ctl, step_t, n if need_norm else 0, workspace, max_norm, skip_nonfinite, betas)
+    wavg_control(state, mode, decay, warmup, ctl=ctl)
+    lr_ptr = None
+    if isinstance(lr, torch.Tensor):
+        lr_ptr, lr = _flat(lr, "lr"), 0.0
+    _k("vmtl_adam_step_wavg", p=p, g=g, m=m, v=v, e=e, ctl=ctl, state=state, lr=lr, lr_ptr=lr_ptr, eps=eps,
+       weight_decay=weight_decay, decoupled=int(bool(decoupled_weight_decay)), grad_scale=grad_scale, n=n)
+    return ctl
+
+
+def wavg_buffer_table(pairs):
+    """Descriptor table of (live buffer, its average) pairs for wavg_buffers / swap_table_: built and uploaded once,
+    never inside a graph capture (the idiom of _EvalBNTable).  The table holds addresses: the tensors must stay where
+    they are, and the returned dict keeps them alive."""
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("wavg_buffer_table: the table must be built before the capture")
+    pairs = [(_flat(s, "buffer"), _flat(a, "buffer average")) for s, a in pairs]
+    if not pairs:
+        raise ValueError("wavg_buffer_table: no buffers")
+    for s, a in pairs:
+        if s.numel() != a.numel() or s.numel() == 0:
+            raise ValueError("wavg_buffer_table: a buffer and its average must hold the same, non-zero number of elements")
+    size = lib().raw("vmtl_wavg_desc_bytes")()
+    blob = b"".join(struct.pack("<QQq", s.data_ptr(), a.data_ptr(), s.numel()).ljust(size, b"\0") for s, a in pairs)
+    return {"descs": torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(pairs[0][0].device), "n": len(pairs),
+            "max_n": max(s.numel() for s, _ in pairs), "pairs": pairs}
+
+
+def wavg_buffers(table, state):
+    """wavg_update over every (buffer, average) pair of a wavg_buffer_table in ONE launch, same weight and flags."""
+    _k("vmtl_wavg_buffers", descs=table["descs"], n=table["n"], max_n=table["max_n"], state=_flat(state, "state"))
+
+
+def swap_(a, b):
+    """Exchange two flat fp32 buffers in place, bit for bit (NaN payloads included); overlapping buffers are refused."""
+    a, b = _flat(a, "a"), _flat(b, "b")
+    if a.numel() != b.numel():
+        raise ValueError("swap_: a and b must hold the same number of elements")
+    _k("vmtl_swap_", a=a, b=b, n=a.numel())
+
+
+def swap_table_(table):
+    """swap_ over every (buffer, average) pair of a wavg_buffer_table in ONE launch."""
+    _k("vmtl_swap_table_", descs=table["descs"], n=table["n"], max_n=table["max_n"])

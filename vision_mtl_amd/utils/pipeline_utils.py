@@ -42,7 +42,11 @@ def build_model(args: argparse.Namespace, data_cfg: DataConfig) -> t.Union[Basic
 
 
 def init_model(args: argparse.Namespace, data_cfg: DataConfig) -> MTLModule:
-    """reference utils/pipeline_utils.py:22-30."""
+    """reference utils/pipeline_utils.py:22-30.
+
+    Averaged weights (dp.ArenaAverage) are not wired here: they live next to a dp.FlatArena,
+    which the caller builds after the model is on its device, so args.weight_average / weight_average_decay /
+    weight_average_warmup are not read - set module.weight_average once the arena exists."""
     model = build_model(args, data_cfg)
     # opt-in (INTEGRATION.md): an ignored label / per-class weights (a sequence of num_classes floats) for the segmentation loss
     module = MTLModule(model=model, num_classes=data_cfg.num_classes, lr=getattr(args, "lr", None),
