@@ -195,10 +195,17 @@ int vmtl_conv2d_wgrad_p(const float* x, const float* dy, float* slabs, int split
 /* Weight gradient of a NARROW 3x3 / stride 1 / pad 1 conv on a strip-walking halo kernel (csrc/conv_wgrad_small.hip): x is read
  * from memory once instead of once per tap.  Replaces the same conv2d backward-weight call sites of the reference as
  * vmtl_conv2d_wgrad (reference models: smp DecoderBlock / SegmentationHead convs, utils/model_utils.py:61-80 DoubleConv) where
- * supported(Cs, ldy, W) says so: Cs, ldy <= 36 (multiples of 4), W a multiple of 32.  slabs: [vmtl_conv3x3_wgrad_small_slabs(B, H, W)]
- * [Nw][9*Cs], summed by vmtl_unpack_weights(..., nslabs) exactly like the slabs of vmtl_conv2d_wgrad. */
+ * supported(Cs, ldy, W) says so: Cs, ldy <= 68 (multiples of 4; which of those widths are routed here is decided there, class
+ * by class, by measurement), W a multiple of 32.  slabs: [vmtl_conv3x3_wgrad_small_slabs_for(B, H, W, Cs, ldy, Nw)][Nw][9*Cs],
+ * summed by vmtl_unpack_weights(..., nslabs) exactly like the slabs of vmtl_conv2d_wgrad.  _slabs(B, H, W) is _slabs_for of a
+ * layer with Cs, ldy <= 36 (wider layers run fewer, longer strip segments).  _supported says what the (fp32) kernel can run;
+ * _supported_p(..., pixels, precision) is the routing question of a training step whose launch of pixels = B*H*W would otherwise
+ * run vmtl_conv2d_wgrad[_p] at `precision` (VMTL_PREC_*): the widths added last (33-36 on both sides, 40-68 on either) come here
+ * in fp32 and from 65,536 pixels only, where they were measured. */
 int vmtl_conv3x3_wgrad_small_supported(int Cs, int ldy, int W);
+int vmtl_conv3x3_wgrad_small_supported_p(int Cs, int ldy, int W, long long pixels, int precision);
 int vmtl_conv3x3_wgrad_small_slabs(int B, int H, int W);
+int vmtl_conv3x3_wgrad_small_slabs_for(int B, int H, int W, int Cs, int ldy, int Nw);
 int vmtl_conv3x3_wgrad_small(const float* x, const float* dy, float* slabs, int nslabs, int B, int H, int W, int Cs,
                              int ldy, int Nw, void* stream);
 

@@ -1,7 +1,10 @@
 """Micro-benchmark (GPU box) of the implicit-GEMM kernels on the `basic` decoder shapes at bs 32,
 called through the C ABI.  VMTL_FORCE_TILE=<id> / VMTL_FORCE_WG_SPLITS=<n> override the host heuristics.
 --precision fp32|bf16|both: operand precision of the covered kernels (VMTL_PREC_*); `both` times the two modes
-alternately on every shape in one process and ends with one JSON line of per-shape times and bf16 speed-ups."""
+alternately on every shape in one process and ends with one JSON line of per-shape times and bf16 speed-ups.
+--wgrad-routes: instead, the weight gradient of every selected 3x3 layer through the product route (ops._wgrad_into: kernel +
+slab sum) under each of the settings in --route-env ("NAME=VALUE[,NAME=VALUE];..." - default: the strip kernel's routing from
+before its tail rows / 80-float pixels against today's), --repeats alternating rounds; one JSON line per layer."""
 import argparse
 import json
 import sys
@@ -17,6 +20,10 @@ ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--only", default="")
 ap.add_argument("--stats", action="store_true", help="forward launches also write the BatchNorm partial rows (as in a training step)")
 ap.add_argument("--precision", choices=["fp32", "bf16", "both"], default="fp32")
+ap.add_argument("--wgrad-routes", action="store_true")
+ap.add_argument("--route-env", default="VMTL_WGRAD_SMALL_WIDE=0;VMTL_WGRAD_SMALL_WIDE=1")
+ap.add_argument("--repeats", type=int, default=3)
+ap.add_argument("--warm-rounds", type=int, default=2, help="--wgrad-routes: unrecorded rounds in front of each layer's recorded ones")
 args = ap.parse_args()
 PRECS = ["fp32", "bf16"] if args.precision == "both" else [args.precision]
 dev = torch.device("cuda:0")
@@ -44,7 +51,9 @@ LAYERS = [("blk0.c1", 32, 8, 16, 1072, 540, 3), ("blk0.c2", 32, 8, 16, 540, 540,
           ("mtan.s2", 16, 64, 64, 128, 128, 3), ("mtan.s3", 16, 32, 32, 256, 256, 3),
           # csnet's full-resolution decoder tail (bs 32, 128x256) and MTAN's first conv
           ("cs.32-16", 32, 128, 256, 32, 16, 3), ("cs.16-16", 32, 128, 256, 16, 16, 3), ("cs.16-19", 32, 128, 256, 16, 19, 3),
-          ("cs.16-1", 32, 128, 256, 16, 1, 3), ("cs.80-32", 32, 64, 128, 80, 32, 3), ("mtan.c0", 16, 256, 256, 3, 32, 3)]
+          ("cs.16-1", 32, 128, 256, 16, 1, 3), ("cs.80-32", 32, 64, 128, 80, 32, 3), ("mtan.c0", 16, 256, 256, 3, 32, 3),
+          # the skip half of blk3.c1 (its own weight-gradient launch) and MTAN's 64 -> 64 at 256x256
+          ("blk3.skip", 32, 64, 128, 16, 67, 3), ("mtan.64@256", 16, 256, 256, 64, 64, 3)]
 
 
 def call(name, prec, *a):
@@ -65,6 +74,48 @@ def timeit(fn):
     e1.synchronize()
     return e0.elapsed_time(e1) / args.reps
 
+
+def wgrad_routes():
+    """kernel + unpack of each layer's weight gradient per routing setting, alternating; us per call"""
+    from vision_mtl_amd import ops
+
+    settings = [dict(kv.split("=") for kv in s.split(",") if kv) for s in args.route_env.split(";")]
+    names = sorted({k for s in settings for k in s})
+    for name, B, H, W, Cin, Cout, K in LAYERS:
+        if K != 3 or (args.only and name not in args.only.split(",")):  # here --only is a comma-separated list of names
+            continue
+        Cs, ldy = c4(Cin), c4(Cout)
+        x = torch.randn(B, H, W, Cs, device=dev)
+        dy = torch.randn(B, H, W, ldy, device=dev)
+        dw = torch.empty(Cout, Cin, 3, 3, device=dev)
+        g = ops.ConvGeom.of(x.shape, ldy, 3, 3, 1, 1)
+        lay = ops.Layout.fwd(Cout, Cin, 9, Cs)
+        rec = ops._RECORD
+        times = [[] for _ in settings]
+        launches = [None] * len(settings)
+        for rnd in range(-args.warm_rounds, args.repeats):  # rounds < 0 are not recorded: the first ~100 ms of a process run slower
+            for i, s in enumerate(settings):
+                for n in names:
+                    os.environ.pop(n, None)
+                os.environ.update(s)
+                L.raw("vmtl_reload_env")()
+                ops._RECORD = []
+                ops._wgrad_into(x, dy, g, lay, dw, 1.0)
+                launches[i] = [(n, kw.get("nslabs", kw.get("splits"))) for n, kw, _, _ in ops._RECORD]
+                ops._RECORD = rec
+                t = round(timeit(lambda: ops._wgrad_into(x, dy, g, lay, dw, 1.0)) * 1e3, 1)
+                if rnd >= 0:
+                    times[i].append(t)
+        for n in names:
+            os.environ.pop(n, None)
+        L.raw("vmtl_reload_env")()
+        print(json.dumps({"layer": name, "B": B, "H": H, "W": W, "Cin": Cin, "Cout": Cout,
+                          "routes": [{"env": s, "launch": l, "us": t} for s, l, t in zip(settings, launches, times)]}), flush=True)
+
+
+if args.wgrad_routes:
+    wgrad_routes()
+    sys.exit(0)
 
 tots = {p: {"fwd": 0.0, "dgrad": 0.0, "wgrad": 0.0} for p in PRECS}
 flops = 0.0
@@ -104,7 +155,7 @@ for name, B, H, W, Cin, Cout, K in LAYERS:
                                     Cout, K, K, 1, K // 2, st))
         t_ws = None
         if prec == "fp32" and K == 3 and L.raw("vmtl_conv3x3_wgrad_small_supported")(Cs, ldy, W):  # the strip-walking halo kernel on the same layer
-            ns = L.raw("vmtl_conv3x3_wgrad_small_slabs")(B, H, W)
+            ns = L.raw("vmtl_conv3x3_wgrad_small_slabs_for")(B, H, W, Cs, ldy, Cout)
             slabs_s = torch.empty(ns, Cout, KK * Cs, device=dev)
             t_ws = timeit(lambda: L.call("vmtl_conv3x3_wgrad_small", x.data_ptr(), dy.data_ptr(), slabs_s.data_ptr(), ns, B, H, W, Cs,
                                          ldy, Cout, st))

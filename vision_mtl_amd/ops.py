@@ -664,9 +664,10 @@ def _wgrad(x, dy, g, *, Nw, flop, xflop=None, prec=0):
     kernel only (the narrow halo-tile kernel stays fp32)."""
     B, H, W, Cs, Ho, Wo, ldy, KH, KW, stride, pad = g
     if (KH == 3 and KW == 3 and stride == 1 and pad == 1 and B * H * W * max(Cs, ldy) * 4 < 1 << 32
-            and lib().raw("vmtl_conv3x3_wgrad_small_supported")(Cs, ldy, W)):
-        # narrow full-resolution layers: the strip-walking halo kernel reads x once instead of once per tap
-        ns = lib().raw("vmtl_conv3x3_wgrad_small_slabs")(B, H, W)
+            and lib().raw("vmtl_conv3x3_wgrad_small_supported_p")(Cs, ldy, W, B * H * W, prec)):
+        # narrow full-resolution layers: the strip-walking halo kernel reads x once instead of once per tap (fp32 in every
+        # mode; the query keeps a launch on the dense kernel where this one was not measured against it: bf16, small maps)
+        ns = lib().raw("vmtl_conv3x3_wgrad_small_slabs_for")(B, H, W, Cs, ldy, Nw)
         slabs = _empty((ns, Nw, 9 * Cs), x)
         _k("vmtl_conv3x3_wgrad_small", _flop=flop, _xflop=xflop, x=x, dy=dy, slabs=slabs, nslabs=ns, B=B, H=H, W=W, Cs=Cs, ldy=ldy,
            Nw=Nw)
