@@ -191,6 +191,16 @@ int vmtl_conv2d_wgrad(const float* x, const float* dy, float* slabs, int splits,
 int vmtl_conv2d_wgrad_p(const float* x, const float* dy, float* slabs, int splits, int B, int H, int W, int Cs,
                         int Ho, int Wo, int ldy, int Nw, int KH, int KW, int stride, int pad, int precision,
                         void* stream);
+/* Host-side routing queries (no launch).  _wgrad_route: what vmtl_conv2d_wgrad[_p] runs for this layer, as
+ * loader + 4 * peeled + 8 * PD + 64 * tile rows (loader 0 = general, 1 = scalar chunk of one output row, 2 = row group:
+ * 32 / Wo whole output rows per chunk; peeled = the branch-free prefetch loop; PD = chunks in flight), -1 = bad arguments.
+ * _pipe_depth: K chunks the implicit GEMM keeps in flight (1 or 2) for a launch of tile id `tile` with gather segments of
+ * Cs (and, up2 != 0, C2s) channels, nk K chunks per workgroup and a grid of `workgroups`.  _last_pipe_depth: what the most
+ * recent implicit-GEMM launch of the calling thread ran (0 before the first one): tests pin the launcher's own arithmetic. */
+int vmtl_conv2d_wgrad_route(int B, int H, int W, int Cs, int Ho, int Wo, int Nw, int KH, int KW, int stride, int pad,
+                            int precision);
+int vmtl_conv2d_pipe_depth(int tile, int Cs, int C2s, int nk, long long workgroups, int up2, int precision);
+int vmtl_conv2d_last_pipe_depth(void);
 
 /* Weight gradient of a NARROW 3x3 / stride 1 / pad 1 conv on a strip-walking halo kernel (csrc/conv_wgrad_small.hip): x is read
  * from memory once instead of once per tap.  Replaces the same conv2d backward-weight call sites of the reference as

@@ -4,7 +4,10 @@ called through the C ABI.  VMTL_FORCE_TILE=<id> / VMTL_FORCE_WG_SPLITS=<n> overr
 alternately on every shape in one process and ends with one JSON line of per-shape times and bf16 speed-ups.
 --wgrad-routes: instead, the weight gradient of every selected 3x3 layer through the product route (ops._wgrad_into: kernel +
 slab sum) under each of the settings in --route-env ("NAME=VALUE[,NAME=VALUE];..." - default: the strip kernel's routing from
-before its tail rows / 80-float pixels against today's), --repeats alternating rounds; one JSON line per layer."""
+before its tail rows / 80-float pixels against today's), --repeats alternating rounds; one JSON line per layer.
+--pipe-routes: instead, the launches of decoder blocks 0-2 of the headline (forward, UP2 forward, data gradient with the fused
+BatchNorm backward, and every weight-gradient launch: conv2, skip part, low-resolution 4x4 / stride 2 part) and MTAN's 128-row
+weight gradients, each through the C ABI under each setting of --route-env, alternating; one JSON line per launch."""
 import argparse
 import json
 import sys
@@ -21,6 +24,8 @@ ap.add_argument("--only", default="")
 ap.add_argument("--stats", action="store_true", help="forward launches also write the BatchNorm partial rows (as in a training step)")
 ap.add_argument("--precision", choices=["fp32", "bf16", "both"], default="fp32")
 ap.add_argument("--wgrad-routes", action="store_true")
+ap.add_argument("--pipe-routes", action="store_true")
+ap.add_argument("--max-slabs", type=int, default=0, help="--pipe-routes: slabs allocated per weight gradient when a setting forces more slices")
 ap.add_argument("--route-env", default="VMTL_WGRAD_SMALL_WIDE=0;VMTL_WGRAD_SMALL_WIDE=1")
 ap.add_argument("--repeats", type=int, default=3)
 ap.add_argument("--warm-rounds", type=int, default=2, help="--wgrad-routes: unrecorded rounds in front of each layer's recorded ones")
@@ -112,6 +117,91 @@ def wgrad_routes():
         print(json.dumps({"layer": name, "B": B, "H": H, "W": W, "Cin": Cin, "Cout": Cout,
                           "routes": [{"env": s, "launch": l, "us": t} for s, l, t in zip(settings, launches, times)]}), flush=True)
 
+
+def pipe_routes():
+    """us per call of each launch under each setting of --route-env, alternating rounds (rounds < 0 unrecorded)"""
+    settings = [dict(kv.split("=") for kv in s.split(",") if kv) for s in args.route_env.split(";")]
+    names = sorted({k for s in settings for k in s})
+    KS = L.raw("vmtl_conv2d_ksplit")
+    UKS = L.raw("vmtl_conv2d_up2_ksplit")
+
+    def fwd(B, H, W, Cin, Cout):
+        Cs, ldy = c4(Cin), c4(Cout)
+        x, wp = torch.randn(B, H, W, Cs, device=dev), torch.randn(Cout, 9 * Cs, device=dev) * 0.01
+        y = torch.empty(B, H, W, ldy, device=dev)
+        ws = torch.empty(max(KS(B, H, W, ldy, 9 * Cs), 1), B, H, W, ldy, device=dev)
+        keep = (x, wp, y, ws)
+        return keep, lambda: L.call("vmtl_conv2d_fwd_ws", x.data_ptr(), wp.data_ptr(), None, y.data_ptr(), ws.data_ptr(), B, H, W, Cs,
+                                    H, W, ldy, Cout, Cout, 3, 3, 1, 1, st)
+
+    def bnbwd(B, H, W, Cin, Cout):  # data gradient of a Cin -> Cout conv: contracts dy (Cout) into dx (Cin)
+        Cs, ldy = c4(Cin), c4(Cout)
+        dy, wd = torch.randn(B, H, W, ldy, device=dev), torch.randn(Cin, 9 * ldy, device=dev) * 0.01
+        dx, ezx = torch.empty(B, H, W, Cs, device=dev), torch.randn(B, H, W, Cs, device=dev)
+        ezs = torch.empty(L.raw("vmtl_conv2d_stats_rows")(B, H, W, Cs) + 1, 2, Cs, device=dev)
+        vec = [torch.rand(Cs, device=dev) + 0.5 for _ in range(4)]
+        keep = (dy, wd, dx, ezx, ezs, vec)
+        return keep, lambda: L.call("vmtl_conv2d_bnbwd", dy.data_ptr(), wd.data_ptr(), dx.data_ptr(), ezs.data_ptr(), ezx.data_ptr(),
+                                    vec[0].data_ptr(), vec[1].data_ptr(), vec[2].data_ptr(), vec[3].data_ptr(), 1, B, H, W, ldy, H, W,
+                                    Cs, Cin, Cin, 3, 3, 1, 1, st)
+
+    def up2(B, H2, W2, C0, C1, Cout):
+        C0s, C1s, ldy = c4(C0), c4(C1), c4(Cout)
+        xl, sk = torch.randn(B, H2, W2, C0s, device=dev), torch.randn(B, 2 * H2, 2 * W2, C1s, device=dev)
+        wp = torch.randn(4, Cout, 4 * C0s + 9 * C1s, device=dev) * 0.01
+        y = torch.empty(B, 2 * H2, 2 * W2, ldy, device=dev)
+        ws = torch.empty(max(UKS(B, H2, W2, ldy, 4 * C0s + 9 * C1s), 1), B, 2 * H2, 2 * W2, ldy, device=dev)
+        keep = (xl, sk, wp, y, ws)
+        return keep, lambda: L.call("vmtl_conv2d_up2_fwd_ws", xl.data_ptr(), sk.data_ptr(), wp.data_ptr(), y.data_ptr(), ws.data_ptr(),
+                                    B, H2, W2, C0s, C1s, ldy, Cout, st)
+
+    def wgrad(B, H, W, Cin, Ho, Wo, Nw, KH, stride, pad):
+        Cs, ldy = c4(Cin), c4(Nw)
+        x, dy = torch.randn(B, H, W, Cs, device=dev), torch.randn(B, Ho, Wo, ldy, device=dev)
+        # the slice count is asked again at every call (memoised): a setting may force it (VMTL_FORCE_WG_SPLITS, a slice-length sweep)
+        splits = lambda: L.raw("vmtl_conv2d_wgrad_splits")(B * Ho * Wo, Nw, KH * KH * Cs)
+        slabs = torch.empty(max(splits(), args.max_slabs), Nw, KH * KH * Cs, device=dev)
+        keep = (x, dy, slabs)
+        return keep, lambda: L.call("vmtl_conv2d_wgrad", x.data_ptr(), dy.data_ptr(), slabs.data_ptr(), splits(), B, H, W, Cs, Ho, Wo, ldy,
+                                    Nw, KH, KH, stride, pad, st)
+
+    # basic at bs 32, 128x256: block b's convs run on (8, 16) << b maps; conv1 = UP2 of (C0 low-res, C1 skip) channels
+    BLK = [(8, 16, 960, 112, 540), (16, 32, 540, 40, 270), (32, 64, 270, 24, 135)]
+    ops = []
+    for b, (H, W, C0, C1, C) in enumerate(BLK):
+        ops += [(f"blk{b}.c2 fwd", fwd, (32, H, W, C, C)), (f"blk{b}.c2 dgrad+bnbwd", bnbwd, (32, H, W, C, C)),
+                (f"blk{b}.c1 up2 fwd", up2, (32, H // 2, W // 2, C0, C1, C)),
+                (f"blk{b}.c2 wgrad", wgrad, (32, H, W, C, H, W, C, 3, 1, 1)),
+                (f"blk{b}.c1 wgrad skip", wgrad, (32, H, W, C1, H, W, C, 3, 1, 1)),
+                (f"blk{b}.c1 wgrad low 4x4s2", wgrad, (32, H, W, C, H // 2, W // 2, C0, 4, 2, 1))]
+    ops += [("mtan.s2 wgrad", wgrad, (16, 64, 64, 128, 64, 64, 128, 3, 1, 1)), ("mtan.s3 wgrad", wgrad, (16, 32, 32, 256, 32, 32, 256, 3, 1, 1))]
+    for name, make, a in ops:
+        if args.only and not any(o in name for o in args.only.split(",")):
+            continue
+        for n in names:
+            os.environ.pop(n, None)
+        L.raw("vmtl_reload_env")()
+        keep, fn = make(*a)  # buffers sized under the default settings (the settings change no split count)
+        times = [[] for _ in settings]
+        for rnd in range(-args.warm_rounds, args.repeats):
+            for i, s in enumerate(settings):
+                for n in names:
+                    os.environ.pop(n, None)
+                os.environ.update(s)
+                L.raw("vmtl_reload_env")()
+                t = round(timeit(fn) * 1e3, 2)
+                if rnd >= 0:
+                    times[i].append(t)
+        for n in names:
+            os.environ.pop(n, None)
+        L.raw("vmtl_reload_env")()
+        print(json.dumps({"launch": name, "shape": a, "routes": [{"env": s, "us": t} for s, t in zip(settings, times)]}), flush=True)
+        del keep
+
+
+if args.pipe_routes:
+    pipe_routes()
+    sys.exit(0)
 
 if args.wgrad_routes:
     wgrad_routes()

@@ -117,7 +117,14 @@ __device__ __forceinline__ void split3(f32x4 v, u32x2& p1, u32x2& p2, u32x2& p3)
   p3 = (u32x2){__builtin_amdgcn_perm(r2[1], r2[0], 0x07060302u), __builtin_amdgcn_perm(r2[3], r2[2], 0x07060302u)};
 }
 
-template <int TM, int TN, int WAVES_M, int WAVES_N, bool UP2 = false, int NT = 0, int NS = 0, int PL = 0>
+// PF = K chunks in flight in staging registers ahead of the one being multiplied (register-staged fp32 path only: NS == 0,
+// PL == 0).  PF = 1 is `load(next); compute(cur); store(next); barrier`.  PF = 2 (host: conv_pipe_depth, the 64x144 tile)
+// follows conv_wgrad_kernel's PIPE: two staging register sets indexed at compile time by unrolling the trip by 2, LDS
+// still double-buffered, load_tile and store_tile issued UNCONDITIONALLY in the steady-state trips, a peeled tail whose
+// loads past the K range use the out-of-range offset, and a straight-line K walk (advance_k below) - so that the wait in
+// front of a staged chunk's ds_writes leaves the younger chunk's loads outstanding.  Same fragment reads, same MFMA
+// order: bit-identical results.
+template <int TM, int TN, int WAVES_M, int WAVES_N, bool UP2 = false, int NT = 0, int NS = 0, int PL = 0, int PF = 1>
 // The 128x160 tile took 264 registers: ONE wave per SIMD, nothing to overlap its loads with.  Its second launch bound asks
 // for two (<= 256 registers: 216-238, no spills): 13-18 % faster on the 145..160-column layers (tools/bench_conv.py dgrad
 // blk1-3.c1: 465 -> 405, 501 -> 426, 590 -> 484 us).  Only that tile: the same bound on every instantiation made the
@@ -135,6 +142,7 @@ __global__ __launch_bounds__(256, (TM * TN >= 20 && WAVES_N == 2) ? 2 : 1) void 
   static_assert(NS == 0 || (NS >= 2 && NS <= 4 && BM % 32 == 0), "LDS-DMA staging: 2..4 buffers, whole 32-row passes");
   static_assert(PL == 0 || PL == 1 || PL == 3, "operand planes: fp32, bf16 or bf16x3");
   static_assert(PL == 0 || (NS == 0 && (NT == 0 || PL == 1)), "bf16 operands: register staging; bf16x3: no tail columns");
+  static_assert(PF == 1 || (PF == 2 && NS == 0 && PL == 0), "prefetch depth 2: register-staged fp32 operands");
 
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* As = smem;                    // [NBUF][BM][LDT]
@@ -216,8 +224,31 @@ __global__ __launch_bounds__(256, (TM * TN >= 20 && WAVES_N == 2) ? 2 : 1) void 
     }
   };
   normalize();
+  // PF = 2: the same walk by ONE conditional step of selects, no loop and no branch between the loads (normalize() is
+  // 13 exec branches per iteration in the ISA, and control flow there makes the compiler drain the younger chunk in
+  // front of the ds_writes).  Valid when every gather segment is at least BK channels wide (host: conv_pipe_depth):
+  // ci < cseg before the step, so ci + BK < 2 cseg, and a segment change lands on ci < BK <= C2s.
+  auto advance_k = [&]() {
+    const bool wrap = ci >= cseg;
+    ci -= wrap ? cseg : 0;
+    dw += wrap ? 1 : 0;
+    const bool roww = wrap & (dw == kwseg);
+    dw = roww ? 0 : dw;
+    dh += roww ? 1 : 0;
+    if (UP2) {
+      const bool to1 = roww & (seg == 0) & (dh == 2);
+      if (p.C2s == 0) {  // uniform: no skip, the K range ends here (kk >= Ktot anyway)
+        dh = to1 ? (1 << 20) : dh;
+      } else {
+        seg = to1 ? 1 : seg;
+        dh = to1 ? 0 : dh;
+        cseg = to1 ? p.C2s : cseg;
+        kwseg = to1 ? 3 : kwseg;
+      }
+    }
+  };
 
-  f32x4 ra[RA], rb[RB];
+  f32x4 ra_s[PF][RA], rb_s[PF][RB];  // staging register sets: the slot index is a compile-time constant after unrolling
 
   // Register staging goes through BUFFER loads: 32-bit byte offsets instead of 64-bit pointer arithmetic, and
   // an out-of-image tap / tile edge is an out-of-range offset, which the hardware answers with zeros - no
@@ -257,51 +288,62 @@ __global__ __launch_bounds__(256, (TM * TN >= 20 && WAVES_N == 2) ? 2 : 1) void 
     const int n = n0 + r0 + 32 * i;
     wrow_ok[i] = n < p.Nw && r0 + 32 * i < BN;
     wrowb[i] = (unsigned)n * (unsigned)p.Ktot * 4u;
+    // PF = 2: the row test lives in the offset itself - a row past the weights starts at the out-of-range offset and the
+    // saturating add in load_tile keeps it there (five lane masks fewer in scalar registers: the UP2 form spilled six)
+    if (PF == 2 && !wrow_ok[i]) wrowb[i] = OOB;
   }
-  auto load_a_seg0 = [&](int i, bool kok, unsigned tapb) {
+  auto load_a_seg0 = [&](f32x4* ra, int i, bool kok, unsigned tapb) {
     const int h = hb[i] + dh, w = wb[i] + dw;
     const bool ok = kok && (unsigned)h < (unsigned)p.H && (unsigned)w < (unsigned)p.W;
     ra[i] = bload(rs_x, ok ? rowb0[i] + tapb : OOB);
   };
-  auto load_a_seg1 = [&](int i, bool kok, unsigned tapb) {
+  auto load_a_seg1 = [&](f32x4* ra, int i, bool kok, unsigned tapb) {
     // full-res skip: output pixel (2*h2 + pa, 2*w2 + pb), tap offset dh-1 / dw-1; hb = h2 - 1 + pa
     const int h = 2 * hb[i] + 1 - pa + dh, w = 2 * wb[i] + 1 - pb + dw;
     const bool ok = kok && (unsigned)h < (unsigned)(2 * p.H) && (unsigned)w < (unsigned)(2 * p.W);
     ra[i] = bload(rs_x2, ok ? rowb1[i] + tapb : OOB);
   };
-  auto load_tile = [&]() {
-    const bool kok = kk < p.Ktot;
+  // live (uniform): the chunk lies inside this launch's K range; a dead chunk is loaded with the out-of-range offset
+  auto load_tile = [&](f32x4* ra, f32x4* rb, bool live = true) {
+    const bool kok = live & (kk < p.Ktot);
     const int seg_end = 4 * p.Cs;  // first K index of segment 1
     const unsigned tap0 = ((unsigned)(dh * p.W + dw) * (unsigned)p.Cs + (unsigned)ci) * 4u;
     if (!UP2 || kchunk + BK <= seg_end || p.C2s == 0) {
 #pragma unroll
-      for (int i = 0; i < RA; ++i) load_a_seg0(i, kok && (!UP2 || seg == 0), tap0);
+      for (int i = 0; i < RA; ++i) load_a_seg0(ra, i, kok && (!UP2 || seg == 0), tap0);
     } else {
       const unsigned tap1 = ((unsigned)(dh * (2 * p.W) + dw) * (unsigned)p.C2s + (unsigned)ci) * 4u;
       if (kchunk >= seg_end) {
 #pragma unroll
-        for (int i = 0; i < RA; ++i) load_a_seg1(i, kok, tap1);
+        for (int i = 0; i < RA; ++i) load_a_seg1(ra, i, kok, tap1);
       } else {  // the chunk straddling the boundary: per lane
 #pragma unroll
         for (int i = 0; i < RA; ++i) {
-          if (seg == 0) load_a_seg0(i, kok, tap0);
-          else load_a_seg1(i, kok, tap1);
+          if (seg == 0) load_a_seg0(ra, i, kok, tap0);
+          else load_a_seg1(ra, i, kok, tap1);
         }
       }
     }
 #pragma unroll
-    for (int i = 0; i < RB; ++i) rb[i] = bload(rs_w, (kok && wrow_ok[i]) ? wrowb[i] + (unsigned)kk * 4u : OOB);
+    for (int i = 0; i < RB; ++i) {
+      if constexpr (PF == 2) {  // no short-circuit on the per-lane row test: it became divergent branches around duplicated loads
+        rb[i] = bload(rs_w, kok ? __builtin_elementwise_add_sat(wrowb[i], (unsigned)kk * 4u) : OOB);
+      } else {
+        rb[i] = bload(rs_w, (kok && wrow_ok[i]) ? wrowb[i] + (unsigned)kk * 4u : OOB);
+      }
+    }
     kchunk += BK;
     // advance to the next BK chunk
     kk += BK;
     ci += BK;
-    normalize();
+    if constexpr (PF == 2) advance_k();
+    else normalize();
   };
   // bf16 LDS image (bytes): A planes [2][PL][BM][64], then B planes [2][PL][BN][64]; the 16-byte slot s of row r
   // sits at s ^ ((r >> 2) & 3) (rows r, r+4, r+8, r+12 of a fragment read would share a bank group otherwise)
   unsigned char* A3 = reinterpret_cast<unsigned char*>(smem);
   unsigned char* B3 = A3 + 2 * (PL ? PL : 1) * BM * 64;
-  auto store_tile = [&](int buf) {
+  auto store_tile = [&](int buf, const f32x4* ra, const f32x4* rb) {
     if constexpr (PL == 1) {
 #pragma unroll
       for (int i = 0; i < RA; ++i) {
@@ -351,10 +393,11 @@ __global__ __launch_bounds__(256, (TM * TN >= 20 && WAVES_N == 2) ? 2 : 1) void 
     const int ks = (k4 ^ (r0 & 7)) * 4;  // (r0 + 32 i) & 7 == r0 & 7
 #pragma unroll
     for (int i = 0; i < RA; ++i)
-      if (BM % 32 == 0 || r0 + 32 * i < BM) *reinterpret_cast<f32x4*>(a + (r0 + 32 * i) * LDT + ks) = ra[i];
+      if (BM % 32 == 0 || (PF == 2 && i < BM / 32) || r0 + 32 * i < BM) *reinterpret_cast<f32x4*>(a + (r0 + 32 * i) * LDT + ks) = ra[i];
 #pragma unroll
     for (int i = 0; i < RB; ++i)
-      if (BN % 32 == 0 || r0 + 32 * i < BN) *reinterpret_cast<f32x4*>(b + (r0 + 32 * i) * LDT + ks) = rb[i];
+      // PF = 2: only the last, partial pass is guarded (r0 < 32 is not known to the compiler: it guarded every pass)
+      if (BN % 32 == 0 || (PF == 2 && i < BN / 32) || r0 + 32 * i < BN) *reinterpret_cast<f32x4*>(b + (r0 + 32 * i) * LDT + ks) = rb[i];
   };
 
   f32x4 acc[TM][TN];
@@ -534,16 +577,51 @@ __global__ __launch_bounds__(256, (TM * TN >= 20 && WAVES_N == 2) ? 2 : 1) void 
       compute(kt % NS);
     }
     __syncthreads();  // the epilogue reuses the staging memory
+  } else if constexpr (PF == 2) {
+    // chunk kt lives in register slot kt % 2 until it is stored to LDS buffer kt & 1
+#pragma unroll
+    for (int d = 0; d < 2; ++d) load_tile(ra_s[d], rb_s[d], d < nk);
+    store_tile(0, ra_s[0], rb_s[0]);
+    __syncthreads();
+    int cur = 0, kt = 0;
+    // steady state: both steps of a trip refill their slot with a chunk inside the K range (the second loads kt + 3),
+    // so both also have a next chunk to stage: no test inside the trip
+    for (; kt + 3 < nk; kt += 2) {
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        load_tile(ra_s[k], rb_s[k]);
+        // the scheduler sank six of the seven loads behind ~60 of the 72 MFMAs: they are to be in flight UNDER them
+        __builtin_amdgcn_sched_barrier(0);
+        compute(cur);
+        store_tile(cur ^ 1, ra_s[k ^ 1], rb_s[k ^ 1]);
+        __syncthreads();
+        cur ^= 1;
+      }
+    }
+    // the tail, at most 3 chunks
+    for (; kt < nk; kt += 2) {
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        if (kt + k < nk) {  // uniform over the workgroup
+          load_tile(ra_s[k], rb_s[k], kt + k + 2 < nk);
+          __builtin_amdgcn_sched_barrier(0);
+          compute(cur);
+          if (kt + k + 1 < nk) store_tile(cur ^ 1, ra_s[k ^ 1], rb_s[k ^ 1]);
+          __syncthreads();
+          cur ^= 1;
+        }
+      }
+    }
   } else {
-    load_tile();
-    store_tile(0);
+    load_tile(ra_s[0], rb_s[0]);
+    store_tile(0, ra_s[0], rb_s[0]);
     __syncthreads();
     int cur = 0;
     for (int kt = 0; kt < nk; ++kt) {
       const bool more = kt + 1 < nk;
-      if (more) load_tile();  // global loads stay in flight under the MFMAs
+      if (more) load_tile(ra_s[0], rb_s[0]);  // global loads stay in flight under the MFMAs
       compute(cur);
-      if (more) store_tile(cur ^ 1);
+      if (more) store_tile(cur ^ 1, ra_s[0], rb_s[0]);
       __syncthreads();
       cur ^= 1;
     }
@@ -874,7 +952,7 @@ static int conv_glds_stages() {
   return (v == 2 || v == 3) ? v : 0;
 }
 
-template <int TM, int TN, int WMV, int WNV, bool UP2, int NT, int NS, int PL = 0>
+template <int TM, int TN, int WMV, int WNV, bool UP2, int NT, int NS, int PL = 0, int PF = 1>
 static int launch_conv_ns(ConvP& p, hipStream_t st) {
   constexpr int BM = WMV * TM * 16, BN = WNV * TN * 16 + NT;
   p.tiles_m = cdiv(p.M, BM) * (UP2 ? 4 : 1);
@@ -886,15 +964,39 @@ static int launch_conv_ns(ConvP& p, hipStream_t st) {
   constexpr int NBUF = NS >= 2 ? NS : 2;
   constexpr int BNR = NS >= 2 ? (BN + 31) / 32 * 32 : BN;
   const size_t lds = PL ? (size_t)2 * PL * (BM + BN) * 64 : (size_t)NBUF * (BM + BNR) * LDT * sizeof(float);
-  const int rc = allow_dynamic_lds(reinterpret_cast<const void*>(&conv_igemm_kernel<TM, TN, WMV, WNV, UP2, NT, NS, PL>), lds);
+  const int rc = allow_dynamic_lds(reinterpret_cast<const void*>(&conv_igemm_kernel<TM, TN, WMV, WNV, UP2, NT, NS, PL, PF>), lds);
   if (rc) return rc;
-  hipLaunchKernelGGL((conv_igemm_kernel<TM, TN, WMV, WNV, UP2, NT, NS, PL>),
+  hipLaunchKernelGGL((conv_igemm_kernel<TM, TN, WMV, WNV, UP2, NT, NS, PL, PF>),
                      dim3(p.tiles_m * p.tiles_n, p.ksplit > 1 ? p.ksplit : 1), dim3(256), lds, st, p);
   return vmtl_check_launch();
 }
 
+// K chunks in flight in the register-staged fp32 main loop (conv_igemm_kernel PF).  2 only on the 64x144 tile (id 11), when
+// every gather segment is at least BK channels wide (the straight-line K walk), the workgroup runs at least
+// VMTL_IG_PIPE_MIN_CHUNKS K chunks, and the grid is at most two workgroups per CU (the second register set costs the
+// third wave per SIMD, which such a grid does not have anyway).  VMTL_IG_PIPE=0: the one-chunk loop everywhere.  The UP2
+// class measured 0.5-1.2 % SLOWER per launch at depth 2 (196 VGPRs, the segment branches between its loads) and is left
+// off: VMTL_IG_PIPE_UP2=1 switches it on for same-build comparisons.
+#define VMTL_PIPE_TILE 11
+#define VMTL_TWO_PER_CU 512  // workgroups of a grid that gives every CU of the MI355X (256) two
+static thread_local int g_last_pipe_depth = 0;  // what the last implicit-GEMM launch of this thread ran (test hook)
+static int conv_pipe_depth(int tile, int Cs, int C2s, int nk, long long workgroups, bool up2, int prec) {
+  static EnvInt e_pipe{"VMTL_IG_PIPE", 1}, e_up2{"VMTL_IG_PIPE_UP2", 0}, e_min{"VMTL_IG_PIPE_MIN_CHUNKS", 4};
+  if (!env_int(e_pipe) || (up2 && !env_int(e_up2)) || prec != VMTL_PREC_FP32 || tile != VMTL_PIPE_TILE) return 1;
+  if (Cs < BK || (up2 && C2s != 0 && C2s < BK)) return 1;
+  if (nk < env_int(e_min) || workgroups > VMTL_TWO_PER_CU) return 1;
+  return 2;
+}
+
+extern "C" int vmtl_conv2d_last_pipe_depth(void) { return g_last_pipe_depth; }
+
+extern "C" int vmtl_conv2d_pipe_depth(int tile, int Cs, int C2s, int nk, long long workgroups, int up2, int precision) {
+  return conv_pipe_depth(tile, Cs, C2s, nk, workgroups, up2 != 0, precision);
+}
+
 template <int TM, int TN, int WMV, int WNV, bool UP2, int NT>
 static int launch_conv(ConvP& p, hipStream_t st, int prec) {
+  g_last_pipe_depth = 1;
   // bf16 precision: one plane, register staging; the tuning switches below (VMTL_BF16X3, VMTL_GLDS) are fp32-only
   if (prec == VMTL_PREC_BF16) return launch_conv_ns<TM, TN, WMV, WNV, UP2, NT, 0, 1>(p, st);
   if constexpr (NT == 0 && WNV * TN >= 5) {
@@ -906,6 +1008,15 @@ static int launch_conv(ConvP& p, hipStream_t st, int prec) {
     const int ns = conv_glds_stages();
     if (ns == 2) return launch_conv_ns<TM, TN, WMV, WNV, UP2, NT, 2>(p, st);
     if (ns == 3) return launch_conv_ns<TM, TN, WMV, WNV, UP2, NT, 3>(p, st);
+  }
+  if constexpr (TM == 1 && TN == 9 && WMV == 4 && WNV == 1 && NT == 0) {  // tile VMTL_PIPE_TILE
+    const int nk = p.ksplit > 1 ? p.ksteps_per_split : cdiv(p.Ktot, BK);
+    const long long wgs = (long long)cdiv(p.M, WMV * TM * 16) * (UP2 ? 4 : 1) * cdiv(p.shuffle ? p.Nw : p.ldy, WNV * TN * 16) *
+                          (p.ksplit > 1 ? p.ksplit : 1);
+    if (conv_pipe_depth(VMTL_PIPE_TILE, p.Cs, p.C2s, nk, wgs, UP2, prec) == 2) {
+      g_last_pipe_depth = 2;
+      return launch_conv_ns<TM, TN, WMV, WNV, UP2, NT, 0, 0, 2>(p, st);
+    }
   }
   return launch_conv_ns<TM, TN, WMV, WNV, UP2, NT, 0>(p, st);
 }
@@ -1026,7 +1137,7 @@ __global__ __launch_bounds__(256) void sum_slabs_kernel(const float* __restrict_
 // (fewer than VMTL_KSPLIT_BLOCKS workgroups, default 512 = two per CU: one 4-wave workgroup per CU is one wave per SIMD
 // and hides no latency - decoder block 0 at bs 32 ran at 82 TF on 256 workgroups), at least 16 K steps per slice
 static int ksplit_for(long long blocks, int nk, int ldy) {
-  static EnvInt e_blocks{"VMTL_KSPLIT_BLOCKS", 512};  // tuning aid
+  static EnvInt e_blocks{"VMTL_KSPLIT_BLOCKS", VMTL_TWO_PER_CU};  // tuning aid
   const int target = env_int(e_blocks);
   if (blocks <= 0 || blocks >= target || nk < 32 || (ldy & 3)) return 1;
   long long s = cdivll(target, blocks);

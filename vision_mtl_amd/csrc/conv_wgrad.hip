@@ -70,8 +70,14 @@ static_assert(wg_ld(16) == 16 && wg_ld(20) == 80 && wg_ld(144) == 144 && wg_ld(1
 // With the uniform guards `if (pp + PD * BP < p_end)` around load_tile inside the loop, the compiler's wait in front of
 // the staged slot's ds_write assumed the worst path and drained every younger chunk: PD bought one compute phase of
 // cover, not PD.  The order of the MFMAs is the same: bit-identical slabs.
+// The tall tiles (TM >= 8: 128 / 144 rows, fp32) take the peeled loop at PD = 2 where the host says so (wgrad_tall_pipe):
+// their 128-144 MFMAs per chunk are about ONE loaded memory latency, and LDS holds them to two workgroups per CU.
+// RG (with FAST; host: wgrad_rowgroup_ok): Wo divides BP and Ho is a multiple of BP / Wo - a chunk is BP / Wo whole
+// consecutive output rows of ONE image.  (image, first row) of the chunk stay uniform; a gather row's (row within the
+// chunk, column) is a per-thread constant, and the row bounds test moves from the chunk to the gather row.  Same chunks,
+// same MFMA order as the general loader: bit-identical slabs.
 template <int TM, int NTR = 0, int PM = 1, int PD = (TM <= 2 ? 3 : (TM <= 4 && NTR == 0) ? 2 : 1), bool FAST = false,
-          bool BF16 = false, bool PIPE = false>
+          bool BF16 = false, bool PIPE = false, bool RG = false>
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradP p) {
   constexpr int TN = 2;
   constexpr int BMM = TM * 16;    // rows covered by MFMA tiles
@@ -136,6 +142,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradP p) {
   // FAST: uniform chunk position (scalar registers) + per-thread constants
   int s_b = 0, s_ho = 0, s_wo = 0;
   int tw[XP];          // input column of gather row i relative to the chunk's first input column
+  int th[RG ? XP : 1]; // RG: input row of gather row i relative to the chunk's first input row
+  const int rg_rows = RG ? BP / p.Wo : 0;  // RG: output rows per chunk
   int toff[XP];        // byte offset of gather row i relative to the chunk's first input pixel (may be negative)
   int tyoff[YIT];      // dY: byte offset relative to the chunk's first dY row, -1 = this lane loads nothing
   if (FAST) {
@@ -145,8 +153,15 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradP p) {
     s_wo = rem - s_ho * p.Wo;
 #pragma unroll
     for (int i = 0; i < XP; ++i) {
-      tw[i] = (xr + XROWS * i) * p.stride + dw;
-      toff[i] = ((dh * p.W + tw[i]) * p.Cs + ci) * 4;
+      if constexpr (RG) {
+        const int pr = (xr + XROWS * i) / p.Wo, pc = (xr + XROWS * i) - pr * p.Wo;  // pixel xr + XROWS i of the chunk
+        tw[i] = pc * p.stride + dw;
+        th[i] = pr * p.stride + dh;
+        toff[i] = ((th[i] * p.W + tw[i]) * p.Cs + ci) * 4;
+      } else {
+        tw[i] = (xr + XROWS * i) * p.stride + dw;
+        toff[i] = ((dh * p.W + tw[i]) * p.Cs + ci) * 4;
+      }
     }
 #pragma unroll
     for (int it = 0; it < YIT; ++it) {
@@ -176,18 +191,38 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradP p) {
       const int win = s_wo * p.stride;
       const unsigned xbase = (unsigned)((s_b * p.H + hin) * p.W + win) * (unsigned)p.Cs * 4u;
       // `&`, not `&&`: a short-circuit on a per-lane condition became divergent branches around duplicated loads
-      const bool hok = xok & live & ((unsigned)(hin + dh) < (unsigned)p.H);
+      const bool hok = xok & live & (RG || (unsigned)(hin + dh) < (unsigned)p.H);
+      if constexpr (RG) {
+        unsigned xoff[XP];  // every offset first, then the loads
 #pragma unroll
-      for (int i = 0; i < XP; ++i) {
-        const bool ok = hok & ((unsigned)(win + tw[i]) < (unsigned)p.W);
-        rx_s[i] = buf_load16(rs_x, ok ? xbase + (unsigned)toff[i] : OOB);
+        for (int i = 0; i < XP; ++i) {
+          const bool ok = hok & ((unsigned)(win + tw[i]) < (unsigned)p.W) & ((unsigned)(hin + th[i]) < (unsigned)p.H);
+          xoff[i] = ok ? xbase + (unsigned)toff[i] : OOB;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < XP; ++i) rx_s[i] = buf_load16(rs_x, xoff[i]);
+      } else {
+#pragma unroll
+        for (int i = 0; i < XP; ++i) {
+          const bool ok = hok & ((unsigned)(win + tw[i]) < (unsigned)p.W);
+          rx_s[i] = buf_load16(rs_x, ok ? xbase + (unsigned)toff[i] : OOB);
+        }
       }
-      s_wo += BP;
-      if (s_wo >= p.Wo) {
-        s_wo = 0;
-        if (++s_ho == p.Ho) {
-          s_ho = 0;
-          ++s_b;
+      if constexpr (RG) {  // the next chunk starts rg_rows rows further down, at column 0
+        // selects, no branch: with a branch here the 144-row tile's wait after the barrier drained every load
+        s_ho += rg_rows;
+        const bool wrap = s_ho >= p.Ho;
+        s_ho = wrap ? 0 : s_ho;
+        s_b += wrap ? 1 : 0;
+      } else {
+        s_wo += BP;
+        if (s_wo >= p.Wo) {
+          s_wo = 0;
+          if (++s_ho == p.Ho) {
+            s_ho = 0;
+            ++s_b;
+          }
         }
       }
       return;
@@ -513,34 +548,91 @@ static bool wgrad_fast_ok(const WgradP& p) {
   return env_int(e) != 0 && p.x2 == nullptr && p.Wo % BP == 0 && p.chunk % BP == 0;
 }
 
-template <int TM, int NTR, int PM, bool FAST, bool BF16, bool PIPE>
+// row-group form of it (conv_wgrad_kernel RG): a chunk is BP / Wo whole output rows of one image.  The 144-row tile only
+// (the decoder's 8- and 16-pixel-wide maps, where it was measured); VMTL_WG_ROWGROUP=0 or VMTL_WG_FAST=0 keep the general
+// loader.
+static bool wgrad_rowgroup_ok(const WgradP& p) {
+  static EnvInt e_fast{"VMTL_WG_FAST", 1}, e_rg{"VMTL_WG_ROWGROUP", 1};
+  return env_int(e_fast) != 0 && env_int(e_rg) != 0 && p.x2 == nullptr && p.Wo > 0 && p.Wo < BP && BP % p.Wo == 0 &&
+         p.Ho % (BP / p.Wo) == 0 && p.chunk % BP == 0;
+}
+
+// PD = 2 and the peeled loop on the tall tiles (fp32, a scalar loader): class by class - VMTL_WG_PIPE_TALL is a mask,
+// 1 = the 144-row tile, 2 = the 128-row tile - and only for slices long enough: a shorter slice is all prologue and tail.
+// Measured crossover (slices of 2 .. 7 chunks forced on one layer per tile, profiles/conv_pipe2/slice_length_sweep.jsonl):
+// the 144-row tile loses at 2, ties at 3 and wins from 4 chunks; the 128-row tile loses up to 4, ties at 5, wins from 6.
+// VMTL_WG_PIPE_MIN_CHUNKS > 0 replaces both.  VMTL_WG_PIPE=0 keeps the guarded PD = 1 loop.
+static bool wgrad_tall_pipe(const WgradP& p, int rows) {
+  static EnvInt e_pipe{"VMTL_WG_PIPE", 1}, e_tall{"VMTL_WG_PIPE_TALL", 3}, e_min{"VMTL_WG_PIPE_MIN_CHUNKS", 0};
+  if (!env_int(e_pipe) || !(env_int(e_tall) & (rows == 144 ? 1 : 2))) return false;
+  const int min_chunks = env_int(e_min) > 0 ? env_int(e_min) : rows == 144 ? 4 : 6;
+  return p.chunk / BP >= min_chunks;
+}
+
+// what a launch runs: L = loader (0 general, 1 scalar chunk, 2 row group), PD and the loop (peeled or guarded)
+struct WgradRoute { int loader, pd; bool pipe; };
+static constexpr int wgrad_default_pd(int TM, int NTR) { return TM <= 2 ? 3 : (TM <= 4 && NTR == 0) ? 2 : 1; }
+
+// p: after the pointwise flattening, chunk set
+static WgradRoute wgrad_route(const WgradP& p, int rows, int prec) {
+  const int TM = rows / 16, NTR = rows % 16;
+  WgradRoute r{0, wgrad_default_pd(TM, NTR), false};
+  if (wgrad_fast_ok(p)) r.loader = 1;
+  else if (TM == 9 && prec == VMTL_PREC_FP32 && wgrad_rowgroup_ok(p)) r.loader = 2;
+  if (r.loader == 0) return r;
+  static EnvInt e{"VMTL_WG_PIPE", 1};  // 0 = the guarded loop (same-build comparisons)
+  // PD == 3 (tile heights 16 / 20 / 32 / 36): always.  PD == 2 (48 / 64 rows): the peeled loop measured 4-5 % SLOWER in
+  // the step (9.9 -> 10.4 us, 15.3 -> 15.9 us per launch, 66 launches each: its slices are four chunks, all prologue and
+  // tail, and the code is twice as long); the general loaders keep the guarded loop too
+  if (r.pd >= 3) r.pipe = env_int(e) != 0;
+  else if (TM >= 8 && prec == VMTL_PREC_FP32 && wgrad_tall_pipe(p, rows)) {
+    r.pd = 2;
+    r.pipe = true;
+  }
+  return r;
+}
+
+template <int TM, int NTR, int PM, int PD, bool FAST, bool BF16, bool PIPE, bool RG = false>
 static int launch_wgrad_pipe(WgradP& p, int splits, hipStream_t st) {
   constexpr int BMC = TM * 16 + NTR;
-  constexpr int PD = (TM <= 2 ? 3 : (TM <= 4 && NTR == 0) ? 2 : 1);
   const size_t lds = (size_t)2 * BP * (wg_ld(BMC, PM) + wg_ld(WG_BNK, PM)) * sizeof(float);
-  const int rc = allow_dynamic_lds(reinterpret_cast<const void*>(&conv_wgrad_kernel<TM, NTR, PM, PD, FAST, BF16, PIPE>), lds);
+  const int rc = allow_dynamic_lds(reinterpret_cast<const void*>(&conv_wgrad_kernel<TM, NTR, PM, PD, FAST, BF16, PIPE, RG>), lds);
   if (rc) return rc;
   if ((long long)p.M * p.ldy * 4 >= (1ll << 32) || (long long)p.B * p.H * p.W * p.Cs * 4 >= (1ll << 32))
     return VMTL_ERR_UNSUPPORTED;  // buffer addressing: 32-bit byte offsets
   p.tiles_kk = cdiv(p.Ktot, WG_BNK);
   p.tiles_co = cdiv(p.Nw, BMC);
   p.splits = splits;
-  hipLaunchKernelGGL((conv_wgrad_kernel<TM, NTR, PM, PD, FAST, BF16, PIPE>), dim3(p.tiles_kk * p.tiles_co * splits), dim3(256), lds, st,
-                     p);
+  hipLaunchKernelGGL((conv_wgrad_kernel<TM, NTR, PM, PD, FAST, BF16, PIPE, RG>), dim3(p.tiles_kk * p.tiles_co * splits), dim3(256), lds,
+                     st, p);
   return vmtl_check_launch();
 }
 
-template <int TM, int NTR, int PM, bool FAST, bool BF16 = false>
-static int launch_wgrad_pm(WgradP& p, int splits, hipStream_t st) {
-  constexpr int PD = (TM <= 2 ? 3 : (TM <= 4 && NTR == 0) ? 2 : 1);
-  // PD == 3 only (tile heights 16 / 20 / 32 / 36): at PD = 2 (48 / 64 rows) the peeled loop measured 4-5 % SLOWER in
-  // the step (9.9 -> 10.4 us, 15.3 -> 15.9 us per launch, 66 launches each: its slices are four chunks, all prologue and
-  // tail, and the code is twice as long); the general loaders keep the guarded loop too
-  if constexpr (PD >= 3 && FAST) {
-    static EnvInt e{"VMTL_WG_PIPE", 1};  // 0 = the guarded loop (same-build comparisons)
-    if (env_int(e)) return launch_wgrad_pipe<TM, NTR, PM, FAST, BF16, true>(p, splits, st);
+template <int TM, int NTR, int PM, bool BF16 = false>
+static int launch_wgrad_pm(WgradP& p, int splits, hipStream_t st, const WgradRoute& r) {
+  constexpr int PD = wgrad_default_pd(TM, NTR);
+  if (r.loader == 0) return launch_wgrad_pipe<TM, NTR, PM, PD, false, BF16, false>(p, splits, st);
+  if constexpr (TM == 9 && !BF16) {
+    if (r.loader == 2) {
+      if (r.pipe) return launch_wgrad_pipe<TM, NTR, PM, 2, true, BF16, true, true>(p, splits, st);
+      return launch_wgrad_pipe<TM, NTR, PM, PD, true, BF16, false, true>(p, splits, st);
+    }
   }
-  return launch_wgrad_pipe<TM, NTR, PM, FAST, BF16, false>(p, splits, st);
+  if (r.loader == 2) return VMTL_ERR_UNSUPPORTED;  // wgrad_route gives row groups to the 144-row tile only
+  if constexpr (TM >= 8 && !BF16) {
+    if (r.pipe) return launch_wgrad_pipe<TM, NTR, PM, 2, true, BF16, true>(p, splits, st);
+  }
+  if constexpr (PD >= 3) {
+    if (r.pipe) return launch_wgrad_pipe<TM, NTR, PM, PD, true, BF16, true>(p, splits, st);
+  }
+  return launch_wgrad_pipe<TM, NTR, PM, PD, true, BF16, false>(p, splits, st);
+}
+
+// a pointwise conv has no borders: one flat row of M pixels (so any image width takes the scalar-chunk loader)
+static void wgrad_flatten_pointwise(WgradP& p) {
+  if (p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && p.x2 == nullptr && p.M % BP == 0) {
+    p.B = 1; p.H = 1; p.W = p.M; p.Ho = 1; p.Wo = p.M;
+  }
 }
 
 template <int TM, int NTR = 0>
@@ -548,23 +640,18 @@ static int launch_wgrad(WgradP& p, int splits, hipStream_t st, int prec) {
   constexpr int PMD = wg_pm<TM * 16 + NTR>();
 #ifdef VMTL_TUNING
   static EnvInt e_pad{"VMTL_WG_PAD", -1};  // force one LDS row-stride rule (wg_ld) for every tile height
+  const WgradRoute general{0, wgrad_default_pd(TM, NTR), false};
   switch (prec == VMTL_PREC_FP32 ? env_int(e_pad) : -1) {
-    case 0: return launch_wgrad_pm<TM, NTR, 0, false>(p, splits, st);
-    case 1: return launch_wgrad_pm<TM, NTR, 1, false>(p, splits, st);
-    case 2: return launch_wgrad_pm<TM, NTR, 2, false>(p, splits, st);
+    case 0: return launch_wgrad_pm<TM, NTR, 0>(p, splits, st, general);
+    case 1: return launch_wgrad_pm<TM, NTR, 1>(p, splits, st, general);
+    case 2: return launch_wgrad_pm<TM, NTR, 2>(p, splits, st, general);
     default: break;
   }
 #endif
-  if (p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && p.x2 == nullptr && p.M % BP == 0) {
-    // a pointwise conv has no borders: one flat row of M pixels (so any image width takes the scalar-chunk loader)
-    p.B = 1; p.H = 1; p.W = p.M; p.Ho = 1; p.Wo = p.M;
-  }
-  if (prec == VMTL_PREC_BF16) {
-    if (wgrad_fast_ok(p)) return launch_wgrad_pm<TM, NTR, PMD, true, true>(p, splits, st);
-    return launch_wgrad_pm<TM, NTR, PMD, false, true>(p, splits, st);
-  }
-  if (wgrad_fast_ok(p)) return launch_wgrad_pm<TM, NTR, PMD, true>(p, splits, st);
-  return launch_wgrad_pm<TM, NTR, PMD, false>(p, splits, st);
+  wgrad_flatten_pointwise(p);
+  const WgradRoute r = wgrad_route(p, TM * 16 + NTR, prec);
+  if (prec == VMTL_PREC_BF16) return launch_wgrad_pm<TM, NTR, PMD, true>(p, splits, st, r);
+  return launch_wgrad_pm<TM, NTR, PMD>(p, splits, st, r);
 }
 
 static int wgrad_dispatch(WgradP& p, int splits, void* stream, int prec) {
@@ -605,6 +692,24 @@ extern "C" int vmtl_conv2d_wgrad(const float* x, const float* dy, float* slabs, 
                                  void* stream) {
   return vmtl_conv2d_wgrad_p(x, dy, slabs, splits, B, H, W, Cs, Ho, Wo, ldy, Nw, KH, KW, stride, pad, VMTL_PREC_FP32,
                              stream);
+}
+
+// The route vmtl_conv2d_wgrad[_p] takes for this layer (a host-side query, no launch): loader + 4 * peeled loop + 8 * PD +
+// 64 * tile rows, loader 0 = general, 1 = scalar chunk (whole output rows), 2 = row group; -1 = bad arguments.
+extern "C" int vmtl_conv2d_wgrad_route(int B, int H, int W, int Cs, int Ho, int Wo, int Nw, int KH, int KW, int stride,
+                                       int pad, int precision) {
+  if (!valid_prec(precision) || B <= 0 || H <= 0 || W <= 0 || Cs <= 0 || Ho <= 0 || Wo <= 0 || Nw <= 0 || KH <= 0 ||
+      KW <= 0 || stride <= 0 || pad < 0)
+    return -1;
+  WgradP p;
+  p.B = B; p.H = H; p.W = W; p.Cs = Cs; p.Ho = Ho; p.Wo = Wo; p.Nw = Nw; p.KH = KH; p.KW = KW; p.stride = stride;
+  p.pad = pad; p.Ktot = KH * KW * Cs; p.M = B * Ho * Wo;
+  const int splits = vmtl_conv2d_wgrad_splits(p.M, Nw, p.Ktot);
+  p.chunk = cdiv(cdiv(p.M, splits), BP) * BP;
+  wgrad_flatten_pointwise(p);
+  const int rows = wgrad_rows(Nw);
+  const WgradRoute r = wgrad_route(p, rows, precision);
+  return r.loader + 4 * (r.pipe ? 1 : 0) + 8 * r.pd + 64 * rows;
 }
 
 // weight gradient of conv1x1(cat[x, x2]) (vmtl_conv1x1_cat_fwd) in one launch: slabs [splits][Nw][K1 + K2s] with
