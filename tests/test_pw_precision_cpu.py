@@ -109,9 +109,9 @@ def test_conv_launch_routes_the_pointwise_precision(monkeypatch):
     calls = []
     monkeypatch.setattr(ops, "_k", lambda name, _flop=None, _xflop=None, **kw: calls.append((name, kw.get("precision"))))
     plan = ops.ConvPlan("pw", 1, 0, 0)
-    geo = (2, 6, 9, 16, 6, 9, 12, 10, 10, 1, 1, 1, 0)  # B H W Cs Ho Wo ldy Nw Cout KH KW stride pad
+    geo = ops.ConvGeom(2, 6, 9, 16, 6, 9, 12, 1, 1, 1, 0)  # B H W Cs Ho Wo ldy KH KW stride pad
     for prec, pw_prec, want in ((0, 0, ("vmtl_conv1x1_fwd", None)), (1, 0, ("vmtl_conv1x1_fwd", None)),
                                 (1, 1, ("vmtl_conv1x1_fwd_p", 1))):
         calls.clear()
-        ops._conv_launch(None, None, None, None, *geo, prec=prec, plan=plan, pw_prec=pw_prec)
+        ops._conv_launch(None, None, None, None, geo, Cout=10, Nw=10, prec=prec, plan=plan, pw_prec=pw_prec)
         assert calls == [want], (prec, pw_prec)

@@ -80,7 +80,7 @@ def conv_bn_act(x, c: nn.Conv2d, bn: nn.BatchNorm2d, act: int, mul: Act | None =
             y, stats = ops.conv1x1_cat(xa.t, xb.t, xb.C, c.weight, c.bias, want_stats=train,
                                        zero_bias_grad=train and c.bias is not None)
             return bn_act(Act(y, c.out_channels), bn, act, mul, res, stats,
-                          stats_rpb=getattr(stats, "_vmtl_rpb", 0) if stats is not None else 0)
+                          stats_rpb=ops.stats_rpb(stats))
         x = cat(xa, xb)
     if c.groups == 1:
         out = ops.conv2d(x.t, c.weight, c.bias, _pair(c.stride), _pair(c.padding), want_stats=train,
@@ -104,11 +104,11 @@ def conv_raw(x, c: nn.Conv2d, train: bool):
         if (c.kernel_size == (1, 1) and _pair(c.stride) == 1 and _pair(c.padding) == 0 and xa.hw == xb.hw
                 and ops.conv1x1_cat_supported(xa.t, xa.C, xb.t)):
             y, stats = ops.conv1x1_cat(xa.t, xb.t, xb.C, c.weight, c.bias, want_stats=train, zero_bias_grad=zb)
-            return y, stats, getattr(stats, "_vmtl_rpb", 0) if stats is not None else 0
+            return y, stats, ops.stats_rpb(stats)
         x = cat(xa, xb)
     out = ops.conv2d(x.t, c.weight, c.bias, _pair(c.stride), _pair(c.padding), want_stats=train, zero_bias_grad=zb)
     y, stats = out if train else (out, None)
-    return y, stats, getattr(stats, "_vmtl_rpb", 0) if stats is not None else 0
+    return y, stats, ops.stats_rpb(stats)
 
 
 def bn_act(x: Act, bn: nn.BatchNorm2d, act: int, mul: Act | None = None, res: Act | None = None,
@@ -202,7 +202,7 @@ def up2_conv_bn_act(x: Act, skip: Act | None, c: nn.Conv2d, bn: nn.BatchNorm2d, 
         raise ValueError("up2_conv_bn_act expects a 3x3 / pad 1 / stride 1 conv without bias")
     y, stats = ops.up2_conv(x.t, x.C, None if skip is None else skip.t, c.weight, want_stats=bn.training)
     return bn_act(Act(y, c.out_channels), bn, act, None, None, stats,
-                  stats_rpb=getattr(stats, "_vmtl_rpb", 0) if stats is not None else 0)
+                  stats_rpb=ops.stats_rpb(stats))
 
 
 def maxpool2(x: Act) -> Act:

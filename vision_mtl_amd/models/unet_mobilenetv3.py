@@ -193,7 +193,7 @@ class InvertedResidual(nn.Module):
             if fused:
                 out = ops.conv2d(x.t, self.conv_pw.weight, None, 1, 0, want_stats=train)
                 raw1, st1 = out if train else (out, None)
-                rpb1 = getattr(st1, "_vmtl_rpb", 0) if st1 is not None else 0
+                rpb1 = ops.stats_rpb(st1)
         if fused:
             # [bn1 + act + conv_dw as one pre-activation node, bn2's statistics from its epilogue] -> bn2 + act
             dw = self.conv_dw
@@ -292,8 +292,7 @@ class MobileNetV3Encoder(nn.Module):
             out = L.ops.conv2d(x.t, m.conv_stem.weight, None, L._pair(m.conv_stem.stride), L._pair(m.conv_stem.padding),
                                want_stats=train)
             raw0, st0 = out if train else (out, None)
-            rpb0 = getattr(st0, "_vmtl_rpb", 0) if st0 is not None else 0
-            y = first.run_pre(raw0, st0, rpb0, m.bn1, ACT_HSWISH)
+            y = first.run_pre(raw0, st0, L.ops.stats_rpb(st0), m.bn1, ACT_HSWISH)
         else:
             y = L.conv_bn_act(x, m.conv_stem, m.bn1, ACT_HSWISH)
         groups = [[0], [1], [2], [3, 4], [5, 6]]
@@ -345,8 +344,7 @@ class DecoderBlock(nn.Module):
         The caller fuses conv1's BatchNorm + ReLU into what follows (ops.decoder_tail)."""
         c, bn = self.conv1[0], self.conv1[1]
         y, stats = L.ops.up2_conv(x.t, x.C, None if skip is None else skip.t, c.weight, want_stats=bn.training)
-        rpb = 0 if stats is None else stats._vmtl_rpb  # up2_conv tags the rows with the pixels each covers
-        return L.Act(y, c.out_channels), stats, rpb
+        return L.Act(y, c.out_channels), stats, L.ops.stats_rpb(stats)  # up2_conv tags the rows with the pixels each covers
 
 
 class UnetDecoder(nn.Module):

@@ -634,14 +634,120 @@ def eval_bn_table(model):
         eval_bn.active = prev
 
 
-def _bn_eval_stats(rm, rv, C, Cs, eps, like):
-    """(mean, invstd) of an eval-mode BatchNorm: from the table in force, else one launch."""
-    e = eval_bn.get(rm, C, eps)
-    if e is not None:
-        return e[0], e[1]
-    mean, invstd = _empty((Cs,), like), _empty((Cs,), like)
-    _k("vmtl_bn_eval_stats", running_mean=rm, running_var=rv, C=C, Cs=Cs, eps=eps, save_mean=mean, save_invstd=invstd)
-    return mean, invstd
+# ----------------------------------------------------------------------------- BatchNorm steps the nodes share
+# (which node uses which, and who resolves the row block)
+def stats_rpb(stats):
+    """Pixels each row of conv-epilogue statistics rows covers: the `_vmtl_rpb` tag their producer put on them, else 0
+    (no rows, or rows nobody tagged)."""
+    return 0 if stats is None else getattr(stats, "_vmtl_rpb", 0)
+
+
+def _resolve_rpb(stats, rpb, shape):
+    """Pixels per row of `stats` for the wrappers that accept untagged rows (bn_act, bn_act_pool2, bn_act_pool3,
+    bn_add_act): the explicit argument, else the rows' tag, else the implicit-GEMM kernel's row block for the activation
+    shape (B, H, W, Cs); 0 without rows.  The pre-activation nodes (bn_act_conv, bn_act_conv1x1, bn_act_dwconv,
+    decoder_tail) do not call this: they hand their rpb argument to the launch as given, and the library refuses a 0."""
+    if stats is None:
+        return 0
+    return rpb or stats_rpb(stats) or lib().raw("vmtl_conv2d_stats_block")(*shape)
+
+
+def _bn_args(bn):
+    """((weight, bias, running_mean, running_var, num_batches_tracked), (training, momentum, eps)) of an nn.BatchNorm2d."""
+    if bn.momentum is None:
+        raise NotImplementedError("BatchNorm2d(momentum=None) (cumulative moving average) is not implemented")
+    return ((bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked),
+            (bn.training, float(bn.momentum), bn.eps))
+
+
+def _bn_stats(x, stats, rpb, rm, rv, nbt, C, training, momentum, eps, affine=None):
+    """(mean, invstd) of a BatchNorm over x; with affine = (gamma, beta) also (coef_a, coef_c), BN(x) = coef_a * x + coef_c
+    per channel (zeros on pad channels).  Train: batch statistics from the producing conv's partial rows `stats` (rpb
+    pixels each, as the caller resolved them) or from a sweep of x, the running buffers moved as torch moves them.
+    Eval: the running statistics, from the eval_bn_table in force (no launch) or one launch."""
+    B, H, W, Cs = x.shape
+    if not training:
+        e = eval_bn.get(rm, C, eps, affine)
+        if e is not None:
+            return e[:2] if affine is None else e
+    mean, invstd = _empty((Cs,), x), _empty((Cs,), x)
+    if affine is None:
+        out, kw = (mean, invstd), {}
+    else:
+        ca, cc = _empty((Cs,), x), _empty((Cs,), x)
+        out, kw = (mean, invstd, ca, cc), {"gamma": affine[0], "beta": affine[1], "coef_a": ca, "coef_c": cc}
+    if training:
+        M = B * H * W
+        if stats is not None:
+            partial, nblk = stats, stats.shape[0]
+        else:
+            partial, nblk, rpb = _empty((_reduce_rows(M), 2, Cs), x), 0, 0
+        _k("vmtl_bn_stats" if affine is None else "vmtl_bn_stats_coef", x=x, M=M, C=C, Cs=Cs, partial=partial,
+           nblk_from_conv=nblk, rows_per_blk_from_conv=rpb, eps=eps, momentum=momentum, running_mean=rm, running_var=rv,
+           num_batches_tracked=nbt, save_mean=mean, save_invstd=invstd, **kw)
+    else:
+        _k("vmtl_bn_eval_stats" if affine is None else "vmtl_bn_eval_stats_coef", running_mean=rm, running_var=rv, C=C,
+           Cs=Cs, eps=eps, save_mean=mean, save_invstd=invstd, **kw)
+    return out
+
+
+def _bn_apply(x, stats, rpb, gamma, beta, rm, rv, nbt, C, training, momentum, eps, act, mul=None, res=None):
+    """(y, mean, invstd) with y = act(BN(x)) [* mul] [+ res], materialised.  Few statistics rows: every thread of the apply
+    launch merges them itself (vmtl_bn_apply_fused), no separate finalize launch."""
+    B, H, W, Cs = x.shape
+    M = B * H * W
+    y = _empty(x.shape, x)
+    if training and stats is not None and stats.shape[0] <= _BN_FUSE_ROWS:
+        mean, invstd = _empty((Cs,), x), _empty((Cs,), x)
+        _k("vmtl_bn_apply_fused", x=x, partial=stats, nblk=stats.shape[0], rows_per_blk=rpb, eps=eps, momentum=momentum,
+           running_mean=rm, running_var=rv, num_batches_tracked=nbt, save_mean=mean, save_invstd=invstd, gamma=gamma,
+           beta=beta, mul=mul, res=res, y=y, M=M, C=C, Cs=Cs, act=act)
+    else:
+        mean, invstd = _bn_stats(x, stats, rpb, rm, rv, nbt, C, training, momentum, eps)
+        _k("vmtl_bn_apply", x=x, mean=mean, invstd=invstd, gamma=gamma, beta=beta, mul=mul, res=res, y=y, M=M, C=C, Cs=Cs,
+           act=act)
+    return y, mean, invstd
+
+
+def _bn_bwd_tail(part, rows, x, dz, mean, invstd, gamma, C, training, slots, want_dx):
+    """(dx, dgamma, dbeta) of a BatchNorm whose backward reduction came out of the producing data gradient's epilogue:
+    dz and its `rows` partial rows `part`.  Finalize the column sums, then (want_dx) the backward-apply sweep.
+    slots = the arena slots of (gamma, beta): a gradient a slot took is handed back as None."""
+    B, H, W, Cs = x.shape
+    M, tr = B * H * W, 1 if training else 0
+    dgamma, dbeta = _grad_buf((C,), slots[0], x), _grad_buf((C,), slots[1], x)
+    _k("vmtl_bn_bwd_finalize", partial=part, nblk=rows, M=M, C=C, Cs=Cs, sum_dz=dbeta, sum_dzx=dgamma, mean=None,
+       invstd=None, gamma=None, training=tr, coef_a=None, coef_b=None, coef_c=None)
+    dx = None
+    if want_dx:
+        dx = _empty(x.shape, x)
+        _k("vmtl_bn_bwd_apply", x=x, dz=dz, mean=mean, invstd=invstd, gamma=gamma, sum_dz=dbeta, sum_dzx=dgamma, dx=dx, M=M,
+           C=C, Cs=Cs, training=tr)
+    return dx, _grad_ret(dgamma, slots[0]), _grad_ret(dbeta, slots[1])
+
+
+def _bn_bwd(x, dy, mean, invstd, gamma, beta, C, training, act, slots, mul=None, want_dmul=False):
+    """(dx, dgamma, dbeta, dmul) of y = act(BN(x)) [* mul] from dy in one launch (reduce + apply); gamma None: of the plain
+    activation.  slots as in _bn_bwd_tail; the kernels write exactly C entries of each sum."""
+    B, H, W, Cs = x.shape
+    M = B * H * W
+    dmul = _empty(x.shape, x) if want_dmul else None
+    partial = dgamma = dbeta = None
+    if gamma is not None or dmul is not None:
+        partial = _empty((_reduce_rows(M), 2, Cs), x)
+    if gamma is not None:
+        dgamma, dbeta = _grad_buf((C,), slots[0], x), _grad_buf((C,), slots[1], x)
+    dx = _empty(x.shape, x)
+    _k("vmtl_bn_bwd", x=x, dy=dy, mean=mean, invstd=invstd, gamma=gamma, beta=beta, mul=mul, dmul=dmul, partial=partial,
+       sum_dz=dbeta, sum_dzx=dgamma, dx=dx, M=M, C=C, Cs=Cs, act=act, training=1 if training else 0)
+    return dx, _grad_ret(dgamma, slots[0]), _grad_ret(dbeta, slots[1]), dmul
+
+
+def _ez_kw(ez):
+    """Keywords of a data-gradient launch whose epilogue runs act' and the BatchNorm-backward reduction of the conv's own
+    input: ez = (x, mean, invstd, gamma, beta, act) of that BatchNorm, None for a launch without the epilogue."""
+    x, mean, invstd, gamma, beta, act = ez or (None, None, None, None, None, ACT_NONE)
+    return dict(ez_x=x, ez_mean=mean, ez_invstd=invstd, ez_gamma=gamma, ez_beta=beta, ez_act=act)
 
 
 def pack(src, R1, R0, T, C, Cs, sr1, sr0, st, sc, flip=0, out=None):
@@ -831,10 +937,8 @@ def up2_plan(B, H2, W2, C0s, C1s, ldy, Cout, prec, want_stats) -> ConvPlan:
 def _mid_halo(x, wp, y, B, H, W, Cs, ldy, Nw, Cout, flop, pa=None, pc=None, act_in=ACT_NONE, a_out=None, bias=None,
               stats=None, ep_mode=0, ez=None):
     """One vmtl_conv3x3_halo launch; ez = (x, mean, invstd, gamma, beta, act) for ep_mode 2."""
-    ez = ez or (None, None, None, None, None, ACT_NONE)
     _k("vmtl_conv3x3_halo", _flop=flop, x=x, pa=pa, pc=pc, act_in=act_in, a_out=a_out, wp=wp, bias=bias, y=y, stats=stats,
-       ep_mode=ep_mode, ez_x=ez[0], ez_mean=ez[1], ez_invstd=ez[2], ez_gamma=ez[3], ez_beta=ez[4], ez_act=ez[5], B=B, H=H,
-       W=W, Cs=Cs, ldy=ldy, Nw=Nw, Cout=Cout)
+       ep_mode=ep_mode, B=B, H=H, W=W, Cs=Cs, ldy=ldy, Nw=Nw, Cout=Cout, **_ez_kw(ez))
 
 
 def _halo_launch(route, x, wp, y, g, Nw, Cout, flop, **kw):
@@ -843,18 +947,12 @@ def _halo_launch(route, x, wp, y, g, Nw, Cout, flop, **kw):
     (_small if route == "small" else _mid_halo)(x, wp, y, g.B, g.H, g.W, g.Cs, g.ldy, Nw, Cout, flop, **kw)
 
 
-def _conv_launch(x, wp, bias, y, g, *legacy, Cout=None, Nw=None, shuffle=0, cin=None, algo_flop=None, prec=0, plan=None, stats=None,
+def _conv_launch(x, wp, bias, y, g, *, Cout, Nw=None, shuffle=0, cin=None, algo_flop=None, prec=0, plan=None, stats=None,
                  pw_prec=0):
     """One dense conv launch of geometry g, dispatched on its plan; a launch without an epilogue may leave the planning to
     this function.  Cout: logical output channels, Nw: rows of the operand wp (Cout unless given).
     stats: the [plan.stats_rows][2][ldy] rows of a plan with the statistics epilogue.  prec: the implicit GEMM's precision,
-    pw_prec: the pointwise GEMM's (the plan itself does not depend on pw_prec).
-    The earlier all-positional run (..., y, B, H, W, Cs, Ho, Wo, ldy, Nw, Cout, KH, KW, stride, pad) is still accepted, for
-    one caller only: tests/test_pw_precision_cpu.py::test_conv_launch_routes_the_pointwise_precision.  Nothing in the package
-    or in tools/ uses it; new code passes a ConvGeom."""
-    if legacy:
-        B, H, W, Cs, Ho, Wo, ldy, Nw, Cout, KH, KW, stride, pad = (g, *legacy)
-        g = ConvGeom(B, H, W, Cs, Ho, Wo, ldy, KH, KW, stride, pad)
+    pw_prec: the pointwise GEMM's (the plan itself does not depend on pw_prec)."""
     B, H, W, Cs, Ho, Wo, ldy, KH, KW, stride, pad = g
     if Nw is None:
         Nw = Cout
@@ -1074,7 +1172,7 @@ class _BNActPw(torch.autograd.Function):
             res = _req(res, "res")
             if tuple(res.shape) != tuple(x.shape) or act != ACT_NONE:
                 raise ValueError("bn_act_conv1x1: the residual operand needs x's shape and no activation (bn3 + skip)")
-        mean, invstd, ca, cc = _bn_fwd_coef(x, stats, rpb, gamma, beta, rm, rv, nbt, C, training, momentum, eps)
+        mean, invstd, ca, cc = _bn_stats(x, stats, rpb, rm, rv, nbt, C, training, momentum, eps, (gamma, beta))
         wp = packs.get(weight, "fwd", Layout.fwd(Cout, Cin, 1, Cs))
         ldy = ceil4(Cout)
         a, y = _empty(x.shape, x), _empty((B, H, W, ldy), x)
@@ -1119,26 +1217,20 @@ class _BNActPw(torch.autograd.Function):
         fork = side.mark()
         # ---- data gradient w.r.t. a = act(BN(x)), with act' and the BatchNorm-backward column sums in the epilogue
         wd = packs.get(weight, "dgrad", Layout.dgrad(Cout, Cin, 1, ldy))
-        dgamma, dbeta = _grad_buf((C,), sg, x), _grad_buf((C,), sb, x)
         dz = _empty(x.shape, x)
         rows = lib().raw("vmtl_conv1x1_stats_rows")(M, Cs, ldy, 0 if d_a is None else 1)
         part = _empty((rows, 2, Cs), x)
+        ez = _ez_kw((x, mean, invstd, gamma, beta, act))
         if d_a is None:
-            _kp("vmtl_conv1x1_bnbwd", ctx.pw_prec, _flop=2.0 * M * Cin * Cout, dy=dy, wp=wd, dz=dz, stats=part, ez_x=x,
-                ez_mean=mean, ez_invstd=invstd, ez_gamma=gamma, ez_beta=beta, ez_act=act, M=M, Ks=ldy, ldy=Cs, Nw=Cin, Cout=Cin)
+            _kp("vmtl_conv1x1_bnbwd", ctx.pw_prec, _flop=2.0 * M * Cin * Cout, dy=dy, wp=wd, dz=dz, stats=part, M=M, Ks=ldy,
+                ldy=Cs, Nw=Cin, Cout=Cin, **ez)
         else:  # + the gradient that reached a through its other consumers, added before act' and the reduction
             if act != ACT_NONE:
                 raise NotImplementedError("bn_act_conv1x1: a second consumer of the activation needs act = none")
             _kp("vmtl_conv1x1_bnbwd_add", ctx.pw_prec, _flop=2.0 * M * Cin * Cout, dy=dy, wp=wd, addend=_req(d_a, "d_a"), dz=dz,
-                stats=part, ez_x=x, ez_mean=mean, ez_invstd=invstd, ez_gamma=gamma, ez_beta=beta, ez_act=act, M=M, Ks=ldy,
-                ldy=Cs, Nw=Cin, Cout=Cin)
-        _k("vmtl_bn_bwd_finalize", partial=part, nblk=rows, M=M, C=C, Cs=Cs, sum_dz=dbeta, sum_dzx=dgamma, mean=None,
-           invstd=None, gamma=None, training=1 if training else 0, coef_a=None, coef_b=None, coef_c=None)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = _empty(x.shape, x)
-            _k("vmtl_bn_bwd_apply", x=x, dz=dz, mean=mean, invstd=invstd, gamma=gamma, sum_dz=dbeta, sum_dzx=dgamma, dx=dx,
-               M=M, C=C, Cs=Cs, training=1 if training else 0)
+                stats=part, M=M, Ks=ldy, ldy=Cs, Nw=Cin, Cout=Cin, **ez)
+        dx, dgamma, dbeta = _bn_bwd_tail(part, rows, x, dz, mean, invstd, gamma, C, training, (sg, sb),
+                                         ctx.needs_input_grad[0])
         # ---- parameter gradients (side stream when they go to arena slots)
         dw = _grad_buf(weight.shape, sw, x)
         with side.branch(sw is not None, M, fork, dy, a):
@@ -1149,8 +1241,7 @@ class _BNActPw(torch.autograd.Function):
             db = _bias_grad(ctx.bias, sbias, dy, M, Cout, ldy, zero_bias, fork)
         # act = none with a residual: d(res) is the gradient w.r.t. a itself = dz (no activation derivative in it)
         dres = dz if has_res and ctx.needs_input_grad[10] else None
-        return (dx, None, None, _grad_ret(dgamma, sg), _grad_ret(dbeta, sb), None, None, None, _grad_ret(dw, sw), db, dres,
-                None)
+        return dx, None, None, dgamma, dbeta, None, None, None, _grad_ret(dw, sw), db, dres, None
 
 
 _BN_PW_MAX_ROWS = int(os.environ.get("VMTL_BN_PW_MAX_ROWS", str(1 << 30)))
@@ -1167,11 +1258,9 @@ def bn_act_conv1x1(x, stats, rpb, bn, C, act, weight, bias=None, want_stats=True
     """(y_raw, stats, rows_per_block[, a]) = conv1x1(a) (+ bias) with a = act(bn(x_raw)) [+ res]; bn = the nn.BatchNorm2d
     container of x's layer; res (act = none only): the skip connection added to the normalised map; return_act: also
     hand back a (differentiable) for its other consumers (the block's own skip branch, a decoder tap)."""
-    if bn.momentum is None:
-        raise NotImplementedError("BatchNorm2d(momentum=None) (cumulative moving average) is not implemented")
-    cfg = (C, bn.training, float(bn.momentum), bn.eps, act, bool(want_stats), bool(zero_bias_grad), bool(return_act))
-    out = _BNActPw.apply(x, stats, rpb, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
-                         weight, bias, res, cfg)
+    tensors, mode = _bn_args(bn)
+    cfg = (C, *mode, act, bool(want_stats), bool(zero_bias_grad), bool(return_act))
+    out = _BNActPw.apply(x, stats, rpb, *tensors, weight, bias, res, cfg)
     y, ostats = out[0], out[1]
     orpb = 0
     if ostats is not None:
@@ -1348,29 +1437,11 @@ class _BNActConv(torch.autograd.Function):
         # input element, written back to a); everything else materialises a first
         pro = not up2 and skip is None and Cin == C and act in (ACT_NONE, ACT_RELU) and plan.route == "mid_halo"
         # ---- BatchNorm + activation (materialised: the weight gradient reads it)
-        a = _empty(x.shape, x)
         if pro:
-            mean, invstd, ca, cc = _bn_fwd_coef(x, stats, rpb, gamma, beta, rm, rv, nbt, C, training, momentum, eps)
-        elif training:
-            mean, invstd = _empty((Cs,), x), _empty((Cs,), x)
-            if stats is not None:
-                partial, nblk = stats, stats.shape[0]
-            else:
-                partial, nblk, rpb = _empty((_reduce_rows(M), 2, Cs), x), 0, 0
-            if 0 < nblk <= _BN_FUSE_ROWS:
-                _k("vmtl_bn_apply_fused", x=x, partial=partial, nblk=nblk, rows_per_blk=rpb, eps=eps, momentum=momentum,
-                   running_mean=rm, running_var=rv, num_batches_tracked=nbt, save_mean=mean, save_invstd=invstd,
-                   gamma=gamma, beta=beta, mul=None, res=None, y=a, M=M, C=C, Cs=Cs, act=act)
-            else:
-                _k("vmtl_bn_stats", x=x, M=M, C=C, Cs=Cs, partial=partial, nblk_from_conv=nblk, rows_per_blk_from_conv=rpb,
-                   eps=eps, momentum=momentum, running_mean=rm, running_var=rv, num_batches_tracked=nbt, save_mean=mean,
-                   save_invstd=invstd)
-                _k("vmtl_bn_apply", x=x, mean=mean, invstd=invstd, gamma=gamma, beta=beta, mul=None, res=None, y=a, M=M,
-                   C=C, Cs=Cs, act=act)
+            a = _empty(x.shape, x)
+            mean, invstd, ca, cc = _bn_stats(x, stats, rpb, rm, rv, nbt, C, training, momentum, eps, (gamma, beta))
         else:
-            mean, invstd = _bn_eval_stats(rm, rv, C, Cs, eps, x)
-            _k("vmtl_bn_apply", x=x, mean=mean, invstd=invstd, gamma=gamma, beta=beta, mul=None, res=None, y=a, M=M, C=C,
-               Cs=Cs, act=act)
+            a, mean, invstd = _bn_apply(x, stats, rpb, gamma, beta, rm, rv, nbt, C, training, momentum, eps, act)
         # ---- the conv on a
         if up2:
             if skip is not None:
@@ -1431,8 +1502,6 @@ class _BNActConv(torch.autograd.Function):
             wd = packs.get(weight, "dgrad", Layout.dgrad(Cout, Cin, 9, ldy))
             geo = gfwd.dgrad()
             flop = xflop = 2.0 * M * Cin * 9 * Cout
-        dgamma, dbeta = _grad_buf((C,), sg, x), _grad_buf((C,), sb, x)
-        dx = _empty(x.shape, x) if ctx.needs_input_grad[0] else None
         plan = conv_plan(*geo, prec=ctx.prec, epilogue="bnbwd")
         if plan.stats_rows:  # fused: the halo-tile kernels (ep_mode 2) or the implicit GEMM's BatchNorm-backward epilogue
             dz = _empty(x.shape, x)
@@ -1441,20 +1510,14 @@ class _BNActConv(torch.autograd.Function):
             if plan.route in ("small", "mid_halo"):
                 _halo_launch(plan.route, dy, wd, dz, geo, C, C, flop, stats=part, ep_mode=2, ez=ez)
             else:
-                _kp("vmtl_conv2d_bnbwd", ctx.prec, _flop=flop, _xflop=xflop, x=dy, wp=wd, y=dz, stats=part, ez_x=x, ez_mean=mean,
-                    ez_invstd=invstd, ez_gamma=gamma, ez_beta=beta, ez_act=act, Nw=C, Cout=C, **geo._asdict())
-            _k("vmtl_bn_bwd_finalize", partial=part, nblk=plan.stats_rows, M=M, C=C, Cs=Cs, sum_dz=dbeta, sum_dzx=dgamma,
-               mean=None, invstd=None, gamma=None, training=1 if training else 0, coef_a=None, coef_b=None, coef_c=None)
-            if dx is not None:
-                _k("vmtl_bn_bwd_apply", x=x, dz=dz, mean=mean, invstd=invstd, gamma=gamma, sum_dz=dbeta, sum_dzx=dgamma,
-                   dx=dx, M=M, C=C, Cs=Cs, training=1 if training else 0)
+                _kp("vmtl_conv2d_bnbwd", ctx.prec, _flop=flop, _xflop=xflop, x=dy, wp=wd, y=dz, stats=part, Nw=C, Cout=C,
+                    **_ez_kw(ez), **geo._asdict())
+            dx, dgamma, dbeta = _bn_bwd_tail(part, plan.stats_rows, x, dz, mean, invstd, gamma, C, training, (sg, sb),
+                                             ctx.needs_input_grad[0])
         else:  # split-K data gradient (tile-starved layers) or VMTL_BNBWD_FUSE=0: unfused BatchNorm backward
             da = _empty(x.shape, x)
             _conv_launch(dy, wd, None, da, geo, Cout=C, cin=Cout, algo_flop=flop, prec=ctx.prec, plan=plan)
-            part = _empty((_reduce_rows(M), 2, Cs), x)
-            _k("vmtl_bn_bwd", x=x, dy=da, mean=mean, invstd=invstd, gamma=gamma, beta=beta, mul=None, dmul=None,
-               partial=part, sum_dz=dbeta, sum_dzx=dgamma, dx=dx if dx is not None else _empty(x.shape, x), M=M, C=C, Cs=Cs,
-               act=act, training=1 if training else 0)
+            dx, dgamma, dbeta, _ = _bn_bwd(x, da, mean, invstd, gamma, beta, C, training, act, (sg, sb))
         dskip = None
         if up2 and skip is not None and ctx.needs_input_grad[9]:
             dskip = _up2_dskip(dy, weight, skip, C, ctx.prec)
@@ -1466,24 +1529,20 @@ class _BNActConv(torch.autograd.Function):
             else:
                 _wgrad_into(a, dy, gfwd, Layout.fwd(Cout, Cin, 9, Cs), dw, 2.0 * M * Cout * 9 * Cin, ctx.prec)
             stamp(f"side bnconv N={Cout} Cin={Cin}")
-        return (dx, None, None, _grad_ret(dgamma, sg), _grad_ret(dbeta, sb), None, None, None, _grad_ret(dw, sw), dskip,
-                None)
+        return dx, None, None, dgamma, dbeta, None, None, None, _grad_ret(dw, sw), dskip, None
 
 
 def bn_act_conv(x, stats, rpb, bn, C, act, weight, skip=None, up2=False, want_stats=True):
     """(y_raw, stats, rows_per_block) = conv3x3(act(bn(x_raw)))  (up2: nearest-x2 of it, concatenated with skip, first);
     bn is the nn.BatchNorm2d parameter container of x's layer, C its logical channel count."""
-    if bn.momentum is None:
-        raise NotImplementedError("BatchNorm2d(momentum=None) (cumulative moving average) is not implemented")
+    tensors, mode = _bn_args(bn)
     B, H, W, Cs = x.shape
     Cout, prec = weight.shape[0], conv_prec_code()
     if up2:
         plan = up2_plan(B, H, W, Cs, 0 if skip is None else skip.shape[3], ceil4(Cout), Cout, prec, want_stats)
     else:
         plan = conv_plan(B, H, W, Cs, H, W, ceil4(Cout), 3, 3, 1, 1, prec=prec, epilogue="stats" if want_stats else None)
-    cfg = (C, bn.training, float(bn.momentum), bn.eps, act, bool(up2), plan)
-    y, ostats = _BNActConv.apply(x, stats, rpb, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                                 bn.num_batches_tracked, weight, skip, cfg)
+    y, ostats = _BNActConv.apply(x, stats, rpb, *tensors, weight, skip, (C, *mode, act, bool(up2), plan))
     return y, ostats, plan.rpb
 
 
@@ -1627,7 +1686,7 @@ class _BNActDw(torch.autograd.Function):
             raise ValueError("bn_act_dwconv: weight must be (C, 1, K, K) over x's channels with pad (K-1)//2")
         Ho = (H + 2 * pad - K) // stride + 1
         Wo = (W + 2 * pad - K) // stride + 1
-        mean, invstd, ca, cc = _bn_fwd_coef(x, stats, rpb, gamma, beta, rm, rv, nbt, C, training, momentum, eps)
+        mean, invstd, ca, cc = _bn_stats(x, stats, rpb, rm, rv, nbt, C, training, momentum, eps, (gamma, beta))
         wp = packs.get(weight, "dw", Layout.dw(C, K, Cs))
         need_bwd = any(ctx.needs_input_grad)
         a = _empty(x.shape, x) if need_bwd or return_act else None
@@ -1660,7 +1719,6 @@ class _BNActDw(torch.autograd.Function):
         B, H, W, Cs = x.shape
         K = weight.shape[2]
         _, Ho, Wo, _ = dy.shape
-        M = B * H * W
         stamp(f"main bndw M={B * Ho * Wo} C={C}")
         fork = side.mark()
         da = _empty(x.shape, x)
@@ -1669,28 +1727,22 @@ class _BNActDw(torch.autograd.Function):
                K=K, stride=stride, pad=pad)
         else:
             _k("vmtl_dwconv_bwd_data", dy=dy, wp=wp, dx=da, B=B, H=H, W=W, Cs=Cs, Ho=Ho, Wo=Wo, K=K, stride=stride, pad=pad)
-        dgamma, dbeta = _grad_buf((C,), sg, x), _grad_buf((C,), sb, x)
-        dx = _empty(x.shape, x)
-        part = _empty((_reduce_rows(M), 2, Cs), x)
-        _k("vmtl_bn_bwd", x=x, dy=da, mean=mean, invstd=invstd, gamma=gamma, beta=beta, mul=None, dmul=None, partial=part,
-           sum_dz=dbeta, sum_dzx=dgamma, dx=dx, M=M, C=C, Cs=Cs, act=act, training=1 if training else 0)
+        dx, dgamma, dbeta, _ = _bn_bwd(x, da, mean, invstd, gamma, beta, C, training, act, (sg, sb))
         dw = _grad_buf(weight.shape, sw, x)
         with side.branch(sw is not None, B * Ho * Wo, fork, a, dy):
             partial = _empty((lib().raw("vmtl_dwconv_bwd_weight_rows")(B * Ho * Wo, Cs), K * K, Cs), x)
             _k("vmtl_dwconv_bwd_weight", x=a, dy=dy, partial=partial, dw=dw, B=B, H=H, W=W, C=C, Cs=Cs, Ho=Ho, Wo=Wo, K=K,
                stride=stride, pad=pad)
             stamp(f"side bndw C={C}")
-        return dx, None, None, _grad_ret(dgamma, sg), _grad_ret(dbeta, sb), None, None, None, _grad_ret(dw, sw), None
+        return dx, None, None, dgamma, dbeta, None, None, None, _grad_ret(dw, sw), None
 
 
 def bn_act_dwconv(x, stats, rpb, bn, C, act, weight, stride=1, pad=1, want_stats=True, return_act=False):
     """(y_raw, stats, rows_per_block[, a]) = dwconv(act(bn(x_raw))); bn = the nn.BatchNorm2d container of x's layer;
     return_act: also hand back a = act(bn(x_raw)) (differentiable) for a second consumer of the activation."""
-    if bn.momentum is None:
-        raise NotImplementedError("BatchNorm2d(momentum=None) (cumulative moving average) is not implemented")
-    cfg = (C, bn.training, float(bn.momentum), bn.eps, act, stride, pad, bool(want_stats), bool(return_act))
-    out = _BNActDw.apply(x, stats, rpb, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                         bn.num_batches_tracked, weight, cfg)
+    tensors, mode = _bn_args(bn)
+    cfg = (C, *mode, act, stride, pad, bool(want_stats), bool(return_act))
+    out = _BNActDw.apply(x, stats, rpb, *tensors, weight, cfg)
     y, ostats = out[0], out[1]
     orpb = lib().raw("vmtl_dwconv_bn_stats_block")(y.shape[0] * y.shape[1] * y.shape[2], y.shape[3]) if ostats is not None else 0
     return (y, ostats, orpb, out[2]) if return_act else (y, ostats, orpb)
@@ -1714,39 +1766,17 @@ class _BNAct(torch.autograd.Function):
                 act, stats_rpb=0):
         x = _req(x, "x")
         B, H, W, Cs = x.shape
-        M = B * H * W
-        mean = invstd = None
         if mul is not None:
             mul = _req(mul, "mul")
         if res is not None:
             res = _req(res, "res")
-        y = _empty(x.shape, x)
-        fused = False
-        if gamma is not None:
-            if training:
-                mean, invstd = _empty((Cs,), x), _empty((Cs,), x)
-                if stats is not None:
-                    partial, nblk = stats, stats.shape[0]
-                    rpb = stats_rpb if stats_rpb else lib().raw("vmtl_conv2d_stats_block")(B, H, W, Cs)
-                    if nblk <= _BN_FUSE_ROWS:
-                        # few statistics rows: every thread merges them itself, no separate finalize launch
-                        _k("vmtl_bn_apply_fused", x=x, partial=partial, nblk=nblk, rows_per_blk=rpb, eps=eps,
-                           momentum=momentum, running_mean=running_mean, running_var=running_var,
-                           num_batches_tracked=nbt, save_mean=mean, save_invstd=invstd, gamma=gamma, beta=beta, mul=mul,
-                           res=res, y=y, M=M, C=C, Cs=Cs, act=act)
-                        fused = True
-                else:
-                    partial, nblk, rpb = _empty((_reduce_rows(M), 2, Cs), x), 0, 0
-                if not fused:
-                    _k("vmtl_bn_stats", x=x, M=M, C=C, Cs=Cs, partial=partial, nblk_from_conv=nblk,
-                       rows_per_blk_from_conv=rpb, eps=eps,
-                       momentum=momentum, running_mean=running_mean, running_var=running_var, num_batches_tracked=nbt,
-                       save_mean=mean, save_invstd=invstd)
-            else:
-                mean, invstd = _bn_eval_stats(running_mean, running_var, C, Cs, eps, x)
-        if not fused:
-            _k("vmtl_bn_apply", x=x, mean=mean, invstd=invstd, gamma=gamma, beta=beta, mul=mul, res=res, y=y, M=M, C=C,
+        if gamma is None:  # plain activation: nothing to normalise with
+            y, mean, invstd = _empty(x.shape, x), None, None
+            _k("vmtl_bn_apply", x=x, mean=None, invstd=None, gamma=None, beta=beta, mul=mul, res=res, y=y, M=B * H * W, C=C,
                Cs=Cs, act=act)
+        else:
+            y, mean, invstd = _bn_apply(x, stats, stats_rpb, gamma, beta, running_mean, running_var, nbt, C, training,
+                                        momentum, eps, act, mul, res)
         ctx.save_for_backward(x, gamma, beta, mean, invstd, mul)
         ctx.cfg = (C, training, act, res is not None)
         ctx.slots = (_slot(gamma), _slot(beta))
@@ -1757,32 +1787,17 @@ class _BNAct(torch.autograd.Function):
         x, gamma, beta, mean, invstd, mul = ctx.saved_tensors
         C, training, act, has_res = ctx.cfg
         dy = _req(dy, "dy")
-        B, H, W, Cs = x.shape
-        M = B * H * W
-        need_sums = gamma is not None
-        dmul = _empty(x.shape, x) if (mul is not None and ctx.needs_input_grad[6]) else None
-        partial = sum_dz = sum_dzx = None
-        if need_sums or dmul is not None:
-            partial = _empty((_reduce_rows(M), 2, Cs), x)
-        if need_sums:  # the kernels write exactly C entries: [dbeta | dgamma] may be arena slots
-            sum_dzx, sum_dz = _grad_buf((C,), ctx.slots[0], x), _grad_buf((C,), ctx.slots[1], x)
-        dx = _empty(x.shape, x)
-        _k("vmtl_bn_bwd", x=x, dy=dy, mean=mean, invstd=invstd, gamma=gamma, beta=beta, mul=mul, dmul=dmul,
-           partial=partial, sum_dz=sum_dz, sum_dzx=sum_dzx, dx=dx, M=M, C=C, Cs=Cs, act=act,
-           training=1 if training else 0)
-        dgamma, dbeta = _grad_ret(sum_dzx, ctx.slots[0]), _grad_ret(sum_dz, ctx.slots[1])  # both None without a BatchNorm
+        dx, dgamma, dbeta, dmul = _bn_bwd(x, dy, mean, invstd, gamma, beta, C, training, act, ctx.slots, mul,
+                                          mul is not None and ctx.needs_input_grad[6])
         return (dx, dgamma, dbeta, None, None, None, dmul, dy if has_res else None, None, None, None, None, None,
                 None, None)
 
 
 def bn_act(x, gamma, beta, running_mean, running_var, nbt, C, training, momentum=0.1, eps=1e-5, act=ACT_NONE,
            mul=None, res=None, stats=None, stats_rpb=0):
-    """stats: BatchNorm partial rows from the producing conv's epilogue, stats_rpb pixels each (0: taken from the
-    `_vmtl_rpb` tag ops.conv2d puts on them, else the implicit-GEMM kernel's row block for this shape)."""
-    if stats is not None and not stats_rpb:
-        stats_rpb = getattr(stats, "_vmtl_rpb", 0)
+    """stats: BatchNorm partial rows from the producing conv's epilogue, stats_rpb pixels each (0: _resolve_rpb)."""
     return _BNAct.apply(x, gamma, beta, running_mean, running_var, nbt, mul, res, stats, C, training, momentum, eps,
-                        act, stats_rpb)
+                        act, _resolve_rpb(stats, stats_rpb, x.shape))
 
 
 class _BNActPool(torch.autograd.Function):
@@ -1793,19 +1808,7 @@ class _BNActPool(torch.autograd.Function):
     def forward(ctx, x, gamma, beta, running_mean, running_var, nbt, stats, C, training, momentum, eps, act, stats_rpb):
         x = _req(x, "x")
         B, H, W, Cs = x.shape
-        M = B * H * W
-        if training:
-            mean, invstd = _empty((Cs,), x), _empty((Cs,), x)
-            if stats is not None:
-                partial, nblk = stats, stats.shape[0]
-                rpb = stats_rpb if stats_rpb else lib().raw("vmtl_conv2d_stats_block")(B, H, W, Cs)
-            else:
-                partial, nblk, rpb = _empty((_reduce_rows(M), 2, Cs), x), 0, 0
-            _k("vmtl_bn_stats", x=x, M=M, C=C, Cs=Cs, partial=partial, nblk_from_conv=nblk, rows_per_blk_from_conv=rpb,
-               eps=eps, momentum=momentum, running_mean=running_mean, running_var=running_var, num_batches_tracked=nbt,
-               save_mean=mean, save_invstd=invstd)
-        else:
-            mean, invstd = _bn_eval_stats(running_mean, running_var, C, Cs, eps, x)
+        mean, invstd = _bn_stats(x, stats, stats_rpb, running_mean, running_var, nbt, C, training, momentum, eps)
         y = _empty((B, H // 2, W // 2, Cs), x)
         _k("vmtl_bn_act_pool2_fwd", x=x, mean=mean, invstd=invstd, gamma=gamma, beta=beta, y=y, B=B, H=H, W=W, C=C, Cs=Cs,
            act=act)
@@ -1836,31 +1839,11 @@ def bn_act_pool2(x, gamma, beta, running_mean, running_var, nbt, C, training, mo
                  stats=None, stats_rpb=0):
     """maxpool2(act(BN(x))); falls back to the two separate nodes for odd extents (MaxPool2d floors) or when switched off."""
     B, H, W, Cs = x.shape
-    if stats is not None and not stats_rpb:
-        stats_rpb = getattr(stats, "_vmtl_rpb", 0)
+    stats_rpb = _resolve_rpb(stats, stats_rpb, x.shape)
     if not FUSE_BN_POOL or (H & 1) or (W & 1) or H < 2 or W < 2:
         return maxpool2(bn_act(x, gamma, beta, running_mean, running_var, nbt, C, training, momentum, eps, act, stats=stats,
                                stats_rpb=stats_rpb))
     return _BNActPool.apply(x, gamma, beta, running_mean, running_var, nbt, stats, C, training, momentum, eps, act, stats_rpb)
-
-
-def _bn_mean_invstd(x, stats, rpb, rm, rv, nbt, C, training, momentum, eps):
-    """(mean, invstd) of a BatchNorm over x: batch statistics from the producing conv's partial rows `stats` (rpb pixels
-    each) or a sweep of x, the running buffers moved as torch moves them (train); the running statistics (eval, from the
-    eval_bn_table when one is in force)."""
-    B, H, W, Cs = x.shape
-    if not training:
-        return _bn_eval_stats(rm, rv, C, Cs, eps, x)
-    M = B * H * W
-    mean, invstd = _empty((Cs,), x), _empty((Cs,), x)
-    if stats is not None:
-        partial, nblk = stats, stats.shape[0]
-        rpb = rpb if rpb else lib().raw("vmtl_conv2d_stats_block")(B, H, W, Cs)
-    else:
-        partial, nblk, rpb = _empty((_reduce_rows(M), 2, Cs), x), 0, 0
-    _k("vmtl_bn_stats", x=x, M=M, C=C, Cs=Cs, partial=partial, nblk_from_conv=nblk, rows_per_blk_from_conv=rpb, eps=eps,
-       momentum=momentum, running_mean=rm, running_var=rv, num_batches_tracked=nbt, save_mean=mean, save_invstd=invstd)
-    return mean, invstd
 
 
 class _BNActPool3(torch.autograd.Function):
@@ -1877,7 +1860,7 @@ class _BNActPool3(torch.autograd.Function):
         bn = rm is not None
         mean = invstd = None
         if bn:
-            mean, invstd = _bn_mean_invstd(x, stats, stats_rpb, rm, rv, nbt, C, training, momentum, eps)
+            mean, invstd = _bn_stats(x, stats, stats_rpb, rm, rv, nbt, C, training, momentum, eps)
         Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
         a = _empty(x.shape, x) if bn else None
         p = _empty((B, Ho, Wo, Cs), x)
@@ -1921,16 +1904,12 @@ FUSE_STEM_POOL = os.environ.get("VMTL_FUSE_STEM_POOL", "1") != "0"  # ResNet ste
 def bn_act_pool3(x, bn, C, act, stats=None, stats_rpb=0):
     """(act(bn(x)), maxpool3x3/s2/p1 of it): the activated map and its pool from one node (FUSE_STEM_POOL), else a
     BatchNorm node followed by the plain pool node."""
-    if stats is not None and not stats_rpb:
-        stats_rpb = getattr(stats, "_vmtl_rpb", 0)
-    if bn.momentum is None:
-        raise NotImplementedError("BatchNorm2d(momentum=None) (cumulative moving average) is not implemented")
+    stats_rpb = _resolve_rpb(stats, stats_rpb, x.shape)
+    tensors, mode = _bn_args(bn)
     if not FUSE_STEM_POOL:
-        a = bn_act(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, C, bn.training,
-                   float(bn.momentum), bn.eps, act, stats=stats, stats_rpb=stats_rpb)
+        a = bn_act(x, *tensors, C, *mode, act, stats=stats, stats_rpb=stats_rpb)
         return a, maxpool3s2(a, C)
-    cfg = (C, bn.training, float(bn.momentum), bn.eps, act, stats_rpb)
-    return _BNActPool3.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, stats, cfg)
+    return _BNActPool3.apply(x, *tensors, stats, (C, *mode, act, stats_rpb))
 
 
 def maxpool3s2(x, C):
@@ -1950,13 +1929,13 @@ class _BNAddAct(torch.autograd.Function):
         z = _req(z, "z")
         B, H, W, Cs = z.shape
         M = B * H * W
-        mean_a, invstd_a = _bn_mean_invstd(z, stats, rpb, rma, rva, nbta, C, training, mom_a, eps_a)
+        mean_a, invstd_a = _bn_stats(z, stats, rpb, rma, rva, nbta, C, training, mom_a, eps_a)
         mean_b = invstd_b = None
         if zd is not None:
             zd = _req(zd, "zd")
             if zd.shape != z.shape:
                 raise ValueError(f"bn_add_act: downsample branch {tuple(zd.shape)} vs main branch {tuple(z.shape)}")
-            mean_b, invstd_b = _bn_mean_invstd(zd, statsd, rpbd, rmb, rvb, nbtb, C, training, mom_b, eps_b)
+            mean_b, invstd_b = _bn_stats(zd, statsd, rpbd, rmb, rvb, nbtb, C, training, mom_b, eps_b)
         else:
             res = _req(res, "res")
             if res.shape != z.shape:
@@ -1994,21 +1973,14 @@ class _BNAddAct(torch.autograd.Function):
 
 def bn_add_act(z, stats, rpb, bn, C, act, res=None, zd=None, statsd=None, rpbd=0, bn_d=None):
     """act(bn(z) + res)  or  act(bn(z) + bn_d(zd)): z / zd raw conv outputs with their statistics rows (rpb pixels each)."""
-    for m in (bn, bn_d):
-        if m is not None and m.momentum is None:
-            raise NotImplementedError("BatchNorm2d(momentum=None) (cumulative moving average) is not implemented")
+    ta, (training, mom_a, eps_a) = _bn_args(bn)
+    tb, (_, mom_b, eps_b) = _bn_args(bn_d) if bn_d is not None else ((None,) * 5, (training, 0.1, 1e-5))
     if (res is None) == (zd is None):
         raise ValueError("bn_add_act: give exactly one of res (identity) and zd (downsample branch)")
-    if stats is not None and not rpb:
-        rpb = getattr(stats, "_vmtl_rpb", 0)
-    if statsd is not None and not rpbd:
-        rpbd = getattr(statsd, "_vmtl_rpb", 0)
-    d = bn_d
-    cfg = (C, bn.training, float(bn.momentum), bn.eps, rpb, float(d.momentum) if d else 0.1, d.eps if d else 1e-5, rpbd,
+    # zd has z's shape (the node checks it)
+    cfg = (C, training, mom_a, eps_a, _resolve_rpb(stats, rpb, z.shape), mom_b, eps_b, _resolve_rpb(statsd, rpbd, z.shape),
            act)
-    return _BNAddAct.apply(z, stats, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, res, zd,
-                           statsd, d.weight if d else None, d.bias if d else None, d.running_mean if d else None,
-                           d.running_var if d else None, d.num_batches_tracked if d else None, cfg)
+    return _BNAddAct.apply(z, stats, *ta, res, zd, statsd, *tb, cfg)
 
 
 def activation(x, act, C, mul=None):
@@ -2682,35 +2654,8 @@ def conv3x3_small_supported(Cs: int, Nw: int) -> bool:
 def _small(x, wp, y, B, H, W, Cs, ldy, Nw, Cout, flop, x2=None, pa=None, pb=None, pc=None, act_in=ACT_NONE, a_out=None,
            bias=None, yb=None, Ca=0, stats=None, ep_mode=0, ez=None):
     """One vmtl_conv3x3_small launch (csrc/conv_small.hip); ez = (x, mean, invstd, gamma, beta, act) for ep_mode 2."""
-    ez = ez or (None, None, None, None, None, ACT_NONE)
     _k("vmtl_conv3x3_small", _flop=flop, x=x, x2=x2, pa=pa, pb=pb, pc=pc, act_in=act_in, a_out=a_out, wp=wp, bias=bias,
-       y=y, yb=yb, Ca=Ca, stats=stats, ep_mode=ep_mode, ez_x=ez[0], ez_mean=ez[1], ez_invstd=ez[2], ez_gamma=ez[3],
-       ez_beta=ez[4], ez_act=ez[5], B=B, H=H, W=W, Cs=Cs, ldy=ldy, Nw=Nw, Cout=Cout)
-
-
-def _bn_fwd_coef(x, stats, rpb, gamma, beta, rm, rv, nbt, C, training, momentum, eps):
-    """BatchNorm statistics (from conv-epilogue partial rows `stats` of `rpb` pixels each, or a sweep of x when
-    stats is None; running buffers in eval mode) -> (mean, invstd, coef_a, coef_c) with
-    BN(x) = coef_a * x + coef_c per channel (zeros on pad channels)."""
-    B, H, W, Cs = x.shape
-    M = B * H * W
-    if not training:
-        e = eval_bn.get(rm, C, eps, (gamma, beta))
-        if e is not None:
-            return e
-    mean, invstd, ca, cc = (_empty((Cs,), x) for _ in range(4))
-    if training:
-        if stats is not None:
-            partial, nblk = stats, stats.shape[0]
-        else:
-            partial, nblk, rpb = _empty((_reduce_rows(M), 2, Cs), x), 0, 0
-        _k("vmtl_bn_stats_coef", x=x, M=M, C=C, Cs=Cs, partial=partial, nblk_from_conv=nblk, rows_per_blk_from_conv=rpb,
-           eps=eps, momentum=momentum, running_mean=rm, running_var=rv, num_batches_tracked=nbt, save_mean=mean,
-           save_invstd=invstd, gamma=gamma, beta=beta, coef_a=ca, coef_c=cc)
-    else:
-        _k("vmtl_bn_eval_stats_coef", running_mean=rm, running_var=rv, C=C, Cs=Cs, eps=eps, save_mean=mean,
-           save_invstd=invstd, gamma=gamma, beta=beta, coef_a=ca, coef_c=cc)
-    return mean, invstd, ca, cc
+       y=y, yb=yb, Ca=Ca, stats=stats, ep_mode=ep_mode, B=B, H=H, W=W, Cs=Cs, ldy=ldy, Nw=Nw, Cout=Cout, **_ez_kw(ez))
 
 
 class _DecoderTail(torch.autograd.Function):
@@ -2740,14 +2685,14 @@ class _DecoderTail(torch.autograd.Function):
         M = B * H * W
         tiles = lib().raw("vmtl_conv3x3_small_stat_rows")(B, H, W)  # statistics rows ...
         rpb = lib().raw("vmtl_conv3x3_small_stat_block")(B, H, W)   # ... of this many pixels each
-        mean1, invstd1, pa1, pc1 = _bn_fwd_coef(x1, stats1, rpb1, g1, b1, rm1, rv1, nbt1, C1, tr1, mom1, eps1)
+        mean1, invstd1, pa1, pc1 = _bn_stats(x1, stats1, rpb1, rm1, rv1, nbt1, C1, tr1, mom1, eps1, (g1, b1))
         wp2 = packs.get(w2, "fwd", Layout.fwd(C2, C1, 9, Cs1))
         a1 = _empty(x1.shape, x1) if need_bwd else None
         x2 = _empty((B, H, W, ldy2), x1)
         stats2 = _empty((tiles, 2, ldy2), x1) if tr2 else None
         _small(x1, wp2, x2, B, H, W, Cs1, ldy2, C2, C2, 2.0 * M * C2 * 9 * C1, pa=pa1, pc=pc1, act_in=ACT_RELU, a_out=a1,
                stats=stats2, ep_mode=1 if tr2 else 0)
-        mean2, invstd2, pa2, pc2 = _bn_fwd_coef(x2, stats2, rpb, g2, b2, rm2, rv2, nbt2, C2, tr2, mom2, eps2)
+        mean2, invstd2, pa2, pc2 = _bn_stats(x2, stats2, rpb, rm2, rv2, nbt2, C2, tr2, mom2, eps2, (g2, b2))
         # both heads as ONE GEMM operand / bias vector, kept packed by the step's batched packing launch
         wph = packs.shared(wa, "heads_fwd", (N, 9 * ldy2))
         packs.get(wa, "heads_fwd", Layout.fwd(Ca, C2, 9, ldy2), out=wph[:Ca])
@@ -2824,20 +2769,14 @@ class _DecoderTail(torch.autograd.Function):
         _small(dz2, wd2, dz1, B, H, W, ldy2, Cs1, C1, C1, 2.0 * M * C1 * 9 * C2, x2=x2, pa=cA, pb=cB, pc=cC, a_out=dx2,
                stats=part1, ep_mode=2, ez=(x1, mean1, invstd1, g1, b1, ACT_RELU))
         fork = side.mark()  # AFTER the launch above: the weight gradient reads the dx2 it wrote
-        dbeta1, dgamma1 = _grad_buf((C1,), sb1, x1), _grad_buf((C1,), sg1, x1)
-        _k("vmtl_bn_bwd_finalize", partial=part1, nblk=tiles, M=M, C=C1, Cs=Cs1, sum_dz=dbeta1, sum_dzx=dgamma1, mean=None,
-           invstd=None, gamma=None, training=1 if tr1 else 0, coef_a=None, coef_b=None, coef_c=None)
-        dx1 = None
-        if ctx.needs_input_grad[0]:
-            dx1 = _empty(x1.shape, x1)
-            _k("vmtl_bn_bwd_apply", x=x1, dz=dz1, mean=mean1, invstd=invstd1, gamma=g1, sum_dz=dbeta1, sum_dzx=dgamma1,
-               dx=dx1, M=M, C=C1, Cs=Cs1, training=1 if tr1 else 0)
+        dx1, dgamma1, dbeta1 = _bn_bwd_tail(part1, tiles, x1, dz1, mean1, invstd1, g1, C1, tr1, (sg1, sb1),
+                                            ctx.needs_input_grad[0])
         with side.branch(sw2 is not None, M, fork, a1, dx2):
             dw2 = _grad_buf(w2.shape, sw2, x1)
             _wgrad_into(a1, dx2, ConvGeom(B, H, W, Cs1, H, W, ldy2, 3, 3, 1, 1), Layout.fwd(C2, C1, 9, Cs1), dw2,
                         2.0 * M * C2 * 9 * C1, ctx.prec)
             stamp("side tail conv2")
-        return (dx1, None, None, _grad_ret(dgamma1, sg1), _grad_ret(dbeta1, sb1), None, None, None, _grad_ret(dw2, sw2),
+        return (dx1, None, None, dgamma1, dbeta1, None, None, None, _grad_ret(dw2, sw2),
                 _grad_ret(dgamma2, sg2), _grad_ret(dbeta2, sb2), None, None, None, dwa, dba, dwb, dbb, None)
 
 
@@ -2851,15 +2790,8 @@ def decoder_tail_supported(x1_shape, C1, C2, N) -> bool:
 def decoder_tail(x1, stats1, rpb1, bn1, conv2_weight, bn2, wa, ba, wb, bb):
     """(head_a, head_b) NCHW = heads(relu(bn2(conv2(relu(bn1(x1)))))); bn1 / bn2 are nn.BatchNorm2d parameter
     containers, x1 the raw conv output feeding bn1 (stats1 = its conv-epilogue partial rows of rpb1 pixels, or None)."""
-    def mom(bn):
-        if bn.momentum is None:
-            raise NotImplementedError("BatchNorm2d(momentum=None) (cumulative moving average) is not implemented")
-        return float(bn.momentum)
-
-    cfg = (bn1.training, mom(bn1), bn1.eps, bn2.training, mom(bn2), bn2.eps)
-    return _DecoderTail.apply(x1, stats1, rpb1, bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var,
-                              bn1.num_batches_tracked, conv2_weight, bn2.weight, bn2.bias, bn2.running_mean,
-                              bn2.running_var, bn2.num_batches_tracked, wa, ba, wb, bb, cfg)
+    (t1, mode1), (t2, mode2) = _bn_args(bn1), _bn_args(bn2)
+    return _DecoderTail.apply(x1, stats1, rpb1, *t1, conv2_weight, *t2, wa, ba, wb, bb, (*mode1, *mode2))
 
 
 def _copy_vec(src, dst, n):
