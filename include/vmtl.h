@@ -347,6 +347,9 @@ int vmtl_unpack_weights(const float* packed, float* grad, int R1, int R0, int T,
  * replaces nn.BatchNorm2d/ReLU/Sigmoid/mul at utils/model_utils.py:72-76;
  * models/mtan_model.py:67-81,139-167. */
 int vmtl_reduce_rows(int M); /* partial rows used by the two-stage reductions */
+/* Statistics rows (partial [nblk][2][Cs], vmtl_bn_stats with nblk_from_conv > 0 and vmtl_bn_apply_fused): row b holds
+ * (mean_b, M2_b) of the rows [b*rows_per_blk, min(M, (b+1)*rows_per_blk)); any M <= nblk * rows_per_blk < 2^31 is accepted and
+ * a row that lies wholly past M may hold anything: both consumers skip it. */
 int vmtl_bn_stats(const float* x, int M, int C, int Cs, float* partial, int nblk_from_conv,
                   int rows_per_blk_from_conv, float eps, float momentum, float* running_mean, float* running_var, long long* num_batches_tracked,
                   float* save_mean, float* save_invstd, void* stream);

@@ -25,7 +25,7 @@ pytestmark = pytest.mark.gpu
 
 # every test of these modules is swept
 SWEPT_MODULES = ("test_kernels_gpu", "test_conv_small_gpu", "test_resnet_kernels_gpu", "test_se_gate_gpu",
-                 "test_stitch_mix_gpu", "test_dwconv_kernels_gpu")
+                 "test_stitch_mix_gpu", "test_dwconv_kernels_gpu", "test_bn_kernels_gpu")
 
 # of these modules, the functions that call ops nodes directly and build no model (the bf16 instantiations are
 # different kernels from the fp32 ones the modules above reach)

@@ -194,6 +194,7 @@ static int bn_stats_impl(const float* x, int M, int C, int Cs, float* partial, i
                          const float* beta, float* coef_a, float* coef_c, void* stream) {
   VMTL_ENTER();
   if ((coef_a == nullptr) != (coef_c == nullptr)) return VMTL_ERR_ARG;
+  if ((running_mean == nullptr) != (running_var == nullptr)) return VMTL_ERR_ARG;  // the kernel tests running_mean only
   if (!partial || !save_mean || !save_invstd || M <= 0 || C <= 0 || C > Cs || (Cs & 3)) return VMTL_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   int nblk = nblk_from_conv, rows_per_blk = rows_per_blk_from_conv;
@@ -202,8 +203,8 @@ static int bn_stats_impl(const float* x, int M, int C, int Cs, float* partial, i
     nblk = red_blocks(M);
     rows_per_blk = cdiv(M, nblk);
     hipLaunchKernelGGL(bn_stats_kernel, dim3(nblk), dim3(RED_THREADS), 0, st, x, M, Cs, partial);
-  } else if (rows_per_blk <= 0 || (long long)nblk * rows_per_blk < M) {
-    return VMTL_ERR_ARG;
+  } else if (rows_per_blk <= 0 || (long long)nblk * rows_per_blk < M || (long long)nblk * rows_per_blk > 0x7fffffffLL) {
+    return VMTL_ERR_ARG;  // the kernels compute b * rows_per_blk in int
   }
   hipLaunchKernelGGL(bn_finalize_kernel, dim3(Cs >> 2), dim3(256), 0, st, partial, nblk, rows_per_blk, M, C, Cs, eps,
                      momentum, running_mean, running_var, num_batches_tracked, save_mean, save_invstd, gamma, beta,
@@ -232,7 +233,7 @@ extern "C" int vmtl_bn_stats_coef(const float* x, int M, int C, int Cs, float* p
 extern "C" int vmtl_bn_eval_stats(const float* running_mean, const float* running_var, int C, int Cs, float eps,
                                   float* save_mean, float* save_invstd, void* stream) {
   VMTL_ENTER();
-  if (!running_mean || !running_var || !save_mean || !save_invstd || C <= 0 || C > Cs) return VMTL_ERR_ARG;
+  if (!running_mean || !running_var || !save_mean || !save_invstd || C <= 0 || C > Cs || (Cs & 3)) return VMTL_ERR_ARG;
   hipLaunchKernelGGL(bn_eval_stats_kernel, dim3(cdiv(Cs, 128)), dim3(128), 0, (hipStream_t)stream, running_mean,
                      running_var, C, Cs, eps, save_mean, save_invstd, nullptr, nullptr, nullptr, nullptr);
   return vmtl_check_launch();
@@ -242,7 +243,7 @@ extern "C" int vmtl_bn_eval_stats_coef(const float* running_mean, const float* r
                                        float* save_mean, float* save_invstd, const float* gamma, const float* beta,
                                        float* coef_a, float* coef_c, void* stream) {
   VMTL_ENTER();
-  if (!running_mean || !running_var || !save_mean || !save_invstd || !coef_a || !coef_c || C <= 0 || C > Cs)
+  if (!running_mean || !running_var || !save_mean || !save_invstd || !coef_a || !coef_c || C <= 0 || C > Cs || (Cs & 3))
     return VMTL_ERR_ARG;
   hipLaunchKernelGGL(bn_eval_stats_kernel, dim3(cdiv(Cs, 128)), dim3(128), 0, (hipStream_t)stream, running_mean,
                      running_var, C, Cs, eps, save_mean, save_invstd, gamma, beta, coef_a, coef_c);
@@ -329,6 +330,8 @@ __global__ __launch_bounds__(RED_THREADS) void bn_apply_kernel(const float* __re
 // channel quad with Chan's formula in fp64 (nblk <= VMTL_BN_FUSE_MAX_ROWS float4 pairs out of L2) instead
 // of waiting for a separate one-workgroup-per-channel finalize launch; workgroup 0 also publishes
 // mean / invstd for the backward pass and updates the running buffers.
+// Row contract, shared with bn_finalize_kernel: row b covers [b*rows_per_blk, min(M, (b+1)*rows_per_blk)), any
+// M <= nblk * rows_per_blk < 2^31 is accepted, and a row that lies wholly past M is never read into a result.
 #define VMTL_BN_FUSE_MAX_ROWS 64
 
 template <int ACT>
@@ -344,10 +347,12 @@ __global__ __launch_bounds__(RED_THREADS) void bn_apply_fused_kernel(
         auto rows_of = [&](int b) { return max(0, min(rows_per_blk, M - b * rows_per_blk)); };
         double s[4] = {0.0, 0.0, 0.0, 0.0};
         for (int b = 0; b < nblk; ++b) {
-          const f32x4 mb = *reinterpret_cast<const f32x4*>(partial + ((size_t)b * 2 + 0) * Cs + (size_t)q * 4);
           const double nb = rows_of(b);
+          if (nb > 0.0) {  // rows past M may hold anything (0 * NaN), as in bn_finalize_kernel
+            const f32x4 mb = *reinterpret_cast<const f32x4*>(partial + ((size_t)b * 2 + 0) * Cs + (size_t)q * 4);
 #pragma unroll
-          for (int e = 0; e < 4; ++e) s[e] += nb * (double)mb[e];
+            for (int e = 0; e < 4; ++e) s[e] += nb * (double)mb[e];
+          }
         }
         double m2[4] = {0.0, 0.0, 0.0, 0.0};
         for (int b = 0; b < nblk; ++b) {
@@ -441,8 +446,10 @@ extern "C" int vmtl_bn_apply_fused(const float* x, const float* partial, int nbl
   VMTL_ENTER();
   if (!x || !y || !partial || !save_mean || !save_invstd || M <= 0 || M > 0x7fffffffLL || C <= 0 || C > Cs || (Cs & 3))
     return VMTL_ERR_ARG;
-  if (nblk <= 0 || nblk > VMTL_BN_FUSE_MAX_ROWS || rows_per_blk <= 0 || (long long)nblk * rows_per_blk < M)
+  if (nblk <= 0 || nblk > VMTL_BN_FUSE_MAX_ROWS || rows_per_blk <= 0 || (long long)nblk * rows_per_blk < M ||
+      (long long)nblk * rows_per_blk > 0x7fffffffLL)  // the kernel computes b * rows_per_blk in int
     return VMTL_ERR_ARG;
+  if ((running_mean == nullptr) != (running_var == nullptr)) return VMTL_ERR_ARG;
   const int nb = sweep_blocks(M, Cs);
 #define CALL(A)                                                                                                    \
   hipLaunchKernelGGL((bn_apply_fused_kernel<A>), dim3(nb), dim3(RED_THREADS), 0, (hipStream_t)stream, x, partial, \
@@ -644,7 +651,8 @@ extern "C" int vmtl_bn_bwd_finalize(const float* partial, int nblk, int M, int C
   VMTL_ENTER();
   if (!partial || nblk <= 0 || M <= 0 || C <= 0 || C > Cs || (Cs & 3) || !sum_dz || !sum_dzx) return VMTL_ERR_ARG;
   const bool want = coef_a != nullptr;
-  if (want && (!coef_b || !coef_c || !mean || !invstd)) return VMTL_ERR_ARG;
+  if (want != (coef_b != nullptr) || want != (coef_c != nullptr)) return VMTL_ERR_ARG;  // all three or none
+  if (want && (!mean || !invstd)) return VMTL_ERR_ARG;
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(want ? Cs >> 2 : (C + 3) >> 2), dim3(256), 0, (hipStream_t)stream, partial,
                      nblk, C, Cs,
                      sum_dz, sum_dzx, mean, invstd, gamma, 1.f / (float)M, training, coef_a, coef_b, coef_c);

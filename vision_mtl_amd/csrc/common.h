@@ -108,8 +108,10 @@ __device__ __forceinline__ float act_fwd(float v, int act) {
 __device__ __forceinline__ float sigmoid_exact(float v) { return 1.f / (1.f + expf(-v)); }
 
 // derivative of act at pre-activation v (torch conventions: relu'(0)=0,
-// hardswish' = 0 for v<-3, 1 for v>3, (2v+3)/6 between (torch uses < and >,
-// the boundary points take the middle formula), hardsigmoid' = 1/6 on (-3,3)).
+// hardswish' = 0 for v<-3, 1 for v>3, (2v+3)/6 between (the torch releases this was written
+// against use < and >: the boundary points take the middle formula; torch 2.10 returns 0 at -3
+// and 1 at 3 - tests/test_bn_kernels_gpu.py pins the values here and prints torch's),
+// hardsigmoid' = 1/6 on (-3,3)).
 __device__ __forceinline__ float act_grad(float v, int act) {
   switch (act) {
     case VMTL_ACT_RELU: return v > 0.f ? 1.f : 0.f;
