@@ -881,6 +881,39 @@ int vmtl_swap_table_(const void* descs, int n, long long max_n, void* stream);
 /* a <-> b in place, moved as integers (NaN payloads survive); overlapping ranges are refused with VMTL_ERR_ARG */
 int vmtl_swap_(float* a, float* b, long long n, void* stream);
 
+/* ---- two-task gradient surgery on a pair of fp32 gradients (csrc/surgery.hip) -------------
+ * PCGrad (Yu et al. 2020), the two-point MGDA min-norm solution (Sener & Koltun 2018) and the gradient part of IMTL-G
+ * (Liu et al. 2021) need the 2x2 Gram matrix of the two per-task gradients and nothing else.  a and b are `rows` rows
+ * of `width` floats with leading dimensions lda, ldb >= width (in floats): two maps, two flat buffers (rows 1), or the
+ * two halves of one interleaved [rows][2*Cs] map (b = a + Cs, lda = ldb = 2*Cs).  Pointers need 4-byte alignment; the
+ * 16-byte body is taken when pointers, width and leading dimensions allow it, a scalar body otherwise.
+ * `state`: 12 four-byte words, 8-byte aligned, zeroed once by the caller:
+ *   [0] n_a = <a,a>  [1] d = <a,b>  [2] n_b = <b,b>  [3] alpha  [4] beta  [5] cosine d / sqrt(n_a n_b)  [6..7] unused
+ *   [8..9] steps seen (one 64-bit integer)  [10..11] steps with d < 0 (one 64-bit integer) */
+#define VMTL_SURGERY_STATE_FLOATS 12
+#define VMTL_SURGERY_SUM 0    /* alpha = beta = 1: Gram matrix, cosine and counters only */
+#define VMTL_SURGERY_PCGRAD 1 /* d < 0: alpha = 1 - d / n_a, beta = 1 - d / n_b; else 1, 1 */
+#define VMTL_SURGERY_MGDA 2   /* alpha = clip((n_b - d) / (n_a - 2 d + n_b), 0, 1) (0.5 when that denominator is <= 0), beta = 1 - alpha */
+#define VMTL_SURGERY_IMTL_G 3 /* alpha = sqrt(n_b) / (sqrt(n_a) + sqrt(n_b)), beta = 1 - alpha */
+long long vmtl_surgery_workspace_bytes(long long rows, long long width); /* host only; 0 for a bad shape */
+/* per-workgroup partial sums of a*a, a*b, b*b into workspace (8-byte aligned): products and sums in fp64, fixed order,
+ * no atomics */
+int vmtl_surgery_gram(const float* a, long long lda, const float* b, long long ldb, long long rows, long long width,
+                      void* workspace, void* stream);
+/* One workgroup.  Folds the partials of vmtl_surgery_gram(rows, width) in fp64, stores the Gram matrix as fp32, derives
+ * (alpha, beta) in fp64 FROM THOSE fp32 VALUES and rounds them once; steps += 1, conflicts += 1 when d < 0.
+ * n_a == 0, n_b == 0 (fp32 underflow included) or a Gram entry that is not finite: alpha = beta = 1 for every method,
+ * cosine = 0, the conflict counter stays.  An unknown method returns -3 without a launch. */
+int vmtl_surgery_control(const void* workspace, long long rows, long long width, int method, float* state,
+                         void* stream);
+/* out[r][c] = alpha * a[r][c] + beta * b[r][c], evaluated in fp64 and rounded to fp32 once, for c < width, alpha = state[3],
+ * beta = state[4]; ldo >= width.
+ * out may be a (same pointer, ldo == lda); any other overlap of out with a or b (elements, not byte ranges: the
+ * interleaved halves of one map do not overlap) returns -1.  Lanes [width, ldo) of out are LEFT ALONE: in the interleaved layout they
+ * hold b. */
+int vmtl_surgery_combine(const float* a, long long lda, const float* b, long long ldb, const float* state, float* out,
+                         long long ldo, long long rows, long long width, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

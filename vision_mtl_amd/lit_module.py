@@ -18,6 +18,8 @@ from . import metrics as M
 from . import ops
 from .balancing import TaskBalancer
 from .losses import CrossEntropyLoss, SILogGradLoss, SILogLoss
+from .models.basic_model import BasicMTLModel
+from .surgery import GradSurgery, resolve as resolve_surgery
 from .utils.loss_utils import summarize_epoch_metrics
 
 
@@ -30,7 +32,8 @@ class MTLModule(nn.Module):
                  segm_ohem_min_kept: t.Optional[int] = None, segm_ohem_thresh: t.Optional[float] = None,
                  depth_grad_weight: t.Optional[float] = None, depth_grad_scales: int = 4,
                  segm_region_weight: t.Optional[float] = None, segm_region_alpha: float = 0.5,
-                 segm_region_beta: float = 0.5, segm_region_smooth: float = 0.0):
+                 segm_region_beta: float = 0.5, segm_region_smooth: float = 0.0,
+                 grad_surgery: t.Union[None, str, GradSurgery] = None):
         """segm_ignore_index / segm_class_weights (opt-in, INTEGRATION.md): the `ignore_index` and per-class `weight`
         of the segmentation criterion; the ignore index also keeps those pixels out of the segmentation metrics.
         loss_balancing (opt-in): "uncertainty" | "dwa" | "geometric" or a balancing.TaskBalancer
@@ -44,8 +47,16 @@ class MTLModule(nn.Module):
         part of the loss definition, like the class weights.
         segm_region_weight / segm_region_alpha / _beta / _smooth (opt-in): `segm_criterion`
         becomes cross entropy + segm_region_weight * the Dice / Tversky region term (losses.CrossEntropyLoss with
-        region_weight), in every stage, like depth_grad_weight; it does not combine with segm_ohem_min_kept."""
+        region_weight), in every stage, like depth_grad_weight; it does not combine with segm_ohem_min_kept.
+        grad_surgery (opt-in): "sum" | "pcgrad" | "mgda" | "imtl_g" or a surgery.GradSurgery -
+        the training step's backward pass combines the two tasks' gradients of the shared decoder map by that method.  It
+        is set on the model (`BasicMTLModel.grad_surgery`; `csnet` and `mtan` have no single shared representation and
+        are refused) and acts on the gradient, so it combines with everything above that acts on the losses."""
         super().__init__()
+        grad_surgery = resolve_surgery(grad_surgery)
+        if grad_surgery is not None and not isinstance(model, BasicMTLModel):  # checked before anything is built
+            raise ValueError(f"MTLModule: grad_surgery needs a model whose tasks share one representation "
+                             f"(BasicMTLModel), got {type(model).__name__}")
         region = {}
         if segm_region_weight is not None:  # checked before anything is built
             if segm_ohem_min_kept is not None or segm_ohem_thresh is not None:
@@ -81,6 +92,9 @@ class MTLModule(nn.Module):
                         "segm_class_weights": None if segm_class_weights is None else segm_class_weights.tolist()}
         if loss_balancing is not None:  # the default module keeps the hparams it always had
             self.hparams.update(loss_balancing=loss_balancing.method, dwa_temperature=loss_balancing.temperature)
+        if grad_surgery is not None:  # the default module keeps the hparams it always had
+            self.hparams.update(grad_surgery=grad_surgery.method)
+            model.grad_surgery = grad_surgery
         self.num_classes = num_classes
         self.model = model
         if region:  # the default module keeps the hparams and the criterion it always had
@@ -140,6 +154,19 @@ class MTLModule(nn.Module):
         # construction whether it was set.  An attribute like train_augment: hparams and state_dict() keys do not change
         self.weight_average = None
         self._mining = False  # True inside a training step's calc_losses
+
+    @property
+    def grad_surgery(self) -> t.Optional[GradSurgery]:
+        """The model's surgery.GradSurgery (None by default): its .stats / .coefficients / .conflict_rate() are device
+        tensors that show the last training step."""
+        return getattr(self.model, "grad_surgery", None)
+
+    @grad_surgery.setter
+    def grad_surgery(self, value) -> None:
+        value = resolve_surgery(value)
+        if value is not None and not isinstance(self.model, BasicMTLModel):
+            raise ValueError(f"MTLModule: grad_surgery needs a BasicMTLModel, got {type(self.model).__name__}")
+        self.model.grad_surgery = value
 
     def forward(self, x: torch.Tensor) -> dict:
         return self.model(x)

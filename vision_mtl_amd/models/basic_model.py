@@ -25,6 +25,11 @@ class BasicMTLModel(nn.Module):
         last = self.backbone.decoder_channels[-1]
         self.segm_head = SegmentationHead(last, segm_classes, activation=activation, kernel_size=3)
         self.depth_head = SegmentationHead(last, 1, activation=activation, kernel_size=3)
+        # a surgery.GradSurgery: a TRAINING forward with gradients enabled then takes the unfused tail and hands the object
+        # to ops.dual_head, whose backward combines the two heads' gradients of the shared decoder map by the object's
+        # method (every other forward takes the route it always took).  An attribute like MTLModule.train_augment: no
+        # parameters, no buffers, state_dict() keys do not change
+        self.grad_surgery = None
 
     def forward(self, x: torch.Tensor) -> t.Dict[str, torch.Tensor]:
         ops.packs.refresh()  # one batched weight-packing launch for the whole step
@@ -33,7 +38,11 @@ class BasicMTLModel(nn.Module):
         x1, stats1, rpb1 = self.backbone.run(L.from_nchw(x), raw_tail=True)  # raw conv1 output of the last block
         c2, bn1, bn2 = last.conv2[0], last.conv1[1], last.conv2[1]
         heads_3x3 = tuple(sh.kernel_size) == (3, 3) and tuple(dh.kernel_size) == (3, 3) and sh.padding[0] == 1
-        if heads_3x3 and ops.decoder_tail_supported(x1.t.shape, x1.C, c2.out_channels, sh.out_channels + dh.out_channels):
+        surgery = self.grad_surgery if self.training and torch.is_grad_enabled() else None
+        if surgery is not None:  # the fused tail's data-gradient epilogue cannot be split per task
+            dec = L.conv_bn_act(L.bn_act(x1, bn1, ops.ACT_RELU, stats=stats1, stats_rpb=rpb1), c2, bn2, ops.ACT_RELU)
+            segm, depth = ops.dual_head(dec.t, sh.weight, sh.bias, dh.weight, dh.bias, pad=sh.padding[0], surgery=surgery)
+        elif heads_3x3 and ops.decoder_tail_supported(x1.t.shape, x1.C, c2.out_channels, sh.out_channels + dh.out_channels):
             # the narrow full-resolution tail (BN+ReLU -> conv2 -> BN+ReLU -> both heads) on the halo-tile kernel
             segm, depth = ops.decoder_tail(x1.t, stats1, rpb1, bn1, c2.weight, bn2, sh.weight, sh.bias, dh.weight, dh.bias)
         else:

@@ -2805,13 +2805,14 @@ class _DualHead(torch.autograd.Function):
     tensors; outputs are the two contiguous NCHW maps the reference returns."""
 
     @staticmethod
-    def forward(ctx, x, wa, ba, wb, bb, pad):
+    def forward(ctx, x, wa, ba, wb, bb, pad, surgery=None):
         x, wa, wb = _req(x, "x"), _req(wa, "weight a"), _req(wb, "weight b")
         B, H, W, Cs = x.shape
         Ca, Cin, KH, KW = wa.shape
         Cb = wb.shape[0]
         if tuple(wb.shape[1:]) != (Cin, KH, KW) or ceil4(Cin) != Cs or ba is None or bb is None:
             raise ValueError("dual_head: both heads must share input channels / kernel size and have a bias")
+        ctx.surgery = surgery
         N, KK = Ca + Cb, KH * KW
         ldy, Ktot = ceil4(N), KK * Cs
         wp = _empty((N, Ktot), x)
@@ -2853,7 +2854,21 @@ class _DualHead(torch.autograd.Function):
         _k("vmtl_nchw_to_nhwc", x=gb, y=dyf[Ca:], B=B, C=Cb, HW=H * W, Cs=ldy, Cw=ldy - Ca)  # also zeroes pad lanes
         dx = None
         fork = side.mark()
-        if ctx.needs_input_grad[0]:
+        if ctx.needs_input_grad[0] and ctx.surgery is not None:
+            # the two heads' data gradients kept apart, still ONE launch that reads dy once: a block-diagonal operand of
+            # Cs + Cin rows - rows [0, Cin) carry head a's lanes co < Ca, rows [Cs, Cs + Cin) head b's lanes [Ca, Ca + Cb),
+            # every other lane and row is zero - whose output is the interleaved map [M][g_a | g_b], 2 * Cs wide
+            # (the buffer is the surgery object's, zeroed once: only the two heads' lanes change from step to step)
+            wd = ctx.surgery.head_operand(Cs + Cin, KK * ldy, x)
+            pack(wa, *Layout.dgrad(Ca, Cin, KK, ldy), out=wd[:Cin])
+            _k("vmtl_pack_weights_slice", src=wb, dst=wd[Cs:].view(-1)[Ca:], R0=Cin, T=KK, C=Cb, group=ldy, sr0=KK, st=1,
+               sc=Cin * KK, flip=1)
+            gab = _empty((B, H, W, 2 * Cs), x)
+            _conv_launch(dy, wd, None, gab, g.dgrad()._replace(ldy=2 * Cs), Cout=Cs + Cin, cin=N, prec=ctx.prec,
+                         pw_prec=ctx.pw_prec)
+            dx = _empty((B, H, W, Cs), x)
+            ctx.surgery.apply(gab, dx, B * H * W, Cs)
+        elif ctx.needs_input_grad[0]:
             # one tap-flipped, transposed operand [ci][tap'][co]: head a fills co < Ca and zeroes the rest of
             # every ldy-wide group, head b then fills co in [Ca, Ca+Cb)
             wd = pack(wa, *Layout.dgrad(Ca, Cin, KK, ldy))
@@ -2865,11 +2880,14 @@ class _DualHead(torch.autograd.Function):
             dwa, dba, dwb, dbb = _wgrad_two_heads(x, dy, g, Layout.fwd(Ca, Cin, KK, Cs), Layout.fwd(Cb, Cin, KK, Cs), wa, wb,
                                                   ctx.slots, 2.0 * B * H * W * N * KK * Cin, ctx.prec)
             stamp("side head")
-        return dx, dwa, dba, dwb, dbb, None
+        return dx, dwa, dba, dwb, dbb, None, None
 
 
-def dual_head(x, wa, ba, wb, bb, pad=1):
-    return _DualHead.apply(x, wa, ba, wb, bb, pad)
+def dual_head(x, wa, ba, wb, bb, pad=1, surgery=None):
+    """surgery (opt-in, a surgery.GradSurgery): the backward hands x the combination alpha * g_a + beta * g_b of the two
+    heads' data gradients that the object's method derives from their Gram matrix, instead of their sum.  The forward
+    and the heads' own parameter gradients are those of the plain node."""
+    return _DualHead.apply(x, wa, ba, wb, bb, pad, surgery)
 
 
 class _Sigmoid(torch.autograd.Function):
@@ -3714,3 +3732,94 @@ def swap_(a, b):
 def swap_table_(table):
     """swap_ over every (buffer, average) pair of a wavg_buffer_table in ONE launch."""
     _k("vmtl_swap_table_", descs=table["descs"], n=table["n"], max_n=table["max_n"])
+
+
+# ----------------------------------------------------------------------------- gradient surgery (csrc/surgery.hip)
+# The 2x2 Gram matrix of two per-task gradients, the coefficients a two-task method derives from it and their
+# combination.  Plain launches like the optimizer's: no autograd, no host sync; surgery.GradSurgery owns the buffers.
+SURGERY_STATE_FLOATS = 12  # state block (include/vmtl.h)
+SURGERY_NA, SURGERY_D, SURGERY_NB, SURGERY_ALPHA, SURGERY_BETA, SURGERY_COSINE = range(6)
+SURGERY_COUNTERS = 8  # first of the four words that hold the two int64 counters (steps, conflicts)
+SURGERY_METHODS = {"sum": 0, "pcgrad": 1, "mgda": 2, "imtl_g": 3}
+
+
+def surgery_method(method) -> int:
+    if method not in SURGERY_METHODS:
+        raise ValueError(f"gradient surgery: method must be one of {sorted(SURGERY_METHODS)}, got {method!r}")
+    return SURGERY_METHODS[method]
+
+
+def surgery_state(like):
+    """A zeroed state block (both counters start at 0)."""
+    return _empty((SURGERY_STATE_FLOATS,), like).zero_()
+
+
+def surgery_counters(state):
+    """(steps seen, steps with d < 0) as a 2-element int64 view of the state block."""
+    return state[SURGERY_COUNTERS:SURGERY_COUNTERS + 4].view(torch.int64)
+
+
+def surgery_workspace(rows: int, width: int, like):
+    """Workspace of surgery_gram for `rows` rows of `width` floats: three fp64 partials per workgroup."""
+    nbytes = lib().raw("vmtl_surgery_workspace_bytes")(rows, width)
+    if nbytes <= 0:
+        raise ValueError(f"gradient surgery: bad shape rows = {rows}, width = {width}")
+    return _empty((nbytes // 4,), like).view(torch.float64)
+
+
+def surgery_workspace_max(like):
+    """A workspace large enough for surgery_gram at ANY shape (the grid is capped): what an owner allocates once when a
+    captured launch will hold the address."""
+    return surgery_workspace(1 << 40, 1, like)
+
+
+def _surgery_operand(t, name):
+    """An fp32 device operand exactly as given (a strided view of a map is fine: the launch takes its leading dimension)."""
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} is on {t.device}: the vmtl hot path only runs as HIP kernels on an MI355X "
+                           "(there is deliberately no CPU fallback)")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name} must be float32, got {t.dtype}")
+    return t
+
+
+def _surgery_pair(a, b, rows, width, lda, ldb):
+    """(rows, width, lda, ldb) of a pair of operands: flat buffers of equal length unless the caller says otherwise."""
+    _surgery_operand(a, "a"), _surgery_operand(b, "b")
+    if rows is None:
+        if a.numel() != b.numel():
+            raise ValueError("gradient surgery: a and b must hold the same number of elements")
+        rows, width = 1, a.numel()
+    lda = width if lda is None else lda
+    ldb = width if ldb is None else ldb
+    return rows, width, lda, ldb
+
+
+def surgery_gram(a, b, workspace=None, *, rows=None, width=None, lda=None, ldb=None):
+    """Per-workgroup fp64 partial sums of a*a, a*b, b*b into `workspace` (returned); deterministic.  a, b: two flat
+    buffers, or `rows` rows of `width` floats with leading dimensions lda / ldb (a and b may be views of one map)."""
+    rows, width, lda, ldb = _surgery_pair(a, b, rows, width, lda, ldb)
+    if workspace is None:
+        workspace = surgery_workspace(rows, width, a)
+    _k("vmtl_surgery_gram", a=a, lda=lda, b=b, ldb=ldb, rows=rows, width=width, workspace=workspace)
+    return workspace
+
+
+def surgery_control(workspace, state, method, rows, width):
+    """Partials of surgery_gram(rows, width) -> Gram matrix, coefficients, cosine and counters in `state`.  One launch of
+    one workgroup."""
+    _k("vmtl_surgery_control", workspace=workspace, rows=rows, width=width, method=surgery_method(method),
+       state=_flat(state, "state"))
+
+
+def surgery_combine(a, b, state, out=None, *, rows=None, width=None, lda=None, ldb=None, ldo=None):
+    """out = alpha * a + beta * b with the coefficients read from `state`; out may be a.  Lanes [width, ldo) of out are
+    left alone."""
+    rows, width, lda, ldb = _surgery_pair(a, b, rows, width, lda, ldb)
+    if out is None:
+        out = _empty((rows, width) if rows > 1 else (width,), a)
+    ldo = width if ldo is None else ldo
+    _k("vmtl_surgery_combine", a=a, lda=lda, b=b, ldb=ldb, state=_flat(state, "state"), out=_surgery_operand(out, "out"),
+       ldo=ldo,
+       rows=rows, width=width)
+    return out

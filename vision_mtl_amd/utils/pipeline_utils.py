@@ -47,6 +47,14 @@ def init_model(args: argparse.Namespace, data_cfg: DataConfig) -> MTLModule:
     Averaged weights (dp.ArenaAverage) are not wired here: they live next to a dp.FlatArena,
     which the caller builds after the model is on its device, so args.weight_average / weight_average_decay /
     weight_average_warmup are not read - set module.weight_average once the arena exists."""
+    grad_surgery = getattr(args, "grad_surgery", None)
+    if grad_surgery is not None:  # checked before the networks are built
+        from ..surgery import resolve
+
+        grad_surgery = resolve(grad_surgery)
+        if args.model_name != "basic":
+            raise ValueError(f"init_model: grad_surgery needs the single shared representation of model_name 'basic', got "
+                             f"{args.model_name!r} (INTEGRATION.md section 17)")
     model = build_model(args, data_cfg)
     # opt-in (INTEGRATION.md): an ignored label / per-class weights (a sequence of num_classes floats) for the segmentation loss
     module = MTLModule(model=model, num_classes=data_cfg.num_classes, lr=getattr(args, "lr", None),
@@ -67,7 +75,10 @@ def init_model(args: argparse.Namespace, data_cfg: DataConfig) -> MTLModule:
                        segm_region_weight=getattr(args, "segm_region_weight", None),
                        segm_region_alpha=getattr(args, "segm_region_alpha", 0.5),
                        segm_region_beta=getattr(args, "segm_region_beta", 0.5),
-                       segm_region_smooth=getattr(args, "segm_region_smooth", 0.0))
+                       segm_region_smooth=getattr(args, "segm_region_smooth", 0.0),
+                       # opt-in: "sum" | "pcgrad" | "mgda" | "imtl_g" gradient surgery at the
+                       # shared decoder map of `basic`
+                       grad_surgery=grad_surgery)
     # opt-in: test-time augmentation / output-size predictions of the predict step; an
     # attribute like train_augment, nothing goes into hparams
     scales, flip = getattr(args, "predict_scales", None), getattr(args, "predict_flip", None)
